@@ -26,11 +26,23 @@ Multi-GPU: edge-cut (contiguous nnz-balanced node ranges), RCCL reduce-scatter p
 and all-reduce of weight grads inside the C++ engine; the graph is fixed, so scaling is
 STRONG (value = epochs of the whole graph per second, all ranks together).
 
-Extra fields: "roofline" for the dominant kernel (GraphSum: algorithmic bytes per call over
-its HIP-event-timed duration on the engine's stream, peak 8 TB/s), "cpu_baseline" (the
-reference's own sequential code, oracle/_ref/libhpdga_ref.so, 2 epochs of the same workload
-on this host, 1 thread) and "parity" (those reference epochs' losses against a fresh engine's
-first epochs on the same data: the reddit-114M epoch checked end to end).
+A plain run does what the headline needs and no more: generate the data, build the engine,
+warm up, time the K steps, write `--dump-outputs DIR` if asked, print the line.  Everything
+else is behind `--full`:
+
+`--full` extra fields: "roofline" for the dominant kernel (GraphSum: algorithmic bytes per call
+over its HIP-event-timed duration on the engine's stream, peak 8 TB/s) and "mfma" (2 profiled
+epochs after the timed ones), `value_restricted` / `value_reference_order` (engines of their
+own), "cpu_baseline" (the reference's own sequential code, oracle/_ref/libhpdga_ref.so, 2
+epochs of the same workload on this host, 1 thread) and "parity" (those reference epochs'
+losses against a fresh engine's first epochs on the same data: the reddit-114M epoch checked
+end to end; at N > 1 the exchange against a one-GPU engine, before and after the timing).
+
+`--dump-outputs DIR`: after the timed steps, what the last timed step left for a caller, as
+float32 DIR/<name>.npy -- `epoch_line` (train_loss, train_acc, val_loss, val_acc: results()),
+`logits` (the output variable after its eval(2), every rank's rows in rank order), `w_first` and
+`w_last` (the first and the output layer's weights after its Adam step).  The data is seeded,
+so two builds run with the same arguments are compared array for array.
 """
 import argparse
 import contextlib
@@ -218,6 +230,11 @@ def main():
                          "the peers cannot be mapped) or RCCL reduce-scatters")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: print the --gpus N partition (per-rank nnz, exchange bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: roofline / mfma (2 profiled epochs), the secondary engines, the "
+                         "CPU baseline and parity (N > 1: the exchange against a one-GPU engine)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float32 DIR/<name>.npy")
     args = ap.parse_args()
     args.hidden = args.hidden.replace("+", ",")
     if args.dry_run:
@@ -440,6 +457,33 @@ def main():
         dist.broadcast_object_list(res, src=0)
         return res[0]
 
+    def dump_outputs(g, path, cap=64 << 20):
+        """--dump-outputs: what the last timed step left for a caller (see the module text);
+        rank 0 writes.  Arrays over the `cap` bytes in all are cut to a fixed seeded sample of
+        their values (the reddit line's 9.55 M logits, 38 MB, go out whole)."""
+        nv = g.num_vars()
+        if dist is not None:
+            logits = gather_rows(g, 1)
+        else:
+            logits = np.asarray(g.get_var(nv - 1), np.float32).ravel()
+        if rank != 0:
+            return
+        if logits.size == 0:
+            raise SystemExit("bench.py: --dump-outputs: a rank's logits could not be read")
+        arrays = {"epoch_line": np.asarray(g.results(1), np.float32).ravel(),
+                  "w_first": np.asarray(g.get_var(2), np.float32).ravel(),
+                  "w_last": np.asarray(g.get_var(nv - 2), np.float32).ravel(),
+                  "logits": logits}
+        os.makedirs(path, exist_ok=True)
+        left = cap - 4096  # the .npy headers
+        for i, (name, a) in enumerate(arrays.items()):
+            share = left // (len(arrays) - i) // 4  # values this array may take
+            if a.size > share:
+                keep = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+                a = a[keep]
+            left -= a.nbytes
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
     head_knobs = dict(kv.split("=") for kv in args.knob)
     # the headline knobs stay set through its timing and profiling (some are read per launch)
     head_ctx = contextlib.ExitStack()
@@ -468,7 +512,8 @@ def main():
             max_over_ranks(g.query("eval_ax_us") / 1000.0)
 
     parity_fresh = None
-    if world > 1 and not args.profile_only:
+    verify = world > 1 and args.full and not args.profile_only
+    if verify:
         parity_fresh = verify_fresh(g)
         pre_epochs = parity_fresh["epochs"]
         if not parity_fresh["pass"] and comm_kind[0] == "peer":
@@ -484,13 +529,15 @@ def main():
         # the peer exchange failed at run time on some rank (a wait that gave up)
         g, info, ax_ms = to_rccl(g, "peer exchange failed at run time")
         pre_epochs = 0
-        if world > 1 and not args.profile_only:
+        if verify:
             parity_fresh = verify_fresh(g)
             pre_epochs = parity_fresh["epochs"]
         elapsed, ok = timed(g, args.steps, args.warmup)
         if not ok:
             raise SystemExit("bench.py: the timed epochs failed on RCCL too")
     res = g.results(min(args.steps, 4))
+    if args.dump_outputs:
+        dump_outputs(g, args.dump_outputs)
 
     if args.profile_only:
         head_ctx.close()
@@ -498,34 +545,47 @@ def main():
             print(json.dumps({"elapsed_s": elapsed, "steps": args.steps}))
         return
 
-    # roofline of the dominant kernel: GraphSum, timed with HIP events on the engine stream
-    g.profile(True)
-    for _ in range(2):
-        g.epoch_async()
-    gs_ms, gs_calls, gs_bytes = g.profile_read()
-    mm_ms, mm_calls, mm_flops = g.profile_read_mm()
-    g.profile(False)
-    parity_after = None
-    if parity_fresh is not None:
-        parity_after = verify_after(g, pre_epochs + args.warmup + args.steps + 2)
+    roofline = mfma = parity_after = None
+    if args.full:
+        # roofline of the dominant kernel: GraphSum, timed with HIP events on the engine stream
+        g.profile(True)
+        for _ in range(2):
+            g.epoch_async()
+        gs_ms, gs_calls, gs_bytes = g.profile_read()
+        mm_ms, mm_calls, mm_flops = g.profile_read_mm()
+        g.profile(False)
+        if parity_fresh is not None:
+            parity_after = verify_after(g, pre_epochs + args.warmup + args.steps + 2)
+        avg_ms = gs_ms / max(gs_calls, 1)
+        bytes_per_call = gs_bytes / max(gs_calls, 1)
+        achieved = bytes_per_call / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        traffic = None
+        tpath = os.path.join(REPO, "profiles", "traffic_graphsum.json")
+        if os.path.exists(tpath) and world == 1:
+            try:
+                t = json.load(open(tpath))
+                # only PMC passes of the kernel sources this bench runs count; per workload and
+                # model (the 4-layer line: "reddit-114M hidden=128,128,128")
+                from stamp import graphsum_stamp
+                key = args.workload if hidden == (16,) else f"{args.workload} hidden={args.hidden}"
+                if not head_knobs and t.get("source_stamp") == graphsum_stamp():
+                    traffic = t.get(key)
+            except (OSError, ValueError):
+                traffic = None
+        roofline = {"kernel": "graphsum", "bound": "hbm", "achieved": achieved,
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic, "avg_call_ms": avg_ms,
+                    "algorithmic_bytes_per_call": bytes_per_call, "calls": gs_calls}
+        # the XW contractions (dense X W1, H W of the hidden layers and their gradients) on
+        # the fp32 MFMA kernels: flops over their event time, against the 157.3 TF fp32 peak
+        mfma = ({"kernels": "k_xstream_nn/tn, k_gemm_nn/tn (v_mfma_f32_16x16x4f32)",
+                 "achieved": mm_flops / (mm_ms * 1e-3) / 1e12, "peak": MFMA_F32_PEAK_TF,
+                 "unit": "TFLOP/s",
+                 "frac": mm_flops / (mm_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF,
+                 "ms_per_epoch": mm_ms / 2, "flops_per_epoch": mm_flops / 2,
+                 "calls": mm_calls} if mm_ms > 0 else None)
     head_ctx.close()
     g.close()
-    avg_ms = gs_ms / max(gs_calls, 1)
-    bytes_per_call = gs_bytes / max(gs_calls, 1)
-    achieved = bytes_per_call / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    traffic = None
-    tpath = os.path.join(REPO, "profiles", "traffic_graphsum.json")
-    if os.path.exists(tpath) and world == 1:
-        try:
-            t = json.load(open(tpath))
-            # only PMC passes of the kernel sources this bench runs count; per workload and
-            # model (the 4-layer line: "reddit-114M hidden=128,128,128")
-            from stamp import graphsum_stamp
-            key = args.workload if hidden == (16,) else f"{args.workload} hidden={args.hidden}"
-            if not head_knobs and t.get("source_stamp") == graphsum_stamp():
-                traffic = t.get(key)
-        except (OSError, ValueError):
-            traffic = None
 
     # the reference's 100-epoch run() pays the Â X precompute once: charged per epoch
     amortised = args.steps * ax_ms * 1e-3 / 100.0
@@ -556,18 +616,6 @@ def main():
         "eval_ax_build_ms": ax_ms,
         "eval_ax_amortised_ms_per_epoch": ax_ms / 100.0,
         "value_unamortised": args.steps / elapsed,
-        "roofline": {"kernel": "graphsum", "bound": "hbm", "achieved": achieved,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic, "avg_call_ms": avg_ms,
-                     "algorithmic_bytes_per_call": bytes_per_call, "calls": gs_calls},
-        # the XW contractions (dense X W1, H W of the hidden layers and their gradients) on
-        # the fp32 MFMA kernels: flops over their event time, against the 157.3 TF fp32 peak
-        "mfma": ({"kernels": "k_xstream_nn/tn, k_gemm_nn/tn (v_mfma_f32_16x16x4f32)",
-                  "achieved": mm_flops / (mm_ms * 1e-3) / 1e12, "peak": MFMA_F32_PEAK_TF,
-                  "unit": "TFLOP/s",
-                  "frac": mm_flops / (mm_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TF,
-                  "ms_per_epoch": mm_ms / 2, "flops_per_epoch": mm_flops / 2,
-                  "calls": mm_calls} if mm_ms > 0 else None),
         "last_epoch": ({"train_loss": float(res[-1, 0]), "train_acc": float(res[-1, 1]),
                         "val_loss": float(res[-1, 2]), "val_acc": float(res[-1, 3])}
                        if len(res) else None),
@@ -583,7 +631,9 @@ def main():
             raise SystemExit("bench.py: a secondary engine's epochs failed")
         return steps2 / el
 
-    if not args.no_extra and world == 1 and not args.edge_cut:
+    if args.full:
+        out["roofline"], out["mfma"] = roofline, mfma
+    if args.full and not args.no_extra and world == 1 and not args.edge_cut:
         # the diagnostic output-layer row restriction (round 1's headline): logits outside the
         # current split are not produced
         out["value_restricted"] = secondary({"split_rows": 1})
@@ -592,7 +642,9 @@ def main():
         out["value_reference_order"] = secondary(
             {"train_ahead": 0, "split_rows": 0, "split_cols": 0, "eval_ax": 0})
         params.reassociate_last = 1
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and hidden != (16,):
+    if not args.full:
+        pass
+    elif rank == 0 and world == 1 and not args.no_cpu_baseline and hidden != (16,):
         out["cpu_baseline"] = None  # the reference's sequential build is the 2-layer H = 16 GCN
     elif rank == 0 and world == 1 and not args.no_cpu_baseline:
         kind, times, ref_lines, ref_logits = cpu_baseline(ds, args.cpu_epochs)

@@ -32,7 +32,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for d in "${LIBS[@]}"; do
     tag=${d:-default}
     lib=${d:+parallel-gcn_amd/$d/libpgcn.so}
-    PGCN_LIB=$lib timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-extra ${BENCH_EXTRA:-} \
+    PGCN_LIB=$lib timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-extra ${BENCH_EXTRA:-} \
         > "gpurun_out/ab_${tag}_$r.json" 2> "gpurun_out/ab_${tag}_$r.err"
     rc=$?
     python3 -c "import json; d=json.load(open('gpurun_out/ab_${tag}_$r.json')); print('$tag', round(d['value'],1), 'eps gs_ms', round(d['roofline']['avg_call_ms'],4))" || { echo "$tag bench rc=$rc"; tail -5 "gpurun_out/ab_${tag}_$r.err"; exit 1; }

@@ -9,7 +9,8 @@
 #   pytest[:<pytest args>]     python -m pytest -m gpu -v <args, default tests> (no -x); '~' is
 #                              a space inside an argument (-k,a~or~b)
 #   smoke                      __graft_entry__.smoke()
-#   bench:<tag>[:<args>]       bench.py <args> -> <tag>.json (+ .err)
+#   bench:<tag>[:<args>]       bench.py <args> -> <tag>.json (+ .err); --full among the args for
+#                              the roofline, secondary, CPU-baseline and parity legs
 #   g2:<tag>[:<args>]          bench.py --gpus 2 on this one GPU (PGCN_BENCH_SHARE_GPU=1)
 #   rank[:<worlds>[,...]]      tools/rank_epoch.py (solo rank epochs, RANK_STEPS/RANK_WARMUP env)
 #   datasets                   tools/datasets_bench.py (cora, citeseer, pubmed_synth)

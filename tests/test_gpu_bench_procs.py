@@ -20,9 +20,9 @@ def test_bench_gpus2_shared_gpu():
     env = dict(os.environ, PGCN_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps",
-                        "3", "--warmup", "1", "--workload", "reddit-11.6M", "--no-cpu-baseline",
-                        "--no-extra"], cwd=REPO, env=env, capture_output=True, text=True,
-                       timeout=600)
+                        "3", "--warmup", "1", "--workload", "reddit-11.6M", "--full",
+                        "--no-cpu-baseline", "--no-extra"], cwd=REPO, env=env,
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 only
@@ -41,15 +41,15 @@ def test_bench_gpus2_shared_gpu():
 
 
 def test_bench_one_gpu_default_line():
-    """bench.py at N = 1 with its secondary measurements (the restricted-output and reference-
-    order engines) -- the driver's default invocation minus the CPU leg, on the small
-    reddit-11.6M workload: one JSON line with the contract's keys, the roofline object and the
+    """bench.py --full at N = 1 with its secondary measurements (the restricted-output and
+    reference-order engines) -- the full line minus the CPU leg, on the small reddit-11.6M
+    workload: one JSON line with the contract's keys, the roofline object and the
     secondary values."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup",
-                        "1", "--workload", "reddit-11.6M", "--no-cpu-baseline"], cwd=REPO, env=env,
-                       capture_output=True, text=True, timeout=600)
+                        "1", "--workload", "reddit-11.6M", "--full", "--no-cpu-baseline"],
+                       cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -60,3 +60,39 @@ def test_bench_one_gpu_default_line():
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["value"] > 0
     assert out["roofline"]["bound"] == "hbm" and 0 < out["roofline"]["frac"] < 1
     assert out["value_restricted"] > 0 and out["value_reference_order"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the measurements that take runs
+    of their own, and --dump-outputs writes the last timed step's outputs: float32 arrays, the
+    epoch line equal to the line's last_epoch, every row's logits, both weight matrices, finite
+    and within the 64 MB allowance."""
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps",
+                        "3", "--warmup", "1", "--workload", "reddit-11.6M", "--dump-outputs",
+                        str(out_dir)], cwd=REPO, env=env, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for k in ("roofline", "mfma", "value_restricted", "value_reference_order", "cpu_baseline",
+              "parity"):
+        assert k not in out, k
+    got = {f.name: np.load(f) for f in out_dir.iterdir()}
+    assert sorted(got) == ["epoch_line.npy", "logits.npy", "w_first.npy", "w_last.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["logits.npy"].size == 232965 * 41
+    assert got["w_first.npy"].size == 602 * 16 and got["w_last.npy"].size == 16 * 41
+    last = out["last_epoch"]
+    assert got["epoch_line.npy"].tolist() == [last["train_loss"], last["train_acc"],
+                                             last["val_loss"], last["val_acc"]]
+    assert got["logits.npy"].std() > 0 and got["w_first.npy"].std() > 0

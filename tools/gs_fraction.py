@@ -1,5 +1,5 @@
 """GraphSum roofline fraction two ways from ONE bench run (diagnostic tool, host side):
-rocprofv3 --kernel-trace of `bench.py` (not --profile-only) gives the kernel durations of the
+rocprofv3 --kernel-trace of `bench.py --full` (not --profile-only) gives the kernel durations of the
 bench's two HIP-event-profiled epochs, the last `calls` GraphSum calls (prescale when launched +
 k_graphsum_ring + k_gs_lds_combine, the launches the events bracket); the bench's JSON line
 gives the event-timed figure of the same calls.  Prints one JSON object with both fractions.
