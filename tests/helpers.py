@@ -226,6 +226,47 @@ def parse_line(line):
     return out
 
 
+# --------------------------------------------------------------------------- graph builders
+def random_graph(n, avg_deg, seed, hubs=0, hub_deg=0, empty_rows=0):
+    """Symmetric random graph in the hpdga CSR form (self loop first, duplicates allowed).
+    empty_rows = k > 0: every k-th row (i % k == k - 1) loses all its slots, its self loop
+    included (the pattern is then no longer symmetric: for pgcn_graph_create_values)."""
+    rng = np.random.default_rng(seed)
+    m = n * avg_deg // 2
+    u = rng.integers(0, n, m)
+    v = rng.integers(0, n, m)
+    if hubs:
+        hu = rng.integers(0, n, hubs)
+        extra_u = np.repeat(hu, hub_deg)
+        extra_v = rng.integers(0, n, hubs * hub_deg)
+        u, v = np.concatenate([u, extra_u]), np.concatenate([v, extra_v])
+    keep = u != v
+    u, v = u[keep], v[keep]
+    src = np.concatenate([u, v, np.arange(n)])
+    dst = np.concatenate([v, u, np.arange(n)])
+    if empty_rows:
+        keep = src % empty_rows != empty_rows - 1
+        src, dst = src[keep], dst[keep]
+    order = np.lexsort((dst, src != dst, src))  # self loop first within a row
+    src, dst = src[order], dst[order]
+    indptr = np.zeros(n + 1, np.int64)
+    np.add.at(indptr, src + 1, 1)
+    indptr = np.cumsum(indptr).astype(np.int32)
+    return indptr, dst.astype(np.int32)
+
+
+def csr_reference(indptr, indices, vals, x, n_cols=None):
+    """(A x, |A| |x|) in float64 through scipy's CSR product (duplicates add up): GraphSum's
+    reference and the scale of its fp32 reordering error, per output element."""
+    import scipy.sparse as sps
+    shape = (len(indptr) - 1, x.shape[0] if n_cols is None else n_cols)
+    v64 = np.asarray(vals, np.float64)
+    x64 = np.asarray(x, np.float64)
+    a = sps.csr_matrix((v64, indices, indptr), shape=shape)
+    b = sps.csr_matrix((np.abs(v64), indices, indptr), shape=shape)
+    return a @ x64, b @ np.abs(x64)
+
+
 # --------------------------------------------------------------------------- engine knobs
 # pgcn_debug_set defaults of the engine (include/pgcn.h; parallel-gcn_amd/csrc/host/gcn.cpp)
 ENGINE_DEFAULTS = {"train_ahead": 1, "split_rows": 0, "split_cols": 1, "eval_ax": 1,

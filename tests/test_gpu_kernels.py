@@ -26,27 +26,7 @@ def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def random_graph(n, avg_deg, seed, hubs=0, hub_deg=0, empty_rows=0):
-    """Symmetric random graph in the hpdga CSR form (self loop first, duplicates allowed)."""
-    rng = np.random.default_rng(seed)
-    m = n * avg_deg // 2
-    u = rng.integers(0, n, m)
-    v = rng.integers(0, n, m)
-    if hubs:
-        hu = rng.integers(0, n, hubs)
-        extra_u = np.repeat(hu, hub_deg)
-        extra_v = rng.integers(0, n, hubs * hub_deg)
-        u, v = np.concatenate([u, extra_u]), np.concatenate([v, extra_v])
-    keep = u != v
-    u, v = u[keep], v[keep]
-    src = np.concatenate([u, v, np.arange(n)])
-    dst = np.concatenate([v, u, np.arange(n)])
-    order = np.lexsort((dst, src != dst, src))  # self loop first within a row
-    src, dst = src[order], dst[order]
-    indptr = np.zeros(n + 1, np.int64)
-    np.add.at(indptr, src + 1, 1)
-    indptr = np.cumsum(indptr).astype(np.int32)
-    return indptr, dst.astype(np.int32)
+random_graph = helpers.random_graph
 
 
 def _merge_graphs(ip1, ix1, ip2, ix2):
@@ -425,6 +405,46 @@ def test_dropout_apply(pgcn):
     pgcn.lib.pgcn_dropout_apply(vp(x), n, vp(words), 2.0, stream())
     torch.cuda.synchronize()
     np.testing.assert_array_equal(x.cpu().numpy(), ref.astype(np.float32))
+
+
+def test_relu_fwd_bwd(pgcn):
+    """pgcn_relu_fwd / pgcn_relu_bwd bit for bit over normals, +-0, +-denormals, +-inf and NaN:
+    x <- where(x > 0, x, +0) and mask <- x > 0 when training (NaN and -0 give +0 and mask 0);
+    training 0 leaves the mask buffer alone; the backward zeroes exactly the entries whose mask
+    is 0; nothing past n is written."""
+    n, guard = 100_003, 64
+    rng = np.random.default_rng(11)
+    x = rng.standard_normal(n + guard).astype(np.float32)
+    special = np.array([0.0, -0.0, 1e-45, -1e-45, 1.1754942e-38, -1.1754942e-38, 3e-39, -3e-39,
+                        np.inf, -np.inf, np.nan, -np.nan], np.float32)
+    x[rng.choice(n, 40 * len(special), replace=False)] = np.tile(special, 40)
+    x[:len(special)] = special
+    x[n - len(special):n] = special  # the last block's tail
+    keep = x[:n] > 0
+    want = x.copy()
+    want[:n] = np.where(keep, x[:n], np.float32(0.0))
+    for training in (1, 0):
+        dx = torch.from_numpy(x).to(DEV)
+        mask = torch.full((n + guard,), 0xAB, dtype=torch.uint8, device=DEV)
+        pgcn.check(pgcn.lib.pgcn_relu_fwd(vp(dx), n, vp(mask), training, stream()), "relu_fwd")
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(dx.cpu().numpy().view(np.uint32), want.view(np.uint32))
+        m = mask.cpu().numpy()
+        if training:
+            np.testing.assert_array_equal(m[:n], keep.astype(np.uint8))
+            np.testing.assert_array_equal(m[n:], 0xAB)
+        else:
+            np.testing.assert_array_equal(m, 0xAB)
+    g = rng.standard_normal(n + guard).astype(np.float32)
+    g[rng.choice(n, 4 * len(special), replace=False)] = np.tile(special, 4)
+    hm = np.full(n + guard, 0, np.uint8)  # zero past n: a write there would show
+    hm[:n] = keep
+    want_g = g.copy()
+    want_g[:n][~keep] = np.float32(0.0)
+    dg, dm = torch.from_numpy(g).to(DEV), torch.from_numpy(hm).to(DEV)
+    pgcn.check(pgcn.lib.pgcn_relu_bwd(vp(dg), n, vp(dm), stream()), "relu_bwd")
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(dg.cpu().numpy().view(np.uint32), want_g.view(np.uint32))
 
 
 def mask_window(mask, base, M, K):
