@@ -157,6 +157,23 @@ int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, i
 int pgcn_finalize(const float *partials, int n_blocks, int count, const float *w_l2,
                   long long n_l2, float weight_decay, float *out4, void *stream);
 
+/* --- per-row prediction and confusion matrix (new: the reference keeps nothing per node) - */
+/* cls[i] = lowest index of the row's maximum over columns [0,c); conf[i] = its softmax
+ * probability; probs (may be NULL) [n][ld_probs] = the whole softmax row (columns
+ * [c, round_up4(c)) are written as zero, further padding is left alone).  The softmax is
+ * made of pgcn_xent_fwd's pieces (max shift, exp, summation order, rounded quotient) with the
+ * shift's rounding corrected: within (c + 3) 2^-24 relative of the exact one.  Columns >= c of logits are never read into the result (they
+ * may hold anything, NaN included).  logits is not modified.  1 <= c <= 128, ld and ld_probs
+ * multiples of 4 and >= c.  cls/conf may be NULL.  PGCN_PREDICT_ROWS rows per workgroup. */
+#define PGCN_PREDICT_ROWS 64
+int pgcn_predict_rows(const float *logits, int ld, int n, int c, int *cls, float *conf,
+                      float *probs, int ld_probs, void *stream);
+/* counts[t*c + p] = rows with truth[i] == t >= 0 and cls[i] == p (truth < 0: skipped, the
+ * pgcn_xent_fwd convention; labels or classes outside [0,c) are skipped too).  The call zeroes
+ * counts first.  Integer adds only: the result does not depend on the order. */
+int pgcn_confusion(const int *cls, const int *truth, int n, int c, unsigned int *counts,
+                   void *stream);
+
 /* --- Adam (src/optim.cu:42-95; hpdga optim.cpp:23-35) ---------------------------------- */
 int pgcn_adam(float *w, const float *g, float *m, float *v, long long n, float step_size,
               float beta1, float beta2, float eps, float weight_decay, int decay, void *stream);
@@ -246,6 +263,7 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "comm_bytes" (collectives enqueued since creation and the bytes this rank sends in them,
  * ring algorithm: a reduce-scatter (W-1)/W of its send buffer, an all-reduce twice that), "reassociated",
  * "graph_symmetric", "graphsum_lds" (width-16 GraphSums take the LDS kernel), "epochs",
+ * "adam_steps" (optimizer steps taken; 0 again after a weights-only load),
  * "eval_ax_us" (device time of the Â X precompute at engine build, µs; 0 when not used).
  * Returns the value (>= 0) or PGCN_E_INVALID for an unknown key. */
 long long pgcn_gcn_query(pgcn_gcn *g, const char *key);
@@ -268,6 +286,40 @@ int pgcn_gcn_run(pgcn_gcn *g, int verbose);
  * ("split_rows" on): their rows outside the split are stale. */
 long long pgcn_gcn_get_var(pgcn_gcn *g, int idx, int which, float *host_dst);
 int pgcn_gcn_num_vars(pgcn_gcn *g);
+/* Weights only (idx must be a weight variable, which == 0), in get_var's layout and count;
+ * anything else PGCN_E_INVALID.  Invalidates every product computed ahead from the old
+ * weights.  Edge-cut: the caller sets the same values on every rank. */
+int pgcn_gcn_set_var(pgcn_gcn *g, int idx, int which, const float *host_src, long long count);
+/* Whole training state to one file: weights, Adam m/v and step count, epoch count, dropout
+ * stream position, the results history that pgcn_gcn_results would return, and what
+ * identifies the model (layer dims, num_nodes, seed, dropouts).  Syncs first.  Written to
+ * path + ".tmp" and renamed.  Every rank of an edge-cut engine writes the same bytes; one of
+ * them saving is enough.  Format: INTEGRATION.md. */
+int pgcn_gcn_save(pgcn_gcn *g, const char *path);
+#define PGCN_LOAD_WEIGHTS_ONLY 1
+/* flags 0: resume -- after it the engine continues exactly as the engine that saved would
+ * have (same masks, same Adam steps, same results rows), whether `g` is fresh or has trained
+ * past or short of the save point, on one GPU or as edge-cut ranks (every rank loads).
+ * PGCN_LOAD_WEIGHTS_ONLY: weights from the file, Adam m/v and step count reset to zero, epoch
+ * count, results and dropout position kept.
+ * PGCN_E_INVALID: the file is for another model (dims, num_nodes; for flags 0 also seed and
+ * dropouts).  PGCN_E_IO: missing, truncated, corrupted or unknown version.  On any error
+ * the engine is untouched. */
+int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags);
+/* Host-only look at a checkpoint file (no device, no engine): validates it as pgcn_gcn_load
+ * does and fills info[8] = {version, n_layers, num_nodes, input_dim, output_dim, adam_steps,
+ * epochs, weight count}.  PGCN_E_IO as pgcn_gcn_load. */
+int pgcn_checkpoint_info(const char *path, long long info[8]);
+/* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
+ * "split_rows" says), then pgcn_predict_rows.  Host outputs, any may be NULL; probs is
+ * [rows][output_dim] dense.  Returns the row count (node_range's) or a status < 0.  Leaves
+ * the training state exactly as it was: no results slot written, epoch count, Adam and
+ * dropout position unchanged, and training continued after it is bit-identical to training
+ * without it.  Edge-cut: a collective, every rank calls it. */
+long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs);
+/* predict + pgcn_confusion against split's labels: counts[c*c], this rank's rows (the caller
+ * adds the ranks' matrices, as it concatenates get_var's rows). */
+int pgcn_gcn_confusion(pgcn_gcn *g, int split, long long *counts);
 /* per-call device timing of the GraphSum kernels (enable before the timed region) */
 int pgcn_gcn_profile(pgcn_gcn *g, int enable);
 int pgcn_gcn_profile_read(pgcn_gcn *g, double *graphsum_ms_total, long long *graphsum_calls,

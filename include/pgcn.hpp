@@ -333,6 +333,18 @@ class GCN {
   void run();
   std::pair<real, real> train_epoch();
   std::pair<real, real> eval(natural current_split);
+  // New with the engine (the reference keeps no model and predicts nothing per node); the
+  // contracts are those of pgcn_gcn_set_var / _save / _load / _predict / _confusion in pgcn.h.
+  // They throw std::runtime_error where the C entries return a status.
+  void set_var(natural idx, const std::vector<real> &values);  // a weight variable's data
+  void save(const std::string &path);
+  void load(const std::string &path, bool weights_only = false);
+  // every node's class (lowest index of the maximum), its softmax probability and, when
+  // probs is not null, the softmax rows [num_nodes][output_dim]
+  void predict(std::vector<integer> *cls, std::vector<real> *conf,
+               std::vector<real> *probs = nullptr);
+  // counts[t * output_dim + p]: nodes of `split` with label t predicted p
+  std::vector<long long> confusion(natural split);
 
  private:
   std::unique_ptr<pgcn::GCN> impl_;

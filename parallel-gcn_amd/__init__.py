@@ -25,6 +25,8 @@ PGCN_E_IO = -3
 PGCN_E_COMM = -4
 PGCN_E_NODEVICE = -5
 MAX_LAYERS = 16
+PGCN_LOAD_WEIGHTS_ONLY = 1
+PREDICT_ROWS = 64  # PGCN_PREDICT_ROWS: rows per workgroup of pgcn_predict_rows
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is not built: run `make -C parallel-gcn_amd` "
@@ -128,6 +130,15 @@ _sig("pgcn_gcn_results", c_int, c_void_p, c_int, P(c_float))
 _sig("pgcn_gcn_run", c_int, c_void_p, c_int)
 _sig("pgcn_gcn_get_var", c_ll, c_void_p, c_int, c_int, P(c_float))
 _sig("pgcn_gcn_num_vars", c_int, c_void_p)
+_sig("pgcn_gcn_set_var", c_int, c_void_p, c_int, c_int, c_void_p, c_ll)
+_sig("pgcn_gcn_save", c_int, c_void_p, ctypes.c_char_p)
+_sig("pgcn_gcn_load", c_int, c_void_p, ctypes.c_char_p, c_int)
+_sig("pgcn_checkpoint_info", c_int, ctypes.c_char_p, P(c_ll))
+_sig("pgcn_gcn_predict", c_ll, c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+     c_int, c_void_p)
+_sig("pgcn_confusion", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p)
 _sig("pgcn_gcn_profile", c_int, c_void_p, c_int)
 _sig("pgcn_gcn_profile_read", c_int, c_void_p, P(c_double), P(c_ll), P(c_double))
 _sig("pgcn_gcn_profile_read_mm", c_int, c_void_p, P(c_double), P(c_ll), P(c_double))
@@ -365,6 +376,40 @@ class GCN:
             lib.pgcn_gcn_get_var(self._h, idx, which, out.ctypes.data_as(P(c_float)))
         return out
 
+    def set_var(self, idx, values, which=0):
+        """Writes a weight variable (get_var's layout and count); anything else is refused."""
+        a = np.ascontiguousarray(values, np.float32).ravel()
+        check(lib.pgcn_gcn_set_var(self._h, idx, which, _ptr(a), a.size), "set_var")
+
+    def save(self, path):
+        """The whole training state to one checkpoint file (pgcn_gcn_save)."""
+        check(lib.pgcn_gcn_save(self._h, os.fsencode(path)), f"save {path}")
+
+    def load(self, path, weights_only=False):
+        """Resume from a checkpoint (bit-exact continuation), or take only its weights."""
+        check(lib.pgcn_gcn_load(self._h, os.fsencode(path),
+                                PGCN_LOAD_WEIGHTS_ONLY if weights_only else 0), f"load {path}")
+
+    def predict(self, probs=False):
+        """(classes int32 [rows], confidences float32 [rows]) of this rank's rows from an
+        eval-mode forward; with probs=True also the softmax rows [rows, output_dim]."""
+        a, b = self.node_range()
+        n, c = b - a, self.params.output_dim
+        cls, conf = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        pr = np.zeros((n, c), np.float32) if probs else None
+        got = lib.pgcn_gcn_predict(self._h, _ptr(cls), _ptr(conf), _ptr(pr) if probs else None)
+        if got < 0:
+            raise PgcnError(int(got), "predict")
+        assert got == n
+        return (cls, conf, pr) if probs else (cls, conf)
+
+    def confusion(self, split):
+        """counts[t, p]: this rank's rows of `split` with label t predicted p (int64)."""
+        c = self.params.output_dim
+        out = np.zeros((c, c), np.int64)
+        check(lib.pgcn_gcn_confusion(self._h, split, _ptr(out)), "confusion")
+        return out
+
     def profile(self, on):
         check(lib.pgcn_gcn_profile(self._h, 1 if on else 0), "profile")
 
@@ -383,7 +428,7 @@ class GCN:
 
     def query(self, key):
         """Engine facts: world, rank, comm (0 none / 1 RCCL / 2 loopback), reassociated,
-        graph_symmetric, graphsum_lds, epochs."""
+        graph_symmetric, graphsum_lds, epochs, adam_steps."""
         v = lib.pgcn_gcn_query(self._h, key.encode())
         if v < 0:
             raise PgcnError(int(v), f"query {key}")
@@ -475,6 +520,16 @@ def run_ranks(world, fn):
     return out
 
 
+def checkpoint_info(path):
+    """Host-only look at a checkpoint file: dict of version, n_layers, num_nodes, input_dim,
+    output_dim, adam_steps, epochs, weights.  PgcnError(PGCN_E_IO) for an invalid file."""
+    info = (c_ll * 8)()
+    check(lib.pgcn_checkpoint_info(os.fsencode(path), info), f"checkpoint_info {path}")
+    keys = ("version", "n_layers", "num_nodes", "input_dim", "output_dim", "adam_steps", "epochs",
+            "weights")
+    return dict(zip(keys, (int(x) for x in info)))
+
+
 def comm_unique_id():
     buf = ctypes.create_string_buffer(128)
     check(lib.pgcn_comm_unique_id(buf), "comm_unique_id")
@@ -556,6 +611,8 @@ EXPORTED = [
     "pgcn_gcn_create_loopback", "pgcn_gcn_query", "pgcn_gcn_destroy", "pgcn_gcn_train_epoch", "pgcn_gcn_eval",
     "pgcn_gcn_epoch_async", "pgcn_gcn_sync", "pgcn_gcn_results", "pgcn_gcn_run",
     "pgcn_gcn_get_var", "pgcn_gcn_num_vars", "pgcn_gcn_profile", "pgcn_gcn_profile_read",
+    "pgcn_gcn_set_var", "pgcn_gcn_save", "pgcn_gcn_load", "pgcn_checkpoint_info",
+    "pgcn_gcn_predict", "pgcn_gcn_confusion", "pgcn_predict_rows", "pgcn_confusion",
     "pgcn_gcn_profile_read_mm",
     "pgcn_gcn_node_range", "pgcn_dataset_load", "pgcn_dataset_load_cached", "pgcn_dataset_save",
     "pgcn_dataset_load_binary", "pgcn_dataset_binarize", "pgcn_dataset_synthetic",

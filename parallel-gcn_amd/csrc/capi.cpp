@@ -5,6 +5,7 @@
 
 #include "../../include/pgcn.h"
 #include "common.hpp"
+#include "host/checkpoint.hpp"
 #include "host/comm.hpp"
 #include "host/data.hpp"
 #include "host/gcn.hpp"
@@ -134,7 +135,7 @@ const char *pgcn_status_string(int s) {
   }
 }
 
-int pgcn_version(void) { return 100; }
+int pgcn_version(void) { return 110; }
 
 // ---------------------------------------------------------------- graph + kernels
 int pgcn_graph_create(int n, const int *indptr, const int *indices, pgcn_graph **out) {
@@ -401,6 +402,24 @@ int pgcn_finalize(const float *partials, int n_blocks, int count, const float *w
   });
 }
 
+int pgcn_predict_rows(const float *logits, int ld, int n, int c, int *cls, float *conf,
+                      float *probs, int ld_probs, void *stream) {
+  return guarded([&] {
+    check_device();
+    launch_predict_rows(logits, ld, n, c, cls, conf, probs, ld_probs, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_confusion(const int *cls, const int *truth, int n, int c, unsigned int *counts,
+                   void *stream) {
+  return guarded([&] {
+    check_device();
+    launch_confusion(cls, truth, n, c, counts, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_adam(float *w, const float *g, float *m, float *v, long long n, float step_size,
               float beta1, float beta2, float eps, float weight_decay, int decay, void *stream) {
   return guarded([&] {
@@ -553,6 +572,7 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
   if (!std::strcmp(key, "epochs")) return e.epochs_run();
+  if (!std::strcmp(key, "adam_steps")) return e.adam_steps();
   if (!std::strcmp(key, "eval_ax_us")) return (long long)(e.eval_ax_build_ms() * 1000.0f);
   return PGCN_E_INVALID;
 }
@@ -607,6 +627,52 @@ long long pgcn_gcn_get_var(pgcn_gcn *g, int idx, int which, float *dst) {
   return st == PGCN_OK ? n : st;
 }
 int pgcn_gcn_num_vars(pgcn_gcn *g) { return g->g->num_vars(); }
+int pgcn_gcn_set_var(pgcn_gcn *g, int idx, int which, const float *src, long long count) {
+  return guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_set_var: null engine");
+    g->g->set_var(idx, which, src, count);
+  });
+}
+int pgcn_gcn_save(pgcn_gcn *g, const char *path) {
+  return guarded([&] {
+    PGCN_CHECK(g && path, PGCN_E_INVALID, "gcn_save args");
+    g->g->save(path);
+  });
+}
+int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags) {
+  return guarded([&] {
+    PGCN_CHECK(g && path, PGCN_E_INVALID, "gcn_load args");
+    g->g->load(path, flags);
+  });
+}
+int pgcn_checkpoint_info(const char *path, long long info[8]) {
+  return guarded([&] {
+    PGCN_CHECK(path && info, PGCN_E_INVALID, "checkpoint_info args");
+    const Checkpoint ck = read_checkpoint(path);
+    info[0] = kCheckpointVersion;
+    info[1] = ck.n_layers;
+    info[2] = ck.num_nodes;
+    info[3] = ck.dims.front();
+    info[4] = ck.dims.back();
+    info[5] = ck.adam_steps;
+    info[6] = ck.epochs;
+    info[7] = (long long)ck.w.size();
+  });
+}
+long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs) {
+  long long n = -1;
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_predict: null engine");
+    n = g->g->predict(cls, conf, probs);
+  });
+  return st == PGCN_OK ? n : st;
+}
+int pgcn_gcn_confusion(pgcn_gcn *g, int split, long long *counts) {
+  return guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_confusion: null engine");
+    g->g->confusion(split, counts);
+  });
+}
 int pgcn_gcn_profile(pgcn_gcn *g, int enable) {
   return guarded([&] { g->g->set_profile(enable != 0); });
 }

@@ -703,5 +703,28 @@ void GCN::run() {
 std::pair<real, real> GCN::train_epoch() { return impl_->train_epoch(); }
 std::pair<real, real> GCN::eval(natural current_split) { return impl_->eval((int)current_split); }
 
+void GCN::set_var(natural idx, const std::vector<real> &values) {
+  impl_->set_var((int)idx, 0, values.data(), (long long)values.size());
+}
+void GCN::save(const std::string &path) { impl_->save(path); }
+void GCN::load(const std::string &path, bool weights_only) {
+  impl_->load(path, weights_only ? PGCN_LOAD_WEIGHTS_ONLY : 0);
+}
+void GCN::predict(std::vector<integer> *cls, std::vector<real> *conf, std::vector<real> *probs) {
+  const size_t n = (size_t)(impl_->partition().last() - impl_->partition().first());
+  const size_t c = (size_t)impl_->get_params().output_dim;
+  if (cls) cls->resize(n);
+  if (conf) conf->resize(n);
+  if (probs) probs->resize(n * c);
+  impl_->predict(cls ? cls->data() : nullptr, conf ? conf->data() : nullptr,
+                 probs ? probs->data() : nullptr);
+}
+std::vector<long long> GCN::confusion(natural split) {
+  const size_t c = (size_t)impl_->get_params().output_dim;
+  std::vector<long long> counts(c * c);
+  impl_->confusion((int)split, counts.data());
+  return counts;
+}
+
 }  // namespace api
 }  // namespace pgcn

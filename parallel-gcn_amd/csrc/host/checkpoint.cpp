@@ -1,0 +1,118 @@
+// parallel-gcn_amd/csrc/host/checkpoint.cpp -- see checkpoint.hpp for the format.
+#include "checkpoint.hpp"
+
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+
+#include "../common.hpp"
+#include "data.hpp"
+
+namespace pgcn {
+
+namespace {
+constexpr char kCkMagic[8] = {'P', 'G', 'C', 'N', 'C', 'K', '0', '1'};
+
+struct CkHeader {
+  char magic[8];
+  uint32_t version, n_layers;
+  int64_t num_nodes;
+  int32_t dims[18];
+  float dropouts[16];
+  uint32_t seed, reserved;
+  int64_t adam_steps, draw_epochs, epochs, n_results, n_weights;
+  uint64_t checksum;
+};
+static_assert(sizeof(CkHeader) == 216, "checkpoint header layout");
+
+uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
+  uint64_t x = fnv1a(kFnvBasis, &h, offsetof(CkHeader, checksum));
+  for (const auto *vec : {&ck.results, &ck.w, &ck.m, &ck.v})
+    x = fnv1a(x, vec->data(), vec->size() * sizeof(float));
+  return x;
+}
+
+bool write_floats(std::FILE *f, const std::vector<float> &v) {
+  return v.empty() || std::fwrite(v.data(), sizeof(float), v.size(), f) == v.size();
+}
+
+bool read_floats(std::FILE *f, std::vector<float> &v, long long n) {
+  v.resize((size_t)n);
+  return n == 0 || std::fread(v.data(), sizeof(float), (size_t)n, f) == (size_t)n;
+}
+
+long long weight_count(const int32_t *dims, int n_layers) {
+  long long n = 0;
+  for (int l = 0; l < n_layers; l++) n += (long long)dims[l] * dims[l + 1];
+  return n;
+}
+}  // namespace
+
+void write_checkpoint(const std::string &path, const Checkpoint &ck) {
+  const int L = ck.n_layers;
+  PGCN_CHECK(L >= 2 && L <= PGCN_MAX_LAYERS && (int)ck.dims.size() == L + 1 &&
+                 (int)ck.dropouts.size() == L && ck.results.size() % 4 == 0 &&
+                 ck.results.size() / 4 <= (size_t)kCheckpointMaxResults &&
+                 ck.m.size() == ck.w.size() && ck.v.size() == ck.w.size(),
+             PGCN_E_INVALID, "checkpoint: inconsistent state");
+  CkHeader h{};
+  std::memcpy(h.magic, kCkMagic, 8);
+  h.version = kCheckpointVersion;
+  h.n_layers = (uint32_t)L;
+  h.num_nodes = ck.num_nodes;
+  for (int l = 0; l <= L; l++) h.dims[l] = ck.dims[(size_t)l];
+  for (int l = 0; l < L; l++) h.dropouts[l] = ck.dropouts[(size_t)l];
+  h.seed = ck.seed;
+  h.adam_steps = ck.adam_steps;
+  h.draw_epochs = ck.draw_epochs;
+  h.epochs = ck.epochs;
+  h.n_results = (int64_t)(ck.results.size() / 4);
+  h.n_weights = (int64_t)ck.w.size();
+  PGCN_CHECK(h.n_weights == weight_count(h.dims, L), PGCN_E_INVALID,
+             "checkpoint: weight count does not match the layer dims");
+  h.checksum = ck_hash(h, ck);
+  const std::string tmp = path + ".tmp";
+  std::FILE *f = std::fopen(tmp.c_str(), "wb");
+  if (!f) throw Error(PGCN_E_IO, "checkpoint: cannot write " + tmp);
+  bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1 && write_floats(f, ck.results) &&
+            write_floats(f, ck.w) && write_floats(f, ck.m) && write_floats(f, ck.v);
+  ok = (std::fclose(f) == 0) && ok;
+  if (ok) ok = std::rename(tmp.c_str(), path.c_str()) == 0;  // readers never see a partial file
+  if (!ok) {
+    std::remove(tmp.c_str());
+    throw Error(PGCN_E_IO, "checkpoint: cannot write " + path);
+  }
+}
+
+Checkpoint read_checkpoint(const std::string &path) {
+  std::FILE *f = std::fopen(path.c_str(), "rb");
+  if (!f) throw Error(PGCN_E_IO, "checkpoint: cannot open " + path);
+  CkHeader h{};
+  Checkpoint ck;
+  bool ok = std::fread(&h, sizeof(h), 1, f) == 1 && std::memcmp(h.magic, kCkMagic, 8) == 0 &&
+            h.version == (uint32_t)kCheckpointVersion && h.n_layers >= 2 &&
+            h.n_layers <= PGCN_MAX_LAYERS && h.num_nodes > 0 && h.reserved == 0;
+  const int L = ok ? (int)h.n_layers : 0;
+  for (int l = 0; ok && l <= L; l++) ok = h.dims[l] > 0 && h.dims[l] <= (1 << 24);
+  ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
+       h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
+       h.n_weights == weight_count(h.dims, L) && h.n_weights < (1LL << 31);
+  ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
+       read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);
+  ok = ok && std::fgetc(f) == EOF;  // nothing trailing
+  std::fclose(f);
+  if (!ok || ck_hash(h, ck) != h.checksum)
+    throw Error(PGCN_E_IO, "checkpoint: not a valid checkpoint (truncated, corrupted or another "
+                           "version): " + path);
+  ck.n_layers = L;
+  ck.num_nodes = h.num_nodes;
+  ck.dims.assign(h.dims, h.dims + L + 1);
+  ck.dropouts.assign(h.dropouts, h.dropouts + L);
+  ck.seed = h.seed;
+  ck.adam_steps = h.adam_steps;
+  ck.draw_epochs = h.draw_epochs;
+  ck.epochs = h.epochs;
+  return ck;
+}
+
+}  // namespace pgcn

@@ -1,0 +1,43 @@
+// parallel-gcn_amd/csrc/host/checkpoint.hpp -- the training checkpoint file (host only).
+//
+// One little-endian file: a fixed 216-byte header, then the payload.
+//   header   char magic[8] "PGCNCK01"; u32 version (1); u32 n_layers; i64 num_nodes;
+//            i32 dims[18] (input, hidden..., output; the rest 0); f32 dropouts[16];
+//            u32 seed; u32 reserved (0); i64 adam_steps; i64 draw_epochs; i64 epochs;
+//            i64 n_results; i64 n_weights; u64 checksum
+//   payload  f32 results[n_results][4]; f32 weights[n_weights]; f32 m[n_weights];
+//            f32 v[n_weights]                     (tensors in layer order, row-major)
+// checksum = FNV-1a 64 of the header's bytes before it, continued over the payload.
+// draw_epochs counts the training forwards since the engine was built: the dropout stream
+// stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
+// stored and the file does not depend on the world size.  Nothing newer than the reference:
+// it keeps no model (src/gcn.cu:347-436 prints a test accuracy and exits).
+#pragma once
+#include <string>
+#include <vector>
+
+namespace pgcn {
+
+constexpr int kCheckpointVersion = 1;
+constexpr int kCheckpointMaxResults = 1024;  // the engine's results ring
+
+struct Checkpoint {
+  int n_layers = 0;
+  long long num_nodes = 0;
+  std::vector<int> dims;        // n_layers + 1
+  std::vector<float> dropouts;  // n_layers
+  unsigned seed = 0;
+  long long adam_steps = 0, draw_epochs = 0, epochs = 0;
+  std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
+  std::vector<float> w, m, v;  // every weight tensor in layer order
+};
+
+// Writes path + ".tmp", then renames it over path (a run killed in mid-save keeps the
+// previous file).  Error(PGCN_E_IO) when the file cannot be written.
+void write_checkpoint(const std::string &path, const Checkpoint &ck);
+// The whole file, validated (magic, version, counts against the dims, exact length, checksum)
+// before anything is returned.  Error(PGCN_E_IO): missing, truncated, corrupted, trailing
+// bytes or an unknown version.
+Checkpoint read_checkpoint(const std::string &path);
+
+}  // namespace pgcn

@@ -403,6 +403,12 @@ void make_synthetic(GCNData *d, int n, int f, int c, long long undirected_edges,
 // ------------------------------------------------------------------------------------------
 // binary dataset cache
 // ------------------------------------------------------------------------------------------
+uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
+  const unsigned char *b = static_cast<const unsigned char *>(p);
+  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
+  return h;
+}
+
 namespace {
 constexpr char kMagic[8] = {'P', 'G', 'C', 'N', 'D', 'S', '0', '1'};
 
@@ -413,19 +419,13 @@ struct BinHeader {
   unsigned long long checksum;
 };
 
-uint64_t fnv1a(uint64_t h, const void *p, size_t n) {
-  const unsigned char *b = static_cast<const unsigned char *>(p);
-  for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
-  return h;
-}
-
 template <class T>
 uint64_t hash_vec(uint64_t h, const std::vector<T> &v) {
   return fnv1a(h, v.data(), v.size() * sizeof(T));
 }
 
 uint64_t payload_hash(const GCNData &d) {
-  uint64_t h = 14695981039346656037ull;
+  uint64_t h = kFnvBasis;
   h = hash_vec(h, d.graph.indptr);
   h = hash_vec(h, d.graph.indices);
   h = hash_vec(h, d.feature_index.indptr);

@@ -50,6 +50,10 @@ void make_synthetic(GCNData *d, int n, int f, int c, long long undirected_edges,
 // FNV-1a 64 checksum of the payload).  load_binary fails (returns false) on a missing file,
 // another version, stamps that differ from `stamps` (when given), a short file or a checksum
 // mismatch; the caller then parses the text.
+// FNV-1a 64 over n bytes, continued from h (kFnvBasis to start): the checksum of the binary
+// files this library writes (the dataset cache here, training checkpoints in checkpoint.cpp)
+constexpr uint64_t kFnvBasis = 14695981039346656037ull;
+uint64_t fnv1a(uint64_t h, const void *p, size_t n);
 struct FileStamp {
   long long size = -1, mtime_ns = -1;
 };

@@ -9,6 +9,7 @@
 
 #include "../kernels.hpp"
 #include "../rng.hpp"
+#include "checkpoint.hpp"
 
 namespace pgcn {
 
@@ -141,6 +142,29 @@ void Adam::step_each(const std::vector<hipStream_t> &streams,
 void Adam::step_graph(const Stream &s, const float *table, const int *ctr, int cap,
                       TnDeferList *defer, const PeerRecv *peer, const float *arena) const {
   launch(s, 0.0f, table, ctr, cap, defer, peer, arena);
+}
+
+void Adam::moments_to_host(std::vector<float> *m, std::vector<float> *v) const {
+  for (const auto &x : vars) {
+    const size_t n = (size_t)x.w->size, at = m->size();
+    m->resize(at + n);
+    v->resize(at + n);
+    x.m.download(m->data() + at, n);
+    x.v.download(v->data() + at, n);
+  }
+}
+
+void Adam::restore(const float *m, const float *v, int steps) {
+  size_t at = 0;
+  for (auto &x : vars) {
+    const size_t n = (size_t)x.w->size;
+    if (m) x.m.upload(m + at, n);
+    else x.m.zero();
+    if (v) x.v.upload(v + at, n);
+    else x.v.zero();
+    at += n;
+  }
+  step_count = steps;
 }
 
 // every weight in one launch when they fit one AdamBatch (the 2-layer model: W1 and W2); a
@@ -283,15 +307,10 @@ void build_dev_features(DevFeatures &feats, const int *fptr, const int *indices,
 int g_mask_per = 0;
 constexpr long long kMaskPer2Chunks = 1LL << 20;
 
-void init_dropout_rng_range(DropoutRng &r, const uint64_t seed[2], unsigned long long offset,
-                            long long elem_begin, long long elem_end) {
-  r.elem_begin = elem_begin;
-  r.elem_end = elem_end;
-  r.chunk_lo = r.elem_begin / kDropChunk;
-  const long long chunk_hi = ceil_div(r.elem_end, kDropChunk);
-  r.n_chunks = std::max(0LL, chunk_hi - r.chunk_lo);
-  r.per = g_mask_per ? g_mask_per : (r.n_chunks >= kMaskPer2Chunks ? 2 : 1);
-  r.mask_base = r.elem_begin - kDropChunk * r.chunk_lo;
+// The stored states of r (its range, chunks and `per` set) with the dropout's next draw of
+// global element 0 at stream position `offset`: jump-ahead from the seed state
+static std::vector<uint64_t> dropout_states(const DropoutRng &r, const uint64_t seed[2],
+                                            unsigned long long offset) {
   // one state per r.per mask words: the stream's state at the first draw of words per * k
   const long long n_states = ceil_div(r.n_chunks, (long long)r.per);
   const int span = kDropChunk * r.per;
@@ -306,6 +325,19 @@ void init_dropout_rng_range(DropoutRng &r, const uint64_t seed[2], unsigned long
       for (int k = 0; k < span; k++) xs_advance(s);
     }
   });
+  return st;
+}
+
+void init_dropout_rng_range(DropoutRng &r, const uint64_t seed[2], unsigned long long offset,
+                            long long elem_begin, long long elem_end) {
+  r.elem_begin = elem_begin;
+  r.elem_end = elem_end;
+  r.chunk_lo = r.elem_begin / kDropChunk;
+  const long long chunk_hi = ceil_div(r.elem_end, kDropChunk);
+  r.n_chunks = std::max(0LL, chunk_hi - r.chunk_lo);
+  r.per = g_mask_per ? g_mask_per : (r.n_chunks >= kMaskPer2Chunks ? 2 : 1);
+  r.mask_base = r.elem_begin - kDropChunk * r.chunk_lo;
+  const std::vector<uint64_t> st = dropout_states(r, seed, offset);
   r.states.allocate(st.size());
   r.states.upload(st);
   // (+1, rounded up to an even count: the X-stream ring kernels stage the bitmap in 16-B pieces)
@@ -403,6 +435,8 @@ void GCN::init_dropout_rng(const GCNData &data, long long glorot_draws) {
   // draws per training epoch: the input dropout (nnz_X) then each hidden dropout (N*h_l)
   unsigned long long period = (unsigned long long)nnz_x_global;
   for (int l = 1; l < L; l++) period += (unsigned long long)N * dims[(size_t)l];
+  draw_period = period;
+  this->glorot_draws = glorot_draws;
   std::vector<uint64_t> table(16 * 256 * 2);
   xs_byte_tables(xs_jump_matrix(period), table.data());
   jump_table.allocate(table.size() * sizeof(uint64_t));
@@ -427,6 +461,27 @@ void GCN::init_dropout_rng(const GCNData &data, long long glorot_draws) {
     offset += (l == 0) ? (unsigned long long)nnz_x_global
                        : (unsigned long long)N * dims[(size_t)l];
   }
+}
+
+// The chunk states of every dropout as after `epochs` training forwards (each consumes exactly
+// draw_period draws): init_dropout_rng's offsets moved by epochs * draw_period, into the
+// buffers the modules (and a captured epoch graph) already hold.  The caller has synchronised.
+void GCN::reseed_dropout(long long epochs) {
+  uint64_t seed[2];
+  if (params.seed) pgcn_rng_seed_glibc(params.seed, seed);
+  else pgcn_rng_seed(seed);
+  unsigned long long offset =
+      (unsigned long long)glorot_draws + (unsigned long long)epochs * draw_period;
+  for (int l = 0; l < L; l++) {
+    DropoutRng &r = *rngs[(size_t)l];
+    const std::vector<uint64_t> st = dropout_states(r, seed, offset);
+    PGCN_CHECK(st.size() == r.states.size(), PGCN_E_INVALID, "dropout states changed size");
+    r.states.upload(st);
+    offset += (unsigned long long)(l == 0 ? nnz_x_global
+                                          : (long long)params.num_nodes *
+                                                params.hidden_dims[(size_t)l - 1]);
+  }
+  draw_epochs = epochs;
 }
 
 void GCN::build(const GCNData &data) {
@@ -1228,6 +1283,7 @@ void GCN::epoch_async() {
   }
   last_forward_training = false;
   epoch_count++;
+  draw_epochs++;
 }
 
 std::pair<float, float> GCN::train_epoch() {
@@ -1245,6 +1301,7 @@ std::pair<float, float> GCN::train_epoch() {
                  ctx.jump_table);
   ctr_valid = false;
   last_forward_training = true;
+  draw_epochs++;
   return read_slot((int)(slot * 4));
 }
 
@@ -1302,10 +1359,15 @@ std::vector<float> GCN::results(int n) {
     results_ring.download(all.data(), all.size());
   }
   n = (int)std::min<long long>(n, std::min<long long>(epoch_count, ring_cap));
+  // epochs before a checkpoint load's point come from the loaded rows (as far as they reach)
+  const long long hist_rows = (long long)hist.size() / 4, hist_lo = hist_end - hist_rows;
+  if (epoch_count - n < hist_end) n = (int)std::min<long long>(n, epoch_count - hist_lo);
   std::vector<float> out((size_t)n * 4);
   for (int k = 0; k < n; k++) {
     const long long e = epoch_count - n + k;
-    std::memcpy(&out[(size_t)k * 4], &all[(size_t)(e % ring_cap) * 4], 4 * sizeof(float));
+    const float *row = e < hist_end ? &hist[(size_t)(e - hist_lo) * 4]
+                                    : &all[(size_t)(e % ring_cap) * 4];
+    std::memcpy(&out[(size_t)k * 4], row, 4 * sizeof(float));
   }
   return out;
 }
@@ -1314,7 +1376,9 @@ std::vector<float> GCN::results(int n) {
 void GCN::run(bool verbose) {
   std::vector<float> loss_history;
   double total = 0;
-  int epoch = 1;
+  // (after a checkpoint load the numbering continues from the epochs already run)
+  const int first = hist_end > 0 ? (int)epoch_count + 1 : 1;
+  int epoch = first;
   for (; epoch <= params.epochs; epoch++) {
     const auto t0 = std::chrono::high_resolution_clock::now();
     auto tr = train_epoch();
@@ -1325,9 +1389,10 @@ void GCN::run(bool verbose) {
       printf("epoch=%d train_loss=%.5f train_acc=%.5f val_loss=%.5f val_acc=%.5f time=%.5f\n",
              epoch, tr.first, tr.second, va.first, va.second, dt);
     loss_history.push_back(va.first);
-    if (params.early_stopping > 0 && epoch >= params.early_stopping) {
+    if (params.early_stopping > 0 && epoch - first + 1 >= params.early_stopping) {
       float recent = 0.0f;
-      for (int i = epoch - params.early_stopping; i < epoch; i++) recent += loss_history[(size_t)i];
+      for (int i = epoch - first + 1 - params.early_stopping; i < epoch - first + 1; i++)
+        recent += loss_history[(size_t)i];
       if (va.first > recent / (float)params.early_stopping) {
         if (verbose) printf("Early stopping...\n");
         break;
@@ -1335,7 +1400,7 @@ void GCN::run(bool verbose) {
     }
   }
   if (verbose) {
-    const int done = std::min(epoch, params.epochs);
+    const int done = std::max(1, std::min(epoch, params.epochs) - first + 1);
     printf("TMR_TRAIN average time: %.3fms\n", total * 1000.0 / done);
     const auto t0 = std::chrono::high_resolution_clock::now();
     auto te = eval(3);
@@ -1389,6 +1454,152 @@ std::vector<float> GCN::get_var(int idx, int which) {
                         std::find(weights.begin(), weights.end(), v) == weights.end();
   if (node_var) out.resize((size_t)part.local_rows() * v->cols);
   return out;
+}
+
+void GCN::forget_ahead(bool masks) {
+  for (const auto &m : modules)
+    if (const auto *sm = dynamic_cast<const SparseMatmul *>(m.get())) sm->forget_ahead();
+  if (masks)
+    for (const Dropout *d : dropouts_)
+      if (d) d->forget_draws();
+  ctr_valid = false;
+}
+
+void GCN::set_var(int idx, int which, const float *host_src, long long count) {
+  PGCN_CHECK(idx >= 0 && idx < (int)variables.size() && which == 0 && host_src, PGCN_E_INVALID,
+             "set_var: a weight variable's data only");
+  const auto &v = variables[(size_t)idx];
+  PGCN_CHECK(v && std::find(weights.begin(), weights.end(), v) != weights.end(), PGCN_E_INVALID,
+             "set_var: not a weight variable");
+  PGCN_CHECK(count == v->size, PGCN_E_INVALID, "set_var: element count");
+  sync();
+  v->dev_data.upload(host_src, (size_t)count);
+  forget_ahead(false);
+}
+
+void GCN::save(const std::string &path) {
+  Checkpoint ck;
+  ck.results = results(ring_cap);  // (syncs)
+  ck.n_layers = L;
+  ck.num_nodes = params.num_nodes;
+  ck.dims.push_back(params.input_dim);
+  for (int h : params.hidden_dims) ck.dims.push_back(h);
+  ck.dims.push_back(params.output_dim);
+  ck.dropouts = params.dropouts;
+  ck.seed = params.seed;
+  ck.adam_steps = optimizer.steps();
+  ck.draw_epochs = draw_epochs;
+  ck.epochs = epoch_count;
+  for (const auto &w : weights) {
+    const std::vector<float> h = w->to_host(0);
+    ck.w.insert(ck.w.end(), h.begin(), h.end());
+  }
+  optimizer.moments_to_host(&ck.m, &ck.v);
+  write_checkpoint(path, ck);
+}
+
+void GCN::load(const std::string &path, int flags) {
+  PGCN_CHECK(flags == 0 || flags == PGCN_LOAD_WEIGHTS_ONLY, PGCN_E_INVALID, "load: flags");
+  const Checkpoint ck = read_checkpoint(path);  // the whole file, validated, before any change
+  const bool resume = flags == 0;
+  bool same = ck.n_layers == L && ck.num_nodes == params.num_nodes &&
+              ck.dims.front() == params.input_dim && ck.dims.back() == params.output_dim;
+  for (int l = 0; same && l + 1 < L; l++)
+    same = ck.dims[(size_t)l + 1] == params.hidden_dims[(size_t)l];
+  if (same && resume) {
+    same = ck.seed == params.seed;
+    for (int l = 0; same && l < L; l++) same = ck.dropouts[(size_t)l] == params.dropouts[(size_t)l];
+  }
+  PGCN_CHECK(same, PGCN_E_INVALID, "load: the checkpoint is for another model");
+  PGCN_CHECK(ck.adam_steps < (1LL << 31), PGCN_E_INVALID, "load: step count");
+  sync();
+  size_t at = 0;
+  for (const auto &w : weights) {
+    w->dev_data.upload(ck.w.data() + at, (size_t)w->size);
+    at += (size_t)w->size;
+  }
+  if (!resume) {  // weights only: a fresh optimizer; epochs, results and dropout position stay
+    optimizer.restore(nullptr, nullptr, 0);
+    forget_ahead(false);
+    return;
+  }
+  optimizer.restore(ck.m.data(), ck.v.data(), (int)ck.adam_steps);
+  epoch_count = ck.epochs;
+  hist = ck.results;
+  hist_end = ck.epochs;
+  reseed_dropout(ck.draw_epochs);
+  forget_ahead(true);
+  last_forward_training = false;
+}
+
+// An eval forward as GCN::eval's, over every row and with no labelled row: the loss module
+// (which computes the fused output layer's logits) shifts nothing, counts nothing and finishes
+// no results slot.  Masks or products the pass draws or computes ahead are the ones the next
+// training forward would have made itself (the same stream positions, the same weights).
+void GCN::predict_forward() {
+  if (!truth[0]) {
+    const std::vector<int> none((size_t)part.maxrows, -1);
+    truth[0].allocate(none.size());
+    truth[0].upload(none);
+  }
+  ctx.truth = truth[0].get();
+  ctx.count = 1;
+  modules.back()->set_num_samples(1);
+  ctx.split_graph = nullptr;
+  ctx.split_rows = nullptr;
+  ctx.split_colgraph = nullptr;
+  ctx.chunk_split_graphs.clear();
+  ctx.chunk_split_rows.clear();
+  ctx.chunk_col_graphs.clear();
+  ctx.compact_n = 0;
+  ctx.compact_truth = nullptr;
+  ctx.xent_blocks = xent_blocks(part.maxrows);
+  out_restricted = false;
+  ctx.fin = nullptr;
+  ctx.fin_taken = false;
+  ctx.xs_draw.n = 0;
+  for (const auto &m : modules) m->forward(false, stream);
+  ctx.fin_taken = false;
+  last_forward_training = false;
+}
+
+long long GCN::predict(int *cls, float *conf, float *probs) {
+  const auto *ce = dynamic_cast<const CrossEntropyLoss *>(modules.back().get());
+  PGCN_CHECK(ce, PGCN_E_INVALID, "predict: no output layer");
+  const Variable &z = *ce->input();
+  const int n = part.local_rows(), C = params.output_dim, ldp = round_up4(C);
+  if (!pred_cls) {
+    pred_cls.allocate((size_t)std::max(part.maxrows, 1));
+    pred_conf.allocate((size_t)std::max(part.maxrows, 1));
+  }
+  if (probs && !pred_probs) pred_probs.allocate((size_t)std::max(part.maxrows, 1) * ldp);
+  predict_forward();
+  launch_predict_rows(z.dev_data.get(), z.ld, n, C, pred_cls.get(), pred_conf.get(),
+                      probs ? pred_probs.get() : nullptr, ldp, stream.get());
+  sync();
+  if (cls) pred_cls.download(cls, (size_t)n);
+  if (conf) pred_conf.download(conf, (size_t)n);
+  if (probs && ldp == C) pred_probs.download(probs, (size_t)n * C);
+  if (probs && ldp != C) {
+    std::vector<float> raw((size_t)n * ldp);
+    pred_probs.download(raw.data(), raw.size());
+    for (int i = 0; i < n; i++)
+      std::memcpy(probs + (size_t)i * C, &raw[(size_t)i * ldp], sizeof(float) * (size_t)C);
+  }
+  return n;
+}
+
+void GCN::confusion(int split, long long *counts) {
+  PGCN_CHECK(split >= 1 && split <= 3 && counts, PGCN_E_INVALID, "confusion: split 1, 2 or 3");
+  const int C = params.output_dim;
+  predict(nullptr, nullptr, nullptr);
+  if (!pred_counts) pred_counts.allocate((size_t)C * C);
+  launch_confusion(pred_cls.get(), truth[split].get(), part.local_rows(), C, pred_counts.get(),
+                   stream.get());
+  sync();
+  std::vector<unsigned> h((size_t)C * C);
+  pred_counts.download(h.data(), h.size());
+  for (size_t i = 0; i < h.size(); i++) counts[i] = (long long)h[i];
 }
 
 void GCN::set_profile(bool on) {

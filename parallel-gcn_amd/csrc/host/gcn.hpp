@@ -8,6 +8,7 @@
 // xorshift128+ dropout masks and glorot init, loss normalised by the labelled count.
 #pragma once
 #include <memory>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -77,6 +78,11 @@ class Adam {
                   const float *arena = nullptr) const;
   void advance() { step_count++; }
   int steps() const { return step_count; }
+  // the moments of every tensor in order, appended to m / v (checkpoints)
+  void moments_to_host(std::vector<float> *m, std::vector<float> *v) const;
+  // the moments from host arrays laid out as moments_to_host writes them (null: zero) and
+  // the step count; the caller has synchronised the engine's streams
+  void restore(const float *m, const float *v, int steps);
   float step_size(int t) const;  // hpdga optim.cpp:24, step t (1-based)
 
  private:
@@ -111,6 +117,17 @@ class GCN {
 
   int num_vars() const { return (int)variables.size(); }
   std::vector<float> get_var(int idx, int which);
+  // weights only, get_var's layout; drops what was computed ahead from the old weights
+  void set_var(int idx, int which, const float *host_src, long long count);
+  // whole training state to / from one file (host/checkpoint.hpp); load flags: PGCN_LOAD_*
+  void save(const std::string &path);
+  void load(const std::string &path, int flags);
+  // eval-mode forward over every row of this rank (no split, no row restriction), then
+  // k_predict_rows; host outputs, any may be null; the training state is left as it was
+  long long predict(int *cls, float *conf, float *probs);
+  // predict + k_confusion against `split`'s labels: counts[c * c] of this rank's rows
+  void confusion(int split, long long *counts);
+  long long adam_steps() const { return optimizer.steps(); }
   void set_profile(bool on);
   void profile_read_mm(double *ms, long long *calls, double *flops);  // XW contractions
   void profile_read(double *ms, long long *calls, double *bytes);
@@ -151,6 +168,13 @@ class GCN {
   void join_side();
   int fused_tails_ = 0;  // GraphSum epilogues carrying ReLU / Dropout work (forward + backward)
   void set_split(int split);
+  // the eval forward of predict(): every row, no labels, no results slot; the logits stay in
+  // the loss module's input variable
+  void predict_forward();
+  // every mask and product computed ahead of its use is dropped (masks: a load moved the RNG
+  // stream; products: the weights changed), and the epoch graph's device counters re-sync
+  void forget_ahead(bool masks);
+  void reseed_dropout(long long draw_epochs);
   void finalize(int slot_offset, bool graph = false, hipStream_t s = nullptr);
   // the eval forward + finalize of ring slot offset `off` (eval_tail: its last GraphSum's
   // exchange and the output layer on side_stream, ModuleContext::tail_stream)
@@ -175,7 +199,7 @@ class GCN {
   std::unique_ptr<DevGraph> graph;                    // one GPU: the whole Â
   std::vector<std::unique_ptr<DevGraph>> chunk_graphs;  // edge-cut: Â's column block per RS chunk
   DevFeatures feats;
-  DeviceBuffer<int> truth[4];
+  DeviceBuffer<int> truth[4];  // [1..3] per split; [0] no labels at all (predict_forward)
   int counts[4] = {0, 0, 0, 0};
   // output-layer row restriction (set_split): per split, its labelled rows and Â on them
   std::vector<int> split_rows_host[4];
@@ -223,6 +247,19 @@ class GCN {
   PinnedBuffer<float> pinned;
   int ring_cap = 1024;
   long long epoch_count = 0;
+  // training forwards since the build: the dropout stream stands at glorot_draws + draw_epochs
+  // * draw_period (differs from the Adam step count after a weights-only load)
+  long long draw_epochs = 0;
+  long long glorot_draws = 0;
+  unsigned long long draw_period = 0;
+  // a loaded checkpoint's results rows: epochs [hist_end - rows, hist_end), served by results()
+  // in place of the device ring (one GPU keeps composed rows there, edge-cut raw sums)
+  std::vector<float> hist;
+  long long hist_end = 0;
+  // predict()'s device outputs (allocated at its first call)
+  DeviceBuffer<int> pred_cls;
+  DeviceBuffer<float> pred_conf, pred_probs;
+  DeviceBuffer<unsigned> pred_counts;
   bool last_forward_training = false;
   bool reassociated_ = false;
   float ax_build_ms = 0.0f;

@@ -219,6 +219,13 @@ class Dropout : public Module {
   // (GCN::build, "co_draw"; sparse X only: the dense input has its own layouts)
   const Dropout *co_draw = nullptr;
   mutable bool pre_drawn = false;
+  // a checkpoint load moved the RNG stream (GCN::load): any mask drawn ahead or with another
+  // module's draw came from the old position and is dropped
+  void forget_draws() const {
+    ahead = false;
+    ahead_ready = nullptr;
+    pre_drawn = false;
+  }
 
  private:
   void draw(hipStream_t s, uint64_t *mask, int max_blocks = 0) const;
@@ -250,6 +257,9 @@ class SparseMatmul : public Module {
   const GraphSum *consumer = nullptr;
   void forward(bool training, const Stream &s) const override;
   void backward(const Stream &s) const override;
+  // the weights changed outside an optimizer step (GCN::set_var / load): a product computed
+  // ahead from the old ones is dropped
+  void forget_ahead() const { ahead_valid = false; }
 };
 
 // include/module.cuh:72-86

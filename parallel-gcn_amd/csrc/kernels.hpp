@@ -386,6 +386,16 @@ size_t tn_reduce_blocks_workspace(int n_blocks, int K, int ldp);
 void launch_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c,
                      int count, int training, float *partials, hipStream_t s, int write_back = 1,
                      const XentFinal *fin = nullptr);
+// Per-row prediction from logits [n][ld] (k_predict.hip): cls[i] = lowest index of row i's
+// maximum over columns [0, c), conf[i] = its softmax probability, probs (optional) [n][ld_probs]
+// the softmax row (columns [c, round_up4(c)) written as zero) -- from the loss kernel's softmax
+// pieces.  kPredictRows rows per workgroup; any of cls / conf / probs may be null.
+constexpr int kPredictRows = 64, kPredictMaxClasses = 128;
+void launch_predict_rows(const float *logits, int ld, int n, int c, int *cls, float *conf,
+                         float *probs, int ld_probs, hipStream_t s);
+// counts[t * c + p] = rows with truth[i] == t >= 0 and cls[i] == p, zeroed first (integer adds)
+void launch_confusion(const int *cls, const int *truth, int n, int c, unsigned int *counts,
+                      hipStream_t s);
 // sums (optional): {loss sum, wrong}; out2 (optional): the composed {loss + l2, accuracy};
 // raw4 (optional): {loss sum, wrong, sum w^2, count} for a composition after an all-reduce
 void launch_reduce_scalars(const float *partials, int n_blocks, const float *w, long long n_w,

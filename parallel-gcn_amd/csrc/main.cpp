@@ -1,4 +1,5 @@
-// parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]`
+// parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
+//   [epochs=<n>] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -6,6 +7,10 @@
 // beta1, beta2, eps, seed (srand seed of the xorshift state); the CUDA launch knobs
 // num_blocks_factor/num_threads are accepted and ignored) -- our own tiny parser, GetPot is
 // not vendored.  no_feature=1 is the PART2 NO_FEATURE build (feature values 1.0).
+// New with the engine: load= resumes from a checkpoint before the run (the epoch lines go on
+// from its epoch count, up to `epochs`), save= writes one after it, predict= writes one line
+// `node class confidence` per node after it; epochs= overrides the parameter file's.
+#include <vector>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -66,11 +71,17 @@ int main(int argc, char **argv) {
   std::string root = ".", file;
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
+  std::string load, save, predict;
+  int epochs = -1;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
     if (!std::strcmp(argv[i], "cache=1")) cache = true;
     if (!std::strcmp(argv[i], "no_feature=1")) no_feature = true;
+    if (!std::strncmp(argv[i], "load=", 5)) load = argv[i] + 5;
+    if (!std::strncmp(argv[i], "save=", 5)) save = argv[i] + 5;
+    if (!std::strncmp(argv[i], "predict=", 8)) predict = argv[i] + 8;
+    if (!std::strncmp(argv[i], "epochs=", 7)) epochs = std::atoi(argv[i] + 7);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -78,6 +89,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "cannot read parameter file %s\n", file.c_str());
     return EXIT_FAILURE;
   }
+  if (epochs >= 0) p.epochs = epochs;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
@@ -95,7 +107,27 @@ int main(int argc, char **argv) {
     fprintf(stderr, "GCN creation failed: %s\n", pgcn_status_string(st));
     return EXIT_FAILURE;
   }
+  if (!load.empty() && (st = pgcn_gcn_load(g, load.c_str(), 0)) != PGCN_OK) {
+    fprintf(stderr, "cannot resume from %s: %s\n", load.c_str(), pgcn_status_string(st));
+    return EXIT_FAILURE;
+  }
   st = pgcn_gcn_run(g, 1);
+  if (st == PGCN_OK && !save.empty() && (st = pgcn_gcn_save(g, save.c_str())) != PGCN_OK)
+    fprintf(stderr, "cannot save %s: %s\n", save.c_str(), pgcn_status_string(st));
+  if (st == PGCN_OK && !predict.empty()) {
+    std::vector<int> cls((size_t)view.num_nodes);
+    std::vector<float> conf((size_t)view.num_nodes);
+    const long long n = pgcn_gcn_predict(g, cls.data(), conf.data(), nullptr);
+    FILE *f = n >= 0 ? std::fopen(predict.c_str(), "w") : nullptr;
+    if (!f) {
+      fprintf(stderr, "cannot write predictions to %s\n", predict.c_str());
+      st = n < 0 ? (int)n : PGCN_E_IO;
+    } else {
+      for (long long i = 0; i < n; i++)
+        fprintf(f, "%lld %d %.6f\n", i, cls[(size_t)i], conf[(size_t)i]);
+      std::fclose(f);
+    }
+  }
   pgcn_gcn_destroy(g);
   pgcn_dataset_free(ds);
   return st == PGCN_OK ? EXIT_SUCCESS : EXIT_FAILURE;
