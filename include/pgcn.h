@@ -146,6 +146,12 @@ int pgcn_dropout_apply(float *x, long long n, const uint64_t *mask, float scale,
 int pgcn_relu_fwd(float *x, long long n, uint8_t *mask, int training, void *stream);
 int pgcn_relu_bwd(float *g, long long n, const uint8_t *mask, void *stream);
 
+/* --- ResidualConnection (src/module.cu:566-593) ------------------------------------------
+ * forward: cur[i] += prev[i]; backward (empty in the reference): prev_grad[i] += cur_grad[i].
+ * One fp32 add per element, any alignment; the arrays must not overlap. */
+int pgcn_residual_fwd(float *cur, const float *prev, long long n, void *stream);
+int pgcn_residual_bwd(float *prev_grad, const float *cur_grad, long long n, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -203,6 +209,13 @@ typedef struct {
    * hpdga rand.cpp:6-14); else the xorshift state is the first two rand() values after
    * srand(seed).  Glorot init and every dropout mask follow from it. */
   unsigned int seed;
+  /* != 0: every middle layer 1 <= l <= n_layers - 2 whose width equals the layer before it
+   * (hidden_dims[l] == hidden_dims[l-1]) gets the reference's ResidualConnection after its ReLU
+   * (include/module.cuh:149-161): H_l = relu(Â (A W_l)) + A, with A the layer's input as it
+   * read it (in training, after that layer's Dropout), and a real backward (the reference's is
+   * empty).  No projection for unequal widths; none qualifying (n_layers == 2): the plain
+   * engine, bit for bit. */
+  int residual;
 } pgcn_params;
 
 /* hpdga defaults: 2 layers, hidden 16, dropout .5/.5, 100 epochs, Adam lr .01, wd 5e-4,
@@ -264,7 +277,10 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * ring algorithm: a reduce-scatter (W-1)/W of its send buffer, an all-reduce twice that), "reassociated",
  * "graph_symmetric", "graphsum_lds" (width-16 GraphSums take the LDS kernel), "epochs",
  * "adam_steps" (optimizer steps taken; 0 again after a weights-only load),
- * "eval_ax_us" (device time of the Â X precompute at engine build, µs; 0 when not used).
+ * "eval_ax_us" (device time of the Â X precompute at engine build, µs; 0 when not used),
+ * "residual_layers" (layers with a ResidualConnection, pgcn_params.residual) and
+ * "fused_residuals" (how many of them the last training forward added inside a GraphSum's
+ * final write instead of a launch of their own).
  * Returns the value (>= 0) or PGCN_E_INVALID for an unknown key. */
 long long pgcn_gcn_query(pgcn_gcn *g, const char *key);
 /* GCN::train_epoch / GCN::eval (src/gcn.cu:293-343): out2 = {loss, accuracy} */
@@ -283,7 +299,12 @@ int pgcn_gcn_run(pgcn_gcn *g, int verbose);
  * include/gcn.cuh:85). which: 0 data, 1 grad. Returns element count (>= 0) or status. For
  * the edge-cut engine node-sized variables cover this rank's rows only.  PGCN_E_INVALID for
  * the output layer's node variables after a forward with the diagnostic row restriction
- * ("split_rows" on): their rows outside the split are stale. */
+ * ("split_rows" on): their rows outside the split are stale.
+ * Residual layers (pgcn_params.residual): var2 of layer l holds relu(Z_l) + A_{l-1}, and its
+ * grad (which = 1) is G = dLoss/dH_l, the gradient of that sum after the next layer's Dropout
+ * backward, NOT masked by the layer's ReLU: the masked gradient G * [Z_l > 0] that the
+ * GraphSum backward reads is kept in a buffer of the engine's own, so that G can be added to
+ * the grad of var2 of layer l-1 when the layer's Matmul backward writes it. */
 long long pgcn_gcn_get_var(pgcn_gcn *g, int idx, int which, float *host_dst);
 int pgcn_gcn_num_vars(pgcn_gcn *g);
 /* Weights only (idx must be a weight variable, which == 0), in get_var's layout and count;
@@ -302,14 +323,22 @@ int pgcn_gcn_save(pgcn_gcn *g, const char *path);
  * past or short of the save point, on one GPU or as edge-cut ranks (every rank loads).
  * PGCN_LOAD_WEIGHTS_ONLY: weights from the file, Adam m/v and step count reset to zero, epoch
  * count, results and dropout position kept.
- * PGCN_E_INVALID: the file is for another model (dims, num_nodes; for flags 0 also seed and
- * dropouts).  PGCN_E_IO: missing, truncated, corrupted or unknown version.  On any error
+ * PGCN_E_INVALID: the file is for another model (dims, num_nodes; for flags 0 also seed,
+ * dropouts and whether the model is residual -- a weights-only load ignores that flag, the
+ * tensors having the same shapes, so a plain model's weights can warm-start a residual one).  PGCN_E_IO: missing, truncated, corrupted or unknown version.  On any error
  * the engine is untouched. */
 int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags);
 /* Host-only look at a checkpoint file (no device, no engine): validates it as pgcn_gcn_load
  * does and fills info[8] = {version, n_layers, num_nodes, input_dim, output_dim, adam_steps,
  * epochs, weight count}.  PGCN_E_IO as pgcn_gcn_load. */
 int pgcn_checkpoint_info(const char *path, long long info[8]);
+/* Host-only: the file's header flags (>= 0; bit 0: saved by a residual engine), validated as
+ * pgcn_checkpoint_info does, or a status < 0 (PGCN_E_IO also for flag bits this library does
+ * not know). */
+int pgcn_checkpoint_flags(const char *path);
+#define PGCN_CKPT_RESIDUAL 1
+/* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
+int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
  * "split_rows" says), then pgcn_predict_rows.  Host outputs, any may be NULL; probs is
  * [rows][output_dim] dense.  Returns the row count (node_range's) or a status < 0.  Leaves

@@ -5,7 +5,7 @@
  *   Variable                      include/variable.cuh:11-29
  *   Module, Dropout, SparseMatmul,
  *   GraphSum, ReLU, Matmul,
- *   CrossEntropyLoss              include/module.cuh:21-145
+ *   CrossEntropyLoss, ResidualConnection  include/module.cuh:21-161
  *   AdamParams, Adam              include/optim.cuh:16-50
  *   SparseIndex, DevSparseIndex   include/sparse.cuh:11-29
  *   GCNParams, GCNData, GCN       include/gcn.cuh:40-122
@@ -224,6 +224,27 @@ class ReLU : public Module {
   shared_ptr<Impl> impl_;
 };
 
+// include/module.cuh:149-161: current += prev ("works only if hidden dimension are the same").
+// forward as in the reference (src/module.cu:566-593), whatever `training` is.  backward: the
+// reference's is empty (no gradient takes the skip path, and its GCN never inserts the module);
+// here prev.grad += current.grad is real.  Because Matmul::backward overwrites its input's
+// grad after this module's turn in the reverse order, the add is made by the Matmul whose input
+// is `prev`, right after it writes prev.grad, and the ReLU on `current` leaves current.grad
+// unmasked (it keeps the masked gradient the GraphSum backward reads in a buffer of its own):
+// the usual reverse-order loop over the modules gives dLoss/dprev = (Â dZ) W^T + dLoss/dcurrent.
+// This module's own backward() launches nothing.  Build it after the modules that produce both
+// variables; a size mismatch throws std::runtime_error (the reference prints and exit(1)s).
+class ResidualConnection : public Module {
+ public:
+  ResidualConnection(shared_ptr<Variable> prev_, shared_ptr<Variable> current_);
+  void forward(bool training, const smart_stream &stream) const override;
+  void backward(const smart_stream &stream) const override;
+  struct Impl;
+
+ private:
+  shared_ptr<Impl> impl_;
+};
+
 // include/module.cuh:103-124: c = a * b  (a [m][n], b [n][p])
 class Matmul : public Module {
  public:
@@ -296,6 +317,9 @@ struct GCNParams {
   natural train_dim{0}, val_dim{0}, test_dim{0};
   natural n_layers{2};
   unsigned seed{0};  // PART2 `seed` (0: hpdga's unseeded stream)
+  // middle layers as wide as the layer before them get a ResidualConnection after their ReLU
+  // (pgcn_params.residual, pgcn.h)
+  bool residual{false};
 };
 
 struct GCNData {

@@ -44,7 +44,7 @@ class PgcnParams(ctypes.Structure):
                 ("dropouts", c_float * MAX_LAYERS), ("epochs", c_int), ("early_stopping", c_int),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
                 ("beta2", c_float), ("eps", c_float), ("reassociate_last", c_int),
-                ("seed", ctypes.c_uint)]
+                ("seed", ctypes.c_uint), ("residual", c_int)]
 
 
 class PgcnData(ctypes.Structure):
@@ -98,6 +98,9 @@ _sig("pgcn_dropout_mask", c_int, c_void_p, c_ll, c_ll, c_ll, c_float, c_void_p, 
 _sig("pgcn_dropout_apply", c_int, c_void_p, c_ll, c_void_p, c_float, c_void_p)
 _sig("pgcn_relu_fwd", c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p)
 _sig("pgcn_relu_bwd", c_int, c_void_p, c_ll, c_void_p, c_void_p)
+_sig("pgcn_residual_fwd", c_int, c_void_p, c_void_p, c_ll, c_void_p)
+_sig("pgcn_residual_bwd", c_int, c_void_p, c_void_p, c_ll, c_void_p)
+_sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
      c_void_p, c_void_p)
@@ -134,6 +137,7 @@ _sig("pgcn_gcn_set_var", c_int, c_void_p, c_int, c_int, c_void_p, c_ll)
 _sig("pgcn_gcn_save", c_int, c_void_p, ctypes.c_char_p)
 _sig("pgcn_gcn_load", c_int, c_void_p, ctypes.c_char_p, c_int)
 _sig("pgcn_checkpoint_info", c_int, ctypes.c_char_p, P(c_ll))
+_sig("pgcn_checkpoint_flags", c_int, ctypes.c_char_p)
 _sig("pgcn_gcn_predict", c_ll, c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -283,9 +287,10 @@ class Dataset:
 
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
-                reassociate_last=True, seed=0):
+                reassociate_last=True, seed=0, residual=False):
     p = PgcnParams()
     lib.pgcn_params_default(ctypes.byref(p))
+    p.residual = 1 if residual else 0
     p.reassociate_last = 1 if reassociate_last else 0
     p.seed = seed
     p.num_nodes, p.input_dim, p.output_dim = ds.num_nodes, ds.input_dim, ds.output_dim
@@ -530,6 +535,17 @@ def checkpoint_info(path):
     return dict(zip(keys, (int(x) for x in info)))
 
 
+CKPT_RESIDUAL = 1
+
+
+def checkpoint_flags(path):
+    """Host-only: a checkpoint file's header flags (bit 0, CKPT_RESIDUAL: saved by an engine with
+    residual layers).  PgcnError(PGCN_E_IO) for an invalid file or unknown flag bits."""
+    st = lib.pgcn_checkpoint_flags(os.fsencode(path))
+    check(min(st, 0), f"checkpoint_flags {path}")
+    return st
+
+
 def comm_unique_id():
     buf = ctypes.create_string_buffer(128)
     check(lib.pgcn_comm_unique_id(buf), "comm_unique_id")
@@ -603,7 +619,8 @@ EXPORTED = [
     "pgcn_gemm_tn_xstream", "pgcn_gemm_xstream_flat", "pgcn_gemm_tn_xstream_flat",
     "pgcn_spmm_csr", "pgcn_spmm_csc_bwd", "pgcn_csr_transpose",
     "pgcn_rng_jump_table", "pgcn_dropout_mask", "pgcn_dropout_apply", "pgcn_relu_fwd",
-    "pgcn_relu_bwd", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
+    "pgcn_relu_bwd", "pgcn_residual_fwd", "pgcn_residual_bwd", "pgcn_params_sizeof",
+    "pgcn_checkpoint_flags", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
     "pgcn_adam_step_size", "pgcn_params_default", "pgcn_gcn_create", "pgcn_comm_unique_id",
     "pgcn_gcn_create_dist", "pgcn_gcn_create_peer", "pgcn_loopback_create",
     "pgcn_loopback_destroy",

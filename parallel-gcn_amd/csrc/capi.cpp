@@ -92,6 +92,7 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.early_stopping = p->early_stopping;
   q.reassociate_last = p->reassociate_last != 0;
   q.seed = p->seed;
+  q.residual = p->residual != 0;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -382,6 +383,21 @@ int pgcn_relu_fwd(float *x, long long n, uint8_t *mask, int training, void *stre
 int pgcn_relu_bwd(float *g, long long n, const uint8_t *mask, void *stream) {
   return guarded([&] { launch_relu_bwd(g, n, mask, as_stream(stream)); });
 }
+int pgcn_residual_fwd(float *cur, const float *prev, long long n, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && (n == 0 || (cur && prev)), PGCN_E_INVALID, "residual_fwd args");
+    check_device();
+    launch_residual_fwd(cur, prev, n, as_stream(stream));
+  });
+}
+int pgcn_residual_bwd(float *prev_grad, const float *cur_grad, long long n, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && (n == 0 || (prev_grad && cur_grad)), PGCN_E_INVALID,
+               "residual_bwd args");
+    check_device();
+    launch_residual_bwd(prev_grad, cur_grad, n, as_stream(stream));
+  });
+}
 
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
@@ -448,6 +464,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->eps = 1e-8f;
   p->reassociate_last = 1;
   p->seed = 0;
+  p->residual = 0;
 }
 
 int pgcn_gcn_create(const pgcn_params *p, const pgcn_data *d, int device, pgcn_gcn **out) {
@@ -569,6 +586,8 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "comm_bytes")) return c ? (long long)c->bytes : 0;
   if (!std::strcmp(key, "reassociated")) return e.reassociated() ? 1 : 0;
   if (!std::strcmp(key, "fused_tails")) return e.fused_tails();
+  if (!std::strcmp(key, "residual_layers")) return e.residual_layers();
+  if (!std::strcmp(key, "fused_residuals")) return e.fused_residuals();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
   if (!std::strcmp(key, "epochs")) return e.epochs_run();
@@ -659,6 +678,15 @@ int pgcn_checkpoint_info(const char *path, long long info[8]) {
     info[7] = (long long)ck.w.size();
   });
 }
+int pgcn_checkpoint_flags(const char *path) {
+  int flags = 0;
+  const int st = guarded([&] {
+    PGCN_CHECK(path, PGCN_E_INVALID, "checkpoint_flags args");
+    flags = (int)read_checkpoint(path).flags;
+  });
+  return st == PGCN_OK ? flags : st;
+}
+int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }
 long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs) {
   long long n = -1;
   const int st = guarded([&] {

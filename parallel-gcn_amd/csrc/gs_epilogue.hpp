@@ -6,9 +6,11 @@
 // (k_relu_fwd / k_dropout_apply / k_relu_bwd, k_elementwise.hip), so results are bit-identical:
 //   forward  (hpdga gcn.cpp:91-97 module order GraphSum -> ReLU -> Dropout; module.cpp:173-228):
 //     y = y > 0 ? y : 0            (relu_mask[i] = y > 0 when training)
+//     y = y + prev                 (a residual layer's ResidualConnection: res != null)
 //     y = y * (keep_i ? scale : 0) (training only: the hidden Dropout)
 //   backward (reverse order: GraphSum.bwd -> Dropout.bwd -> ReLU.bwd):
 //     g = g * (keep_i ? scale : 0)
+//     (a residual layer: g, the gradient of the sum, also stored to res)
 //     g = relu_mask[i] ? g : 0
 // Element i of row r, column c: relu_mask[r * relu_ld + c], dropout bit drop_base + r * drop_cols + c.
 #pragma once
@@ -32,6 +34,13 @@ struct GsEpilogue {
   float4 *next_table = nullptr;
   const float *next_scale = nullptr;
   int next_sr = 0;
+  // residual layer (ResidualConnection between the ReLU and the Dropout), element res[r *
+  // res_ld + c], columns offset by col0 like the other tails.  mode 1: read -- the layer's input
+  // variable (same width), added after the ReLU, before the dropout and the next table.  mode 2:
+  // written -- the gradient before the ReLU mask is also stored there (the skip path's share).
+  // (One pointer for both: a second one cost k_graphsum16 its fourth wave per SIMD.)
+  float *res = nullptr;
+  int res_ld = 0;
 };
 
 __device__ __forceinline__ uint32_t gs_epi_bits4(const uint64_t *__restrict__ mask, long long idx) {
@@ -50,6 +59,7 @@ struct GsEpiIn {
   uint64_t w0 = 0, w1 = 0;  // dropout words (w1: a nibble that straddles two words)
   uint32_t rm = 0;          // mode 2: the forward's ReLU keep bytes
   float ns = 0.0f;          // next_scale[r]
+  float4 res = {0.0f, 0.0f, 0.0f, 0.0f};  // mode 1: the residual source's float4
 };
 
 __device__ __forceinline__ void gs_epi_load(GsEpiIn &in, long long r, int c0, const GsEpilogue &e) {
@@ -62,6 +72,8 @@ __device__ __forceinline__ void gs_epi_load(GsEpiIn &in, long long r, int c0, co
   }
   if (e.mode == 2) in.rm = *reinterpret_cast<const uint32_t *>(e.relu_mask + r * e.relu_ld + c0);
   if (e.next_table) in.ns = e.next_scale[r];
+  if (e.mode == 1 && e.res)
+    in.res = *reinterpret_cast<const float4 *>(e.res + r * e.res_ld + c0);
 }
 
 // a = the float4 of columns c0 .. c0+3 of row r (c0 % 4 == 0) of the output pointer, i.e.
@@ -80,6 +92,12 @@ __device__ __forceinline__ void gs_epilogue(float4 &a, long long r, int c0, cons
     if (!k1) a.y = 0.0f;
     if (!k2) a.z = 0.0f;
     if (!k3) a.w = 0.0f;
+    if (e.res) {  // k_add_into: one fp32 add per element
+      a.x += in.res.x;
+      a.y += in.res.y;
+      a.z += in.res.z;
+      a.w += in.res.w;
+    }
   }
   if (e.drop_mask) {
     const long long idx = e.drop_base + r * e.drop_cols + c0;
@@ -94,6 +112,7 @@ __device__ __forceinline__ void gs_epilogue(float4 &a, long long r, int c0, cons
     a.w *= (bits & 8) ? s : 0.0f;
   }
   if (e.mode == 2) {
+    if (e.res) *reinterpret_cast<float4 *>(e.res + r * e.res_ld + c0) = a;
     const uint32_t m = in.rm;
     if (!(m & 0xffu)) a.x = 0.0f;
     if (!(m & 0xff00u)) a.y = 0.0f;

@@ -450,6 +450,23 @@ void ReLU::backward(const smart_stream &stream) const {
   impl_->mod->backward(Stream::wrap(stream.get()));
 }
 
+struct ResidualConnection::Impl {
+  std::unique_ptr<pgcn::ResidualConnection> mod;
+};
+ResidualConnection::ResidualConnection(shared_ptr<Variable> prev_, shared_ptr<Variable> current_)
+    : impl_(std::make_shared<Impl>()) {
+  PGCN_CHECK(prev_ && current_ && prev_->impl() && current_->impl(), PGCN_E_INVALID,
+             "ResidualConnection: its variables have no shape yet (build the modules producing "
+             "them first)");
+  impl_->mod = std::make_unique<pgcn::ResidualConnection>(prev_->impl(), current_->impl());
+}
+void ResidualConnection::forward(bool training, const smart_stream &stream) const {
+  impl_->mod->forward(training, Stream::wrap(stream.get()));
+}
+void ResidualConnection::backward(const smart_stream &stream) const {
+  impl_->mod->backward(Stream::wrap(stream.get()));
+}
+
 struct Matmul::Impl {
   std::unique_ptr<pgcn::Matmul> mod;
   // src/module.cu:319-324, 431-472: the forward waits for the weight's optimizer step; the
@@ -656,6 +673,7 @@ GCN::GCN(GCNParams const *params_, AdamParams const *adam_params_, GCNData const
   q.early_stopping = (int)params_->early_stopping;
   q.reassociate_last = true;
   q.seed = params_->seed;
+  q.residual = params_->residual;
   pgcn::AdamParams a;
   a.learning_rate = adam_params_->learning_rate;
   a.beta1 = adam_params_->beta1;

@@ -19,7 +19,7 @@ struct CkHeader {
   int64_t num_nodes;
   int32_t dims[18];
   float dropouts[16];
-  uint32_t seed, reserved;
+  uint32_t seed, flags;
   int64_t adam_steps, draw_epochs, epochs, n_results, n_weights;
   uint64_t checksum;
 };
@@ -63,6 +63,8 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   for (int l = 0; l <= L; l++) h.dims[l] = ck.dims[(size_t)l];
   for (int l = 0; l < L; l++) h.dropouts[l] = ck.dropouts[(size_t)l];
   h.seed = ck.seed;
+  h.flags = ck.flags;
+  PGCN_CHECK((ck.flags & ~kCheckpointKnownFlags) == 0, PGCN_E_INVALID, "checkpoint: unknown flags");
   h.adam_steps = ck.adam_steps;
   h.draw_epochs = ck.draw_epochs;
   h.epochs = ck.epochs;
@@ -91,7 +93,7 @@ Checkpoint read_checkpoint(const std::string &path) {
   Checkpoint ck;
   bool ok = std::fread(&h, sizeof(h), 1, f) == 1 && std::memcmp(h.magic, kCkMagic, 8) == 0 &&
             h.version == (uint32_t)kCheckpointVersion && h.n_layers >= 2 &&
-            h.n_layers <= PGCN_MAX_LAYERS && h.num_nodes > 0 && h.reserved == 0;
+            h.n_layers <= PGCN_MAX_LAYERS && h.num_nodes > 0 && (h.flags & ~kCheckpointKnownFlags) == 0;
   const int L = ok ? (int)h.n_layers : 0;
   for (int l = 0; ok && l <= L; l++) ok = h.dims[l] > 0 && h.dims[l] <= (1 << 24);
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
@@ -109,6 +111,7 @@ Checkpoint read_checkpoint(const std::string &path) {
   ck.dims.assign(h.dims, h.dims + L + 1);
   ck.dropouts.assign(h.dropouts, h.dropouts + L);
   ck.seed = h.seed;
+  ck.flags = h.flags;
   ck.adam_steps = h.adam_steps;
   ck.draw_epochs = h.draw_epochs;
   ck.epochs = h.epochs;

@@ -3,10 +3,13 @@
 // One little-endian file: a fixed 216-byte header, then the payload.
 //   header   char magic[8] "PGCNCK01"; u32 version (1); u32 n_layers; i64 num_nodes;
 //            i32 dims[18] (input, hidden..., output; the rest 0); f32 dropouts[16];
-//            u32 seed; u32 reserved (0); i64 adam_steps; i64 draw_epochs; i64 epochs;
+//            u32 seed; u32 flags; i64 adam_steps; i64 draw_epochs; i64 epochs;
 //            i64 n_results; i64 n_weights; u64 checksum
 //   payload  f32 results[n_results][4]; f32 weights[n_weights]; f32 m[n_weights];
 //            f32 v[n_weights]                     (tensors in layer order, row-major)
+// flags: bit 0 = saved by an engine with residual layers (a plain engine writes 0, the word
+// older libraries require to be 0: they reject flagged files); any other bit is unknown to
+// this library and the file is rejected.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
@@ -20,6 +23,8 @@ namespace pgcn {
 
 constexpr int kCheckpointVersion = 1;
 constexpr int kCheckpointMaxResults = 1024;  // the engine's results ring
+constexpr unsigned kCheckpointResidual = 1u;  // header flags, bit 0
+constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual;
 
 struct Checkpoint {
   int n_layers = 0;
@@ -27,6 +32,7 @@ struct Checkpoint {
   std::vector<int> dims;        // n_layers + 1
   std::vector<float> dropouts;  // n_layers
   unsigned seed = 0;
+  unsigned flags = 0;  // kCheckpoint* bits
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   std::vector<float> w, m, v;  // every weight tensor in layer order

@@ -756,22 +756,32 @@ void GCN::fuse_epilogues() {
       auto *relu = dynamic_cast<ReLU *>(modules[i + 1].get());
       if (relu && relu->variable() == out) {
         gs->fwd_relu = relu;
-        auto *drop = i + 2 < n ? dynamic_cast<Dropout *>(modules[i + 2].get()) : nullptr;
+        // (a residual layer's ResidualConnection sits between the ReLU and the Dropout)
+        auto *res = i + 2 < n ? dynamic_cast<ResidualConnection *>(modules[i + 2].get()) : nullptr;
+        if (res && res->current() == out && res->previous()->ld == out->ld) gs->fwd_res = res;
+        const size_t di = i + (gs->fwd_res ? 3 : 2);
+        auto *drop = di < n ? dynamic_cast<Dropout *>(modules[di].get()) : nullptr;
+        if (res && !gs->fwd_res) drop = nullptr;  // (an add the tail cannot take stays in order)
         if (drop && drop->variable() == out) gs->fwd_drop = drop;
         fused_tails_++;
         // the next forward module reading `out` is a GraphSum (the reassociated output layer)
-        const size_t k = i + (gs->fwd_drop ? 3 : 2);
+        const size_t k = di + (gs->fwd_drop ? 1 : 0);
         auto *next = k < n ? dynamic_cast<GraphSum *>(modules[k].get()) : nullptr;
         if (next && next->input() == out) gs->fwd_next = next;
       }
     }
     if (i >= 1 && in->ld == in->cols) {
       auto *drop = dynamic_cast<Dropout *>(modules[i - 1].get());
-      const size_t ri = drop && drop->variable() == in ? i - 2 : i - 1;
+      const bool has_drop = drop && drop->variable() == in;
+      size_t ri = has_drop ? i - 2 : i - 1;
+      // (a residual layer: the ResidualConnection between them launches nothing in backward;
+      // the epilogue keeps the unmasked gradient for the skip path, GsEpilogue::res)
+      auto *res = ri < n ? dynamic_cast<ResidualConnection *>(modules[ri].get()) : nullptr;
+      if (res && res->current() == in) ri--;
       auto *relu = ri < n ? dynamic_cast<ReLU *>(modules[ri].get()) : nullptr;
       if (relu && relu->variable() == in) {
         gs->bwd_relu = relu;
-        if (ri + 1 < i) gs->bwd_drop = drop;
+        if (has_drop) gs->bwd_drop = drop;
         fused_tails_++;
         // the next backward after ReLU(in)'s is a GraphSum's whose output is `in`
         auto *next = ri >= 1 ? dynamic_cast<GraphSum *>(modules[ri - 1].get()) : nullptr;
@@ -792,6 +802,9 @@ void GCN::fuse_matmul_tails() {
     if (!mm || mm->input()->ld != mm->input()->cols) continue;
     const Variable *a = mm->input(), *c = mm->output();
     if (!xstream_ok(a->cols, c->cols) || xstream_ring_ok(c->cols, c->ld)) continue;
+    // next to a ResidualConnection the skip gradient is added between the product and these
+    // tails (Matmul::add_skip_grad): they stay modules of their own
+    if (a->skip_from || a->dev_grad_z) continue;
     auto *drop = dynamic_cast<Dropout *>(modules[i - 1].get());
     if (drop && drop->variable() != a) drop = nullptr;
     const size_t ri = drop ? i - 2 : i - 1;
@@ -850,6 +863,13 @@ void GCN::insert_layer(int in_dim, int out_dim, float dropout, int layer) {
   variables.push_back(var2);
   modules.push_back(std::make_unique<GraphSum>(var1, var2, graph.get(), out_dim, &ctx));
   modules.push_back(std::make_unique<ReLU>(var2));
+  // residual layer: var2 = relu(Â (prev W)) + prev, prev as this layer read it (equal widths
+  // only, as the reference's ResidualConnection; no projection)
+  if (params.residual && in_dim == out_dim) {
+    auto res = std::make_unique<ResidualConnection>(prev, var2);
+    residuals_.push_back(res.get());
+    modules.push_back(std::move(res));
+  }
 }
 
 // src/gcn.cu:116-142
@@ -1409,6 +1429,12 @@ void GCN::run(bool verbose) {
   }
 }
 
+int GCN::fused_residuals() const {
+  int n = 0;
+  for (const ResidualConnection *r : residuals_) n += r->last_fused ? 1 : 0;
+  return n;
+}
+
 bool GCN::graphsum_lds() const {
   if (graph) return graph->uses_lds(16);
   return !chunk_graphs.empty() && chunk_graphs.front()->uses_lds(16);
@@ -1487,6 +1513,7 @@ void GCN::save(const std::string &path) {
   ck.dims.push_back(params.output_dim);
   ck.dropouts = params.dropouts;
   ck.seed = params.seed;
+  ck.flags = residuals_.empty() ? 0u : kCheckpointResidual;
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1507,7 +1534,8 @@ void GCN::load(const std::string &path, int flags) {
   for (int l = 0; same && l + 1 < L; l++)
     same = ck.dims[(size_t)l + 1] == params.hidden_dims[(size_t)l];
   if (same && resume) {
-    same = ck.seed == params.seed;
+    // (a weights-only load ignores the residual flag: the tensors have the same shapes)
+    same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty();
     for (int l = 0; same && l < L; l++) same = ck.dropouts[(size_t)l] == params.dropouts[(size_t)l];
   }
   PGCN_CHECK(same, PGCN_E_INVALID, "load: the checkpoint is for another model");

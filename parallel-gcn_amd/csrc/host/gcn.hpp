@@ -37,6 +37,9 @@ struct GCNParams {
   // (hidden < classes); exact algebra, fp32 rounding order only (see insert_last_layer)
   bool reassociate_last = false;
   unsigned seed = 0;  // PART2 `seed`: 0 = hpdga's unseeded rand(), else srand(seed)
+  // middle layers whose width equals the layer before get a ResidualConnection after their
+  // ReLU: H_l = relu(Â (A_{l-1} W_l)) + A_{l-1} (insert_layer)
+  bool residual = false;
 };
 
 struct AdamParams {
@@ -143,6 +146,9 @@ class GCN {
   // the output layer runs as (Â H) W (reassociate_last requested, hidden < classes, Â symmetric)
   bool reassociated() const { return reassociated_; }
   int fused_tails() const { return fused_tails_; }
+  int residual_layers() const { return (int)residuals_.size(); }
+  // ... of which the last training forward ran inside a GraphSum's final write
+  int fused_residuals() const;
 
  private:
   void build(const GCNData &data);
@@ -166,6 +172,7 @@ class GCN {
   // mask_xstream: the next training forward's masks drawn by eval's first-layer product
   bool mask_in_eval() const;
   void join_side();
+  std::vector<const ResidualConnection *> residuals_;
   int fused_tails_ = 0;  // GraphSum epilogues carrying ReLU / Dropout work (forward + backward)
   void set_split(int split);
   // the eval forward of predict(): every row, no labels, no results slot; the logits stay in

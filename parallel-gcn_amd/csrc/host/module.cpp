@@ -449,6 +449,11 @@ GsEpilogue GraphSum::forward_epilogue(bool training, const Stream &s, const DevG
     e.drop_cols = out->cols;
     e.drop_scale = fwd_drop->scale();
   }
+  if (fwd_res) {  // ResidualConnection: out = relu(out) + prev, before the dropout and the table
+    e.res = const_cast<float *>(fwd_res->previous()->dev_data.get());  // (read only)
+    e.res_ld = fwd_res->previous()->ld;
+    fwd_res->skip_forward = true;
+  }
   fwd_relu->skip_forward = true;
   if (fwd_next) stage_next(e, fwd_next, fwd_next->forward_table_graph(), true);
   return e;
@@ -471,8 +476,16 @@ GsEpilogue GraphSum::backward_epilogue(const DevGraph *g) const {
     bwd_drop->skip_backward = true;
   }
   bwd_relu->skip_backward = true;
+  if (in->dev_grad_z) {  // residual layer: in.grad keeps the unmasked gradient
+    e.res = in->dev_grad.get();
+    e.res_ld = in->ld;
+  }
   if (bwd_next) stage_next(e, bwd_next, bwd_next->backward_table_graph(), false);
   return e;
+}
+
+float *GraphSum::backward_dst(const GsEpilogue &e) const {
+  return e.mode == 2 && e.res ? in->dev_grad_z.get() : in->dev_grad.get();
 }
 
 void GraphSum::run(const float *src, float *dst, const Stream &s, int mode,
@@ -645,13 +658,15 @@ void GraphSum::backward(const Stream &s) const {
     // edge-cut: out.grad is zero outside the training split's rows, so each chunk graph keeps
     // only the edges from those columns (all rows stay: the partials are written whole)
     const GsEpilogue epi = backward_epilogue(ctx->chunk_col_graphs[0]);
-    run(out->dev_grad.get(), in->dev_grad.get(), s, 2, &epi, pre);
+    run(out->dev_grad.get(), backward_dst(epi), s, 2, &epi, pre);
     return;
   }
   DevGraph *cg = last_layer && !ctx->comm ? ctx->split_colgraph : nullptr;
   if (!cg) {
     const GsEpilogue epi = backward_epilogue(graph);
-    run(out->dev_grad.get(), in->dev_grad.get(), s, 0, &epi, pre);
+    // (a residual layer's out.grad stays unmasked: its ReLU backward wrote dev_grad_z)
+    const float *src = out->dev_grad_z ? out->dev_grad_z.get() : out->dev_grad.get();
+    run(src, backward_dst(epi), s, 0, &epi, pre);
     return;
   }
   // output layer: out.grad is the loss gradient, zero outside the split's labelled rows, so
@@ -666,7 +681,7 @@ void GraphSum::backward(const Stream &s) const {
   // as its columns directly; else it gathers them from the full rows)
   const float *g_in = ctx->compact_n ? ctx->compact_z->dev_grad.get() : out->dev_grad.get();
   const GsEpilogue epi = backward_epilogue(cg);
-  cg->graphsum(g_in, out->ld, in->dev_grad.get(), in->ld, dim, s.get(), ctx->compact_n > 0, &epi,
+  cg->graphsum(g_in, out->ld, backward_dst(epi), in->ld, dim, s.get(), ctx->compact_n > 0, &epi,
                pre);
   if (ctx->profile) {
     e1.record(s.get());
@@ -696,8 +711,47 @@ void ReLU::backward(const Stream &s) const {
     skip_backward = false;
     return;
   }
-  launch_relu_bwd(in->dev_grad.get(), (long long)in->rows * in->ld, mask.get(), s.get());
+  if (in->dev_grad_z)  // residual layer: dev_grad stays the gradient of the sum
+    launch_relu_bwd_to(in->dev_grad.get(), (long long)in->rows * in->ld, mask.get(),
+                       in->dev_grad_z.get(), s.get());
+  else
+    launch_relu_bwd(in->dev_grad.get(), (long long)in->rows * in->ld, mask.get(), s.get());
 }
+
+// ------------------------------------------------------------------------------------------
+// ResidualConnection (src/module.cu:566-593)
+// ------------------------------------------------------------------------------------------
+ResidualConnection::ResidualConnection(shared_ptr<Variable> prev_, shared_ptr<Variable> current_)
+    : prev(std::move(prev_)), cur(std::move(current_)) {
+  PGCN_CHECK(prev && cur && prev != cur, PGCN_E_INVALID, "residual: two distinct variables");
+  PGCN_CHECK(prev->rows == cur->rows && prev->cols == cur->cols && prev->ld == cur->ld,
+             PGCN_E_INVALID, "residual: prev and current must have the same size");
+  PGCN_CHECK(!prev->skip_from && !cur->dev_grad_z, PGCN_E_INVALID,
+             "residual: one connection per variable pair");
+  if (prev->dev_grad && cur->dev_grad) {
+    cur->dev_grad_z.allocate(cur->dev_grad.size());
+    cur->dev_grad_z.zero();
+    prev->skip_from = cur.get();
+  }
+}
+
+ResidualConnection::~ResidualConnection() {
+  if (prev->skip_from == cur.get()) prev->skip_from = nullptr;
+}
+
+void ResidualConnection::forward(bool training, const Stream &s) const {
+  if (skip_forward) {  // added by the GraphSum before it (epilogue)
+    skip_forward = false;
+    if (training) last_fused = true;
+    return;
+  }
+  if (training) last_fused = false;
+  launch_residual_fwd(cur->dev_data.get(), prev->dev_data.get(), (long long)cur->rows * cur->ld,
+                      s.get());
+}
+
+// prev.grad += current.grad is made by the Matmul that writes prev.grad (Variable::skip_from)
+void ResidualConnection::backward(const Stream &) const {}
 
 // ------------------------------------------------------------------------------------------
 // Matmul (src/module.cu:270-472; hpdga module.cpp:13-38)
@@ -718,6 +772,15 @@ void Matmul::forward(bool training, const Stream &s) const {
 void Matmul::backward_input(const Stream &s) const {
   launch_gemm_nn(m, n, p, c->dev_grad.get(), c->ld, b->dev_data.get(), b->ld, 1, a->dev_grad.get(),
                  a->ld, nullptr, 0, 0, 1.0f, s.get());
+  add_skip_grad(s);
+}
+
+// a is the `prev` of a ResidualConnection: a.grad += current.grad (the unmasked gradient of
+// relu(Z) + a), one element-wise launch over this rank's rows
+void Matmul::add_skip_grad(const Stream &s) const {
+  if (!a->skip_from || !a->dev_grad) return;
+  launch_residual_bwd(a->dev_grad.get(), a->skip_from->dev_grad.get(), (long long)m * a->ld,
+                      s.get());
 }
 
 void Matmul::backward_weight(hipStream_t s, void *ws) const {
@@ -746,7 +809,9 @@ void Matmul::backward(const Stream &s) const {
   }
   // a.grad = c.grad * b^T   (b stored [n][p] => trans_b); the Dropout / ReLU backward on a
   // in its final write when gemm_nn would take k_xstream_nn anyway (same product, same bits)
-  if (!a_done && bwd_relu && !cmp && A.ld == n && xstream_ok(n, p) && !xstream_ring_ok(p, C.ld)) {
+  // (not next to a ResidualConnection: the skip gradient comes between the product and the tail)
+  if (!a_done && bwd_relu && !cmp && !A.skip_from && !A.dev_grad_z && A.ld == n &&
+      xstream_ok(n, p) && !xstream_ring_ok(p, C.ld)) {
     XsEpilogue e;
     if (bwd_drop) {
       e.bwd_drop = bwd_drop->state().mask.get();
@@ -762,6 +827,7 @@ void Matmul::backward(const Stream &s) const {
     launch_gemm_nn(rows, n, p, C.dev_grad.get(), C.ld, b->dev_data.get(), b->ld, 1,
                    A.dev_grad.get(), A.ld, nullptr, 0, 0, 1.0f, s.get());
   }
+  if (!cmp) add_skip_grad(s);
   // b.grad = a^T * c.grad (deterministic split-M reduction)
   if (!side && !b_done)
     launch_gemm_tn(rows, p, n, A.dev_data.get(), A.ld, C.dev_grad.get(), C.ld, b->dev_grad.get(),

@@ -1,7 +1,7 @@
 // parallel-gcn_amd/csrc/host/module.hpp -- Variable and the Module family.
 //
 // Same classes, constructor shapes and forward/backward contract as the reference's
-// include/variable.cuh:11-29 and include/module.cuh:21-145:
+// include/variable.cuh:11-29 and include/module.cuh:21-161:
 //   virtual void forward(bool training, const Stream &) const;
 //   virtual void backward(const Stream &) const;
 // Each module launches its HIP kernels asynchronously on the stream it is given; data
@@ -30,6 +30,13 @@ using std::shared_ptr;
 class Variable {
  public:
   DeviceBuffer<float> dev_data, dev_grad;
+  // ResidualConnection(prev, current) links its two variables (module.hpp, ResidualConnection):
+  //   current->dev_grad_z: the ReLU backward on `current` writes its masked gradient here and
+  //     leaves dev_grad -- the gradient of relu(Z) + prev -- as it is; the GraphSum backward
+  //     that produced `current` reads dev_grad_z;
+  //   prev->skip_from = current: the Matmul that writes prev.grad adds current.grad to it.
+  DeviceBuffer<float> dev_grad_z;
+  const Variable *skip_from = nullptr;
   int rows = 0, cols = 0, ld = 0;
   long long size = 0;  // logical rows * cols
   Variable(int rows_, int cols_, bool requires_grad, int ld_ = -1);
@@ -91,6 +98,7 @@ class Module {
 class ReLU;
 class GraphSum;
 class Dropout;
+class ResidualConnection;
 
 // "fuse_epilogue" bits (host/gcn.cpp g_fuse_epilogue) and "fuse_output" (g_fuse_output)
 constexpr int kFuseTails = 1, kFusePrestage = 2, kFuseXstream = 4, kFuseMatmulTails = 8;
@@ -290,6 +298,7 @@ class GraphSum : public Module {
   // modules run on their own): forward, the ReLU (and Dropout) on `out` that follow it;
   // backward, the Dropout (and ReLU) on `in` whose backward follows it
   ReLU *fwd_relu = nullptr;
+  const ResidualConnection *fwd_res = nullptr;  // between that ReLU and that Dropout
   const Dropout *fwd_drop = nullptr;
   ReLU *bwd_relu = nullptr;
   const Dropout *bwd_drop = nullptr;
@@ -324,6 +333,9 @@ class GraphSum : public Module {
   bool tail_ok(const DevGraph *g, int ld_in, int ld_out) const;
   GsEpilogue forward_epilogue(bool training, const Stream &s, const DevGraph *g) const;
   GsEpilogue backward_epilogue(const DevGraph *g) const;
+  // where this call's backward writes in.grad: in.dev_grad_z when the fused tail masks it for a
+  // residual layer's ReLU (the epilogue stores the unmasked gradient to in.dev_grad: GsEpilogue::res)
+  float *backward_dst(const GsEpilogue &e) const;
 };
 
 // include/module.cuh:90-99
@@ -338,6 +350,25 @@ class ReLU : public Module {
   const Variable *variable() const { return in.get(); }
   uint8_t *mask_ptr() const { return const_cast<uint8_t *>(mask.get()); }
   mutable bool skip_forward = false, skip_backward = false;  // done by a GraphSum epilogue
+};
+
+// include/module.cuh:149-161: current += prev, "works only if hidden dimension are the same".
+// The reference's backward is empty (and its GCN never inserts the module); here the skip
+// gradient prev.grad += current.grad is real.  Matmul::backward overwrites prev.grad after this
+// module's place in the reverse order, so the add is made there (Variable::skip_from), from
+// current.grad kept unmasked (Variable::dev_grad_z): this module's own backward launches nothing.
+class ResidualConnection : public Module {
+  shared_ptr<Variable> prev, cur;
+
+ public:
+  ResidualConnection(shared_ptr<Variable> prev_, shared_ptr<Variable> current_);
+  ~ResidualConnection() override;
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+  const Variable *previous() const { return prev.get(); }
+  const Variable *current() const { return cur.get(); }
+  mutable bool skip_forward = false;  // done by a GraphSum epilogue
+  mutable bool last_fused = false;    // ... in the last training forward
 };
 
 // include/module.cuh:103-124: c = a * b
@@ -369,6 +400,9 @@ class Matmul : public Module {
   // caller when the stream is not the module's usual one)
   void backward_input(const Stream &s) const;
   void backward_weight(hipStream_t s, void *ws) const;
+
+ private:
+  void add_skip_grad(const Stream &s) const;
 };
 
 // include/module.cuh:128-145

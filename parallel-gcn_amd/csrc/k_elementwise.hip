@@ -132,6 +132,35 @@ __global__ __launch_bounds__(256) void k_relu_bwd(float *__restrict__ g, long lo
     if (!mask[i]) g[i] = 0.0f;
 }
 
+// ReLU backward out of place: z = mask ? g : 0, g kept (a residual layer's var2.grad stays the
+// gradient of the sum, which the skip path adds to prev.grad; the GraphSum backward reads z)
+__global__ __launch_bounds__(256) void k_relu_bwd_to(const float *__restrict__ g, long long n,
+                                                     const uint8_t *__restrict__ mask,
+                                                     float *__restrict__ z) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x)
+    z[i] = mask[i] ? g[i] : 0.0f;
+}
+
+// ResidualConnection (reference src/module.cu:566-593, current += prev): y[i] += x[i], one fp32
+// add per element; the same kernel adds the skip gradient (prev.grad += current.grad).
+// n4 float4s when both pointers are 16-byte aligned (else 0), then the scalar rest.
+__global__ __launch_bounds__(256) void k_add_into(float *y, const float *x, long long n4,
+                                                  long long n) {
+  const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = t0; i < n4; i += stride) {
+    float4 a = reinterpret_cast<float4 *>(y)[i];
+    const float4 b = reinterpret_cast<const float4 *>(x)[i];
+    a.x += b.x;
+    a.y += b.y;
+    a.z += b.z;
+    a.w += b.w;
+    reinterpret_cast<float4 *>(y)[i] = a;
+  }
+  for (long long i = 4 * n4 + t0; i < n; i += stride) y[i] += x[i];
+}
+
 // ------------------------------------------------------------------------------------------
 // Block reductions (wave64 shuffles, fixed tree => deterministic)
 // ------------------------------------------------------------------------------------------
@@ -950,6 +979,27 @@ void launch_relu_fwd(float *x, long long n, uint8_t *mask, int training, hipStre
 void launch_relu_bwd(float *g, long long n, const uint8_t *mask, hipStream_t s) {
   if (n <= 0) return;
   PGCN_LAUNCH(k_relu_bwd, dim3(grid_for(n)), dim3(256), 0, s, g, n, mask);
+}
+
+void launch_relu_bwd_to(const float *g, long long n, const uint8_t *mask, float *z,
+                        hipStream_t s) {
+  if (n <= 0) return;
+  PGCN_LAUNCH(k_relu_bwd_to, dim3(grid_for(n)), dim3(256), 0, s, g, n, mask, z);
+}
+
+static void launch_add_into(float *y, const float *x, long long n, hipStream_t s) {
+  if (n <= 0) return;
+  const bool al = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+  const long long n4 = al ? n / 4 : 0;
+  PGCN_LAUNCH(k_add_into, dim3(grid_for(std::max(n4, n - 4 * n4))), dim3(256), 0, s, y, x, n4, n);
+}
+
+void launch_residual_fwd(float *cur, const float *prev, long long n, hipStream_t s) {
+  launch_add_into(cur, prev, n, s);
+}
+
+void launch_residual_bwd(float *prev_grad, const float *cur_grad, long long n, hipStream_t s) {
+  launch_add_into(prev_grad, cur_grad, n, s);
 }
 
 int xent_blocks(int n) { return (int)ceil_div(n, XR); }

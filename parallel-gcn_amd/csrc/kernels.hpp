@@ -326,6 +326,11 @@ void launch_dropout_apply_based(float *x, long long n, const uint64_t *mask, lon
                                 float scale, hipStream_t s);
 void launch_relu_fwd(float *x, long long n, uint8_t *mask, int training, hipStream_t s);
 void launch_relu_bwd(float *g, long long n, const uint8_t *mask, hipStream_t s);
+// z = mask ? g : 0 with g kept (a residual layer's ReLU backward)
+void launch_relu_bwd_to(const float *g, long long n, const uint8_t *mask, float *z, hipStream_t s);
+// ResidualConnection, unfused: cur += prev; prev_grad += cur_grad (one fp32 add per element)
+void launch_residual_fwd(float *cur, const float *prev, long long n, hipStream_t s);
+void launch_residual_bwd(float *prev_grad, const float *cur_grad, long long n, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's
