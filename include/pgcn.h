@@ -473,6 +473,70 @@ int pgcn_debug_exp_check(const float *x, long long n, float *mine, float *lib, v
  * division below 2^-125); device pointers */
 int pgcn_debug_div_check(const float *a, const float *b, long long n, float *q, void *stream);
 
+/* --- the loss kernel family, every argument exposed (kernel tests) ----------------------
+ * Arguments are checked before anything touches the device (PGCN_E_INVALID); n = 0 (n_blocks =
+ * 0 for the reductions) is PGCN_OK and launches nothing.  Device pointers throughout. */
+/* The pass's scalars finished by the loss kernel's last block instead of pgcn_finalize: every
+ * block stores {loss, wrong, its slice of sum w^2, 0} to part4[block] (16 B each) and arrives on
+ * *ticket; the last one sums them and writes out2 = {loss / count + wd * sum w^2 / 2, (count -
+ * wrong) / count} (with ctr, a device {step, epoch} pair: at out2 + 4 * (ctr[1] % ring_cap)),
+ * sums = {loss, wrong} when given, and zeroes the ticket.  group > 0: two levels -- blocks
+ * arrive in groups of `group` on gticket[16 g], a group's last block sums its partials into
+ * gpart4[g] (16 B each) and arrives on *ticket; ceil(blocks / group) groups.  ticket and
+ * gticket must be zero before the first launch; w may be NULL when n_w = 0. */
+typedef struct {
+  const float *w;
+  long long n_w;
+  float wd;
+  float *out2;
+  const int *ctr;
+  int ring_cap;
+  float *sums;
+  unsigned int *ticket;
+  void *part4;
+  int group;
+  unsigned int *gticket;
+  void *gpart4;
+} pgcn_xent_final;
+/* rows per slice of the ring GraphSum's prescaled table (the layout pgcn_debug_out_xent's
+ * table is written in) */
+int pgcn_debug_ring_slice_rows(void);
+/* pgcn_xent_fwd with write_back (0: the logits buffer is left untouched) and the fused finish
+ * (NULL: none).  1 <= c <= ld <= 124, ld a multiple of 4; grad may be NULL when !training. */
+int pgcn_debug_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c,
+                        int count, int training, float *partials, int write_back,
+                        const pgcn_xent_final *fin, void *stream);
+/* The output layer fused into the loss: logits = H W (H [n][ldh], 1 <= kh <= 16 columns; W
+ * [kh][ldw]) written max-shifted on labelled rows, then pgcn_xent_fwd's loss / grad / partials
+ * (1 <= c <= ld <= 116, ld a multiple of 4).  training with dH: dH [n][lddh] = grad W^T, columns
+ * [kh, min(16, lddh)) zero, lddh >= kh.  training with dWp (ld <= 48): per-block partials
+ * [pgcn_xent_blocks(n)][kh][48] of H^T grad, columns [c, 48) zero, for
+ * pgcn_debug_tn_reduce_blocks.  training with dH and table (kh = 16, scale given): float4
+ * (p / S) * 4 S + v * S + p % S of table = scale[p] * dH[i][4 v .. 4 v + 3] for v < 4, with S =
+ * pgcn_debug_ring_slice_rows() and p = pos[i] (skipped when < 0), or p = i for i < table_rows
+ * when pos is NULL.  fin as above (NULL: none). */
+int pgcn_debug_out_xent(const float *H, int ldh, int kh, const float *W, int ldw, float *logits,
+                        int ld, float *grad, const int *truth, int n, int c, int count,
+                        int training, float *partials, float *dH, int lddh, float *dWp,
+                        float *table, const float *scale, const int *pos, int table_rows,
+                        const pgcn_xent_final *fin, void *stream);
+/* pgcn_finalize's launch with the results-ring slot: out2 (2 floats written) at out2 + 4 *
+ * (ctr[1] % ring_cap) when ctr (a device {step, epoch} pair) is given; sums (may be NULL) =
+ * {loss sum, wrong}. */
+int pgcn_debug_finalize_ring(const float *partials, int n_blocks, int count, const float *w_l2,
+                             long long n_l2, float weight_decay, float *out2, const int *ctr,
+                             int ring_cap, float *sums, void *stream);
+/* C [K][ldc] (columns [N, ldc) zero) = the n_blocks partials [K][ldp] summed in a fixed order:
+ * groups of spg consecutive partials in order, then the group sums in order, spg the smallest
+ * multiple of 16 with spg^2 >= n_blocks (one sequential pass when n_blocks <= spg).  `partial`
+ * holds pgcn_debug_tn_reduce_blocks_workspace bytes: the partials first, the group sums after
+ * them.  N <= ldc <= ldp.  The one-pass form sums n partials sequentially, no workspace. */
+size_t pgcn_debug_tn_reduce_blocks_workspace(int n_blocks, int K, int ldp);
+int pgcn_debug_tn_reduce_blocks(float *partial, int n_blocks, int K, int N, int ldp, float *C,
+                                int ldc, void *stream);
+int pgcn_debug_tn_reduce_one_pass(const float *partial, int n, int K, int N, int ldp, float *C,
+                                  int ldc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,14 @@ class PgcnData(ctypes.Structure):
                 ("feat_values", P(c_float)), ("label", P(c_int)), ("split", P(c_int))]
 
 
+class PgcnXentFinal(ctypes.Structure):
+    """pgcn_xent_final: the loss kernel's fused finish (device pointers as integers)."""
+    _fields_ = [("w", c_void_p), ("n_w", c_ll), ("wd", c_float), ("out2", c_void_p),
+                ("ctr", c_void_p), ("ring_cap", c_int), ("sums", c_void_p),
+                ("ticket", c_void_p), ("part4", c_void_p), ("group", c_int),
+                ("gticket", c_void_p), ("gpart4", c_void_p)]
+
+
 def _sig(name, res, *args):
     if os.environ.get("PGCN_LIB") and not hasattr(lib, name):
         return None  # an A/B build from before this entry point: the bench does not call it
@@ -160,6 +168,19 @@ _sig("pgcn_debug_path_count", c_ll, ctypes.c_char_p, c_int)
 _sig("pgcn_debug_empty_launches", c_int, c_int, c_void_p)
 _sig("pgcn_debug_exp_check", c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_debug_div_check", c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p)
+_sig("pgcn_debug_ring_slice_rows", c_int)
+_sig("pgcn_debug_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+     c_int, c_void_p, c_int, P(PgcnXentFinal), c_void_p)
+_sig("pgcn_debug_out_xent", c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+     c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+     c_void_p, c_void_p, c_void_p, c_int, P(PgcnXentFinal), c_void_p)
+_sig("pgcn_debug_finalize_ring", c_int, c_void_p, c_int, c_int, c_void_p, c_ll, c_float,
+     c_void_p, c_void_p, c_int, c_void_p, c_void_p)
+_sig("pgcn_debug_tn_reduce_blocks_workspace", c_size_t, c_int, c_int, c_int)
+_sig("pgcn_debug_tn_reduce_blocks", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+     c_void_p)
+_sig("pgcn_debug_tn_reduce_one_pass", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+     c_int, c_void_p)
 _sig("pgcn_debug_lds_check", c_int, c_int, c_int, c_void_p, c_void_p, c_int, P(ctypes.c_double),
      P(c_ll))
 _sig("pgcn_debug_lds_counts", c_ll, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll,
@@ -637,4 +658,7 @@ EXPORTED = [
     "pgcn_dataset_free", "pgcn_partition_bounds", "pgcn_partition_subgraph", "pgcn_debug_set",
     "pgcn_debug_lds_check", "pgcn_debug_lds_counts", "pgcn_debug_path_count",
     "pgcn_debug_empty_launches", "pgcn_debug_exp_check", "pgcn_debug_div_check",
+    "pgcn_debug_ring_slice_rows", "pgcn_debug_xent_fwd", "pgcn_debug_out_xent",
+    "pgcn_debug_finalize_ring", "pgcn_debug_tn_reduce_blocks_workspace",
+    "pgcn_debug_tn_reduce_blocks", "pgcn_debug_tn_reduce_one_pass",
 ]

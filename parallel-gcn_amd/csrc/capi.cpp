@@ -977,6 +977,137 @@ int pgcn_debug_div_check(const float *a, const float *b, long long n, float *q, 
   });
 }
 
+// ---------------------------------------------------------------- loss kernel family (tests)
+}  // extern "C"
+
+namespace {
+// the C mirror of XentFinal, checked as the launchers check theirs (and ring_cap, n_w)
+void check_final(const pgcn_xent_final *f, const char *what) {
+  if (!f) return;
+  PGCN_CHECK(f->ticket && f->part4 && f->out2, PGCN_E_INVALID, what);
+  PGCN_CHECK(f->group >= 0 && (f->group == 0 || (f->gticket && f->gpart4)), PGCN_E_INVALID, what);
+  PGCN_CHECK(f->n_w >= 0 && (f->n_w == 0 || f->w) && (!f->ctr || f->ring_cap >= 1),
+             PGCN_E_INVALID, what);
+}
+XentFinal to_final(const pgcn_xent_final &f) {
+  XentFinal x;
+  x.w = f.w;
+  x.n_w = f.n_w;
+  x.wd = f.wd;
+  x.out2 = f.out2;
+  x.ctr = f.ctr;
+  x.ring_cap = f.ctr ? f.ring_cap : 1;
+  x.sums = f.sums;
+  x.ticket = f.ticket;
+  x.part4 = static_cast<float4 *>(f.part4);
+  x.group = f.group;
+  x.gticket = f.gticket;
+  x.gpart4 = static_cast<float4 *>(f.gpart4);
+  return x;
+}
+}  // namespace
+
+extern "C" {
+
+int pgcn_debug_ring_slice_rows(void) { return RING_SR; }
+
+int pgcn_debug_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c,
+                        int count, int training, float *partials, int write_back,
+                        const pgcn_xent_final *fin, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && c >= 1 && c <= ld && ld <= 124 && ld % 4 == 0 && count >= 0,
+               PGCN_E_INVALID, "debug_xent_fwd: 1 <= c <= ld <= 124, ld % 4 == 0");
+    PGCN_CHECK(n == 0 || (logits && truth && partials && (grad || !training)), PGCN_E_INVALID,
+               "debug_xent_fwd: null argument");
+    check_final(fin, "debug_xent_fwd: the finish needs its ticket, partials and output");
+    if (n == 0) return;
+    XentFinal xf;
+    if (fin) xf = to_final(*fin);
+    launch_xent_fwd(logits, ld, grad, truth, n, c, count, training, partials, as_stream(stream),
+                    write_back != 0, fin ? &xf : nullptr);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_out_xent(const float *H, int ldh, int kh, const float *W, int ldw, float *logits,
+                        int ld, float *grad, const int *truth, int n, int c, int count,
+                        int training, float *partials, float *dH, int lddh, float *dWp,
+                        float *table, const float *scale, const int *pos, int table_rows,
+                        const pgcn_xent_final *fin, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && kh >= 1 && kh <= 16 && ldh >= kh, PGCN_E_INVALID,
+               "debug_out_xent: 1 <= kh <= 16, ldh >= kh");
+    PGCN_CHECK(c >= 1 && c <= ld && ld <= 116 && ld % 4 == 0 && ldw >= c && count >= 0,
+               PGCN_E_INVALID, "debug_out_xent: 1 <= c <= ld <= 116, ld % 4 == 0, ldw >= c");
+    PGCN_CHECK(!dH || lddh >= kh, PGCN_E_INVALID, "debug_out_xent: lddh >= kh");
+    PGCN_CHECK(!dWp || ld <= 48, PGCN_E_INVALID,
+               "debug_out_xent: the weight-grad partial needs <= 48 classes");
+    PGCN_CHECK(!table || (kh == 16 && scale && dH && (pos || table_rows >= 0)), PGCN_E_INVALID,
+               "debug_out_xent: a prescaled table of a 16-column dH");
+    PGCN_CHECK(n == 0 || (H && W && logits && truth && partials && (grad || !training)),
+               PGCN_E_INVALID, "debug_out_xent: null argument");
+    check_final(fin, "debug_out_xent: the finish needs its ticket, partials and output");
+    if (n == 0) return;
+    XentFinal xf;
+    if (fin) xf = to_final(*fin);
+    XentTable tb;
+    tb.table = table;
+    tb.scale = scale;
+    tb.pos = pos;
+    tb.rows = table_rows;
+    launch_out_xent(H, ldh, kh, W, ldw, logits, ld, grad, truth, n, c, count, training, partials,
+                    as_stream(stream), dH, lddh, dWp, table ? &tb : nullptr,
+                    fin ? &xf : nullptr);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_finalize_ring(const float *partials, int n_blocks, int count, const float *w_l2,
+                             long long n_l2, float weight_decay, float *out2, const int *ctr,
+                             int ring_cap, float *sums, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n_blocks >= 0 && n_l2 >= 0 && (n_l2 == 0 || w_l2) && (!ctr || ring_cap >= 1),
+               PGCN_E_INVALID, "debug_finalize_ring args");
+    PGCN_CHECK(n_blocks == 0 || (partials && out2), PGCN_E_INVALID,
+               "debug_finalize_ring: null argument");
+    if (n_blocks == 0) return;
+    launch_reduce_scalars(partials, n_blocks, w_l2, n_l2, sums, as_stream(stream), count,
+                          weight_decay, out2, ctr, ctr ? ring_cap : 1);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+size_t pgcn_debug_tn_reduce_blocks_workspace(int n_blocks, int K, int ldp) {
+  if (n_blocks < 0 || K < 1 || ldp < 1) return 0;
+  return tn_reduce_blocks_workspace(n_blocks, K, ldp);
+}
+
+int pgcn_debug_tn_reduce_blocks(float *partial, int n_blocks, int K, int N, int ldp, float *C,
+                                int ldc, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n_blocks >= 0 && K >= 1 && N >= 1 && N <= ldc && ldc <= ldp, PGCN_E_INVALID,
+               "debug_tn_reduce_blocks: K >= 1, 1 <= N <= ldc <= ldp");
+    PGCN_CHECK(n_blocks == 0 || (partial && C), PGCN_E_INVALID,
+               "debug_tn_reduce_blocks: null argument");
+    if (n_blocks == 0) return;
+    launch_tn_reduce_blocks(partial, n_blocks, K, N, ldp, C, ldc, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_tn_reduce_one_pass(const float *partial, int n, int K, int N, int ldp, float *C,
+                                  int ldc, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && K >= 1 && N >= 1 && N <= ldc && ldc <= ldp, PGCN_E_INVALID,
+               "debug_tn_reduce_one_pass: K >= 1, 1 <= N <= ldc <= ldp");
+    PGCN_CHECK(n == 0 || (partial && C), PGCN_E_INVALID,
+               "debug_tn_reduce_one_pass: null argument");
+    if (n == 0) return;
+    launch_tn_reduce_one_pass(partial, n, K, N, ldp, C, ldc, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 long long pgcn_debug_path_count(const char *name, int reset) {
   const bool thread = (reset & 2) != 0, zero = (reset & 1) != 0;
   if (reset & ~3) return PGCN_E_INVALID;
