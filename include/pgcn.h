@@ -152,6 +152,40 @@ int pgcn_relu_bwd(float *g, long long n, const uint8_t *mask, void *stream);
 int pgcn_residual_fwd(float *cur, const float *prev, long long n, void *stream);
 int pgcn_residual_bwd(float *prev_grad, const float *cur_grad, long long n, void *stream);
 
+/* --- LayerNorm over the columns of a node variable (new: the reference has no such module) -
+ * forward: y [n][ld_y] = gamma * xhat + beta with xhat = (x - mean_row(x)) * rstd and rstd =
+ * 1 / sqrtf(var_row(x) + eps), the biased variance over the d columns, mean and variance in two
+ * passes over the row.  1 <= d <= 1024; every ld a multiple of 4 and >= d; every row 16-byte
+ * aligned; gamma, beta [d].  The float4s covering columns [0, round_up4(d)) of y are written,
+ * zero from column d on; columns beyond them are left alone.  Padding columns of x are never
+ * read into the result.  x == y (in place) is allowed.  xhat [n][ld_xhat] and rstd [n] (both or
+ * neither; a training forward) receive the normalised rows and the row scales the backward
+ * reads.
+ * backward: dx = rstd * (g - mean_row(g) - xhat * mean_row(g * xhat)) with g = dy * gamma (dx
+ * == dy allowed); dgamma[c] = sum over the rows of dy * xhat, dbeta[c] = sum of dy.  The column
+ * sums go through per-workgroup partials in `workspace` (pgcn_layernorm_bwd_workspace(n, d)
+ * bytes) and one reducing launch, in an order that depends on (n, d) only: two calls give the
+ * same bits.  No float atomics.
+ * PGCN_E_INVALID for bad arguments (nothing is launched); n == 0 launches nothing; the calls are
+ * asynchronous on `stream`, allocate nothing and may be captured. */
+int pgcn_layernorm_fwd(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                       const float *gamma, const float *beta, float eps, float *xhat,
+                       int ld_xhat, float *rstd, void *stream);
+size_t pgcn_layernorm_bwd_workspace(int n, int d);
+int pgcn_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
+                       const float *rstd, const float *gamma, int n, int d, float *dx, int ld_dx,
+                       float *dgamma, float *dbeta, void *workspace, void *stream);
+/* The forward with the engine's fused tail in its final write (kernel tests): after the
+ * LayerNorm, pgcn_relu_fwd (relu_mask [n][relu_ld] bytes, NULL: no mask kept), pgcn_residual_fwd
+ * (res [n][res_ld], NULL: none) and pgcn_dropout_apply (keep bit drop_base + r * d + c of
+ * drop_mask, NULL: none), bit for bit.  Needs ld_y == d, relu_ld and res_ld multiples of 4 and
+ * >= d. */
+int pgcn_debug_layernorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                                  const float *gamma, const float *beta, float eps, float *xhat,
+                                  int ld_xhat, float *rstd, uint8_t *relu_mask, int relu_ld,
+                                  const float *res, int res_ld, const uint64_t *drop_mask,
+                                  long long drop_base, float drop_scale, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -209,7 +243,13 @@ typedef struct {
    * hpdga rand.cpp:6-14); else the xorshift state is the first two rand() values after
    * srand(seed).  Glorot init and every dropout mask follow from it. */
   unsigned int seed;
-  /* != 0: every middle layer 1 <= l <= n_layers - 2 whose width equals the layer before it
+  /* != 0: every hidden layer 0 <= l <= n_layers - 2 gets a LayerNorm between its
+   * GraphSum and its ReLU: H_l = relu(gamma_l * xhat + beta_l) [+ A], xhat the row-normalised
+   * Â (A W_l) (pgcn_layernorm_fwd, eps 1e-5).  gamma = 1 and beta = 0 at the start (no RNG
+   * draw: weights and dropout masks equal the plain engine's); Adam updates them without weight
+   * decay.  Hidden widths up to 1024.  0: the plain engine, bit for bit. */
+  int layer_norm;
+  /* (the struct's last member) != 0: every middle layer 1 <= l <= n_layers - 2 whose width equals the layer before it
    * (hidden_dims[l] == hidden_dims[l-1]) gets the reference's ResidualConnection after its ReLU
    * (include/module.cuh:149-161): H_l = relu(Â (A W_l)) + A, with A the layer's input as it
    * read it (in training, after that layer's Dropout), and a real backward (the reference's is
@@ -280,7 +320,11 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "eval_ax_us" (device time of the Â X precompute at engine build, µs; 0 when not used),
  * "residual_layers" (layers with a ResidualConnection, pgcn_params.residual) and
  * "fused_residuals" (how many of them the last training forward added inside a GraphSum's
- * final write instead of a launch of their own).
+ * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
+ * pgcn_params.layer_norm) and "fused_norm_tails" (how many of them ran the ReLU / residual add /
+ * Dropout behind them inside the LayerNorm kernel in the last training forward);
+ * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
+ * the normalised variables -- always 0).
  * Returns the value (>= 0) or PGCN_E_INVALID for an unknown key. */
 long long pgcn_gcn_query(pgcn_gcn *g, const char *key);
 /* GCN::train_epoch / GCN::eval (src/gcn.cu:293-343): out2 = {loss, accuracy} */
@@ -304,7 +348,14 @@ int pgcn_gcn_run(pgcn_gcn *g, int verbose);
  * grad (which = 1) is G = dLoss/dH_l, the gradient of that sum after the next layer's Dropout
  * backward, NOT masked by the layer's ReLU: the masked gradient G * [Z_l > 0] that the
  * GraphSum backward reads is kept in a buffer of the engine's own, so that G can be added to
- * the grad of var2 of layer l-1 when the layer's Matmul backward writes it. */
+ * the grad of var2 of layer l-1 when the layer's Matmul backward writes it.
+ * LayerNorm engines (pgcn_params.layer_norm) have one more variable, index 3 * n_layers + 1: the
+ * scale / shift tensor, per hidden layer gamma_l[d_l] then beta_l[d_l], layers in order (which =
+ * 1: its gradient); pgcn_gcn_num_vars is 3 * n_layers + 2 for them.  pgcn_gcn_set_var accepts
+ * it.  The LayerNorm backward transforms in place the buffer the layer's GraphSum backward
+ * reads: after a training epoch the grad of var2 of such a layer is dLoss/dZ, the gradient with
+ * respect to the GraphSum's output (on a residual layer that buffer is the engine's own masked
+ * one, and var2's grad stays G as above). */
 long long pgcn_gcn_get_var(pgcn_gcn *g, int idx, int which, float *host_dst);
 int pgcn_gcn_num_vars(pgcn_gcn *g);
 /* Weights only (idx must be a weight variable, which == 0), in get_var's layout and count;
@@ -325,18 +376,26 @@ int pgcn_gcn_save(pgcn_gcn *g, const char *path);
  * count, results and dropout position kept.
  * PGCN_E_INVALID: the file is for another model (dims, num_nodes; for flags 0 also seed,
  * dropouts and whether the model is residual -- a weights-only load ignores that flag, the
- * tensors having the same shapes, so a plain model's weights can warm-start a residual one).  PGCN_E_IO: missing, truncated, corrupted or unknown version.  On any error
+ * tensors having the same shapes, so a plain model's weights can warm-start a residual one;
+ * for flags 0 also whether the model has LayerNorm -- a weights-only load crosses that too: from
+ * a file without the scale / shift tensor the engine's gamma / beta keep their values, from a
+ * file with it a plain engine ignores it).  PGCN_E_IO: missing, truncated, corrupted or unknown version.  On any error
  * the engine is untouched. */
 int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags);
 /* Host-only look at a checkpoint file (no device, no engine): validates it as pgcn_gcn_load
  * does and fills info[8] = {version, n_layers, num_nodes, input_dim, output_dim, adam_steps,
  * epochs, weight count}.  PGCN_E_IO as pgcn_gcn_load. */
 int pgcn_checkpoint_info(const char *path, long long info[8]);
-/* Host-only: the file's header flags (>= 0; bit 0: saved by a residual engine), validated as
+/* Host-only: the file's header flags (>= 0; bit 0: saved by a residual engine; bit 1: by a
+ * LayerNorm engine), validated as
  * pgcn_checkpoint_info does, or a status < 0 (PGCN_E_IO also for flag bits this library does
  * not know). */
 int pgcn_checkpoint_flags(const char *path);
 #define PGCN_CKPT_RESIDUAL 1
+/* bit 1: saved by a LayerNorm engine -- a version-2 file, whose weight count and w / m / v
+ * payloads include the scale / shift tensor after the layer weights (version-1 files never
+ * carry it: there the bit is unknown) */
+#define PGCN_CKPT_LAYERNORM 2
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever

@@ -320,6 +320,9 @@ struct GCNParams {
   // middle layers as wide as the layer before them get a ResidualConnection after their ReLU
   // (pgcn_params.residual, pgcn.h)
   bool residual{false};
+  // every hidden layer gets a LayerNorm between its GraphSum and its ReLU
+  // (pgcn_params.layer_norm, pgcn.h)
+  bool layer_norm{false};
 };
 
 struct GCNData {

@@ -44,7 +44,7 @@ class PgcnParams(ctypes.Structure):
                 ("dropouts", c_float * MAX_LAYERS), ("epochs", c_int), ("early_stopping", c_int),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
                 ("beta2", c_float), ("eps", c_float), ("reassociate_last", c_int),
-                ("seed", ctypes.c_uint), ("residual", c_int)]
+                ("seed", ctypes.c_uint), ("layer_norm", c_int), ("residual", c_int)]
 
 
 class PgcnData(ctypes.Structure):
@@ -108,6 +108,14 @@ _sig("pgcn_relu_fwd", c_int, c_void_p, c_ll, c_void_p, c_int, c_void_p)
 _sig("pgcn_relu_bwd", c_int, c_void_p, c_ll, c_void_p, c_void_p)
 _sig("pgcn_residual_fwd", c_int, c_void_p, c_void_p, c_ll, c_void_p)
 _sig("pgcn_residual_bwd", c_int, c_void_p, c_void_p, c_ll, c_void_p)
+_sig("pgcn_layernorm_fwd", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+     c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p)
+_sig("pgcn_layernorm_bwd_workspace", c_size_t, c_int, c_int)
+_sig("pgcn_layernorm_bwd", c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+     c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_debug_layernorm_fwd_tail", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+     c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+     c_void_p, c_ll, c_float, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -308,10 +316,11 @@ class Dataset:
 
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
-                reassociate_last=True, seed=0, residual=False):
+                reassociate_last=True, seed=0, residual=False, layer_norm=False):
     p = PgcnParams()
     lib.pgcn_params_default(ctypes.byref(p))
     p.residual = 1 if residual else 0
+    p.layer_norm = 1 if layer_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
     p.seed = seed
     p.num_nodes, p.input_dim, p.output_dim = ds.num_nodes, ds.input_dim, ds.output_dim
@@ -454,7 +463,7 @@ class GCN:
 
     def query(self, key):
         """Engine facts: world, rank, comm (0 none / 1 RCCL / 2 loopback), reassociated,
-        graph_symmetric, graphsum_lds, epochs, adam_steps."""
+        graph_symmetric, graphsum_lds, epochs, adam_steps, norm_layers, fused_norm_tails, ..."""
         v = lib.pgcn_gcn_query(self._h, key.encode())
         if v < 0:
             raise PgcnError(int(v), f"query {key}")
@@ -557,11 +566,13 @@ def checkpoint_info(path):
 
 
 CKPT_RESIDUAL = 1
+CKPT_LAYERNORM = 2  # version-2 files: the scale / shift tensor behind the layer weights
 
 
 def checkpoint_flags(path):
     """Host-only: a checkpoint file's header flags (bit 0, CKPT_RESIDUAL: saved by an engine with
-    residual layers).  PgcnError(PGCN_E_IO) for an invalid file or unknown flag bits."""
+    residual layers; bit 1, CKPT_LAYERNORM: by one with LayerNorm).  PgcnError(PGCN_E_IO) for an
+    invalid file or unknown flag bits."""
     st = lib.pgcn_checkpoint_flags(os.fsencode(path))
     check(min(st, 0), f"checkpoint_flags {path}")
     return st
@@ -641,6 +652,8 @@ EXPORTED = [
     "pgcn_spmm_csr", "pgcn_spmm_csc_bwd", "pgcn_csr_transpose",
     "pgcn_rng_jump_table", "pgcn_dropout_mask", "pgcn_dropout_apply", "pgcn_relu_fwd",
     "pgcn_relu_bwd", "pgcn_residual_fwd", "pgcn_residual_bwd", "pgcn_params_sizeof",
+    "pgcn_layernorm_fwd", "pgcn_layernorm_bwd_workspace", "pgcn_layernorm_bwd",
+    "pgcn_debug_layernorm_fwd_tail",
     "pgcn_checkpoint_flags", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
     "pgcn_adam_step_size", "pgcn_params_default", "pgcn_gcn_create", "pgcn_comm_unique_id",
     "pgcn_gcn_create_dist", "pgcn_gcn_create_peer", "pgcn_loopback_create",

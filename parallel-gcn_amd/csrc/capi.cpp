@@ -93,6 +93,7 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.reassociate_last = p->reassociate_last != 0;
   q.seed = p->seed;
   q.residual = p->residual != 0;
+  q.layer_norm = p->layer_norm != 0;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -136,7 +137,7 @@ const char *pgcn_status_string(int s) {
   }
 }
 
-int pgcn_version(void) { return 110; }
+int pgcn_version(void) { return 111; }
 
 // ---------------------------------------------------------------- graph + kernels
 int pgcn_graph_create(int n, const int *indptr, const int *indices, pgcn_graph **out) {
@@ -399,6 +400,87 @@ int pgcn_residual_bwd(float *prev_grad, const float *cur_grad, long long n, void
   });
 }
 
+
+namespace {
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool ln_ld_ok(int ld, int d) { return ld >= d && ld % 4 == 0; }
+void layernorm_fwd_checked(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                           const float *gamma, const float *beta, float eps, float *xhat,
+                           int ld_xhat, float *rstd, const GsEpilogue *epi, void *stream) {
+  PGCN_CHECK(n >= 0 && d >= 1 && d <= kLayerNormMaxWidth && ln_ld_ok(ld_x, d) && ln_ld_ok(ld_y, d),
+             PGCN_E_INVALID, "layernorm_fwd: 1 <= d <= 1024, ld % 4 == 0, ld >= d");
+  PGCN_CHECK(eps >= 0.0f && (xhat != nullptr) == (rstd != nullptr) &&
+                 (!xhat || ln_ld_ok(ld_xhat, d)),
+             PGCN_E_INVALID, "layernorm_fwd: xhat and rstd together, ld_xhat % 4 == 0 >= d");
+  PGCN_CHECK(n == 0 || (x && y && gamma && beta && aligned16(x) && aligned16(y) && aligned16(xhat)),
+             PGCN_E_INVALID, "layernorm_fwd: null or misaligned argument");
+  if (epi && epi->mode) {
+    PGCN_CHECK(ld_y == d && ln_ld_ok(epi->relu_ld, d) && (!epi->res || ln_ld_ok(epi->res_ld, d)) &&
+                   aligned16(epi->res) && (reinterpret_cast<uintptr_t>(epi->relu_mask) & 3) == 0 &&
+                   epi->drop_base >= 0,
+               PGCN_E_INVALID, "layernorm_fwd_tail: the tail needs ld_y == d and padded strides");
+  }
+  check_device();
+  if (n == 0) return;
+  launch_layernorm_fwd(x, ld_x, y, ld_y, n, d, gamma, beta, eps, xhat, ld_xhat, rstd, epi,
+                       as_stream(stream));
+  PGCN_HIP(hipGetLastError());
+}
+}  // namespace
+
+int pgcn_layernorm_fwd(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                       const float *gamma, const float *beta, float eps, float *xhat,
+                       int ld_xhat, float *rstd, void *stream) {
+  return guarded([&] {
+    layernorm_fwd_checked(x, ld_x, y, ld_y, n, d, gamma, beta, eps, xhat, ld_xhat, rstd, nullptr,
+                          stream);
+  });
+}
+
+int pgcn_debug_layernorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                                  const float *gamma, const float *beta, float eps, float *xhat,
+                                  int ld_xhat, float *rstd, uint8_t *relu_mask, int relu_ld,
+                                  const float *res, int res_ld, const uint64_t *drop_mask,
+                                  long long drop_base, float drop_scale, void *stream) {
+  return guarded([&] {
+    GsEpilogue e;
+    e.mode = 1;
+    e.relu_mask = relu_mask;
+    e.relu_ld = relu_ld;
+    e.res = const_cast<float *>(res);  // (mode 1 reads it)
+    e.res_ld = res_ld;
+    e.drop_mask = drop_mask;
+    e.drop_base = drop_base;
+    e.drop_cols = d;
+    e.drop_scale = drop_scale;
+    layernorm_fwd_checked(x, ld_x, y, ld_y, n, d, gamma, beta, eps, xhat, ld_xhat, rstd, &e,
+                          stream);
+  });
+}
+
+size_t pgcn_layernorm_bwd_workspace(int n, int d) {
+  if (n < 0 || d < 1 || d > kLayerNormMaxWidth) return 0;
+  return layernorm_bwd_workspace(n, d);
+}
+
+int pgcn_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
+                       const float *rstd, const float *gamma, int n, int d, float *dx, int ld_dx,
+                       float *dgamma, float *dbeta, void *workspace, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && d >= 1 && d <= kLayerNormMaxWidth && ln_ld_ok(ld_dy, d) &&
+                   ln_ld_ok(ld_xhat, d) && ln_ld_ok(ld_dx, d),
+               PGCN_E_INVALID, "layernorm_bwd: 1 <= d <= 1024, ld % 4 == 0, ld >= d");
+    PGCN_CHECK(n == 0 || (dy && xhat && rstd && gamma && dx && dgamma && dbeta && workspace &&
+                          aligned16(dy) && aligned16(xhat) && aligned16(dx)),
+               PGCN_E_INVALID, "layernorm_bwd: null or misaligned argument");
+    check_device();
+    if (n == 0) return;
+    launch_layernorm_bwd(dy, ld_dy, xhat, ld_xhat, rstd, gamma, n, d, dx, ld_dx, dgamma, dbeta,
+                         workspace, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -464,6 +546,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->eps = 1e-8f;
   p->reassociate_last = 1;
   p->seed = 0;
+  p->layer_norm = 0;
   p->residual = 0;
 }
 
@@ -588,6 +671,13 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "fused_tails")) return e.fused_tails();
   if (!std::strcmp(key, "residual_layers")) return e.residual_layers();
   if (!std::strcmp(key, "fused_residuals")) return e.fused_residuals();
+  if (!std::strcmp(key, "norm_padding_nonzero")) {
+    long long n = PGCN_E_INVALID;
+    const int st = guarded([&] { n = g->g->norm_padding_nonzero(); });
+    return st == PGCN_OK ? n : st;
+  }
+  if (!std::strcmp(key, "norm_layers")) return e.norm_layers();
+  if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
   if (!std::strcmp(key, "epochs")) return e.epochs_run();
@@ -668,7 +758,7 @@ int pgcn_checkpoint_info(const char *path, long long info[8]) {
   return guarded([&] {
     PGCN_CHECK(path && info, PGCN_E_INVALID, "checkpoint_info args");
     const Checkpoint ck = read_checkpoint(path);
-    info[0] = kCheckpointVersion;
+    info[0] = ck.version;
     info[1] = ck.n_layers;
     info[2] = ck.num_nodes;
     info[3] = ck.dims.front();

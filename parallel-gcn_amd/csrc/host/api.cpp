@@ -674,6 +674,7 @@ GCN::GCN(GCNParams const *params_, AdamParams const *adam_params_, GCNData const
   q.reassociate_last = true;
   q.seed = params_->seed;
   q.residual = params_->residual;
+  q.layer_norm = params_->layer_norm;
   pgcn::AdamParams a;
   a.learning_rate = adam_params_->learning_rate;
   a.beta1 = adam_params_->beta1;

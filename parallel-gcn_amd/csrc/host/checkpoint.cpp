@@ -46,7 +46,28 @@ long long weight_count(const int32_t *dims, int n_layers) {
   for (int l = 0; l < n_layers; l++) n += (long long)dims[l] * dims[l + 1];
   return n;
 }
+
+long long norm_count_of(const int32_t *dims, int n_layers) {
+  long long n = 0;
+  for (int l = 1; l < n_layers; l++) n += 2LL * dims[l];
+  return n;
+}
+
+// whether a file of this version may carry these flag bits (false: unknown version or bit)
+bool version_flags_ok(uint32_t version, uint32_t flags) {
+  if (version == (uint32_t)kCheckpointVersion) return (flags & ~kCheckpointKnownFlags) == 0;
+  if (version == (uint32_t)kCheckpointVersionLayerNorm)
+    return (flags & kCheckpointLayerNorm) &&
+           (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm)) == 0;
+  return false;
+}
+
+long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags) {
+  return weight_count(dims, n_layers) +
+         ((flags & kCheckpointLayerNorm) ? norm_count_of(dims, n_layers) : 0);
+}
 }  // namespace
+
 
 void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   const int L = ck.n_layers;
@@ -57,20 +78,21 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
              PGCN_E_INVALID, "checkpoint: inconsistent state");
   CkHeader h{};
   std::memcpy(h.magic, kCkMagic, 8);
-  h.version = kCheckpointVersion;
+  h.version = (uint32_t)ck.version;
   h.n_layers = (uint32_t)L;
   h.num_nodes = ck.num_nodes;
   for (int l = 0; l <= L; l++) h.dims[l] = ck.dims[(size_t)l];
   for (int l = 0; l < L; l++) h.dropouts[l] = ck.dropouts[(size_t)l];
   h.seed = ck.seed;
   h.flags = ck.flags;
-  PGCN_CHECK((ck.flags & ~kCheckpointKnownFlags) == 0, PGCN_E_INVALID, "checkpoint: unknown flags");
+  PGCN_CHECK(version_flags_ok(h.version, ck.flags), PGCN_E_INVALID,
+             "checkpoint: flags unknown to the file's version");
   h.adam_steps = ck.adam_steps;
   h.draw_epochs = ck.draw_epochs;
   h.epochs = ck.epochs;
   h.n_results = (int64_t)(ck.results.size() / 4);
   h.n_weights = (int64_t)ck.w.size();
-  PGCN_CHECK(h.n_weights == weight_count(h.dims, L), PGCN_E_INVALID,
+  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags), PGCN_E_INVALID,
              "checkpoint: weight count does not match the layer dims");
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
@@ -92,13 +114,13 @@ Checkpoint read_checkpoint(const std::string &path) {
   CkHeader h{};
   Checkpoint ck;
   bool ok = std::fread(&h, sizeof(h), 1, f) == 1 && std::memcmp(h.magic, kCkMagic, 8) == 0 &&
-            h.version == (uint32_t)kCheckpointVersion && h.n_layers >= 2 &&
-            h.n_layers <= PGCN_MAX_LAYERS && h.num_nodes > 0 && (h.flags & ~kCheckpointKnownFlags) == 0;
+            version_flags_ok(h.version, h.flags) && h.n_layers >= 2 &&
+            h.n_layers <= PGCN_MAX_LAYERS && h.num_nodes > 0;
   const int L = ok ? (int)h.n_layers : 0;
   for (int l = 0; ok && l <= L; l++) ok = h.dims[l] > 0 && h.dims[l] <= (1 << 24);
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
        h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
-       h.n_weights == weight_count(h.dims, L) && h.n_weights < (1LL << 31);
+       h.n_weights == expected_weights(h.dims, L, h.flags) && h.n_weights < (1LL << 31);
   ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
        read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);
   ok = ok && std::fgetc(f) == EOF;  // nothing trailing
@@ -106,6 +128,7 @@ Checkpoint read_checkpoint(const std::string &path) {
   if (!ok || ck_hash(h, ck) != h.checksum)
     throw Error(PGCN_E_IO, "checkpoint: not a valid checkpoint (truncated, corrupted or another "
                            "version): " + path);
+  ck.version = (int)h.version;
   ck.n_layers = L;
   ck.num_nodes = h.num_nodes;
   ck.dims.assign(h.dims, h.dims + L + 1);

@@ -1,7 +1,7 @@
 // parallel-gcn_amd/csrc/host/checkpoint.hpp -- the training checkpoint file (host only).
 //
 // One little-endian file: a fixed 216-byte header, then the payload.
-//   header   char magic[8] "PGCNCK01"; u32 version (1); u32 n_layers; i64 num_nodes;
+//   header   char magic[8] "PGCNCK01"; u32 version (1, or 2: LayerNorm); u32 n_layers; i64 num_nodes;
 //            i32 dims[18] (input, hidden..., output; the rest 0); f32 dropouts[16];
 //            u32 seed; u32 flags; i64 adam_steps; i64 draw_epochs; i64 epochs;
 //            i64 n_results; i64 n_weights; u64 checksum
@@ -10,6 +10,11 @@
 // flags: bit 0 = saved by an engine with residual layers (a plain engine writes 0, the word
 // older libraries require to be 0: they reject flagged files); any other bit is unknown to
 // this library and the file is rejected.
+// Version 2 = the same header with flags bit 1 set: saved by an engine with LayerNorm.  Its
+// n_weights and its w / m / v payloads carry the scale / shift tensor (per hidden layer gamma_l
+// then beta_l, 2 * sum of the hidden dims floats) after the layer weights.  Engines without
+// LayerNorm keep writing version 1, byte for byte; in a version-1 file bit 1 stays unknown, and
+// a version-2 file without it is rejected.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
@@ -21,12 +26,15 @@
 
 namespace pgcn {
 
-constexpr int kCheckpointVersion = 1;
+constexpr int kCheckpointVersion = 1;           // ... of a file without LayerNorm
+constexpr int kCheckpointVersionLayerNorm = 2;  // ... of a file with it
 constexpr int kCheckpointMaxResults = 1024;  // the engine's results ring
 constexpr unsigned kCheckpointResidual = 1u;  // header flags, bit 0
-constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual;
+constexpr unsigned kCheckpointLayerNorm = 2u;  // header flags, bit 1 (version 2 only)
+constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual;  // ... of a version-1 file
 
 struct Checkpoint {
+  int version = kCheckpointVersion;  // 2 exactly when flags has kCheckpointLayerNorm
   int n_layers = 0;
   long long num_nodes = 0;
   std::vector<int> dims;        // n_layers + 1
@@ -35,7 +43,7 @@ struct Checkpoint {
   unsigned flags = 0;  // kCheckpoint* bits
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
-  std::vector<float> w, m, v;  // every weight tensor in layer order
+  std::vector<float> w, m, v;  // every weight tensor in layer order (+ the norm tensor)
 };
 
 // Writes path + ".tmp", then renames it over path (a run killed in mid-save keeps the

@@ -362,6 +362,10 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
   for (int h : params.hidden_dims)
     PGCN_CHECK(h > 0 && h % 4 == 0 && h <= 4096, PGCN_E_INVALID,
                "hidden dims must be multiples of 4 in [4,4096]");
+  if (params.layer_norm)
+    for (int h : params.hidden_dims)
+      PGCN_CHECK(h <= kLayerNormMaxWidth, PGCN_E_INVALID,
+                 "layer_norm: hidden dims up to 1024");
   PGCN_CHECK(params.output_dim >= 1 && params.output_dim <= 128, PGCN_E_INVALID,
              "output_dim must be in [1,128]");
   PGCN_CHECK(data.num_nodes == params.num_nodes, PGCN_E_INVALID, "num_nodes mismatch");
@@ -388,6 +392,8 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
         const int b = l == L - 1 ? params.output_dim : params.hidden_dims[(size_t)l];
         wtotal += (long long)a * b;
       }
+      if (params.layer_norm)  // the scale / shift gradients ride the same all-reduce
+        for (int h : params.hidden_dims) wtotal += 2LL * h;
       const size_t cap = std::max((size_t)part.maxrows * ld, (size_t)wtotal);
       if (dist->solo) {  // timing only: every peer is this rank (PeerComm's solo form)
         comm = std::make_unique<PeerComm>(rank, world, cap, nullptr, false, nullptr, true);
@@ -573,7 +579,10 @@ void GCN::build(const GCNData &data) {
   dims.push_back(params.output_dim);
   long long wtotal = 0;
   for (int l = 0; l < L; l++) wtotal += (long long)dims[(size_t)l] * dims[(size_t)l + 1];
-  grad_arena.allocate((size_t)wtotal);
+  long long ntotal = 0;  // layer_norm: gamma and beta of every hidden layer, behind the weights
+  if (params.layer_norm)
+    for (int h : params.hidden_dims) ntotal += 2LL * h;
+  grad_arena.allocate((size_t)(wtotal + ntotal));
   grad_arena.zero();
   uint64_t rs[2];
   if (params.seed) pgcn_rng_seed_glibc(params.seed, rs);
@@ -589,6 +598,17 @@ void GCN::build(const GCNData &data) {
     woff += w->size;
     weights.push_back(w);
     decays.push_back(l == 0);
+  }
+  if (ntotal > 0) {  // gamma = 1, beta = 0: no RNG draw (weights and masks as without it)
+    norm_var = std::make_shared<Variable>(1, (int)ntotal, false);
+    std::vector<float> h((size_t)ntotal, 0.0f);
+    size_t at = 0;
+    for (int d : params.hidden_dims) {
+      std::fill(h.begin() + at, h.begin() + at + d, 1.0f);
+      at += 2 * (size_t)d;
+    }
+    norm_var->dev_data.upload(h);
+    norm_var->dev_grad = grad_arena.slice((size_t)woff, (size_t)ntotal);
   }
   init_dropout_rng(data, wtotal);
 
@@ -633,6 +653,11 @@ void GCN::build(const GCNData &data) {
     insert_layer(params.hidden_dims[(size_t)l - 1], params.hidden_dims[(size_t)l],
                  params.dropouts[(size_t)l], l);
   insert_last_layer();
+  if (norm_var) {  // one more variable (index 3L + 1) and optimizer entry, without decay
+    variables.push_back(norm_var);
+    weights.push_back(norm_var);
+    decays.push_back(false);
+  }
   // (edge-cut: the tails run in k_gs_finish on the rank's rows after the reduce-scatter)
   if (g_fuse_epilogue & kFuseTails) fuse_epilogues();
   if (g_fuse_epilogue & kFuseMatmulTails) fuse_matmul_tails();
@@ -749,6 +774,21 @@ void GCN::fuse_output_layer() {
 void GCN::fuse_epilogues() {
   const size_t n = modules.size();
   for (size_t i = 0; i < n; i++) {
+    // LayerNorm -> ReLU [-> ResidualConnection] [-> Dropout]: the GraphSum before it keeps no
+    // forward tail (its next module is not the ReLU); the LayerNorm's final write takes it
+    if (auto *ln = dynamic_cast<LayerNorm *>(modules[i].get())) {
+      const Variable *v = ln->variable();
+      auto *relu = i + 1 < n ? dynamic_cast<ReLU *>(modules[i + 1].get()) : nullptr;
+      if (!relu || relu->variable() != v || v->ld != v->cols) continue;
+      ln->fwd_relu = relu;
+      auto *res = i + 2 < n ? dynamic_cast<ResidualConnection *>(modules[i + 2].get()) : nullptr;
+      if (res && res->current() == v && res->previous()->ld == v->ld) ln->fwd_res = res;
+      const size_t di = i + (ln->fwd_res ? 3 : 2);
+      auto *drop = di < n ? dynamic_cast<Dropout *>(modules[di].get()) : nullptr;
+      if (res && !ln->fwd_res) drop = nullptr;  // (an add the tail cannot take stays in order)
+      if (drop && drop->variable() == v) ln->fwd_drop = drop;
+      continue;
+    }
     auto *gs = dynamic_cast<GraphSum *>(modules[i].get());
     if (!gs) continue;
     const Variable *out = gs->output(), *in = gs->input();
@@ -844,7 +884,19 @@ void GCN::insert_first_layer() {
     gs->first_layer = true;
   }
   modules.push_back(std::move(gs));
+  insert_layer_norm(var2, 0);
   modules.push_back(std::make_unique<ReLU>(var2));
+}
+
+// layer_norm: the LayerNorm of hidden layer `layer` on its var2, right behind its GraphSum (and
+// behind eval's (Â X) W1 product, which writes layer 0's var2 itself)
+void GCN::insert_layer_norm(const shared_ptr<Variable> &var2, int layer) {
+  if (!norm_var) return;
+  long long off = 0;
+  for (int l = 0; l < layer; l++) off += 2LL * params.hidden_dims[(size_t)l];
+  auto ln = std::make_unique<LayerNorm>(var2, norm_var, off, part.local_rows());
+  norms_.push_back(ln.get());
+  modules.push_back(std::move(ln));
 }
 
 // src/gcn.cu:85-112
@@ -862,6 +914,7 @@ void GCN::insert_layer(int in_dim, int out_dim, float dropout, int layer) {
   auto var2 = std::make_shared<Variable>(prow, out_dim, true, round_up4(out_dim));
   variables.push_back(var2);
   modules.push_back(std::make_unique<GraphSum>(var1, var2, graph.get(), out_dim, &ctx));
+  insert_layer_norm(var2, layer);
   modules.push_back(std::make_unique<ReLU>(var2));
   // residual layer: var2 = relu(Â (prev W)) + prev, prev as this layer read it (equal widths
   // only, as the reference's ResidualConnection; no projection)
@@ -1429,6 +1482,24 @@ void GCN::run(bool verbose) {
   }
 }
 
+int GCN::fused_norm_tails() const {
+  int n = 0;
+  for (const LayerNorm *l : norms_) n += l->last_fused ? 1 : 0;
+  return n;
+}
+
+long long GCN::norm_padding_nonzero() {
+  sync();
+  long long bad = 0;
+  for (const LayerNorm *l : norms_) {
+    const Variable &v = *l->variable();
+    std::vector<float> raw((size_t)v.rows * v.ld);
+    v.dev_data.download(raw.data(), raw.size());
+    for (size_t i = (size_t)part.local_rows() * v.ld; i < raw.size(); i++) bad += raw[i] != 0.0f;
+  }
+  return bad;
+}
+
 int GCN::fused_residuals() const {
   int n = 0;
   for (const ResidualConnection *r : residuals_) n += r->last_fused ? 1 : 0;
@@ -1514,6 +1585,10 @@ void GCN::save(const std::string &path) {
   ck.dropouts = params.dropouts;
   ck.seed = params.seed;
   ck.flags = residuals_.empty() ? 0u : kCheckpointResidual;
+  if (norm_var) {  // version 2: the scale / shift tensor behind the layer weights
+    ck.flags |= kCheckpointLayerNorm;
+    ck.version = kCheckpointVersionLayerNorm;
+  }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1535,7 +1610,9 @@ void GCN::load(const std::string &path, int flags) {
     same = ck.dims[(size_t)l + 1] == params.hidden_dims[(size_t)l];
   if (same && resume) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
-    same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty();
+    // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)
+    same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty() &&
+           !(ck.flags & kCheckpointLayerNorm) == !norm_var;
     for (int l = 0; same && l < L; l++) same = ck.dropouts[(size_t)l] == params.dropouts[(size_t)l];
   }
   PGCN_CHECK(same, PGCN_E_INVALID, "load: the checkpoint is for another model");
@@ -1543,6 +1620,9 @@ void GCN::load(const std::string &path, int flags) {
   sync();
   size_t at = 0;
   for (const auto &w : weights) {
+    // weights only, a file without the norm tensor: gamma / beta keep their values (a file with
+    // it into a plain engine: the tensor behind the layer weights is not read)
+    if (w == norm_var && !(ck.flags & kCheckpointLayerNorm)) continue;
     w->dev_data.upload(ck.w.data() + at, (size_t)w->size);
     at += (size_t)w->size;
   }

@@ -40,6 +40,9 @@ struct GCNParams {
   // middle layers whose width equals the layer before get a ResidualConnection after their
   // ReLU: H_l = relu(Â (A_{l-1} W_l)) + A_{l-1} (insert_layer)
   bool residual = false;
+  // every hidden layer gets a LayerNorm between its GraphSum and its ReLU (LayerNorm,
+  // module.hpp); its scale / shift tensor is one more weight (no decay) behind the layers'
+  bool layer_norm = false;
 };
 
 struct AdamParams {
@@ -149,6 +152,12 @@ class GCN {
   int residual_layers() const { return (int)residuals_.size(); }
   // ... of which the last training forward ran inside a GraphSum's final write
   int fused_residuals() const;
+  int norm_layers() const { return (int)norms_.size(); }
+  // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
+  int fused_norm_tails() const;
+  // diagnostics (syncs): non-zero elements in the edge-cut padding rows of the variables the
+  // LayerNorms write (a normalised zero row would be beta: they process this rank's rows only)
+  long long norm_padding_nonzero();
 
  private:
   void build(const GCNData &data);
@@ -173,6 +182,12 @@ class GCN {
   bool mask_in_eval() const;
   void join_side();
   std::vector<const ResidualConnection *> residuals_;
+  std::vector<const LayerNorm *> norms_;
+  // layer_norm: per hidden layer gamma_l[d_l] then beta_l[d_l], one tensor (one optimizer entry:
+  // the one-batch Adam paths take at most kAdamBatch tensors), the last of `weights` and of
+  // `variables`; null without layer_norm
+  shared_ptr<Variable> norm_var;
+  void insert_layer_norm(const shared_ptr<Variable> &var2, int layer);
   int fused_tails_ = 0;  // GraphSum epilogues carrying ReLU / Dropout work (forward + backward)
   void set_split(int split);
   // the eval forward of predict(): every row, no labels, no results slot; the logits stay in

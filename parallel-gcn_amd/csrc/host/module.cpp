@@ -1,6 +1,7 @@
 // parallel-gcn_amd/csrc/host/module.cpp
 #include "module.hpp"
 
+#include <algorithm>
 #include <utility>
 
 #include "../kernels.hpp"
@@ -752,6 +753,58 @@ void ResidualConnection::forward(bool training, const Stream &s) const {
 
 // prev.grad += current.grad is made by the Matmul that writes prev.grad (Variable::skip_from)
 void ResidualConnection::backward(const Stream &) const {}
+
+// ------------------------------------------------------------------------------------------
+// LayerNorm (k_layernorm.hip)
+// ------------------------------------------------------------------------------------------
+LayerNorm::LayerNorm(shared_ptr<Variable> in_, shared_ptr<Variable> norm_, long long offset_,
+                     int rows_)
+    : in(std::move(in_)), norm(std::move(norm_)), offset(offset_), rows(rows_) {
+  PGCN_CHECK(in && norm && in->cols >= 1 && in->cols <= kLayerNormMaxWidth && rows >= 0 &&
+                 rows <= in->rows && offset >= 0 && offset + 2LL * in->cols <= norm->size,
+             PGCN_E_INVALID, "layer_norm: widths up to 1024");
+  xhat.allocate((size_t)std::max(in->rows, 1) * in->ld);
+  xhat.zero();
+  rstd.allocate((size_t)std::max(in->rows, 1));
+  rstd.zero();
+  ws.allocate(std::max<size_t>(layernorm_bwd_workspace(rows, in->cols) / sizeof(float), 1));
+}
+
+void LayerNorm::forward(bool training, const Stream &s) const {
+  GsEpilogue e;
+  if (fwd_relu && in->ld == in->cols) {  // the tail's element order is the storage order
+    e.mode = 1;
+    e.relu_mask = training ? fwd_relu->mask_ptr() : nullptr;
+    e.relu_ld = in->ld;
+    if (training && fwd_drop) {
+      fwd_drop->draw_fused(s.get());
+      const DropoutRng &r = fwd_drop->state();
+      e.drop_mask = r.mask.get();
+      e.drop_base = r.mask_base;
+      e.drop_cols = in->cols;
+      e.drop_scale = fwd_drop->scale();
+    }
+    if (fwd_res) {
+      e.res = const_cast<float *>(fwd_res->previous()->dev_data.get());  // (read only)
+      e.res_ld = fwd_res->previous()->ld;
+      fwd_res->skip_forward = true;
+    }
+    fwd_relu->skip_forward = true;
+  }
+  if (training) last_fused = e.mode != 0;
+  const float *gamma = norm->dev_data.get() + offset;
+  launch_layernorm_fwd(in->dev_data.get(), in->ld, in->dev_data.get(), in->ld, rows, in->cols,
+                       gamma, gamma + in->cols, kEps, training ? xhat.get() : nullptr, in->ld,
+                       training ? rstd.get() : nullptr, &e, s.get());
+}
+
+void LayerNorm::backward(const Stream &s) const {
+  if (!in->dev_grad || !norm->dev_grad) return;
+  float *g = in->dev_grad_z ? in->dev_grad_z.get() : in->dev_grad.get();
+  float *dgamma = norm->dev_grad.get() + offset;
+  launch_layernorm_bwd(g, in->ld, xhat.get(), in->ld, rstd.get(), norm->dev_data.get() + offset,
+                       rows, in->cols, g, in->ld, dgamma, dgamma + in->cols, ws.get(), s.get());
+}
 
 // ------------------------------------------------------------------------------------------
 // Matmul (src/module.cu:270-472; hpdga module.cpp:13-38)

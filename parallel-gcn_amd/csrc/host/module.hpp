@@ -371,6 +371,33 @@ class ResidualConnection : public Module {
   mutable bool last_fused = false;    // ... in the last training forward
 };
 
+// LayerNorm over the columns of a hidden layer's var2, between its GraphSum and its ReLU (the
+// reference has none): in = gamma * xhat + beta in place, over this rank's `rows` rows (edge-cut
+// padding rows stay zero: a normalised zero row would be beta).  gamma [d] then beta [d] sit at
+// `offset` of the engine's one scale / shift tensor `norm`; their gradients at the same offset of
+// its grad.  A training forward keeps xhat and rstd for the backward, which transforms in place
+// the buffer the layer's GraphSum backward reads (in.dev_grad, or dev_grad_z on a residual
+// layer) after the Dropout / ReLU backward have run on it.
+class LayerNorm : public Module {
+  shared_ptr<Variable> in, norm;
+  long long offset;
+  int rows;
+  DeviceBuffer<float> xhat, rstd, ws;
+
+ public:
+  static constexpr float kEps = 1e-5f;
+  LayerNorm(shared_ptr<Variable> in_, shared_ptr<Variable> norm_, long long offset_, int rows_);
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+  const Variable *variable() const { return in.get(); }
+  // The element-wise modules behind it, run in this kernel's final write (GCN::fuse_epilogues;
+  // null: they run on their own) -- GraphSum's forward tail without the next table
+  ReLU *fwd_relu = nullptr;
+  const ResidualConnection *fwd_res = nullptr;
+  const Dropout *fwd_drop = nullptr;
+  mutable bool last_fused = false;  // the last training forward ran that tail
+};
+
 // include/module.cuh:103-124: c = a * b
 class Matmul : public Module {
   shared_ptr<Variable> a, b, c;

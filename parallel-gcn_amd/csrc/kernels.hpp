@@ -331,6 +331,24 @@ void launch_relu_bwd_to(const float *g, long long n, const uint8_t *mask, float 
 // ResidualConnection, unfused: cur += prev; prev_grad += cur_grad (one fp32 add per element)
 void launch_residual_fwd(float *cur, const float *prev, long long n, hipStream_t s);
 void launch_residual_bwd(float *prev_grad, const float *cur_grad, long long n, hipStream_t s);
+// ---- LayerNorm over a node variable's columns (k_layernorm.hip) -----------------------------
+// y [n][ld_y] = gamma * xhat + beta, xhat = (x - mean_row) * rstd, rstd = 1 / sqrtf(var_row + eps)
+// (biased variance over the d columns, two passes); 1 <= d <= kLayerNormMaxWidth, every ld a
+// multiple of 4 and >= d, rows 16-byte aligned; x == y allowed.  The float4s covering columns
+// [0, round_up4(d)) are written, zero from column d on; padding columns of x may hold anything.
+// xhat / rstd (training; both or neither): also written.  epi (mode 0 or 1; only where ld_y ==
+// d): the tail applied to the final write.
+constexpr int kLayerNormMaxWidth = 1024;
+void launch_layernorm_fwd(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                          const float *gamma, const float *beta, float eps, float *xhat,
+                          int ld_xhat, float *rstd, const GsEpilogue *epi, hipStream_t s);
+// dx = rstd * (g - mean_row(g) - xhat * mean_row(g * xhat)), g = dy * gamma (dx == dy allowed);
+// dgamma[c] = sum over rows of dy * xhat, dbeta[c] = sum of dy, summed in a fixed order that
+// depends on (n, d) only: per-workgroup partials in `workspace`, then one reducing launch
+size_t layernorm_bwd_workspace(int n, int d);
+void launch_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
+                          const float *rstd, const float *gamma, int n, int d, float *dx, int ld_dx,
+                          float *dgamma, float *dbeta, void *workspace, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -7,7 +7,8 @@
 // beta1, beta2, eps, seed (srand seed of the xorshift state); the CUDA launch knobs
 // num_blocks_factor/num_threads are accepted and ignored) -- our own tiny parser, GetPot is
 // not vendored; residual=1, in the file or on the command line, adds the reference's
-// ResidualConnection to the middle layers of equal width, pgcn_params.residual).  no_feature=1 is the PART2 NO_FEATURE build (feature values 1.0).
+// ResidualConnection to the middle layers of equal width, pgcn_params.residual; layer_norm=1
+// likewise puts a LayerNorm between every hidden layer's GraphSum and ReLU, pgcn_params.layer_norm).  no_feature=1 is the PART2 NO_FEATURE build (feature values 1.0).
 // New with the engine: load= resumes from a checkpoint before the run (the epoch lines go on
 // from its epoch count, up to `epochs`), save= writes one after it, predict= writes one line
 // `node class confidence` per node after it; epochs= overrides the parameter file's.
@@ -60,6 +61,7 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "eps") p->eps = std::strtof(v.c_str(), nullptr);
     else if (k == "seed") p->seed = (unsigned)std::strtoul(v.c_str(), nullptr, 10);
     else if (k == "residual") p->residual = std::atoi(v.c_str());
+    else if (k == "layer_norm") p->layer_norm = std::atoi(v.c_str());
   }
   return true;
 }
@@ -74,7 +76,7 @@ int main(int argc, char **argv) {
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
   std::string load, save, predict;
-  int epochs = -1, residual = -1;
+  int epochs = -1, residual = -1, layer_norm = -1;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -85,6 +87,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "predict=", 8)) predict = argv[i] + 8;
     if (!std::strncmp(argv[i], "epochs=", 7)) epochs = std::atoi(argv[i] + 7);
     if (!std::strncmp(argv[i], "residual=", 9)) residual = std::atoi(argv[i] + 9);
+    if (!std::strncmp(argv[i], "layer_norm=", 11)) layer_norm = std::atoi(argv[i] + 11);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -94,6 +97,7 @@ int main(int argc, char **argv) {
   }
   if (epochs >= 0) p.epochs = epochs;
   if (residual >= 0) p.residual = residual;
+  if (layer_norm >= 0) p.layer_norm = layer_norm;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
