@@ -214,6 +214,35 @@ int pgcn_predict_rows(const float *logits, int ld, int n, int c, int *cls, float
 int pgcn_confusion(const int *cls, const int *truth, int n, int c, unsigned int *counts,
                    void *stream);
 
+/* --- multi-label classification (new: the reference has one class per node) ---------------
+ * Labels are a bit matrix label_bits [n][words] of uint32_t, words = ceil(c / 32), bit j % 32 of
+ * word j / 32 set iff row i has class j; 1 <= c <= 128.  Rows with truth >= 0 are labelled.
+ * pgcn_bce_fwd: pgcn_xent_fwd's contract for the per-class sigmoid with binary cross-entropy.
+ * With x the logits and y the target bits of the labelled rows, columns < c:
+ *   partials[2 b]     = sum over block b's rows of max(x, 0) - x y + log1p(exp(-|x|))
+ *   partials[2 b + 1] = #{(x > 0) != y}                     (pgcn_xent_blocks(n) blocks)
+ *   training: grad [n][ld] = (sigmoid(x) - y) / count, zero on unlabelled rows and in columns
+ *   [c, ld); !training: grad is not touched (may be NULL).
+ * pgcn_finalize then gives loss / count and the Hamming accuracy (count - wrong) / count for
+ * count = labelled rows * c.  logits is never written; its columns [c, ld) are never read into
+ * the result.  No float atomics, a fixed summation order: two calls give the same bits.
+ * PGCN_E_INVALID (before anything touches the device) for c outside [1, 128], ld < c or ld % 4,
+ * words != ceil(c / 32), count < 1; n == 0 launches nothing.  Asynchronous, allocates nothing,
+ * capturable. */
+int pgcn_bce_fwd(const float *logits, int ld, float *grad, const int *truth,
+                 const uint32_t *label_bits, int words, int n, int c, int count, int training,
+                 float *partials, void *stream);
+/* bits [n][words]: bit j of word w set iff logits[i][32 w + j] > 0 (strict, the project's tie
+ * rule), bits from c on zero.  probs (may be NULL) [n][ld_probs]: the sigmoid row, columns
+ * [c, round_up4(c)) zero, further padding left alone.  Same argument rules as pgcn_bce_fwd. */
+int pgcn_predict_multilabel_rows(const float *logits, int ld, int n, int c, uint32_t *bits,
+                                 int words, float *probs, int ld_probs, void *stream);
+/* counts [3][c] = per class tp, fp, fn over the rows with truth >= 0.  The call zeroes counts
+ * first.  Integer adds only, as pgcn_confusion. */
+int pgcn_multilabel_counts(const uint32_t *pred_bits, const uint32_t *label_bits,
+                           const int *truth, int n, int c, int words, unsigned int *counts,
+                           void *stream);
+
 /* --- Adam (src/optim.cu:42-95; hpdga optim.cpp:23-35) ---------------------------------- */
 int pgcn_adam(float *w, const float *g, float *m, float *v, long long n, float step_size,
               float beta1, float beta2, float eps, float weight_decay, int decay, void *stream);
@@ -239,6 +268,14 @@ typedef struct {
    * build: a non-symmetric pattern keeps the reference's order); only the fp32 rounding order
    * differs from the reference.  0: the reference's module order. */
   int reassociate_last;
+  /* != 0: multi-label node classification -- a node carries any subset of the output_dim <= 128
+   * classes (pgcn_data.label_bits, required then), the loss is the per-class sigmoid with binary
+   * cross-entropy, mean over (labelled rows of the split) x classes (pgcn_bce_fwd), and the
+   * accuracy column is the Hamming accuracy.  The output layer's Matmul runs unfused.  Engine
+   * build refuses (PGCN_E_INVALID) data where the labelled rows of any split x classes exceed
+   * 2^24: the loss / wrong sums and their count travel as floats.  0: the single-label engine,
+   * bit for bit. */
+  int multilabel;
   /* PART2 `seed` (src/parser.cpp:234): 0 = hpdga's unseeded glibc rand() (init_rand_state,
    * hpdga rand.cpp:6-14); else the xorshift state is the first two rand() values after
    * srand(seed).  Glorot init and every dropout mask follow from it. */
@@ -269,6 +306,11 @@ typedef struct {
   const int *feat_indptr, *feat_indices;              /* n+1, nnz_x */
   const float *feat_values;                           /* nnz_x */
   const int *label, *split;                           /* n, n */
+  /* read only when pgcn_params.multilabel != 0: the label bit matrix [n][label_words], bit j % 32
+   * of word j / 32 set iff node i has class j, bits from output_dim on zero; label_words =
+   * ceil(output_dim / 32).  A node is labelled iff label[i] >= 0 (the value is not used). */
+  const uint32_t *label_bits;
+  int label_words;
 } pgcn_data;
 
 typedef struct pgcn_gcn pgcn_gcn;
@@ -321,7 +363,8 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "residual_layers" (layers with a ResidualConnection, pgcn_params.residual) and
  * "fused_residuals" (how many of them the last training forward added inside a GraphSum's
  * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
- * pgcn_params.layer_norm) and "fused_norm_tails" (how many of them ran the ReLU / residual add /
+ * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel) and
+ * "fused_norm_tails" (how many of them ran the ReLU / residual add /
  * Dropout behind them inside the LayerNorm kernel in the last training forward);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
  * the normalised variables -- always 0).
@@ -387,7 +430,7 @@ int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags);
  * epochs, weight count}.  PGCN_E_IO as pgcn_gcn_load. */
 int pgcn_checkpoint_info(const char *path, long long info[8]);
 /* Host-only: the file's header flags (>= 0; bit 0: saved by a residual engine; bit 1: by a
- * LayerNorm engine), validated as
+ * LayerNorm engine; bit 2: by a multi-label engine), validated as
  * pgcn_checkpoint_info does, or a status < 0 (PGCN_E_IO also for flag bits this library does
  * not know). */
 int pgcn_checkpoint_flags(const char *path);
@@ -396,6 +439,11 @@ int pgcn_checkpoint_flags(const char *path);
  * payloads include the scale / shift tensor after the layer weights (version-1 files never
  * carry it: there the bit is unknown) */
 #define PGCN_CKPT_LAYERNORM 2
+/* bit 2: saved by a multi-label engine (pgcn_params.multilabel).  No payload or version change;
+ * a flags-0 load refuses a file whose bit differs from the engine's, a weights-only load
+ * crosses it.  (In a version-2 file the bit stays unknown, as it was before it had a meaning: a
+ * multi-label engine with LayerNorm writes version 3, version 2's layout with bits 1 and 2.) */
+#define PGCN_CKPT_MULTILABEL 4
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
@@ -408,6 +456,16 @@ long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs);
 /* predict + pgcn_confusion against split's labels: counts[c*c], this rank's rows (the caller
  * adds the ranks' matrices, as it concatenates get_var's rows). */
 int pgcn_gcn_confusion(pgcn_gcn *g, int split, long long *counts);
+/* Multi-label engines (others: PGCN_E_INVALID; pgcn_gcn_confusion refuses them in turn).
+ * pgcn_gcn_predict's eval-mode forward and guarantees (training state untouched, training
+ * continued after it bit-identical, collective on edge-cut engines), then
+ * pgcn_predict_multilabel_rows: bits [rows][ceil(output_dim / 32)], probs (may be NULL)
+ * [rows][output_dim] dense.  Returns the row count or a status < 0. */
+long long pgcn_gcn_predict_multilabel(pgcn_gcn *g, uint32_t *bits, float *probs);
+/* ... + pgcn_multilabel_counts against split's labels: counts [3][output_dim] = tp, fp, fn per
+ * class over this rank's rows (the caller adds the ranks' counts; micro / macro F1 follow from
+ * the integer sums). */
+int pgcn_gcn_multilabel_counts(pgcn_gcn *g, int split, long long *counts);
 /* per-call device timing of the GraphSum kernels (enable before the timed region) */
 int pgcn_gcn_profile(pgcn_gcn *g, int enable);
 int pgcn_gcn_profile_read(pgcn_gcn *g, double *graphsum_ms_total, long long *graphsum_calls,
@@ -441,6 +499,18 @@ int pgcn_dataset_load_binary(const char *path, pgcn_dataset **out);
  * Chung-Lu power-law undirected graph with `undirected_edges` edges (2x directed slots). */
 int pgcn_dataset_synthetic(int n, int f, int c, long long undirected_edges, uint64_t seed,
                            pgcn_dataset **out);
+/* Multi-label data: attaches the bit matrix bits [num_nodes][words] (copied; words = ceil(c /
+ * 32), 1 <= c <= 128, bits from c on must be zero) and sets output_dim = c.  label[i] of every
+ * node keeps its sign: a node that was labelled stays labelled.  PGCN_E_INVALID otherwise. */
+int pgcn_dataset_set_multilabel(pgcn_dataset *ds, const uint32_t *bits, int words, int c);
+/* The same from the sidecar text file `path` (by convention <root>/data/<name>.labels): line i
+ * holds the class ids of node i separated by spaces; an empty line is a labelled node with no
+ * class.  num_classes 0: max id + 1.  Every node becomes labelled (label[i] >= 0).  PGCN_E_IO for a missing file, a line
+ * count different from num_nodes, a token that is not a number, or an id outside [0,
+ * min(num_classes or 128, 128)).  The .svmlight / .graph / .split parser and the .pgcnbin cache
+ * are untouched: pgcn_dataset_save of a multi-label dataset returns PGCN_E_INVALID. */
+int pgcn_dataset_load_labels(pgcn_dataset *ds, const char *path, int num_classes);
+/* (label_bits / label_words of the view: NULL / 0 for single-label data) */
 int pgcn_dataset_view(const pgcn_dataset *ds, pgcn_data *view, int *input_dim, int *output_dim);
 int pgcn_dataset_free(pgcn_dataset *ds);
 

@@ -283,6 +283,29 @@ class CrossEntropyLoss : public Module {
   shared_ptr<Impl> impl_;
 };
 
+// Multi-label loss (new: the reference has one class per node): the per-class sigmoid with
+// binary cross-entropy against the bit matrix dev_label_bits [rows][words] (device; words =
+// ceil(num_classes / 32), bit j % 32 of word j / 32 = row i has class j; num_classes <= 128),
+// mean over (rows whose dev_truth >= 0) x num_classes (pgcn_bce_fwd).  num_samples counts those
+// rows (0 = count them, with a host sync).  *loss and the gradient as CrossEntropyLoss;
+// accuracy() is the Hamming accuracy.  The logits are not modified.
+class BCEWithLogitsLoss : public Module {
+ public:
+  natural num_samples = 0;
+  BCEWithLogitsLoss(shared_ptr<Variable> logits_, const integer *dev_truth_,
+                    const uint32_t *dev_label_bits_, natural words_, real *loss_,
+                    natural num_classes_);
+  void set_num_samples(natural num_samples_) override;
+  natural get_num_samples() const override;
+  void forward(bool training, const smart_stream &stream) const override;
+  void backward(const smart_stream &stream) const override;
+  real accuracy() const;  // of the last forward (after the stream syncs)
+  struct Impl;
+
+ private:
+  shared_ptr<Impl> impl_;
+};
+
 // include/optim.cuh:16-50
 struct AdamParams {
   real learning_rate{0.01f}, beta1{0.9f}, beta2{0.999f}, eps{1e-8f}, weight_decay{5e-4f};

@@ -44,13 +44,14 @@ class PgcnParams(ctypes.Structure):
                 ("dropouts", c_float * MAX_LAYERS), ("epochs", c_int), ("early_stopping", c_int),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
                 ("beta2", c_float), ("eps", c_float), ("reassociate_last", c_int),
-                ("seed", ctypes.c_uint), ("layer_norm", c_int), ("residual", c_int)]
+                ("multilabel", c_int), ("seed", ctypes.c_uint), ("layer_norm", c_int), ("residual", c_int)]
 
 
 class PgcnData(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("graph_indptr", P(c_int)), ("graph_indices", P(c_int)),
                 ("feat_indptr", P(c_int)), ("feat_indices", P(c_int)),
-                ("feat_values", P(c_float)), ("label", P(c_int)), ("split", P(c_int))]
+                ("feat_values", P(c_float)), ("label", P(c_int)), ("split", P(c_int)),
+                ("label_bits", P(ctypes.c_uint32)), ("label_words", c_int)]
 
 
 class PgcnXentFinal(ctypes.Structure):
@@ -159,6 +160,16 @@ _sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
      c_int, c_void_p)
 _sig("pgcn_confusion", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p)
+_sig("pgcn_bce_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+     c_int, c_int, c_void_p, c_void_p)
+_sig("pgcn_predict_multilabel_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+     c_void_p, c_int, c_void_p)
+_sig("pgcn_multilabel_counts", c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+     c_void_p)
+_sig("pgcn_gcn_predict_multilabel", c_ll, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_gcn_multilabel_counts", c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_dataset_set_multilabel", c_int, c_void_p, c_void_p, c_int, c_int)
+_sig("pgcn_dataset_load_labels", c_int, c_void_p, ctypes.c_char_p, c_int)
 _sig("pgcn_gcn_profile", c_int, c_void_p, c_int)
 _sig("pgcn_gcn_profile_read", c_int, c_void_p, P(c_double), P(c_ll), P(c_double))
 _sig("pgcn_gcn_profile_read_mm", c_int, c_void_p, P(c_double), P(c_ll), P(c_double))
@@ -246,6 +257,9 @@ class Dataset:
 
     def __init__(self, handle):
         self._h = c_void_p(handle)
+        self._refresh()
+
+    def _refresh(self):
         self.view = PgcnData()
         fi, fo = c_int(), c_int()
         check(lib.pgcn_dataset_view(self._h, ctypes.byref(self.view), ctypes.byref(fi),
@@ -267,6 +281,30 @@ class Dataset:
         self.feat_values = arr(self.view.feat_values, nnzx, np.float32)
         self.label = arr(self.view.label, n, np.int32)
         self.split = arr(self.view.split, n, np.int32)
+        # multi-label data: the bit matrix [n][label_words] (None for single-label data)
+        self.label_words = self.view.label_words
+        self.label_bits = None
+        if self.view.label_bits and self.label_words:
+            self.label_bits = np.ctypeslib.as_array(self.view.label_bits,
+                                                    shape=(n, self.label_words))
+
+    def set_multilabel(self, Y):
+        """Attaches the label matrix Y (bool [num_nodes][C], 1 <= C <= 128) and sets output_dim =
+        C; labelled nodes (label >= 0) stay labelled."""
+        Y = np.asarray(Y)
+        if Y.ndim != 2 or Y.shape[0] != self.num_nodes:
+            raise ValueError("set_multilabel: Y must be [num_nodes][C]")
+        bits = pack_label_bits(Y)
+        check(lib.pgcn_dataset_set_multilabel(self._h, _ptr(bits), bits.shape[1], Y.shape[1]),
+              "dataset_set_multilabel")
+        self._refresh()
+
+    def load_labels(self, path, num_classes=0):
+        """Reads the multi-label sidecar file (line i: the class ids of node i; by convention
+        <root>/data/<name>.labels); num_classes 0: max id + 1."""
+        check(lib.pgcn_dataset_load_labels(self._h, os.fsencode(path), num_classes),
+              f"dataset_load_labels {path}")
+        self._refresh()
 
     @staticmethod
     def load(root, name):
@@ -314,11 +352,43 @@ class Dataset:
             self._h = c_void_p()
 
 
+def pack_label_bits(Y):
+    """bool [n][C] -> the uint32 bit matrix [n][ceil(C / 32)] (bit j % 32 of word j / 32)."""
+    Y = np.asarray(Y).astype(bool)
+    n, c = Y.shape
+    words = (c + 31) // 32
+    pad = np.zeros((n, words * 32), np.uint8)
+    pad[:, :c] = Y
+    return np.ascontiguousarray(
+        np.packbits(pad.reshape(n, words, 32), axis=2, bitorder="little").view("<u4")
+        .reshape(n, words).astype(np.uint32))
+
+
+def unpack_label_bits(bits, c):
+    """The inverse: uint32 [n][words] -> bool [n][c]."""
+    bits = np.ascontiguousarray(bits, dtype="<u4")
+    n = bits.shape[0]
+    return np.unpackbits(bits.view(np.uint8).reshape(n, -1), axis=1,
+                         bitorder="little")[:, :c].astype(bool)
+
+
+def f1_scores(counts):
+    """(micro-F1, macro-F1) from per-class counts [3][C] = tp, fp, fn (summed over the ranks).
+    A class with no positives and no predictions (2 tp + fp + fn == 0) has F1 0."""
+    tp, fp, fn = (np.asarray(counts, np.float64)[k] for k in range(3))
+    den = 2 * tp + fp + fn
+    per = np.divide(2 * tp, den, out=np.zeros_like(den), where=den > 0)
+    tot = den.sum()
+    return (float(2 * tp.sum() / tot) if tot > 0 else 0.0), float(per.mean())
+
+
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
-                reassociate_last=True, seed=0, residual=False, layer_norm=False):
+                reassociate_last=True, seed=0, residual=False, layer_norm=False,
+                multilabel=False):
     p = PgcnParams()
     lib.pgcn_params_default(ctypes.byref(p))
+    p.multilabel = 1 if multilabel else 0
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
@@ -445,6 +515,27 @@ class GCN:
         check(lib.pgcn_gcn_confusion(self._h, split, _ptr(out)), "confusion")
         return out
 
+    def predict_multilabel(self, probs=False):
+        """bool [rows][output_dim] of this rank's rows (logit > 0) from an eval-mode forward of a
+        multi-label engine; with probs=True also the sigmoid rows (float32)."""
+        a, b = self.node_range()
+        n, c = b - a, self.params.output_dim
+        bits = np.zeros((n, (c + 31) // 32), np.uint32)
+        pr = np.zeros((n, c), np.float32) if probs else None
+        got = lib.pgcn_gcn_predict_multilabel(self._h, _ptr(bits), _ptr(pr) if probs else None)
+        if got < 0:
+            raise PgcnError(int(got), "predict_multilabel")
+        assert got == n
+        pred = unpack_label_bits(bits, c)
+        return (pred, pr) if probs else pred
+
+    def multilabel_counts(self, split):
+        """counts[3, C] (int64): per class tp, fp, fn over this rank's rows of `split`; add the
+        ranks' arrays, then f1_scores()."""
+        out = np.zeros((3, self.params.output_dim), np.int64)
+        check(lib.pgcn_gcn_multilabel_counts(self._h, split, _ptr(out)), "multilabel_counts")
+        return out
+
     def profile(self, on):
         check(lib.pgcn_gcn_profile(self._h, 1 if on else 0), "profile")
 
@@ -567,11 +658,13 @@ def checkpoint_info(path):
 
 CKPT_RESIDUAL = 1
 CKPT_LAYERNORM = 2  # version-2 files: the scale / shift tensor behind the layer weights
+CKPT_MULTILABEL = 4  # saved by a multi-label engine (no payload change)
 
 
 def checkpoint_flags(path):
     """Host-only: a checkpoint file's header flags (bit 0, CKPT_RESIDUAL: saved by an engine with
-    residual layers; bit 1, CKPT_LAYERNORM: by one with LayerNorm).  PgcnError(PGCN_E_IO) for an
+    residual layers; bit 1, CKPT_LAYERNORM: by one with LayerNorm; bit 2, CKPT_MULTILABEL: by a
+    multi-label one).  PgcnError(PGCN_E_IO) for an
     invalid file or unknown flag bits."""
     st = lib.pgcn_checkpoint_flags(os.fsencode(path))
     check(min(st, 0), f"checkpoint_flags {path}")
@@ -674,4 +767,7 @@ EXPORTED = [
     "pgcn_debug_ring_slice_rows", "pgcn_debug_xent_fwd", "pgcn_debug_out_xent",
     "pgcn_debug_finalize_ring", "pgcn_debug_tn_reduce_blocks_workspace",
     "pgcn_debug_tn_reduce_blocks", "pgcn_debug_tn_reduce_one_pass",
+    "pgcn_bce_fwd", "pgcn_predict_multilabel_rows", "pgcn_multilabel_counts",
+    "pgcn_gcn_predict_multilabel", "pgcn_gcn_multilabel_counts", "pgcn_dataset_set_multilabel",
+    "pgcn_dataset_load_labels",
 ]

@@ -94,6 +94,7 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.seed = p->seed;
   q.residual = p->residual != 0;
   q.layer_norm = p->layer_norm != 0;
+  q.multilabel = p->multilabel != 0;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -119,6 +120,15 @@ GCNData to_data(const pgcn_data *d, const pgcn_params *p) {
   g.feature_value.assign(d->feat_values, d->feat_values + d->feat_indptr[n]);
   g.label.assign(d->label, d->label + n);
   g.split.assign(d->split, d->split + n);
+  if (p->multilabel) {  // (the two trailing members are read only then)
+    PGCN_CHECK(d->label_bits, PGCN_E_INVALID, "multilabel: pgcn_data.label_bits is required");
+    PGCN_CHECK(p->output_dim >= 1 && p->output_dim <= 128 &&
+                   d->label_words == (p->output_dim + 31) / 32,
+               PGCN_E_INVALID,
+               "multilabel: 1 <= output_dim <= 128 and label_words = ceil(output_dim / 32)");
+    g.label_words = d->label_words;
+    g.label_bits.assign(d->label_bits, d->label_bits + (size_t)n * d->label_words);
+  }
   return g;
 }
 }  // namespace
@@ -518,6 +528,42 @@ int pgcn_confusion(const int *cls, const int *truth, int n, int c, unsigned int 
   });
 }
 
+int pgcn_bce_fwd(const float *logits, int ld, float *grad, const int *truth,
+                 const uint32_t *label_bits, int words, int n, int c, int count, int training,
+                 float *partials, void *stream) {
+  return guarded([&] {
+    check_bce_args(ld, words, n, c, count);
+    if (n == 0) return;
+    check_device();
+    launch_bce_fwd(logits, ld, grad, truth, label_bits, words, n, c, count, training, partials,
+                   as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_predict_multilabel_rows(const float *logits, int ld, int n, int c, uint32_t *bits,
+                                 int words, float *probs, int ld_probs, void *stream) {
+  return guarded([&] {
+    check_predict_multilabel_args(ld, n, c, words, probs != nullptr, ld_probs);
+    if (n == 0) return;
+    check_device();
+    launch_predict_multilabel(logits, ld, n, c, bits, words, probs, ld_probs, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_multilabel_counts(const uint32_t *pred_bits, const uint32_t *label_bits,
+                           const int *truth, int n, int c, int words, unsigned int *counts,
+                           void *stream) {
+  return guarded([&] {
+    check_multilabel_counts_args(n, c, words);
+    check_device();
+    launch_multilabel_counts(pred_bits, label_bits, truth, n, c, words, counts,
+                             as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_adam(float *w, const float *g, float *m, float *v, long long n, float step_size,
               float beta1, float beta2, float eps, float weight_decay, int decay, void *stream) {
   return guarded([&] {
@@ -545,6 +591,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->beta2 = 0.999f;
   p->eps = 1e-8f;
   p->reassociate_last = 1;
+  p->multilabel = 0;
   p->seed = 0;
   p->layer_norm = 0;
   p->residual = 0;
@@ -677,6 +724,7 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
     return st == PGCN_OK ? n : st;
   }
   if (!std::strcmp(key, "norm_layers")) return e.norm_layers();
+  if (!std::strcmp(key, "multilabel")) return e.get_params().multilabel ? 1 : 0;
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
@@ -791,6 +839,20 @@ int pgcn_gcn_confusion(pgcn_gcn *g, int split, long long *counts) {
     g->g->confusion(split, counts);
   });
 }
+long long pgcn_gcn_predict_multilabel(pgcn_gcn *g, uint32_t *bits, float *probs) {
+  long long n = -1;
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_predict_multilabel: null engine");
+    n = g->g->predict_multilabel(bits, probs);
+  });
+  return st == PGCN_OK ? n : st;
+}
+int pgcn_gcn_multilabel_counts(pgcn_gcn *g, int split, long long *counts) {
+  return guarded([&] {
+    PGCN_CHECK(g && counts, PGCN_E_INVALID, "gcn_multilabel_counts args");
+    g->g->multilabel_counts(split, counts);
+  });
+}
 int pgcn_gcn_profile(pgcn_gcn *g, int enable) {
   return guarded([&] { g->g->set_profile(enable != 0); });
 }
@@ -831,6 +893,8 @@ int pgcn_dataset_load_cached(const char *root, const char *name, pgcn_dataset **
 int pgcn_dataset_save(const pgcn_dataset *ds, const char *path) {
   return guarded([&] {
     PGCN_CHECK(ds && path, PGCN_E_INVALID, "dataset_save: null argument");
+    PGCN_CHECK(ds->d.label_bits.empty(), PGCN_E_INVALID,
+               "dataset_save: the cache format holds no multi-label data");
     if (!save_binary(ds->d, path, nullptr))
       throw Error(PGCN_E_IO, std::string("cannot write ") + path);
   });
@@ -872,9 +936,44 @@ int pgcn_dataset_view(const pgcn_dataset *ds, pgcn_data *v, int *input_dim, int 
   v->feat_values = ds->d.feature_value.data();
   v->label = ds->d.label.data();
   v->split = ds->d.split.data();
+  v->label_bits = ds->d.label_bits.empty() ? nullptr : ds->d.label_bits.data();
+  v->label_words = ds->d.label_bits.empty() ? 0 : ds->d.label_words;
   if (input_dim) *input_dim = ds->d.input_dim;
   if (output_dim) *output_dim = ds->d.output_dim;
   return PGCN_OK;
+}
+
+int pgcn_dataset_set_multilabel(pgcn_dataset *ds, const uint32_t *bits, int words, int c) {
+  return guarded([&] {
+    PGCN_CHECK(ds && bits && c >= 1 && c <= 128 && words == (c + 31) / 32, PGCN_E_INVALID,
+               "dataset_set_multilabel: 1 <= c <= 128, words = ceil(c / 32)");
+    const size_t n = (size_t)ds->d.num_nodes;
+    if (c % 32) {
+      const uint32_t past = ~((1u << (c % 32)) - 1u);
+      for (size_t i = 0; i < n; i++)
+        PGCN_CHECK(!(bits[i * words + words - 1] & past), PGCN_E_INVALID,
+                   "dataset_set_multilabel: bits at positions >= c must be zero");
+    }
+    ds->d.label_bits.assign(bits, bits + n * words);
+    ds->d.label_words = words;
+    ds->d.output_dim = c;
+  });
+}
+
+int pgcn_dataset_load_labels(pgcn_dataset *ds, const char *path, int num_classes) {
+  return guarded([&] {
+    PGCN_CHECK(ds && path && num_classes >= 0 && num_classes <= 128, PGCN_E_INVALID,
+               "dataset_load_labels: 0 <= num_classes <= 128");
+    std::vector<uint32_t> bits;
+    int words = 0, c = 0;
+    std::string why;
+    if (!read_labels_file(path, ds->d.num_nodes, num_classes, &bits, &words, &c, &why))
+      throw Error(PGCN_E_IO, why);
+    ds->d.label_bits = std::move(bits);
+    ds->d.label_words = words;
+    ds->d.output_dim = c;
+    for (int &l : ds->d.label) l = std::max(l, 0);  // every line is a labelled node
+  });
 }
 
 int pgcn_dataset_free(pgcn_dataset *ds) {

@@ -583,6 +583,73 @@ void CrossEntropyLoss::backward(const smart_stream &stream) const {
 }
 real CrossEntropyLoss::accuracy() const { return impl_->res.get()[1]; }
 
+// ---------------------------------------------------------------------- BCEWithLogitsLoss
+struct BCEWithLogitsLoss::Impl {
+  shared_ptr<Variable> logits;
+  const integer *truth;
+  const uint32_t *bits;
+  int words;
+  real *loss;
+  int classes;
+  std::unique_ptr<pgcn::BCEWithLogitsLoss> mod;
+  PinnedBuffer<float> res{2};
+};
+BCEWithLogitsLoss::BCEWithLogitsLoss(shared_ptr<Variable> logits_, const integer *dev_truth_,
+                                     const uint32_t *dev_label_bits_, natural words_,
+                                     real *loss_, natural num_classes_)
+    : impl_(std::make_shared<Impl>()) {
+  Context &cx = context();
+  PGCN_CHECK(logits_->impl() && logits_->impl()->cols == (int)num_classes_, PGCN_E_INVALID,
+             "BCEWithLogitsLoss: logits need their [rows][num_classes] shape (build the module "
+             "producing them first)");
+  PGCN_CHECK(num_classes_ >= 1 && num_classes_ <= 128 && dev_truth_ && dev_label_bits_ &&
+                 (int)words_ == ((int)num_classes_ + 31) / 32,
+             PGCN_E_INVALID, "BCEWithLogitsLoss: 1 <= classes <= 128, words = ceil(classes / 32)");
+  impl_->logits = std::move(logits_);
+  impl_->truth = dev_truth_;
+  impl_->bits = dev_label_bits_;
+  impl_->words = (int)words_;
+  impl_->loss = loss_;
+  impl_->classes = (int)num_classes_;
+  cx.ensure_xent(impl_->logits->impl()->rows);
+  impl_->mod = std::make_unique<pgcn::BCEWithLogitsLoss>(impl_->logits->impl(), impl_->classes,
+                                                         &cx.ctx);
+}
+void BCEWithLogitsLoss::set_num_samples(natural n) { num_samples = n; }
+natural BCEWithLogitsLoss::get_num_samples() const { return num_samples; }
+void BCEWithLogitsLoss::forward(bool training, const smart_stream &stream) const {
+  Context &cx = context();
+  const int rows = impl_->logits->impl()->rows;
+  long long labelled = (long long)num_samples;
+  if (labelled == 0) {
+    std::vector<int> t((size_t)rows);
+    PGCN_HIP(hipStreamSynchronize(stream.get()));
+    PGCN_HIP(hipMemcpy(t.data(), impl_->truth, t.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int x : t) labelled += x >= 0;
+  }
+  const long long count = labelled * impl_->classes;
+  PGCN_CHECK(count > 0 && count <= (1LL << 24), PGCN_E_INVALID,
+             "BCEWithLogitsLoss: 1 <= labelled rows x classes <= 2^24");
+  ModuleContext &m = cx.ctx;
+  m.truth = impl_->truth;
+  m.label_bits = impl_->bits;
+  m.label_words = impl_->words;
+  m.count = (int)count;
+  m.xent_partials = cx.xent_partials.get();
+  m.xent_blocks = xent_blocks(rows);
+  m.compact_n = 0;
+  impl_->mod->forward(training, Stream::wrap(stream.get()));
+  launch_reduce_scalars(cx.xent_partials.get(), m.xent_blocks, nullptr, 0, cx.sums.get(),
+                        stream.get(), (int)count, 0.0f, cx.out2.get());
+  PGCN_HIP(hipMemcpyAsync(impl_->res.get(), cx.out2.get(), 2 * sizeof(float),
+                          hipMemcpyDeviceToHost, stream.get()));
+  if (impl_->loss)
+    PGCN_HIP(hipMemcpyAsync(impl_->loss, cx.out2.get(), sizeof(float), hipMemcpyDeviceToHost,
+                            stream.get()));
+}
+void BCEWithLogitsLoss::backward(const smart_stream &) const {}  // the forward wrote the gradient
+real BCEWithLogitsLoss::accuracy() const { return impl_->res.get()[1]; }
+
 // ---------------------------------------------------------------------- Adam
 Adam::Adam(const std::vector<shared_ptr<Variable>> &weights, const std::vector<bool> &decays,
            AdamParams const *params_)

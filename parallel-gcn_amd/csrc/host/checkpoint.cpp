@@ -58,6 +58,9 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
   if (version == (uint32_t)kCheckpointVersion) return (flags & ~kCheckpointKnownFlags) == 0;
   if (version == (uint32_t)kCheckpointVersionLayerNorm)
     return (flags & kCheckpointLayerNorm) &&
+           (flags & ~(kCheckpointResidual | kCheckpointLayerNorm)) == 0;
+  if (version == (uint32_t)kCheckpointVersionLayerNormMultilabel)
+    return (flags & kCheckpointLayerNorm) && (flags & kCheckpointMultilabel) &&
            (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm)) == 0;
   return false;
 }

@@ -15,6 +15,10 @@
 // then beta_l, 2 * sum of the hidden dims floats) after the layer weights.  Engines without
 // LayerNorm keep writing version 1, byte for byte; in a version-1 file bit 1 stays unknown, and
 // a version-2 file without it is rejected.
+// flags bit 2 = saved by a multi-label engine (pgcn_params.multilabel): known in a version-1
+// file, no payload change.  In a version-2 file bit 2 stays unknown (as before this bit existed),
+// so a multi-label engine with LayerNorm writes version 3: version 2's layout with bits 1 and 2
+// both set, and nothing else is a version-3 file.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
@@ -31,7 +35,10 @@ constexpr int kCheckpointVersionLayerNorm = 2;  // ... of a file with it
 constexpr int kCheckpointMaxResults = 1024;  // the engine's results ring
 constexpr unsigned kCheckpointResidual = 1u;  // header flags, bit 0
 constexpr unsigned kCheckpointLayerNorm = 2u;  // header flags, bit 1 (version 2 only)
-constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual;  // ... of a version-1 file
+constexpr unsigned kCheckpointMultilabel = 4u;  // header flags, bit 2 (versions 1 and 3)
+constexpr int kCheckpointVersionLayerNormMultilabel = 3;  // version 2's layout with bits 1 and 2
+// ... of a version-1 file
+constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
 struct Checkpoint {
   int version = kCheckpointVersion;  // 2 exactly when flags has kCheckpointLayerNorm

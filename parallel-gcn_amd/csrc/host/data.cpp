@@ -265,6 +265,67 @@ bool Parser::parse() {
   return ok;
 }
 
+bool read_labels_file(const std::string &path, int num_nodes, int num_classes,
+                      std::vector<uint32_t> *bits, int *words, int *classes, std::string *why) {
+  std::ifstream in(path);
+  if (!in) {
+    *why = "cannot open " + path;
+    return false;
+  }
+  const int limit = num_classes > 0 ? std::min(num_classes, 128) : 128;
+  std::vector<std::vector<int>> rows;
+  std::string line;
+  int max_id = -1;
+  while (std::getline(in, line)) {
+    if ((int)rows.size() == num_nodes) {
+      *why = path + ": more lines than nodes";
+      return false;
+    }
+    rows.emplace_back();
+    size_t at = 0;
+    while (at < line.size()) {
+      if (line[at] == ' ' || line[at] == '\t' || line[at] == '\r') {
+        at++;
+        continue;
+      }
+      size_t end = at;
+      long long v = 0;
+      while (end < line.size() && line[end] >= '0' && line[end] <= '9' && end - at < 10)
+        v = v * 10 + (line[end++] - '0');
+      const bool ends = end == line.size() || line[end] == ' ' || line[end] == '\t' ||
+                        line[end] == '\r';
+      if (end == at || !ends) {
+        *why = path + ": line " + std::to_string(rows.size()) + ": not a number";
+        return false;
+      }
+      if (v >= limit) {
+        *why = path + ": line " + std::to_string(rows.size()) + ": class id out of range";
+        return false;
+      }
+      rows.back().push_back((int)v);
+      max_id = std::max(max_id, (int)v);
+      at = end;
+    }
+  }
+  if ((int)rows.size() != num_nodes) {
+    *why = path + ": " + std::to_string(rows.size()) + " lines for " +
+           std::to_string(num_nodes) + " nodes";
+    return false;
+  }
+  const int c = num_classes > 0 ? num_classes : max_id + 1;
+  if (c < 1 || c > 128) {
+    *why = path + ": 1 <= classes <= 128";
+    return false;
+  }
+  const int w = (c + 31) / 32;
+  bits->assign((size_t)num_nodes * w, 0u);
+  for (int i = 0; i < num_nodes; i++)
+    for (int j : rows[(size_t)i]) (*bits)[(size_t)i * w + j / 32] |= 1u << (j % 32);
+  *words = w;
+  *classes = c;
+  return true;
+}
+
 bool features_dense(const GCNData &d) {
   const int n = d.num_nodes, f = d.input_dim;
   if ((long long)d.feature_index.indptr.size() != (long long)n + 1) return false;

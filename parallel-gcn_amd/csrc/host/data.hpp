@@ -24,6 +24,10 @@ struct GCNData {
   std::vector<int> label;
   std::vector<float> feature_value;
   int num_nodes = 0, input_dim = 0, output_dim = 0;
+  // multi-label data (empty / 0: single-label): [num_nodes][label_words] bits, bit j % 32 of
+  // word j / 32 = node i has class j; a node is labelled iff label[i] >= 0
+  std::vector<uint32_t> label_bits;
+  int label_words = 0;
 };
 
 class Parser {
@@ -65,6 +69,13 @@ bool load_binary(GCNData *d, const std::string &path, const FileStamp *stamps);
 // which happened.
 bool load_dataset_cached(GCNData *d, const std::string &root, const std::string &name,
                          bool *from_cache);
+
+// Multi-label sidecar file: line i = the class ids of node i separated by blanks (an empty line:
+// no class).  Fills bits [num_nodes][words] and *classes (num_classes, or max id + 1 when 0);
+// false (with *why) for a missing file, a line count other than num_nodes, a token that is not
+// a number or an id outside [0, min(num_classes or 128, 128)).
+bool read_labels_file(const std::string &path, int num_nodes, int num_classes,
+                      std::vector<uint32_t> *bits, int *words, int *classes, std::string *why);
 
 // True when every row lists all features 0..F-1 in order (a dense matrix in CSR form).
 bool features_dense(const GCNData &d);

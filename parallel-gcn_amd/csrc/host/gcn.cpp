@@ -492,6 +492,23 @@ void GCN::reseed_dropout(long long epochs) {
 
 void GCN::build(const GCNData &data) {
   const int N = params.num_nodes;
+  if (params.multilabel) {
+    const int C = params.output_dim;
+    PGCN_CHECK(C >= 1 && C <= kPredictMaxClasses, PGCN_E_INVALID,
+               "multilabel: 1 <= output_dim <= 128");
+    PGCN_CHECK(data.label_words == (C + 31) / 32 &&
+                   data.label_bits.size() == (size_t)N * data.label_words,
+               PGCN_E_INVALID, "multilabel: label_bits [num_nodes][ceil(output_dim / 32)] required");
+    // the float pipeline behind the loss (partials, raw4[3], the wrong sums) is exact up to 2^24
+    long long labelled[4] = {0, 0, 0, 0};
+    for (int i = 0; i < N; i++) {
+      const int s = data.split[(size_t)i];
+      if (s >= 1 && s <= 3 && data.label[(size_t)i] >= 0) labelled[s]++;
+    }
+    for (int s = 1; s <= 3; s++)
+      PGCN_CHECK(labelled[s] * C <= (1LL << 24), PGCN_E_INVALID,
+                 "multilabel: labelled rows of a split x classes must not exceed 2^24");
+  }
   graph_symmetric = csr_symmetric(N, data.graph.indptr.data(), data.graph.indices.data());
   // adjacency
   if (comm) {
@@ -571,6 +588,26 @@ void GCN::build(const GCNData &data) {
         if (comm) split_rows_global[s].push_back(i);  // edge-cut row restriction (set_split)
       }
     counts[s] = c;
+    if (params.multilabel) {
+      const int w = data.label_words;
+      std::vector<uint32_t> bc(std::max<size_t>(split_rows_host[s].size() * (size_t)w, 1), 0u);
+      for (size_t k = 0; k < split_rows_host[s].size(); k++)
+        std::memcpy(&bc[k * w], &data.label_bits[((size_t)first + split_rows_host[s][k]) * w],
+                    sizeof(uint32_t) * (size_t)w);
+      label_bits_compact[s].allocate(bc.size());
+      label_bits_compact[s].upload(bc);
+    }
+  }
+  if (params.multilabel) {
+    const int w = data.label_words;
+    std::vector<uint32_t> b((size_t)std::max(prow, 1) * w, 0u);
+    if (rows > 0)
+      std::memcpy(b.data(), &data.label_bits[(size_t)first * w], sizeof(uint32_t) * (size_t)rows * w);
+    label_bits.allocate(b.size());
+    label_bits.upload(b);
+    label_words = w;
+    ctx.label_bits = label_bits.get();
+    ctx.label_words = w;
   }
   // weights: glorot in layer order from the default seed (hpdga gcn.cpp:64-128)
   std::vector<int> dims;
@@ -664,7 +701,8 @@ void GCN::build(const GCNData &data) {
   if (g_co_draw && dropouts_.size() >= 2 && (g_co_draw == 2 || !feats.dense) && dropouts_[0] &&
       dropouts_[1])
     const_cast<Dropout *>(dropouts_[0])->co_draw = dropouts_[1];
-  if (g_fuse_output) fuse_output_layer();
+  // (multilabel: the output Matmul runs on its own, the `fuse_output 0` path)
+  if (g_fuse_output && !params.multilabel) fuse_output_layer();
   optimizer = Adam(weights, decays, adam_params);
   prepare_graphs();
   build_eval_ax();
@@ -951,7 +989,8 @@ void GCN::insert_last_layer() {
     auto mm = std::make_unique<Matmul>(z, weights.back(), out, part.local_rows(), hl, C, &ctx);
     mm->last_layer = true;
     modules.push_back(std::move(mm));
-    modules.push_back(std::make_unique<CrossEntropyLoss>(out, C, &ctx));
+    if (params.multilabel) modules.push_back(std::make_unique<BCEWithLogitsLoss>(out, C, &ctx));
+    else modules.push_back(std::make_unique<CrossEntropyLoss>(out, C, &ctx));
     if (!comm && graph) {  // compact output layer buffers (split rows, see ModuleContext)
       size_t mx = 1;
       for (int sp = 1; sp <= 3; sp++) mx = std::max(mx, split_rows_host[sp].size());
@@ -971,13 +1010,15 @@ void GCN::insert_last_layer() {
   restricted_vars.push_back((int)variables.size());
   variables.push_back(out);
   modules.push_back(std::make_unique<GraphSum>(var1, out, graph.get(), C, &ctx, true));
-  modules.push_back(std::make_unique<CrossEntropyLoss>(out, C, &ctx));
+  if (params.multilabel) modules.push_back(std::make_unique<BCEWithLogitsLoss>(out, C, &ctx));
+  else modules.push_back(std::make_unique<CrossEntropyLoss>(out, C, &ctx));
 }
 
 void GCN::set_split(int split) {
   ctx.truth = truth[split].get();
-  ctx.count = counts[split];
-  modules.back()->set_num_samples(counts[split]);
+  ctx.count = loss_count(split);
+  modules.back()->set_num_samples(loss_count(split));
+  ctx.compact_label_bits = label_bits_compact[split].get();
   // output-layer row restriction: Â restricted to the split's labelled rows, built at the
   // split's first use (single GPU; the edge-cut engine restricts its chunk graphs below)
   ctx.split_graph = nullptr;
@@ -1585,9 +1626,11 @@ void GCN::save(const std::string &path) {
   ck.dropouts = params.dropouts;
   ck.seed = params.seed;
   ck.flags = residuals_.empty() ? 0u : kCheckpointResidual;
+  if (params.multilabel) ck.flags |= kCheckpointMultilabel;
   if (norm_var) {  // version 2: the scale / shift tensor behind the layer weights
     ck.flags |= kCheckpointLayerNorm;
-    ck.version = kCheckpointVersionLayerNorm;
+    ck.version = params.multilabel ? kCheckpointVersionLayerNormMultilabel
+                                   : kCheckpointVersionLayerNorm;
   }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
@@ -1612,7 +1655,8 @@ void GCN::load(const std::string &path, int flags) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
     // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)
     same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty() &&
-           !(ck.flags & kCheckpointLayerNorm) == !norm_var;
+           !(ck.flags & kCheckpointLayerNorm) == !norm_var &&
+           !(ck.flags & kCheckpointMultilabel) == !params.multilabel;
     for (int l = 0; same && l < L; l++) same = ck.dropouts[(size_t)l] == params.dropouts[(size_t)l];
   }
   PGCN_CHECK(same, PGCN_E_INVALID, "load: the checkpoint is for another model");
@@ -1697,8 +1741,45 @@ long long GCN::predict(int *cls, float *conf, float *probs) {
   return n;
 }
 
+long long GCN::predict_multilabel(uint32_t *bits, float *probs) {
+  const auto *bl = dynamic_cast<const BCEWithLogitsLoss *>(modules.back().get());
+  PGCN_CHECK(bl, PGCN_E_INVALID, "predict_multilabel: not a multi-label engine");
+  const Variable &z = *bl->input();
+  const int n = part.local_rows(), C = params.output_dim, ldp = round_up4(C), W = label_words;
+  if (!pred_bits) pred_bits.allocate((size_t)std::max(part.maxrows, 1) * W);
+  if (probs && !pred_probs) pred_probs.allocate((size_t)std::max(part.maxrows, 1) * ldp);
+  predict_forward();
+  launch_predict_multilabel(z.dev_data.get(), z.ld, n, C, pred_bits.get(), W,
+                            probs ? pred_probs.get() : nullptr, ldp, stream.get());
+  sync();
+  if (bits) pred_bits.download(bits, (size_t)n * W);
+  if (probs) {
+    std::vector<float> raw((size_t)n * ldp);
+    pred_probs.download(raw.data(), raw.size());
+    for (int i = 0; i < n; i++)
+      std::memcpy(probs + (size_t)i * C, &raw[(size_t)i * ldp], sizeof(float) * (size_t)C);
+  }
+  return n;
+}
+
+void GCN::multilabel_counts(int split, long long *counts) {
+  PGCN_CHECK(split >= 1 && split <= 3 && counts, PGCN_E_INVALID,
+             "multilabel_counts: split 1, 2 or 3");
+  const int C = params.output_dim;
+  predict_multilabel(nullptr, nullptr);
+  if (!pred_counts) pred_counts.allocate((size_t)3 * C);
+  launch_multilabel_counts(pred_bits.get(), label_bits.get(), truth[split].get(),
+                           part.local_rows(), C, label_words, pred_counts.get(), stream.get());
+  sync();
+  std::vector<unsigned> h((size_t)3 * C);
+  pred_counts.download(h.data(), h.size());
+  for (size_t i = 0; i < h.size(); i++) counts[i] = (long long)h[i];
+}
+
 void GCN::confusion(int split, long long *counts) {
   PGCN_CHECK(split >= 1 && split <= 3 && counts, PGCN_E_INVALID, "confusion: split 1, 2 or 3");
+  PGCN_CHECK(!params.multilabel, PGCN_E_INVALID,
+             "confusion: a multi-label engine has per-class counts (multilabel_counts)");
   const int C = params.output_dim;
   predict(nullptr, nullptr, nullptr);
   if (!pred_counts) pred_counts.allocate((size_t)C * C);

@@ -43,6 +43,9 @@ struct GCNParams {
   // every hidden layer gets a LayerNorm between its GraphSum and its ReLU (LayerNorm,
   // module.hpp); its scale / shift tensor is one more weight (no decay) behind the layers'
   bool layer_norm = false;
+  // multi-label classification: GCNData::label_bits targets, BCEWithLogitsLoss as the last
+  // module (the output Matmul unfused), count = labelled rows x classes
+  bool multilabel = false;
 };
 
 struct AdamParams {
@@ -133,6 +136,11 @@ class GCN {
   long long predict(int *cls, float *conf, float *probs);
   // predict + k_confusion against `split`'s labels: counts[c * c] of this rank's rows
   void confusion(int split, long long *counts);
+  // multi-label engines: predict()'s forward, then k_predict_multilabel: bits [rows][words],
+  // probs [rows][C] dense (either may be null); and k_multilabel_counts against `split`'s
+  // labels: counts [3][C] = tp, fp, fn of this rank's rows
+  long long predict_multilabel(uint32_t *bits, float *probs);
+  void multilabel_counts(int split, long long *counts);
   long long adam_steps() const { return optimizer.steps(); }
   void set_profile(bool on);
   void profile_read_mm(double *ms, long long *calls, double *flops);  // XW contractions
@@ -233,6 +241,14 @@ class GCN {
   std::vector<DeviceBuffer<int>> chunk_split_rows[4];
   std::vector<std::unique_ptr<DevGraph>> chunk_col_graphs;  // training split's columns
   DeviceBuffer<int> truth_compact[4];                // the split's labels, compact row order
+  // multilabel: this rank's rows of the label bit matrix ([maxrows][label_words]; the same for
+  // every split: truth[s] selects the rows), and per split its labelled rows' words compacted
+  DeviceBuffer<uint32_t> label_bits, label_bits_compact[4];
+  int label_words = 0;
+  // the loss's count of a split: its labelled rows (global), x classes on a multi-label engine
+  int loss_count(int split) const {
+    return params.multilabel ? counts[split] * params.output_dim : counts[split];
+  }
   std::unique_ptr<Variable> compact_z, compact_out;  // compact output layer (ModuleContext)
   long long nnz_x_global = 0;
   // Â equals its transpose (csr_symmetric at build): the reassociated output layer's
@@ -282,6 +298,7 @@ class GCN {
   DeviceBuffer<int> pred_cls;
   DeviceBuffer<float> pred_conf, pred_probs;
   DeviceBuffer<unsigned> pred_counts;
+  DeviceBuffer<uint32_t> pred_bits;
   bool last_forward_training = false;
   bool reassociated_ = false;
   float ax_build_ms = 0.0f;

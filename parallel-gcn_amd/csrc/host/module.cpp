@@ -962,4 +962,25 @@ void CrossEntropyLoss::forward(bool training, const Stream &s) const {
 
 void CrossEntropyLoss::backward(const Stream &) const {}  // module.cpp:155-156
 
+// ------------------------------------------------------------------------------------------
+// BCEWithLogitsLoss (multi-label; k_multilabel.hip)
+// ------------------------------------------------------------------------------------------
+BCEWithLogitsLoss::BCEWithLogitsLoss(shared_ptr<Variable> logits_, int num_classes_,
+                                     ModuleContext *ctx_)
+    : logits(std::move(logits_)), num_classes(num_classes_), ctx(ctx_) {}
+
+void BCEWithLogitsLoss::forward(bool training, const Stream &s) const {
+  const bool cmp = ctx->compact_n != 0;
+  const Variable &L = cmp ? *ctx->compact_out : *logits;
+  PGCN_CHECK(ctx->label_bits && (!cmp || ctx->compact_label_bits), PGCN_E_INVALID,
+             "BCEWithLogitsLoss: no label bits");
+  launch_bce_fwd(L.dev_data.get(), L.ld, training ? L.dev_grad.get() : nullptr,
+                 cmp ? ctx->compact_truth : ctx->truth,
+                 cmp ? ctx->compact_label_bits : ctx->label_bits, ctx->label_words,
+                 cmp ? ctx->compact_n : logits->rows, num_classes, std::max(ctx->count, 1),
+                 training ? 1 : 0, ctx->xent_partials, s.get());
+}
+
+void BCEWithLogitsLoss::backward(const Stream &) const {}  // the forward wrote the gradient
+
 }  // namespace pgcn

@@ -148,7 +148,12 @@ struct ModuleContext {
   Variable *compact_z = nullptr;       // last GraphSum output / Matmul input (+ grad)
   Variable *compact_out = nullptr;     // logits (+ grad)
   const int *truth = nullptr;  // current split's truth (device)
-  int count = 0;               // labelled rows of the current split (global)
+  // multi-label engines: the label bit matrix of this rank's rows ([rows][label_words]) and of
+  // the current split's rows in compact order (beside compact_truth)
+  const uint32_t *label_bits = nullptr, *compact_label_bits = nullptr;
+  int label_words = 0;
+  // labelled rows of the current split (global); multi-label: times the classes
+  int count = 0;
   float *xent_partials = nullptr;
   int xent_blocks = 0;
   // one GPU ("fuse_finish"): the pass's scalars finished by the loss kernel's last block
@@ -446,6 +451,26 @@ class CrossEntropyLoss : public Module {
   // ... and the GraphSum whose backward reads that Matmul's input grad (the reassociated
   // output layer's): the fused kernel also writes its prescaled table (claim_backward_table)
   const GraphSum *dh_reader = nullptr;
+  const Variable *input() const { return logits.get(); }
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+  void set_num_samples(int n) override { num_samples = n; }
+  int get_num_samples() const override { return num_samples; }
+};
+
+// The multi-label loss in CrossEntropyLoss's place (the reference has none): per-class sigmoid
+// with binary cross-entropy against ctx->label_bits on the rows with ctx->truth >= 0, mean over
+// ctx->count = labelled rows x classes (k_bce_fwd).  Full rows or the compact output layer's, as
+// the unfused branch of CrossEntropyLoss::forward; the logits are left as the Matmul / GraphSum
+// wrote them.  It does not take ctx->fin: GCN::finalize launches k_reduce_scalars.
+class BCEWithLogitsLoss : public Module {
+  shared_ptr<Variable> logits;
+  int num_classes;
+  ModuleContext *ctx;
+  int num_samples = 0;
+
+ public:
+  BCEWithLogitsLoss(shared_ptr<Variable> logits_, int num_classes_, ModuleContext *ctx_);
   const Variable *input() const { return logits.get(); }
   void forward(bool training, const Stream &s) const override;
   void backward(const Stream &s) const override;

@@ -419,6 +419,27 @@ void launch_predict_rows(const float *logits, int ld, int n, int c, int *cls, fl
 // counts[t * c + p] = rows with truth[i] == t >= 0 and cls[i] == p, zeroed first (integer adds)
 void launch_confusion(const int *cls, const int *truth, int n, int c, unsigned int *counts,
                       hipStream_t s);
+// ---- multi-label classification (k_multilabel.hip) ------------------------------------------
+// Sigmoid + binary cross-entropy on logits [n][ld] against the bit matrix label_bits [n][words]
+// (bit j % 32 of word j / 32: row i has class j), rows with truth >= 0 only: launch_xent_fwd's
+// contract (xent_blocks(n) blocks, {loss sum, wrong} per block in `partials`, training: grad =
+// (sigmoid - y) / count, zero in columns [c, ld) and on unlabelled rows), but the logits are
+// never written and 1 <= c <= kPredictMaxClasses.  The check_* functions are the launchers'
+// argument checks alone (no device).
+void check_bce_args(int ld, int words, int n, int c, int count);
+void launch_bce_fwd(const float *logits, int ld, float *grad, const int *truth,
+                    const uint32_t *label_bits, int words, int n, int c, int count, int training,
+                    float *partials, hipStream_t s);
+// bits [n][words]: bit j of word w = logits[i][32 w + j] > 0 (zero from class c on); probs
+// (optional) [n][ld_probs]: the sigmoid row, zero in columns [c, round_up4(c))
+void check_predict_multilabel_args(int ld, int n, int c, int words, bool probs, int ld_probs);
+void launch_predict_multilabel(const float *logits, int ld, int n, int c, uint32_t *bits,
+                               int words, float *probs, int ld_probs, hipStream_t s);
+// counts [3][c] = tp, fp, fn per class over the rows with truth >= 0, zeroed first (integer adds)
+void check_multilabel_counts_args(int n, int c, int words);
+void launch_multilabel_counts(const uint32_t *pred_bits, const uint32_t *label_bits,
+                              const int *truth, int n, int c, int words, unsigned int *counts,
+                              hipStream_t s);
 // sums (optional): {loss sum, wrong}; out2 (optional): the composed {loss + l2, accuracy};
 // raw4 (optional): {loss sum, wrong, sum w^2, count} for a composition after an all-reduce
 void launch_reduce_scalars(const float *partials, int n_blocks, const float *w, long long n_w,

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -12,6 +12,10 @@
 // New with the engine: load= resumes from a checkpoint before the run (the epoch lines go on
 // from its epoch count, up to `epochs`), save= writes one after it, predict= writes one line
 // `node class confidence` per node after it; epochs= overrides the parameter file's.
+// multilabel=1 (command line or parameter file): multi-label classification, pgcn_params.multilabel
+// -- the labels come from the sidecar file data/<name>.labels (line i: the class ids of node i),
+// the epoch lines' accuracy column is the Hamming accuracy, and predict= writes `node id id ...`
+// (the classes with a positive logit) per node.
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -62,6 +66,7 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "seed") p->seed = (unsigned)std::strtoul(v.c_str(), nullptr, 10);
     else if (k == "residual") p->residual = std::atoi(v.c_str());
     else if (k == "layer_norm") p->layer_norm = std::atoi(v.c_str());
+    else if (k == "multilabel") p->multilabel = std::atoi(v.c_str());
   }
   return true;
 }
@@ -76,7 +81,7 @@ int main(int argc, char **argv) {
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
   std::string load, save, predict;
-  int epochs = -1, residual = -1, layer_norm = -1;
+  int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -88,6 +93,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "epochs=", 7)) epochs = std::atoi(argv[i] + 7);
     if (!std::strncmp(argv[i], "residual=", 9)) residual = std::atoi(argv[i] + 9);
     if (!std::strncmp(argv[i], "layer_norm=", 11)) layer_norm = std::atoi(argv[i] + 11);
+    if (!std::strncmp(argv[i], "multilabel=", 11)) multilabel = std::atoi(argv[i] + 11);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -98,6 +104,7 @@ int main(int argc, char **argv) {
   if (epochs >= 0) p.epochs = epochs;
   if (residual >= 0) p.residual = residual;
   if (layer_norm >= 0) p.layer_norm = layer_norm;
+  if (multilabel >= 0) p.multilabel = multilabel;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
@@ -106,6 +113,13 @@ int main(int argc, char **argv) {
     return EXIT_FAILURE;
   }
   if (no_feature) pgcn_dataset_binarize(ds);
+  if (p.multilabel) {
+    const std::string labels = root + "/data/" + name + ".labels";
+    if (pgcn_dataset_load_labels(ds, labels.c_str(), 0) != PGCN_OK) {
+      fprintf(stderr, "Cannot read labels: %s\n", labels.c_str());
+      return EXIT_FAILURE;
+    }
+  }
   pgcn_data view;
   pgcn_dataset_view(ds, &view, &p.input_dim, &p.output_dim);
   p.num_nodes = view.num_nodes;
@@ -122,7 +136,24 @@ int main(int argc, char **argv) {
   st = pgcn_gcn_run(g, 1);
   if (st == PGCN_OK && !save.empty() && (st = pgcn_gcn_save(g, save.c_str())) != PGCN_OK)
     fprintf(stderr, "cannot save %s: %s\n", save.c_str(), pgcn_status_string(st));
-  if (st == PGCN_OK && !predict.empty()) {
+  if (st == PGCN_OK && !predict.empty() && p.multilabel) {
+    const int words = (p.output_dim + 31) / 32;
+    std::vector<uint32_t> bits((size_t)view.num_nodes * words);
+    const long long n = pgcn_gcn_predict_multilabel(g, bits.data(), nullptr);
+    FILE *f = n >= 0 ? std::fopen(predict.c_str(), "w") : nullptr;
+    if (!f) {
+      fprintf(stderr, "cannot write predictions to %s\n", predict.c_str());
+      st = n < 0 ? (int)n : PGCN_E_IO;
+    } else {
+      for (long long i = 0; i < n; i++) {
+        fprintf(f, "%lld", i);
+        for (int j = 0; j < p.output_dim; j++)
+          if ((bits[(size_t)i * words + j / 32] >> (j % 32)) & 1u) fprintf(f, " %d", j);
+        fprintf(f, "\n");
+      }
+      std::fclose(f);
+    }
+  } else if (st == PGCN_OK && !predict.empty()) {
     std::vector<int> cls((size_t)view.num_nodes);
     std::vector<float> conf((size_t)view.num_nodes);
     const long long n = pgcn_gcn_predict(g, cls.data(), conf.data(), nullptr);
