@@ -186,6 +186,46 @@ int pgcn_debug_layernorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, 
                                   const float *res, int res_ld, const uint64_t *drop_mask,
                                   long long drop_base, float drop_scale, void *stream);
 
+/* --- graph attention over a node variable (new: the reference has one aggregation) ---------
+ * Single head, additive (GAT).  `g` comes from pgcn_graph_create with a square pattern; its
+ * values are not used.  Every CSR slot s = (i, j) counts as the pattern has it (self loops, a
+ * duplicated edge twice).  With P [n][ld_p] and the attention vectors a_dst, a_src [d]:
+ *   pgcn_gat_scores: u[i] = P_i . a_dst, v[i] = P_i . a_src (one pass over P).
+ *   pgcn_gat_fwd:    e_s = x > 0 ? x : slope x with x = u[i] + v[j] (strict >), alpha_s = exp(e_s -
+ *     max_row) / sum_row exp(e - max_row), Z_i = sum over row i's slots of alpha_s P_j.  A row
+ *     without a slot gives Z_i = 0.  alpha [nnz] (may be NULL; a training forward) receives the
+ *     slot weights the backward reads.
+ *   pgcn_gat_bwd:    with G [n][ld_g] = dLoss/dZ and the forward's u, v, alpha, Z: dx_s = alpha_s
+ *     (G_i . P_j - G_i . Z_i) (x_s > 0 ? 1 : slope), du_i / dv_j its sums over row i / over the
+ *     slots into column j; dP_j = sum over the slots into j of alpha_s G_i + du_j a_dst + dv_j
+ *     a_src; da [2][d] = {sum du_i P_i, sum dv_j P_j} (a_dst's gradient, then a_src's).
+ *     `workspace`: pgcn_gat_bwd_workspace(g, d) bytes, 16-byte aligned (dx per slot, du, dv and
+ *     the partial sums).  d is passed (after ld_dp): the widths cannot be told from the strides.
+ * 1 <= d <= 128; every ld a multiple of 4 and >= d; every row 16-byte aligned.  The float4s
+ * covering columns [0, round_up4(d)) of Z and dP are written, zero from column d on; columns
+ * beyond them are left alone.  Padding columns of P, Z and G are never read into the result.
+ * The sums into a column walk the transposed index in CSR order (a store pass per slot, then a
+ * sum pass per destination); rows and columns longer than 512 slots are cut into 512-slot
+ * segments summed by separate waves and merged in segment order; da goes through per-workgroup
+ * partials and one reducing launch.  Every order depends on the pattern and d only: two calls
+ * give the same bits.  No float atomics.
+ * PGCN_E_INVALID (before anything touches the device) for d outside [1, 128], an ld that is not
+ * a multiple of 4 or below d, a null required pointer; n == 0 launches nothing.  Asynchronous on
+ * `stream`, allocate nothing and may be captured -- after the graph's first attention call,
+ * which builds and uploads the transposed index (pgcn_gat_bwd_workspace does it too).  The
+ * forward keeps its long rows' partial sums in the graph: two forwards on one graph must not
+ * run side by side. */
+int pgcn_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
+                    const float *a_src, float *u, float *v, void *stream);
+int pgcn_gat_fwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                 float slope, float *Z, int ld_z, int d, float *alpha /* [nnz] or NULL */,
+                 void *stream);
+size_t pgcn_gat_bwd_workspace(const pgcn_graph *g, int d);
+int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                 float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                 int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                 float *da /* [2][d]: dst, src */, void *workspace, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -263,6 +303,17 @@ typedef struct {
   float dropouts[PGCN_MAX_LAYERS];       /* n_layers */
   int epochs, early_stopping;
   float learning_rate, weight_decay, beta1, beta2, eps;
+  /* != 0: graph attention layers -- every layer's GraphSum is replaced by a single-head additive
+   * attention over the node's neighbours (pgcn_gat_fwd, LeakyReLU slope 0.2) on the adjacency
+   * pattern as loaded, directed patterns included; the Â coefficients are not used.  Hidden layers
+   * go on as before ([LayerNorm] -> ReLU -> [Residual] -> Dropout); the output layer is Z itself.
+   * The attention vectors, per layer a_dst[d_l] then a_src[d_l], are one more trainable tensor
+   * (Glorot-uniform, limit sqrt(6 / (d_l + 1)) per vector, drawn after the last layer weight: the
+   * dropout streams start after those draws; Adam without weight decay).  No reassociated output
+   * layer, no Â X precompute, no output-row restriction, the loss unfused.  Hidden widths and
+   * output_dim up to 128; single GPU only (the edge-cut creators return PGCN_E_INVALID: a row's
+   * softmax needs all its columns).  0: the GCN engine, bit for bit. */
+  int attention;
   /* 1: compute the output layer as (Â H) W instead of Â (H W) when hidden < classes, so its
    * GraphSum gathers hidden-width rows.  Exact algebra when Â is symmetric (checked at engine
    * build: a non-symmetric pattern keeps the reference's order); only the fp32 rounding order
@@ -367,7 +418,9 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "fused_norm_tails" (how many of them ran the ReLU / residual add /
  * Dropout behind them inside the LayerNorm kernel in the last training forward);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
- * the normalised variables -- always 0).
+ * the normalised variables -- always 0); "attention_layers" (layers whose aggregation is graph
+ * attention, pgcn_params.attention: n_layers or 0; on such an engine "reassociated", "eval_ax_us"
+ * and "graphsum_lds" are 0).
  * Returns the value (>= 0) or PGCN_E_INVALID for an unknown key. */
 long long pgcn_gcn_query(pgcn_gcn *g, const char *key);
 /* GCN::train_epoch / GCN::eval (src/gcn.cu:293-343): out2 = {loss, accuracy} */
@@ -398,7 +451,11 @@ int pgcn_gcn_run(pgcn_gcn *g, int verbose);
  * it.  The LayerNorm backward transforms in place the buffer the layer's GraphSum backward
  * reads: after a training epoch the grad of var2 of such a layer is dLoss/dZ, the gradient with
  * respect to the GraphSum's output (on a residual layer that buffer is the engine's own masked
- * one, and var2's grad stays G as above). */
+ * one, and var2's grad stays G as above).
+ * Attention engines (pgcn_params.attention) have one more variable behind all others, index
+ * pgcn_gcn_num_vars - 1 (3 * n_layers + 1, or 3 * n_layers + 2 with LayerNorm): the attention
+ * tensor, per layer a_dst[d_l] then a_src[d_l], layers in order (which = 1: its gradient).
+ * pgcn_gcn_set_var accepts it. */
 long long pgcn_gcn_get_var(pgcn_gcn *g, int idx, int which, float *host_dst);
 int pgcn_gcn_num_vars(pgcn_gcn *g);
 /* Weights only (idx must be a weight variable, which == 0), in get_var's layout and count;
@@ -430,7 +487,7 @@ int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags);
  * epochs, weight count}.  PGCN_E_IO as pgcn_gcn_load. */
 int pgcn_checkpoint_info(const char *path, long long info[8]);
 /* Host-only: the file's header flags (>= 0; bit 0: saved by a residual engine; bit 1: by a
- * LayerNorm engine; bit 2: by a multi-label engine), validated as
+ * LayerNorm engine; bit 2: by a multi-label engine; bit 3: by an attention engine), validated as
  * pgcn_checkpoint_info does, or a status < 0 (PGCN_E_IO also for flag bits this library does
  * not know). */
 int pgcn_checkpoint_flags(const char *path);
@@ -444,6 +501,13 @@ int pgcn_checkpoint_flags(const char *path);
  * crosses it.  (In a version-2 file the bit stays unknown, as it was before it had a meaning: a
  * multi-label engine with LayerNorm writes version 3, version 2's layout with bits 1 and 2.) */
 #define PGCN_CKPT_MULTILABEL 4
+/* bit 3: saved by an attention engine (pgcn_params.attention) -- a version-4 file: the existing
+ * layout, the weight count and the w / m / v payloads carrying the attention tensor last (after
+ * the scale / shift tensor when bit 1 is set); bits 0-3 are all known there.  In files of
+ * versions 1-3 the bit stays unknown.  A flags-0 load refuses a file whose bit differs from the
+ * engine's; a weights-only load crosses it as it crosses bit 1 (a file without the tensor leaves
+ * the engine's alone, a plain engine ignores a file's). */
+#define PGCN_CKPT_ATTENTION 8
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
@@ -585,7 +649,8 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * can assert which kernels a configuration took: "xs_nn_ring" / "xs_tn_ring" (loader + MFMA-wave
  * X-stream kernels), "xs_nn" / "xs_tn" (register-streamed X-stream kernels), "gs_ring" (LDS ring
  * GraphSum), "gs_gather" (gather GraphSum), "out_xent" (output layer fused into the loss),
- * "gemm_nn" / "gemm_tn" (general MFMA GEMMs), "launches" (every kernel launch of the library).
+ * "gemm_nn" / "gemm_tn" (general MFMA GEMMs), "gat_fwd" / "gat_bwd" (graph attention forward /
+ * backward calls, pgcn_gat_fwd / pgcn_gat_bwd), "launches" (every kernel launch of the library).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

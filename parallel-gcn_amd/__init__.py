@@ -43,7 +43,8 @@ class PgcnParams(ctypes.Structure):
                 ("n_layers", c_int), ("hidden_dims", c_int * MAX_LAYERS),
                 ("dropouts", c_float * MAX_LAYERS), ("epochs", c_int), ("early_stopping", c_int),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
-                ("beta2", c_float), ("eps", c_float), ("reassociate_last", c_int),
+                ("beta2", c_float), ("eps", c_float), ("attention", c_int),
+                ("reassociate_last", c_int),
                 ("multilabel", c_int), ("seed", ctypes.c_uint), ("layer_norm", c_int), ("residual", c_int)]
 
 
@@ -117,6 +118,14 @@ _sig("pgcn_layernorm_bwd", c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_
 _sig("pgcn_debug_layernorm_fwd_tail", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
      c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
      c_void_p, c_ll, c_float, c_void_p)
+_sig("pgcn_gat_scores", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+     c_void_p, c_void_p)
+_sig("pgcn_gat_fwd", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
+     c_int, c_int, c_void_p, c_void_p)
+_sig("pgcn_gat_bwd_workspace", c_size_t, c_void_p, c_int)
+_sig("pgcn_gat_bwd", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
+     c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+     c_void_p, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -228,7 +237,7 @@ def _ptr(a):
 
 
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
-                "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "launches")
+                "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "launches")
 
 
 def path_counts(reset=False, thread=False):
@@ -385,9 +394,10 @@ def f1_scores(counts):
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
-                multilabel=False):
+                multilabel=False, attention=False):
     p = PgcnParams()
     lib.pgcn_params_default(ctypes.byref(p))
+    p.attention = 1 if attention else 0
     p.multilabel = 1 if multilabel else 0
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
@@ -659,12 +669,13 @@ def checkpoint_info(path):
 CKPT_RESIDUAL = 1
 CKPT_LAYERNORM = 2  # version-2 files: the scale / shift tensor behind the layer weights
 CKPT_MULTILABEL = 4  # saved by a multi-label engine (no payload change)
+CKPT_ATTENTION = 8  # version-4 files: the attention tensor last in the payloads
 
 
 def checkpoint_flags(path):
     """Host-only: a checkpoint file's header flags (bit 0, CKPT_RESIDUAL: saved by an engine with
     residual layers; bit 1, CKPT_LAYERNORM: by one with LayerNorm; bit 2, CKPT_MULTILABEL: by a
-    multi-label one).  PgcnError(PGCN_E_IO) for an
+    multi-label one; bit 3, CKPT_ATTENTION: by an attention one).  PgcnError(PGCN_E_IO) for an
     invalid file or unknown flag bits."""
     st = lib.pgcn_checkpoint_flags(os.fsencode(path))
     check(min(st, 0), f"checkpoint_flags {path}")
@@ -747,6 +758,7 @@ EXPORTED = [
     "pgcn_relu_bwd", "pgcn_residual_fwd", "pgcn_residual_bwd", "pgcn_params_sizeof",
     "pgcn_layernorm_fwd", "pgcn_layernorm_bwd_workspace", "pgcn_layernorm_bwd",
     "pgcn_debug_layernorm_fwd_tail",
+    "pgcn_gat_scores", "pgcn_gat_fwd", "pgcn_gat_bwd_workspace", "pgcn_gat_bwd",
     "pgcn_checkpoint_flags", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
     "pgcn_adam_step_size", "pgcn_params_default", "pgcn_gcn_create", "pgcn_comm_unique_id",
     "pgcn_gcn_create_dist", "pgcn_gcn_create_peer", "pgcn_loopback_create",

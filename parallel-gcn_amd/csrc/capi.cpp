@@ -52,7 +52,8 @@ std::atomic<long long> g_path_hits[KP_COUNT];
 thread_local long long t_path_hits[KP_COUNT];  // the launching host thread's (loopback ranks)
 const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",   "xs_tn",
                                           "gs_ring",    "gs_gather",  "out_xent", "gemm_nn",
-                                          "gemm_tn",    "gemm_nn_w",  "gemm_tn_w", "launches"};
+                                          "gemm_tn",    "gemm_nn_w",  "gemm_tn_w", "gat_fwd",
+                                          "gat_bwd",    "launches"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -80,6 +81,12 @@ void check_device() {
     throw Error(PGCN_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
 }
 
+// the edge-cut creators: a row's softmax needs all its columns
+void refuse_attention(const pgcn_params *p) {
+  PGCN_CHECK(!p->attention, PGCN_E_INVALID,
+             "attention: single GPU only (edge-cut attention is not supported)");
+}
+
 GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   GCNParams q;
   q.num_nodes = d->num_nodes;
@@ -95,6 +102,7 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.residual = p->residual != 0;
   q.layer_norm = p->layer_norm != 0;
   q.multilabel = p->multilabel != 0;
+  q.attention = p->attention != 0;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -491,6 +499,65 @@ int pgcn_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xha
   });
 }
 
+namespace {
+void check_gat_dims(int n, int d, std::initializer_list<int> lds) {
+  PGCN_CHECK(n >= 0 && d >= 1 && d <= kGatMaxWidth, PGCN_E_INVALID, "gat: 1 <= d <= 128");
+  for (int ld : lds) PGCN_CHECK(ln_ld_ok(ld, d), PGCN_E_INVALID, "gat: ld % 4 == 0, ld >= d");
+}
+}  // namespace
+
+int pgcn_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
+                    const float *a_src, float *u, float *v, void *stream) {
+  return guarded([&] {
+    check_gat_dims(n, d, {ld_p});
+    PGCN_CHECK(n == 0 || (P && a_dst && a_src && u && v && aligned16(P)), PGCN_E_INVALID,
+               "gat_scores: null or misaligned argument");
+    if (n == 0) return;
+    check_device();
+    launch_gat_scores(P, ld_p, n, d, a_dst, a_src, u, v, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_gat_fwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                 float slope, float *Z, int ld_z, int d, float *alpha, void *stream) {
+  return guarded([&] {
+    check_gat_dims(0, d, {ld_p, ld_z});
+    PGCN_CHECK(g && g->g && P && u && v && Z && aligned16(P) && aligned16(Z), PGCN_E_INVALID,
+               "gat_fwd: null or misaligned argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_fwd: square pattern");
+    check_device();
+    launch_gat_fwd(g->g->gat_pattern(), P, ld_p, u, v, slope, Z, ld_z, d, alpha,
+                   as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+size_t pgcn_gat_bwd_workspace(const pgcn_graph *g, int d) {
+  if (!g || !g->g || d < 1 || d > kGatMaxWidth || g->g->rows() != g->g->cols()) return 0;
+  size_t bytes = 0;
+  (void)guarded([&] { bytes = gat_bwd_workspace(g->g->gat_pattern(), d); });
+  return bytes;
+}
+
+int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                 float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                 int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                 float *da, void *workspace, void *stream) {
+  return guarded([&] {
+    check_gat_dims(0, d, {ld_p, ld_z, ld_g, ld_dp});
+    PGCN_CHECK(g && g->g && P && u && v && alpha && Z && G && a_dst && a_src && dP && da &&
+                   workspace && aligned16(P) && aligned16(Z) && aligned16(G) && aligned16(dP) &&
+                   aligned16(workspace),
+               PGCN_E_INVALID, "gat_bwd: null or misaligned argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_bwd: square pattern");
+    check_device();
+    launch_gat_bwd(g->g->gat_pattern(), P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst,
+                   a_src, dP, ld_dp, d, da, workspace, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -590,6 +657,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->beta1 = 0.9f;
   p->beta2 = 0.999f;
   p->eps = 1e-8f;
+  p->attention = 0;
   p->reassociate_last = 1;
   p->multilabel = 0;
   p->seed = 0;
@@ -616,6 +684,7 @@ int pgcn_gcn_create_dist(const pgcn_params *p, const pgcn_data *d, int device, i
                          int world, const void *uid, pgcn_gcn **out) {
   return guarded([&] {
     PGCN_CHECK(p && d && out && uid, PGCN_E_INVALID, "gcn_create_dist args");
+    refuse_attention(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -634,6 +703,7 @@ int pgcn_gcn_create_peer(const pgcn_params *p, const pgcn_data *d, int device, i
     PGCN_CHECK(p && d && out && allgather && world >= 1 && world <= kPeerMaxRanks && rank >= 0 &&
                    rank < world,
                PGCN_E_INVALID, "gcn_create_peer args");
+    refuse_attention(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -654,6 +724,7 @@ int pgcn_debug_gcn_create_solo(const pgcn_params *p, const pgcn_data *d, int dev
   return guarded([&] {
     PGCN_CHECK(p && d && out && world >= 1 && rank >= 0 && rank < world, PGCN_E_INVALID,
                "gcn_create_solo args");
+    refuse_attention(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -684,6 +755,7 @@ int pgcn_gcn_create_loopback(const pgcn_params *p, const pgcn_data *d, int devic
                              pgcn_loopback *group, pgcn_gcn **out) {
   return guarded([&] {
     PGCN_CHECK(p && d && out && group && group->g, PGCN_E_INVALID, "gcn_create_loopback args");
+    refuse_attention(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -724,6 +796,7 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
     return st == PGCN_OK ? n : st;
   }
   if (!std::strcmp(key, "norm_layers")) return e.norm_layers();
+  if (!std::strcmp(key, "attention_layers")) return e.attention_layers();
   if (!std::strcmp(key, "multilabel")) return e.get_params().multilabel ? 1 : 0;
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;

@@ -53,6 +53,12 @@ long long norm_count_of(const int32_t *dims, int n_layers) {
   return n;
 }
 
+long long attn_count_of(const int32_t *dims, int n_layers) {
+  long long n = 0;
+  for (int l = 1; l <= n_layers; l++) n += 2LL * dims[l];
+  return n;
+}
+
 // whether a file of this version may carry these flag bits (false: unknown version or bit)
 bool version_flags_ok(uint32_t version, uint32_t flags) {
   if (version == (uint32_t)kCheckpointVersion) return (flags & ~kCheckpointKnownFlags) == 0;
@@ -62,12 +68,16 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
   if (version == (uint32_t)kCheckpointVersionLayerNormMultilabel)
     return (flags & kCheckpointLayerNorm) && (flags & kCheckpointMultilabel) &&
            (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm)) == 0;
+  if (version == (uint32_t)kCheckpointVersionAttention)
+    return (flags & kCheckpointAttention) &&
+           (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm | kCheckpointAttention)) == 0;
   return false;
 }
 
 long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags) {
   return weight_count(dims, n_layers) +
-         ((flags & kCheckpointLayerNorm) ? norm_count_of(dims, n_layers) : 0);
+         ((flags & kCheckpointLayerNorm) ? norm_count_of(dims, n_layers) : 0) +
+         ((flags & kCheckpointAttention) ? attn_count_of(dims, n_layers) : 0);
 }
 }  // namespace
 

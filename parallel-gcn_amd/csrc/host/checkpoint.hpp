@@ -19,6 +19,11 @@
 // file, no payload change.  In a version-2 file bit 2 stays unknown (as before this bit existed),
 // so a multi-label engine with LayerNorm writes version 3: version 2's layout with bits 1 and 2
 // both set, and nothing else is a version-3 file.
+// flags bit 3 = saved by an attention engine (pgcn_params.attention): a version-4 file, the same
+// header, bits 0-3 all known, bit 3 always set.  Its n_weights and w / m / v payloads carry the
+// attention tensor (per layer a_dst then a_src, 2 * (sum of the hidden dims + output dim) floats)
+// last, behind the scale / shift tensor when bit 1 is set.  Every other engine keeps writing
+// versions 1-3 byte for byte; there bit 3 stays unknown.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
@@ -37,6 +42,8 @@ constexpr unsigned kCheckpointResidual = 1u;  // header flags, bit 0
 constexpr unsigned kCheckpointLayerNorm = 2u;  // header flags, bit 1 (version 2 only)
 constexpr unsigned kCheckpointMultilabel = 4u;  // header flags, bit 2 (versions 1 and 3)
 constexpr int kCheckpointVersionLayerNormMultilabel = 3;  // version 2's layout with bits 1 and 2
+constexpr unsigned kCheckpointAttention = 8u;  // header flags, bit 3 (version 4 only)
+constexpr int kCheckpointVersionAttention = 4;  // bits 0-3 known, bit 3 set
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -50,7 +57,8 @@ struct Checkpoint {
   unsigned flags = 0;  // kCheckpoint* bits
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
-  std::vector<float> w, m, v;  // every weight tensor in layer order (+ the norm tensor)
+  // every weight tensor in layer order (+ the norm tensor, + the attention tensor)
+  std::vector<float> w, m, v;
 };
 
 // Writes path + ".tmp", then renames it over path (a run killed in mid-save keeps the

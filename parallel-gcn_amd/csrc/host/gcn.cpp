@@ -369,6 +369,12 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
   PGCN_CHECK(params.output_dim >= 1 && params.output_dim <= 128, PGCN_E_INVALID,
              "output_dim must be in [1,128]");
   PGCN_CHECK(data.num_nodes == params.num_nodes, PGCN_E_INVALID, "num_nodes mismatch");
+  if (params.attention) {
+    PGCN_CHECK(!dist, PGCN_E_INVALID,
+               "attention: single GPU only (a row's softmax needs all its columns)");
+    for (int h : params.hidden_dims)
+      PGCN_CHECK(h <= kGatMaxWidth, PGCN_E_INVALID, "attention: hidden dims up to 128");
+  }
   int lo_prio = 0, hi_prio = 0;
   PGCN_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
   stream = Stream::create(hi_prio);  // the reference uses High priority streams
@@ -559,7 +565,7 @@ void GCN::build(const GCNData &data) {
   upload_features(data);
   // eval_ax (dense X): Â X's buffer now -- the modules built below read it -- and its sums at
   // the end of the build (build_eval_ax)
-  if (g_eval_ax && feats.dense && feats.cols >= 16 && (comm || graph)) {
+  if (g_eval_ax && !params.attention && feats.dense && feats.cols >= 16 && (comm || graph)) {
     feats.ax.allocate(feats.x.size());
     feats.ax.zero();
   }
@@ -619,7 +625,10 @@ void GCN::build(const GCNData &data) {
   long long ntotal = 0;  // layer_norm: gamma and beta of every hidden layer, behind the weights
   if (params.layer_norm)
     for (int h : params.hidden_dims) ntotal += 2LL * h;
-  grad_arena.allocate((size_t)(wtotal + ntotal));
+  long long atotal = 0;  // attention: a_dst and a_src of every layer, behind everything else
+  if (params.attention)
+    for (int l = 0; l < L; l++) atotal += 2LL * dims[(size_t)l + 1];
+  grad_arena.allocate((size_t)(wtotal + ntotal + atotal));
   grad_arena.zero();
   uint64_t rs[2];
   if (params.seed) pgcn_rng_seed_glibc(params.seed, rs);
@@ -647,7 +656,20 @@ void GCN::build(const GCNData &data) {
     norm_var->dev_data.upload(h);
     norm_var->dev_grad = grad_arena.slice((size_t)woff, (size_t)ntotal);
   }
-  init_dropout_rng(data, wtotal);
+  if (atotal > 0) {  // glorot per vector ([d][1]: limit sqrt(6 / (d + 1))), after the last weight
+    attn_var = std::make_shared<Variable>(1, (int)atotal, false);
+    std::vector<float> h;
+    for (int l = 0; l < L; l++)
+      for (int k = 0; k < 2; k++) {
+        std::vector<float> a((size_t)dims[(size_t)l + 1]);
+        glorot_host(a, dims[(size_t)l + 1], 1, rs);
+        h.insert(h.end(), a.begin(), a.end());
+      }
+    attn_var->dev_data.upload(h);
+    attn_var->dev_grad = grad_arena.slice((size_t)(woff + ntotal), (size_t)atotal);
+  }
+  // (the dropout streams start after the attention draws: one draw per element, as the weights)
+  init_dropout_rng(data, wtotal + atotal);
 
   // context buffers
   xent_partials.allocate((size_t)xent_blocks(prow) * 2 + 2);
@@ -693,6 +715,11 @@ void GCN::build(const GCNData &data) {
   if (norm_var) {  // one more variable (index 3L + 1) and optimizer entry, without decay
     variables.push_back(norm_var);
     weights.push_back(norm_var);
+    decays.push_back(false);
+  }
+  if (attn_var) {  // ... and one more behind it (index num_vars - 1), without decay
+    variables.push_back(attn_var);
+    weights.push_back(attn_var);
     decays.push_back(false);
   }
   // (edge-cut: the tails run in k_gs_finish on the rank's rows after the reduce-scatter)
@@ -915,15 +942,32 @@ void GCN::insert_first_layer() {
   modules.push_back(std::move(sm));
   auto var2 = std::make_shared<Variable>(prow, h, true, round_up4(h));
   variables.push_back(var2);
-  auto gs = std::make_unique<GraphSum>(var1, var2, graph.get(), h, &ctx);
-  smp->consumer = gs.get();
-  if (feats.ax) {  // eval: (Â X) W1 -> var2 directly, the GraphSum is skipped
-    smp->eval_out = var2;
-    gs->first_layer = true;
+  if (params.attention) {  // (no consumer, no eval_ax: SparseMatmul's plain products)
+    insert_aggregation(var1, var2, h, 0, false);
+  } else {
+    auto gs = std::make_unique<GraphSum>(var1, var2, graph.get(), h, &ctx);
+    smp->consumer = gs.get();
+    if (feats.ax) {  // eval: (Â X) W1 -> var2 directly, the GraphSum is skipped
+      smp->eval_out = var2;
+      gs->first_layer = true;
+    }
+    modules.push_back(std::move(gs));
   }
-  modules.push_back(std::move(gs));
   insert_layer_norm(var2, 0);
   modules.push_back(std::make_unique<ReLU>(var2));
+}
+
+void GCN::insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,
+                             int dim, int layer, bool last) {
+  if (!attn_var) {
+    modules.push_back(std::make_unique<GraphSum>(var1, var2, graph.get(), dim, &ctx, last));
+    return;
+  }
+  long long off = 0;
+  for (int l = 0; l < layer; l++)
+    off += 2LL * (l == L - 1 ? params.output_dim : params.hidden_dims[(size_t)l]);
+  modules.push_back(
+      std::make_unique<GraphAttention>(var1, var2, graph.get(), dim, attn_var, off));
 }
 
 // layer_norm: the LayerNorm of hidden layer `layer` on its var2, right behind its GraphSum (and
@@ -951,7 +995,7 @@ void GCN::insert_layer(int in_dim, int out_dim, float dropout, int layer) {
                                              part.local_rows(), in_dim, out_dim, &ctx));
   auto var2 = std::make_shared<Variable>(prow, out_dim, true, round_up4(out_dim));
   variables.push_back(var2);
-  modules.push_back(std::make_unique<GraphSum>(var1, var2, graph.get(), out_dim, &ctx));
+  insert_aggregation(var1, var2, out_dim, layer, false);
   insert_layer_norm(var2, layer);
   modules.push_back(std::make_unique<ReLU>(var2));
   // residual layer: var2 = relu(Â (prev W)) + prev, prev as this layer read it (equal widths
@@ -971,7 +1015,7 @@ void GCN::insert_last_layer() {
   dropouts_.push_back(drop.get());
   modules.push_back(std::move(drop));
   const bool small = g_reassoc_small && hl <= 16 && part.bounds.back() < kMmSideRows;
-  if (params.reassociate_last && (hl < C || small) && graph_symmetric) {
+  if (params.reassociate_last && !params.attention && (hl < C || small) && graph_symmetric) {
     // out = Â (H W) computed as (Â H) W: the same product (Â is symmetric, so the backward
     // Â dOut W^T = Â (dOut W^T) and W.grad = H^T Â dOut = (Â H)^T dOut also match), but the
     // GraphSum gathers rows of width hl instead of C.  Only the fp32 rounding order differs.
@@ -1007,9 +1051,9 @@ void GCN::insert_last_layer() {
   modules.push_back(std::make_unique<Matmul>(prev, weights.back(), var1, part.local_rows(), hl,
                                              C, &ctx));
   auto out = std::make_shared<Variable>(prow, C, true, round_up4(C));
-  restricted_vars.push_back((int)variables.size());
+  if (!params.attention) restricted_vars.push_back((int)variables.size());
   variables.push_back(out);
-  modules.push_back(std::make_unique<GraphSum>(var1, out, graph.get(), C, &ctx, true));
+  insert_aggregation(var1, out, C, L - 1, true);
   if (params.multilabel) modules.push_back(std::make_unique<BCEWithLogitsLoss>(out, C, &ctx));
   else modules.push_back(std::make_unique<CrossEntropyLoss>(out, C, &ctx));
 }
@@ -1024,7 +1068,7 @@ void GCN::set_split(int split) {
   ctx.split_graph = nullptr;
   ctx.split_rows = nullptr;
   ctx.split_colgraph = nullptr;
-  if (g_split_rows && !comm && graph) {
+  if (g_split_rows && !comm && graph && !params.attention) {
     if (!split_graphs[split]) {
       split_graphs[split] = graph->row_subset(split_rows_host[split]);
       split_rows_dev[split].allocate(std::max<size_t>(split_rows_host[split].size(), 1));
@@ -1070,7 +1114,7 @@ void GCN::set_split(int split) {
     }
     for (auto &cg : chunk_col_graphs) ctx.chunk_col_graphs.push_back(cg.get());
   }
-  if (g_split_cols && !comm && graph && split == 1) {  // backward only follows training
+  if (g_split_cols && !comm && graph && split == 1 && !params.attention) {  // (after training)
     if (!split_colgraphs[split]) split_colgraphs[split] = graph->col_subset(split_rows_host[split]);
     ctx.split_colgraph = split_colgraphs[split].get();
   }
@@ -1548,6 +1592,7 @@ int GCN::fused_residuals() const {
 }
 
 bool GCN::graphsum_lds() const {
+  if (attn_var) return false;  // no GraphSum runs
   if (graph) return graph->uses_lds(16);
   return !chunk_graphs.empty() && chunk_graphs.front()->uses_lds(16);
 }
@@ -1632,6 +1677,10 @@ void GCN::save(const std::string &path) {
     ck.version = params.multilabel ? kCheckpointVersionLayerNormMultilabel
                                    : kCheckpointVersionLayerNorm;
   }
+  if (attn_var) {  // version 4: the attention tensor last
+    ck.flags |= kCheckpointAttention;
+    ck.version = kCheckpointVersionAttention;
+  }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1656,7 +1705,8 @@ void GCN::load(const std::string &path, int flags) {
     // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)
     same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty() &&
            !(ck.flags & kCheckpointLayerNorm) == !norm_var &&
-           !(ck.flags & kCheckpointMultilabel) == !params.multilabel;
+           !(ck.flags & kCheckpointMultilabel) == !params.multilabel &&
+           !(ck.flags & kCheckpointAttention) == !attn_var;
     for (int l = 0; same && l < L; l++) same = ck.dropouts[(size_t)l] == params.dropouts[(size_t)l];
   }
   PGCN_CHECK(same, PGCN_E_INVALID, "load: the checkpoint is for another model");
@@ -1667,6 +1717,10 @@ void GCN::load(const std::string &path, int flags) {
     // weights only, a file without the norm tensor: gamma / beta keep their values (a file with
     // it into a plain engine: the tensor behind the layer weights is not read)
     if (w == norm_var && !(ck.flags & kCheckpointLayerNorm)) continue;
+    if (w == attn_var && !(ck.flags & kCheckpointAttention)) continue;  // (the same for attn)
+    // (a file's norm tensor sits before its attention tensor: skipped by an engine without one)
+    if (w == attn_var && (ck.flags & kCheckpointLayerNorm) && !norm_var)
+      for (int h : params.hidden_dims) at += 2 * (size_t)h;
     w->dev_data.upload(ck.w.data() + at, (size_t)w->size);
     at += (size_t)w->size;
   }

@@ -46,6 +46,9 @@ struct GCNParams {
   // multi-label classification: GCNData::label_bits targets, BCEWithLogitsLoss as the last
   // module (the output Matmul unfused), count = labelled rows x classes
   bool multilabel = false;
+  // every layer's GraphSum is a GraphAttention (module.hpp) on the pattern as loaded; its
+  // attention vectors are one more weight (no decay), the last of all.  Single GPU, widths <= 128
+  bool attention = false;
 };
 
 struct AdamParams {
@@ -161,6 +164,7 @@ class GCN {
   // ... of which the last training forward ran inside a GraphSum's final write
   int fused_residuals() const;
   int norm_layers() const { return (int)norms_.size(); }
+  int attention_layers() const { return attn_var ? L : 0; }
   // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
   int fused_norm_tails() const;
   // diagnostics (syncs): non-zero elements in the edge-cut padding rows of the variables the
@@ -196,6 +200,12 @@ class GCN {
   // `variables`; null without layer_norm
   shared_ptr<Variable> norm_var;
   void insert_layer_norm(const shared_ptr<Variable> &var2, int layer);
+  // attention: per layer a_dst_l[d_l] then a_src_l[d_l] (d_l the layer's output width), one
+  // tensor, the last of `weights` and of `variables` (behind norm_var); null without attention
+  shared_ptr<Variable> attn_var;
+  // the layer's aggregation from var1 to var2: a GraphSum, or a GraphAttention on attn_var
+  void insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,
+                          int dim, int layer, bool last);
   int fused_tails_ = 0;  // GraphSum epilogues carrying ReLU / Dropout work (forward + backward)
   void set_split(int split);
   // the eval forward of predict(): every row, no labels, no results slot; the logits stay in

@@ -670,6 +670,78 @@ void DevGraph::graphsum(const float *in, int ld_in, float *out, int ld_out, int 
                   epi);
 }
 
+// segs: {id, begin, end, the id's first segment} for every kGatSeg-slot piece of the lists of
+// ptr longer than kGatSeg; longs: {id, its first segment}
+static void gat_segments(int n, const std::vector<int> &ptr, std::vector<int4> *segs,
+                         std::vector<int2> *longs) {
+  for (int i = 0; i < n; i++) {
+    const int b = ptr[(size_t)i], e = ptr[(size_t)i + 1];
+    if (e - b <= kGatSeg) continue;
+    const int first = (int)segs->size();
+    if (longs) longs->push_back(make_int2(i, first));
+    for (int s = b; s < e; s += kGatSeg)
+      segs->push_back(make_int4(i, s, std::min(s + kGatSeg, e), first));
+  }
+}
+
+const GatPattern &DevGraph::gat_pattern() {
+  if (gat_) return gat_->p;
+  PGCN_CHECK(n_rows_ == n_cols_, PGCN_E_INVALID, "graph attention needs a square pattern");
+  auto g = std::make_unique<GatDev>();
+  const int n = n_rows_;
+  std::vector<int> cptr((size_t)n + 1, 0), crow((size_t)nnz_), cpos((size_t)nnz_);
+  for (long long k = 0; k < nnz_; k++) {
+    const int j = h_indices_[(size_t)k];
+    PGCN_CHECK(j >= 0 && j < n, PGCN_E_INVALID, "graph attention: column id out of range");
+    cptr[(size_t)j + 1]++;
+  }
+  for (int j = 0; j < n; j++) cptr[(size_t)j + 1] += cptr[(size_t)j];
+  std::vector<int> fill(cptr.begin(), cptr.end() - 1);
+  for (int i = 0; i < n; i++) {
+    PGCN_CHECK(h_indptr_[(size_t)i] <= h_indptr_[(size_t)i + 1], PGCN_E_INVALID,
+               "graph attention: indptr must not decrease");
+    for (int k = h_indptr_[(size_t)i]; k < h_indptr_[(size_t)i + 1]; k++) {
+      const int o = fill[(size_t)h_indices_[(size_t)k]]++;
+      crow[(size_t)o] = i;
+      cpos[(size_t)o] = k;
+    }
+  }
+  std::vector<int4> rsegs, csegs;
+  std::vector<int2> lcols;
+  gat_segments(n, h_indptr_, &rsegs, nullptr);
+  gat_segments(n, cptr, &csegs, &lcols);
+  auto up = [](auto &buf, const auto &host) {
+    buf.allocate(std::max<size_t>(host.size(), 1));
+    if (!host.empty()) buf.upload(host);
+  };
+  up(g->indptr, h_indptr_);
+  up(g->csc_ptr, cptr);
+  up(g->csc_row, crow);
+  up(g->csc_pos, cpos);
+  up(g->row_segs, rsegs);
+  up(g->col_segs, csegs);
+  up(g->long_cols, lcols);
+  g->row_ws.allocate(std::max<size_t>(rsegs.size() * kGatWsStride, 4));
+  g->row_ws.zero();
+  GatPattern &p = g->p;
+  p.n = n;
+  p.nnz = nnz_;
+  p.indptr = g->indptr.get();
+  p.indices = indices_.get();
+  p.csc_ptr = g->csc_ptr.get();
+  p.csc_row = g->csc_row.get();
+  p.csc_pos = g->csc_pos.get();
+  p.n_row_segs = (int)rsegs.size();
+  p.n_col_segs = (int)csegs.size();
+  p.n_long_cols = (int)lcols.size();
+  p.row_segs = g->row_segs.get();
+  p.col_segs = g->col_segs.get();
+  p.long_cols = g->long_cols.get();
+  p.row_ws = g->row_ws.get();
+  gat_ = std::move(g);
+  return gat_->p;
+}
+
 double DevGraph::algorithmic_bytes(int dim) const {
   // 4(N+1) indptr + 8 nnz (index + value) + 4 N_in d (read) + 4 N d (write)
   return 4.0 * (n_rows_ + 1) + 8.0 * (double)nnz_ + 4.0 * (double)n_cols_ * dim +

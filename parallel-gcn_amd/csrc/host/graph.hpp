@@ -119,6 +119,12 @@ class DevGraph {
   double algorithmic_bytes(int dim) const;
   // schedule statistics (for tests / reports)
   int column_blocks(int dim);
+  // Graph attention (k_gat.hip; square patterns, the values are not used): the device copy of
+  // indptr, the transposed index and the long rows' / columns' segment lists, built and uploaded
+  // at the first call (host work and blocking copies: not inside a stream capture); a graph that
+  // never runs attention allocates none of it.  The forward's segment partials live here too, so
+  // two attention forwards on one graph must not overlap.
+  const GatPattern &gat_pattern();
 
   // Enables the d = 16 LDS path (k_graphsum_ring): out_i = row_scale_i * sum_j col_scale_j
   // in_j over the CSR pattern, i.e. vals_ij = row_scale_i * col_scale_j.
@@ -160,6 +166,14 @@ class DevGraph {
     DeviceBuffer<float> tables;  // every pass's prescaled table of a wide call (lazily)
   };
   std::unique_ptr<LdsSched> lds_;
+  struct GatDev {
+    GatPattern p;
+    DeviceBuffer<int> indptr, csc_ptr, csc_row, csc_pos;
+    DeviceBuffer<int4> row_segs, col_segs;
+    DeviceBuffer<int2> long_cols;
+    DeviceBuffer<float> row_ws;
+  };
+  std::unique_ptr<GatDev> gat_;
   DevGraph *table_owner_ = nullptr;  // share_tables: the graph whose table buffers this one reads
   float *table_scratch();            // the one-pass table (own or the owner's)
   float *table_wide(size_t floats);  // the multi-pass tables (own or the owner's), >= floats

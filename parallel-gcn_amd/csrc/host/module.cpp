@@ -692,6 +692,49 @@ void GraphSum::backward(const Stream &s) const {
 }
 
 // ------------------------------------------------------------------------------------------
+// GraphAttention (k_gat.hip)
+// ------------------------------------------------------------------------------------------
+GraphAttention::GraphAttention(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
+                               DevGraph *graph_, int dim_, shared_ptr<Variable> attn_,
+                               long long offset_)
+    : in(std::move(in_)), out(std::move(out_)), attn(std::move(attn_)), graph(graph_), dim(dim_),
+      offset(offset_) {
+  PGCN_CHECK(in && out && attn && graph && dim >= 1 && dim <= kGatMaxWidth && in->cols == dim &&
+                 out->cols == dim && graph->rows() == graph->cols() && in->rows >= graph->rows() &&
+                 out->rows >= graph->rows() && offset >= 0 && offset + 2LL * dim <= attn->size,
+             PGCN_E_INVALID, "attention: widths up to 128 on a square pattern");
+  const GatPattern &p = graph->gat_pattern();  // (host build and upload: now, not in an epoch)
+  u.allocate((size_t)std::max(p.n, 1));
+  v.allocate((size_t)std::max(p.n, 1));
+  alpha.allocate((size_t)std::max<long long>(p.nnz, 1));
+  ws.allocate(std::max<size_t>(gat_bwd_workspace(p, dim) / sizeof(float), 4));
+  z.allocate((size_t)std::max(p.n, 1) * out->ld);
+  for (const auto *b : {&u, &v, &alpha, &ws, &z}) b->zero();
+}
+
+void GraphAttention::forward(bool training, const Stream &s) const {
+  const GatPattern &p = graph->gat_pattern();
+  const float *a = attn->dev_data.get() + offset;
+  launch_gat_scores(in->dev_data.get(), in->ld, p.n, dim, a, a + dim, u.get(), v.get(), s.get());
+  launch_gat_fwd(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, out->dev_data.get(),
+                 out->ld, dim, training ? alpha.get() : nullptr, s.get());
+  if (training && p.n > 0)
+    PGCN_HIP(hipMemcpyAsync(z.get(), out->dev_data.get(), sizeof(float) * (size_t)p.n * out->ld,
+                            hipMemcpyDeviceToDevice, s.get()));
+}
+
+void GraphAttention::backward(const Stream &s) const {
+  if (!in->dev_grad || !out->dev_grad || !attn->dev_grad) return;
+  const GatPattern &p = graph->gat_pattern();
+  const float *a = attn->dev_data.get() + offset;
+  // (a residual layer's out.grad stays unmasked: its ReLU backward wrote dev_grad_z)
+  const float *g = out->dev_grad_z ? out->dev_grad_z.get() : out->dev_grad.get();
+  launch_gat_bwd(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, alpha.get(), z.get(),
+                 out->ld, g, out->ld, a, a + dim, in->dev_grad.get(), in->ld,
+                 dim, attn->dev_grad.get() + offset, ws.get(), s.get());
+}
+
+// ------------------------------------------------------------------------------------------
 // ReLU (src/module.cu:215-265)
 // ------------------------------------------------------------------------------------------
 ReLU::ReLU(shared_ptr<Variable> in_) : in(std::move(in_)) {

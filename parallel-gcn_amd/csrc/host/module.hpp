@@ -343,6 +343,33 @@ class GraphSum : public Module {
   float *backward_dst(const GsEpilogue &e) const;
 };
 
+// Graph attention in GraphSum's place (the reference has none; k_gat.hip): out = sum over row
+// i's slots of alpha_s in_j with alpha the row softmax of leaky(in_i . a_dst + in_j . a_src), on
+// the adjacency pattern as loaded (the Â coefficients are not used).  a_dst [dim] then a_src [dim]
+// sit at `offset` of the engine's one attention tensor `attn`; their gradients at the same offset
+// of its grad.  A training forward keeps alpha for the backward, which reads out->dev_grad_z when
+// that buffer exists (a residual layer), else out->dev_grad, and writes in->dev_grad.  Single GPU
+// only.  It owns u, v, alpha, the backward's workspace (dx per slot, du, dv, partials) and a copy
+// of Z as the training forward wrote it: the modules behind it (LayerNorm, ReLU, the residual add,
+// Dropout, the loss's max shift) rewrite `out` in place, and the backward needs G_i . Z_i.
+class GraphAttention : public Module {
+  shared_ptr<Variable> in, out, attn;
+  DevGraph *graph;
+  int dim;
+  long long offset;
+  DeviceBuffer<float> u, v, alpha, ws, z;
+
+ public:
+  static constexpr float kSlope = 0.2f;
+  GraphAttention(shared_ptr<Variable> in_, shared_ptr<Variable> out_, DevGraph *graph_, int dim_,
+                 shared_ptr<Variable> attn_, long long offset_);
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+  const Variable *input() const { return in.get(); }
+  const Variable *output() const { return out.get(); }
+  int width() const { return dim; }
+};
+
 // include/module.cuh:90-99
 class ReLU : public Module {
   shared_ptr<Variable> in;

@@ -1,0 +1,536 @@
+// parallel-gcn_amd/csrc/k_gat.hip -- single-head additive graph attention over the CSR slots of
+// a square pattern, for gfx950 (GAT; the reference has no such module): the per-row softmax of
+// the slot scores fused with the weighted row gather, and its backward without float atomics.
+//
+// Layout (every gather kernel): one wave per work item -- a row (forward, backward row pass) or
+// a column of the transposed index (backward column pass).  The wave is cut into 64 / GL
+// neighbour groups of GL lanes, lane li of a group holding the float4 at column 4 * li of its
+// neighbour's row, so 64 / GL neighbours are in flight per step (16 at d <= 16):
+//   d <= 4: GL 1 | <= 8: 2 | <= 16: 4 | <= 32: 8 | <= 64: 16 | <= 128: 32
+// Group q takes slots q, q + 64 / GL, ... of the item; the groups' sums meet in xor butterflies
+// over the lane offsets GL .. 32 (every lane ends with the same bits).  Scalars of a row (its
+// score maximum and exponent sum, du_i) are summed one slot per lane, then over the wave.
+//
+// Items longer than kGatSeg slots (hub rows and hub columns of a power-law graph) are cut into
+// kGatSeg-slot segments, each summed by a wave of its own in the same launch as the short items:
+//   forward: a segment leaves {its max, its exponent sum, its unnormalised partial row}; a second
+//   launch merges a row's segments in segment order (every segment's wave: the row's max and sum,
+//   then its own alpha; the first segment's wave also Z);
+//   backward column pass: a segment leaves {its dv, its partial dP row}; a second launch sums a
+//   column's segments in order.  The backward row pass needs no merge: dx is per slot, and du_i is
+//   summed from dx by the column pass (the wave of column i).
+// da_dst / da_src go through per-workgroup partials and one reducing launch (the shape of
+// k_layernorm_bwd).  Every order depends on the pattern and d only: bit-reproducible.
+#include <algorithm>
+
+#include "common.hpp"
+#include "kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace pgcn {
+
+namespace {
+constexpr int kGatThreads = 256;  // 4 waves: 4 items per workgroup step
+constexpr int kGatWaves = kGatThreads / kWave;
+constexpr int kGatMaxBlocks = 32 * kCUs;
+constexpr int kGatDaBlocks = 256;  // da partials: one reducing chain of <= 256 per element
+
+__device__ __forceinline__ float leaky(float x, float slope) { return x > 0.0f ? x : slope * x; }
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// sum over the GL lanes of a group (offsets below GL) / over the groups of a wave (GL and above)
+template <int GL>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = GL / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int GL>
+__device__ __forceinline__ float across_groups(float v) {
+#pragma unroll
+  for (int off = GL; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int GL>
+__device__ __forceinline__ float4 across_groups4(float4 a) {
+  a.x = across_groups<GL>(a.x);
+  a.y = across_groups<GL>(a.y);
+  a.z = across_groups<GL>(a.z);
+  a.w = across_groups<GL>(a.w);
+  return a;
+}
+
+// the float4 at columns c0 .. c0 + 3 of a row of logical width d: columns >= d read as zero
+// (the padding may hold anything)
+__device__ __forceinline__ float4 row4(const float *p, int c0, int d, bool on) {
+  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (on) {
+    v = *reinterpret_cast<const float4 *>(p + c0);
+    if (c0 + 1 >= d) v.y = 0.0f;
+    if (c0 + 2 >= d) v.z = 0.0f;
+    if (c0 + 3 >= d) v.w = 0.0f;
+  }
+  return v;
+}
+
+__device__ __forceinline__ float4 cols4(const float *p, int c0, int d) {
+  float4 v;
+  v.x = c0 < d ? p[c0] : 0.0f;
+  v.y = c0 + 1 < d ? p[c0 + 1] : 0.0f;
+  v.z = c0 + 2 < d ? p[c0 + 2] : 0.0f;
+  v.w = c0 + 3 < d ? p[c0 + 3] : 0.0f;
+  return v;
+}
+
+__device__ __forceinline__ float dot4(float4 a, float4 b) {
+  return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
+}
+
+__device__ __forceinline__ void axpy4(float4 &acc, float w, float4 p) {
+  acc.x += w * p.x;
+  acc.y += w * p.y;
+  acc.z += w * p.z;
+  acc.w += w * p.w;
+}
+
+// this wave's item of a launch over n_direct + n_segs items, grid-stride
+__device__ __forceinline__ long long first_item() {
+  return ((long long)blockIdx.x * kGatThreads + threadIdx.x) / kWave;
+}
+__device__ __forceinline__ long long item_stride() { return (long long)gridDim.x * kGatWaves; }
+
+// the score maximum of slots [b, e) of row i's index list and the sum of exp(score - max)
+__device__ __forceinline__ void slot_stats(const int *__restrict__ idx, const float *__restrict__ v,
+                                           float ui, float slope, int b, int e, int lane, float *m,
+                                           float *s) {
+  float mx = -INFINITY;
+  for (int k = b + lane; k < e; k += kWave) mx = fmaxf(mx, leaky(ui + v[idx[k]], slope));
+  mx = wave_max(mx);
+  float sm = 0.0f;
+  for (int k = b + lane; k < e; k += kWave) sm += expf(leaky(ui + v[idx[k]], slope) - mx);
+  *m = mx;
+  *s = wave_sum(sm);
+}
+
+// sum over slots [b, e) of w_s P_j with w_s = exp(score_s - m) / s, every lane of group 0 (and
+// all others) ending with the wave's sum; alpha (or null) takes w_s
+template <int GL>
+__device__ __forceinline__ float4 slot_gather(const float *__restrict__ P, int ld_p, int d,
+                                              const int *__restrict__ idx,
+                                              const float *__restrict__ v, float ui, float slope,
+                                              int b, int e, float m, float s, float *alpha,
+                                              int lane) {
+  constexpr int NB = kWave / GL;
+  const int q = lane / GL, li = lane % GL, c0 = 4 * li;
+  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 2
+  for (int k = b + q; k < e; k += NB) {
+    const int j = idx[k];
+    const float w = expf(leaky(ui + v[j], slope) - m) / s;
+    if (alpha && li == 0) alpha[k] = w;
+    axpy4(acc, w, row4(P + (long long)j * ld_p, c0, d, c0 < d));
+  }
+  return across_groups4<GL>(acc);
+}
+}  // namespace
+
+// u[i] = P_i . a_dst, v[i] = P_i . a_src: one row per group of GL lanes
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_scores(const float *__restrict__ P, int ld_p,
+                                                            int n, int d,
+                                                            const float *__restrict__ a_dst,
+                                                            const float *__restrict__ a_src,
+                                                            float *__restrict__ u,
+                                                            float *__restrict__ v) {
+  constexpr int RPB = kGatThreads / GL;
+  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
+  const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
+  for (long long base = (long long)blockIdx.x * RPB; base < n; base += (long long)gridDim.x * RPB) {
+    const long long r = base + grp;
+    const bool live = r < n;
+    const float4 p = row4(P + r * ld_p, c0, d, live && c0 < d);
+    const float su = group_sum<GL>(dot4(p, ad)), sv = group_sum<GL>(dot4(p, as));
+    if (live && li == 0) {
+      u[r] = su;
+      v[r] = sv;
+    }
+  }
+}
+
+// items [0, n): the rows of at most kGatSeg slots, whole; items [n, n + n_row_segs): the long
+// rows' segments, which leave {max, sum, unnormalised partial row} in row_ws
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_fwd(const GatPattern g,
+                                                         const float *__restrict__ P, int ld_p,
+                                                         const float *__restrict__ u,
+                                                         const float *__restrict__ v, float slope,
+                                                         float *__restrict__ Z, int ld_z, int d,
+                                                         float *__restrict__ alpha) {
+  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
+  const long long items = (long long)g.n + g.n_row_segs;
+  for (long long it = first_item(); it < items; it += item_stride()) {
+    if (it < g.n) {
+      const int i = (int)it, b = g.indptr[i], e = g.indptr[i + 1];
+      if (e - b > kGatSeg) continue;
+      float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (e > b) {
+        const float ui = u[i];
+        float m, s;
+        slot_stats(g.indices, v, ui, slope, b, e, lane, &m, &s);
+        z = slot_gather<GL>(P, ld_p, d, g.indices, v, ui, slope, b, e, m, s, alpha, lane);
+      }
+      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
+    } else {
+      const long long t = it - g.n;
+      const int4 sg = g.row_segs[t];
+      const float ui = u[sg.x];
+      float m, s;
+      slot_stats(g.indices, v, ui, slope, sg.y, sg.z, lane, &m, &s);
+      const float4 z =
+          slot_gather<GL>(P, ld_p, d, g.indices, v, ui, slope, sg.y, sg.z, m, 1.0f, nullptr, lane);
+      float *ws = g.row_ws + t * kGatWsStride;
+      if (lane == 0) {
+        ws[0] = m;
+        ws[1] = s;
+      }
+      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 4 + c0) = z;
+    }
+  }
+}
+
+// one wave per segment of a long row: the row's max and sum from its segments in order, the
+// segment's alpha, and (the row's first segment) Z
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_merge(const GatPattern g,
+                                                               const float *__restrict__ u,
+                                                               const float *__restrict__ v,
+                                                               float slope, float *__restrict__ Z,
+                                                               int ld_z, int d,
+                                                               float *__restrict__ alpha) {
+  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
+  for (long long t = first_item(); t < g.n_row_segs; t += item_stride()) {
+    const int4 sg = g.row_segs[t];
+    const int i = sg.x, first = sg.w;
+    const int nseg = (g.indptr[i + 1] - g.indptr[i] + kGatSeg - 1) / kGatSeg;
+    const float *ws = g.row_ws + (long long)first * kGatWsStride;
+    float m = -INFINITY;
+    for (int k = 0; k < nseg; k++) m = fmaxf(m, ws[(long long)k * kGatWsStride]);
+    float s = 0.0f;
+    for (int k = 0; k < nseg; k++)
+      s += ws[(long long)k * kGatWsStride + 1] * expf(ws[(long long)k * kGatWsStride] - m);
+    if (alpha) {
+      const float ui = u[i];
+      for (int k = sg.y + lane; k < sg.z; k += kWave)
+        alpha[k] = expf(leaky(ui + v[g.indices[k]], slope) - m) / s;
+    }
+    if (t == first && lane < GL && c0 < d) {
+      float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      for (int k = 0; k < nseg; k++) {
+        const float *w = ws + (long long)k * kGatWsStride;
+        axpy4(z, expf(w[0] - m), *reinterpret_cast<const float4 *>(w + 4 + c0));
+      }
+      z.x /= s;
+      z.y /= s;
+      z.z /= s;
+      z.w /= s;
+      *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
+    }
+  }
+}
+
+// backward row pass: dx_s = alpha_s (G_i . P_j - G_i . Z_i) leaky'(u_i + v_j) for every slot of
+// the item (items as in k_gat_fwd; a long row's segments need no merge)
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_rows(
+    const GatPattern g, const float *__restrict__ P, int ld_p, const float *__restrict__ u,
+    const float *__restrict__ v, float slope, const float *__restrict__ alpha,
+    const float *__restrict__ Z, int ld_z, const float *__restrict__ G, int ld_g, int d,
+    float *__restrict__ dx) {
+  constexpr int NB = kWave / GL;
+  const int lane = threadIdx.x % kWave, q = lane / GL, li = lane % GL, c0 = 4 * li;
+  const long long items = (long long)g.n + g.n_row_segs;
+  for (long long it = first_item(); it < items; it += item_stride()) {
+    int i, b, e;
+    if (it < g.n) {
+      i = (int)it;
+      b = g.indptr[i];
+      e = g.indptr[i + 1];
+      if (e - b > kGatSeg) continue;
+    } else {
+      const int4 sg = g.row_segs[it - g.n];
+      i = sg.x;
+      b = sg.y;
+      e = sg.z;
+    }
+    if (e <= b) continue;
+    const float4 gi = row4(G + (long long)i * ld_g, c0, d, c0 < d);
+    const float4 zi = row4(Z + (long long)i * ld_z, c0, d, c0 < d);
+    const float c = group_sum<GL>(dot4(gi, zi)), ui = u[i];
+    // (the same trip count for every group: the group sums run under uniform control flow)
+    for (int k0 = b; k0 < e; k0 += NB) {
+      const int k = k0 + q;
+      const bool on = k < e;
+      const int j = on ? g.indices[k] : i;
+      const float t = group_sum<GL>(dot4(gi, row4(P + (long long)j * ld_p, c0, d, on && c0 < d)));
+      if (on && li == 0) dx[k] = alpha[k] * (t - c) * (ui + v[j] > 0.0f ? 1.0f : slope);
+    }
+  }
+}
+
+// one item of the column pass: slots [b, e) of the transposed index; acc = sum alpha_s G_row,
+// dv = sum dx_s, both over the groups (every lane ends with the wave's sums)
+template <int GL>
+__device__ __forceinline__ float4 col_gather(const GatPattern &g, const float *__restrict__ alpha,
+                                             const float *__restrict__ dx,
+                                             const float *__restrict__ G, int ld_g, int d, int b,
+                                             int e, int lane, float *dv_out) {
+  constexpr int NB = kWave / GL;
+  const int q = lane / GL, c0 = 4 * (lane % GL);
+  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float dv = 0.0f;
+#pragma unroll 2
+  for (int o = b + q; o < e; o += NB) {
+    const int r = g.csc_row[o], k = g.csc_pos[o];
+    axpy4(acc, alpha[k], row4(G + (long long)r * ld_g, c0, d, c0 < d));
+    dv += dx[k];
+  }
+  *dv_out = across_groups<GL>(dv);
+  return across_groups4<GL>(acc);
+}
+
+// the final write of column j: du_j from row j's dx (one slot per lane, then the wave), then
+// dP_j = acc + du_j a_dst + dv_j a_src
+template <int GL>
+__device__ __forceinline__ void col_finish(const GatPattern &g, int j, float4 acc, float dv,
+                                           const float *__restrict__ dx,
+                                           const float *__restrict__ a_dst,
+                                           const float *__restrict__ a_src, int d,
+                                           float *__restrict__ dP, int ld_dp,
+                                           float *__restrict__ du_out, float *__restrict__ dv_out,
+                                           int lane) {
+  const int c0 = 4 * (lane % GL);
+  float du = 0.0f;
+  for (int k = g.indptr[j] + lane; k < g.indptr[j + 1]; k += kWave) du += dx[k];
+  du = wave_sum(du);
+  if (lane == 0) {
+    du_out[j] = du;
+    dv_out[j] = dv;
+  }
+  if (lane < GL && c0 < d) {
+    const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
+    float4 o;
+    o.x = (acc.x + du * ad.x) + dv * as.x;
+    o.y = (acc.y + du * ad.y) + dv * as.y;
+    o.z = (acc.z + du * ad.z) + dv * as.z;
+    o.w = (acc.w + du * ad.w) + dv * as.w;
+    *reinterpret_cast<float4 *>(dP + (long long)j * ld_dp + c0) = o;
+  }
+}
+
+// items [0, n): the columns of at most kGatSeg incoming slots, whole; items [n, n + n_col_segs):
+// the long columns' segments, which leave {dv, partial row} in col_ws
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_cols(
+    const GatPattern g, const float *__restrict__ alpha, const float *__restrict__ dx,
+    const float *__restrict__ G, int ld_g, const float *__restrict__ a_dst,
+    const float *__restrict__ a_src, int d, float *__restrict__ dP, int ld_dp,
+    float *__restrict__ du, float *__restrict__ dv, float *__restrict__ col_ws) {
+  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
+  const long long items = (long long)g.n + g.n_col_segs;
+  for (long long it = first_item(); it < items; it += item_stride()) {
+    if (it < g.n) {
+      const int j = (int)it, b = g.csc_ptr[j], e = g.csc_ptr[j + 1];
+      if (e - b > kGatSeg) continue;
+      float dvj;
+      const float4 acc = col_gather<GL>(g, alpha, dx, G, ld_g, d, b, e, lane, &dvj);
+      col_finish<GL>(g, j, acc, dvj, dx, a_dst, a_src, d, dP, ld_dp, du, dv, lane);
+    } else {
+      const long long t = it - g.n;
+      const int4 sg = g.col_segs[t];
+      float dvj;
+      const float4 acc = col_gather<GL>(g, alpha, dx, G, ld_g, d, sg.y, sg.z, lane, &dvj);
+      float *ws = col_ws + t * kGatWsStride;
+      if (lane == 0) ws[0] = dvj;
+      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 4 + c0) = acc;
+    }
+  }
+}
+
+// one wave per long column: its segments' partials in segment order, then the final write
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_colmerge(
+    const GatPattern g, const float *__restrict__ dx, const float *__restrict__ a_dst,
+    const float *__restrict__ a_src, int d, float *__restrict__ dP, int ld_dp,
+    float *__restrict__ du, float *__restrict__ dv, const float *__restrict__ col_ws) {
+  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
+  for (long long t = first_item(); t < g.n_long_cols; t += item_stride()) {
+    const int j = g.long_cols[t].x, first = g.long_cols[t].y;
+    const int nseg = (g.csc_ptr[j + 1] - g.csc_ptr[j] + kGatSeg - 1) / kGatSeg;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float dvj = 0.0f;
+    for (int k = 0; k < nseg; k++) {
+      const float *w = col_ws + (long long)(first + k) * kGatWsStride;
+      dvj += w[0];
+      if (c0 < d) {
+        const float4 p = *reinterpret_cast<const float4 *>(w + 4 + c0);
+        acc.x += p.x;
+        acc.y += p.y;
+        acc.z += p.z;
+        acc.w += p.w;
+      }
+    }
+    col_finish<GL>(g, j, acc, dvj, dx, a_dst, a_src, d, dP, ld_dp, du, dv, lane);
+  }
+}
+
+// this workgroup's rows of sum du_i P_i and sum dv_i P_i: per lane group in row order, then
+// the groups in group order (LDS), into partial [block][2][ldp]
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_da(const float *__restrict__ P, int ld_p,
+                                                        int n, int d, const float *__restrict__ du,
+                                                        const float *__restrict__ dv,
+                                                        float *__restrict__ partial, int ldp) {
+  constexpr int RPB = kGatThreads / GL;
+  constexpr int W = GL * 4;
+  __shared__ __align__(16) float sh[RPB * 2 * W];
+  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
+  float4 ad = make_float4(0.0f, 0.0f, 0.0f, 0.0f), as = ad;
+  for (long long r = (long long)blockIdx.x * RPB + grp; r < n; r += (long long)gridDim.x * RPB) {
+    const float4 p = row4(P + r * ld_p, c0, d, c0 < d);
+    axpy4(ad, du[r], p);
+    axpy4(as, dv[r], p);
+  }
+  *reinterpret_cast<float4 *>(&sh[(grp * 2 + 0) * W + c0]) = ad;
+  *reinterpret_cast<float4 *>(&sh[(grp * 2 + 1) * W + c0]) = as;
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * W; i += kGatThreads) {
+    const int c = i % W;
+    if (c >= ldp) continue;
+    float s = 0.0f;
+    for (int q = 0; q < RPB; q++) s += sh[q * 2 * W + i];
+    partial[((long long)blockIdx.x * 2 + i / W) * ldp + c] = s;
+  }
+}
+
+// da[k][c] = the nb partials [2][ldp] summed in block order
+__global__ __launch_bounds__(kGatThreads) void k_gat_da_reduce(const float *__restrict__ partial,
+                                                               int nb, int ldp, int d,
+                                                               float *__restrict__ da) {
+  const int i = blockIdx.x * kGatThreads + threadIdx.x;
+  if (i >= 2 * ldp) return;
+  const int c = i % ldp;
+  if (c >= d) return;
+  float s = 0.0f;
+#pragma unroll 8
+  for (int b = 0; b < nb; b++) s += partial[(long long)b * 2 * ldp + i];
+  da[(i / ldp) * d + c] = s;
+}
+
+static int gat_gl(int d) {
+  const int d4 = (d + 3) / 4;
+  return d4 <= 1 ? 1 : d4 <= 2 ? 2 : d4 <= 4 ? 4 : d4 <= 8 ? 8 : d4 <= 16 ? 16 : 32;
+}
+
+static dim3 gat_grid(long long items) {
+  return dim3((unsigned)std::max<long long>(1, std::min<long long>(ceil_div(items, kGatWaves),
+                                                                   kGatMaxBlocks)));
+}
+
+static int gat_da_blocks(int n, int d) {
+  return (int)std::max<long long>(
+      1, std::min<long long>(ceil_div(n, kGatThreads / gat_gl(d)), kGatDaBlocks));
+}
+
+#define GAT_DISPATCH(KERNEL, grid, s, ...)                                                  \
+  do {                                                                                      \
+    switch (gat_gl(d)) {                                                                    \
+      case 1: PGCN_LAUNCH((KERNEL<1>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 2: PGCN_LAUNCH((KERNEL<2>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 4: PGCN_LAUNCH((KERNEL<4>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 8: PGCN_LAUNCH((KERNEL<8>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 16: PGCN_LAUNCH((KERNEL<16>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
+      default: PGCN_LAUNCH((KERNEL<32>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
+    }                                                                                       \
+  } while (0)
+
+void launch_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
+                       const float *a_src, float *u, float *v, hipStream_t s) {
+  PGCN_CHECK(d >= 1 && d <= kGatMaxWidth && n >= 0, PGCN_E_INVALID, "gat_scores: 1 <= d <= 128");
+  if (n == 0) return;
+  const dim3 grid((unsigned)std::min<long long>(ceil_div(n, kGatThreads / gat_gl(d)),
+                                                kGatMaxBlocks));
+  GAT_DISPATCH(k_gat_scores, grid, s, P, ld_p, n, d, a_dst, a_src, u, v);
+}
+
+void launch_gat_fwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, float *Z, int ld_z, int d, float *alpha, hipStream_t s) {
+  PGCN_CHECK(d >= 1 && d <= kGatMaxWidth && g.n >= 0, PGCN_E_INVALID, "gat_fwd: 1 <= d <= 128");
+  if (g.n == 0) return;
+  note_path(KP_GAT_FWD);
+  GAT_DISPATCH(k_gat_fwd, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v, slope, Z,
+               ld_z, d, alpha);
+  if (g.n_row_segs > 0)
+    GAT_DISPATCH(k_gat_fwd_merge, gat_grid(g.n_row_segs), s, g, u, v, slope, Z, ld_z, d, alpha);
+}
+
+namespace {
+struct GatBwdWs {
+  size_t dx, du, dv, col_ws, part, floats;
+};
+size_t up4(size_t x) { return (x + 3) / 4 * 4; }
+GatBwdWs gat_bwd_layout(const GatPattern &g, int d) {
+  GatBwdWs w;
+  w.dx = 0;
+  w.du = w.dx + up4((size_t)g.nnz);
+  w.dv = w.du + up4((size_t)g.n);
+  w.col_ws = w.dv + up4((size_t)g.n);
+  w.part = w.col_ws + (size_t)g.n_col_segs * kGatWsStride;
+  w.floats = w.part + (size_t)gat_da_blocks(g.n, d) * 2 * (size_t)((d + 3) / 4 * 4);
+  return w;
+}
+}  // namespace
+
+size_t gat_bwd_workspace(const GatPattern &g, int d) {
+  if (g.n <= 0 || d <= 0) return 0;
+  return gat_bwd_layout(g, d).floats * sizeof(float);
+}
+
+void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                    int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                    float *da, void *workspace, hipStream_t s) {
+  PGCN_CHECK(d >= 1 && d <= kGatMaxWidth && g.n >= 0, PGCN_E_INVALID, "gat_bwd: 1 <= d <= 128");
+  if (g.n == 0) return;
+  note_path(KP_GAT_BWD);
+  const GatBwdWs w = gat_bwd_layout(g, d);
+  float *ws = static_cast<float *>(workspace);
+  float *dx = ws + w.dx, *du = ws + w.du, *dv = ws + w.dv, *col_ws = ws + w.col_ws;
+  float *partial = ws + w.part;
+  GAT_DISPATCH(k_gat_bwd_rows, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v, slope,
+               alpha, Z, ld_z, G, ld_g, d, dx);
+  GAT_DISPATCH(k_gat_bwd_cols, gat_grid((long long)g.n + g.n_col_segs), s, g, alpha, dx, G, ld_g,
+               a_dst, a_src, d, dP, ld_dp, du, dv, col_ws);
+  if (g.n_long_cols > 0)
+    GAT_DISPATCH(k_gat_bwd_colmerge, gat_grid(g.n_long_cols), s, g, dx, a_dst, a_src, d, dP, ld_dp,
+                 du, dv, col_ws);
+  const int nb = gat_da_blocks(g.n, d), ldp = (d + 3) / 4 * 4;
+  GAT_DISPATCH(k_gat_da, dim3((unsigned)nb), s, P, ld_p, g.n, d, du, dv, partial, ldp);
+  PGCN_LAUNCH(k_gat_da_reduce, dim3((unsigned)ceil_div(2 * ldp, kGatThreads)), dim3(kGatThreads),
+              0, s, partial, nb, ldp, d, da);
+}
+
+}  // namespace pgcn

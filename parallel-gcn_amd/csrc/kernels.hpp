@@ -14,7 +14,7 @@ namespace pgcn {
 // which kernels a configuration took
 enum KernelPath {
   KP_XS_NN_RING, KP_XS_TN_RING, KP_XS_NN, KP_XS_TN, KP_GS_RING, KP_GS_GATHER, KP_OUT_XENT,
-  KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_LAUNCHES, KP_COUNT
+  KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_LAUNCHES, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -349,6 +349,44 @@ size_t layernorm_bwd_workspace(int n, int d);
 void launch_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
                           const float *rstd, const float *gamma, int n, int d, float *dx, int ld_dx,
                           float *dgamma, float *dbeta, void *workspace, hipStream_t s);
+// ---- Graph attention over the CSR slots of a square pattern (k_gat.hip) ---------------------
+// Single head, additive (GAT): u_i = P_i . a_dst, v_j = P_j . a_src, e_s = leaky(u_i + v_j) per
+// slot s = (i, j), alpha = softmax of e over the row's slots, Z_i = sum alpha_s P_j.  1 <= d <=
+// kGatMaxWidth, every ld a multiple of 4 and >= d, rows 16-byte aligned; padding columns of the
+// inputs may hold anything, the float4s covering [0, round_up4(d)) of the outputs are written
+// (zero from column d on).  Rows (forward) and columns (backward) longer than kGatSeg slots are
+// cut into kGatSeg-slot segments summed by separate waves and merged in segment order; every
+// summation order depends on the pattern and d only (no float atomics).
+constexpr int kGatMaxWidth = 128;
+constexpr int kGatSeg = 512;
+constexpr int kGatWsStride = 4 + kGatMaxWidth;  // a segment's partial: {max, sum, -, -, row[128]}
+// The pattern on the device (DevGraph::gat_pattern, built at its first use): the CSR, its
+// transposed index (column j's slots in CSR order: csc_row their rows, csc_pos their slots) and
+// the segment lists of the long rows / columns: segs {id, begin, end, the id's first segment}
+struct GatPattern {
+  int n = 0;
+  long long nnz = 0;
+  const int *indptr = nullptr, *indices = nullptr;
+  const int *csc_ptr = nullptr, *csc_row = nullptr, *csc_pos = nullptr;
+  int n_row_segs = 0, n_col_segs = 0, n_long_cols = 0;
+  const int4 *row_segs = nullptr, *col_segs = nullptr;
+  const int2 *long_cols = nullptr;  // {column, its first segment}
+  float *row_ws = nullptr;          // forward: [n_row_segs][kGatWsStride]
+};
+void launch_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
+                       const float *a_src, float *u, float *v, hipStream_t s);
+// alpha [nnz] (training) or null
+void launch_gat_fwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, float *Z, int ld_z, int d, float *alpha, hipStream_t s);
+// workspace: dx [nnz], du [n], dv [n], the long columns' segment partials, the da partials
+size_t gat_bwd_workspace(const GatPattern &g, int d);
+// dP [n][ld_dp] = sum over column j's slots of alpha_s G_i + du_j a_dst + dv_j a_src with dx_s =
+// alpha_s (G_i . P_j - G_i . Z_i) leaky'(u_i + v_j), du_i / dv_j its row / column sums; da [2][d]
+// = {sum du_i P_i, sum dv_j P_j}
+void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                    int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                    float *da, void *workspace, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

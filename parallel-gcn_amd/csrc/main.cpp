@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -16,6 +16,8 @@
 // -- the labels come from the sidecar file data/<name>.labels (line i: the class ids of node i),
 // the epoch lines' accuracy column is the Hamming accuracy, and predict= writes `node id id ...`
 // (the classes with a positive logit) per node.
+// attention=1 (command line or parameter file): graph attention layers in the GraphSums' place,
+// pgcn_params.attention.
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +68,7 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "seed") p->seed = (unsigned)std::strtoul(v.c_str(), nullptr, 10);
     else if (k == "residual") p->residual = std::atoi(v.c_str());
     else if (k == "layer_norm") p->layer_norm = std::atoi(v.c_str());
+    else if (k == "attention") p->attention = std::atoi(v.c_str());
     else if (k == "multilabel") p->multilabel = std::atoi(v.c_str());
   }
   return true;
@@ -81,7 +84,7 @@ int main(int argc, char **argv) {
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
   std::string load, save, predict;
-  int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1;
+  int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -94,6 +97,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "residual=", 9)) residual = std::atoi(argv[i] + 9);
     if (!std::strncmp(argv[i], "layer_norm=", 11)) layer_norm = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "multilabel=", 11)) multilabel = std::atoi(argv[i] + 11);
+    if (!std::strncmp(argv[i], "attention=", 10)) attention = std::atoi(argv[i] + 10);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -105,6 +109,7 @@ int main(int argc, char **argv) {
   if (residual >= 0) p.residual = residual;
   if (layer_norm >= 0) p.layer_norm = layer_norm;
   if (multilabel >= 0) p.multilabel = multilabel;
+  if (attention >= 0) p.attention = attention;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
