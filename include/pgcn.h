@@ -420,7 +420,8 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
  * the normalised variables -- always 0); "attention_layers" (layers whose aggregation is graph
  * attention, pgcn_params.attention: n_layers or 0; on such an engine "reassociated", "eval_ax_us"
- * and "graphsum_lds" are 0).
+ * and "graphsum_lds" are 0); "knob.<key>" (the value of that pgcn_debug_set key the engine was
+ * built with).
  * Returns the value (>= 0) or PGCN_E_INVALID for an unknown key. */
 long long pgcn_gcn_query(pgcn_gcn *g, const char *key);
 /* GCN::train_epoch / GCN::eval (src/gcn.cu:293-343): out2 = {loss, accuracy} */
@@ -593,8 +594,16 @@ long long pgcn_partition_subgraph(int n, const int *indptr, const int *indices, 
  * one GPU.  *rows / *cols give its shape. */
 int pgcn_debug_rank_graph(int n, const int *indptr, const int *indices, int world, int rank,
                           int chunks, int chunk, pgcn_graph **out, int *rows, int *cols);
-/* Engine options (process-wide; most are read when an engine is built).  Each selects between
- * bit-identical or oracle-tested forms of the same reference epoch (19 keys, r05):
+/* Engine options.  pgcn_debug_set writes one process-wide table; an engine (pgcn_gcn_create*)
+ * and a graph (pgcn_graph_create*, pgcn_debug_rank_graph) copy that table when they are created
+ * and follow their copy from then on -- an engine hands its copy to every graph it creates,
+ * those it builds at a later split switch included.  So a key applies to the engines and graphs
+ * created after the call and changes nothing in those that exist.  Two keys are read at the
+ * call instead: "parse_threads" (the loader has no engine) and "xstream_ring" (read where the
+ * X-stream GEMM launchers dispatch, which pgcn_gemm_xstream* share with the engine).  The
+ * reference-shaped C++ API (pgcn.hpp) has no engine: its modules read the table at each call.
+ * Each key selects between bit-identical or oracle-tested forms of the same reference epoch
+ * (19 keys, r05):
  *   "train_ahead" 0/1, "eval_ax" 0/1, "split_cols" 0/1, "epoch_graph" 0/1, "mm_side" 0/1/2,
  *   "eval_tail" 0/1 (edge-cut between processes: the eval pass's last exchange and output
  *   layer beside the next epoch's first kernels, default 0),
@@ -636,6 +645,11 @@ int pgcn_debug_rank_graph(int n, const int *indptr, const int *indices, int worl
  * Returns PGCN_E_INVALID on an unknown key or on a value outside the key's range (nothing is
  * changed then). */
 int pgcn_debug_set(const char *key, int value);
+/* The table behind pgcn_debug_set, row `index` (0, 1, ...): the key's name (a static string)
+ * and its default value; either pointer may be NULL.  PGCN_E_INVALID past the last row.
+ * pgcn_gcn_query(g, "knob.<key>") returns the value engine `g` was built with ("lds_min_kb"
+ * keeps the caller's unit there, and its default reads as -1). */
+int pgcn_debug_knob(int index, const char **name, int *default_value);
 /* Host-only check of the d = 16 LDS ring schedule (window must be 5) of a CSR pattern: builds
  * it, walks it as k_graphsum_ring consumes it over a seeded input and returns the max relative
  * error of the row sums against a direct CSR sum, and the number of 4-step entry blocks. */

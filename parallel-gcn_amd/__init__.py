@@ -192,6 +192,7 @@ _sig("pgcn_dataset_synthetic", c_int, c_int, c_int, c_int, c_ll, c_u64, P(c_void
 _sig("pgcn_dataset_view", c_int, c_void_p, P(PgcnData), P(c_int), P(c_int))
 _sig("pgcn_dataset_free", c_int, c_void_p)
 _sig("pgcn_debug_set", c_int, ctypes.c_char_p, c_int)
+_sig("pgcn_debug_knob", c_int, c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_int))
 _sig("pgcn_debug_path_count", c_ll, ctypes.c_char_p, c_int)
 _sig("pgcn_debug_empty_launches", c_int, c_int, c_void_p)
 _sig("pgcn_debug_exp_check", c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p)
@@ -774,6 +775,7 @@ EXPORTED = [
     "pgcn_dataset_load_binary", "pgcn_dataset_binarize", "pgcn_dataset_synthetic",
     "pgcn_dataset_view",
     "pgcn_dataset_free", "pgcn_partition_bounds", "pgcn_partition_subgraph", "pgcn_debug_set",
+    "pgcn_debug_knob",
     "pgcn_debug_lds_check", "pgcn_debug_lds_counts", "pgcn_debug_path_count",
     "pgcn_debug_empty_launches", "pgcn_debug_exp_check", "pgcn_debug_div_check",
     "pgcn_debug_ring_slice_rows", "pgcn_debug_xent_fwd", "pgcn_debug_out_xent",

@@ -11,6 +11,7 @@
 #include "host/gcn.hpp"
 #include "host/graph.hpp"
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "rng.hpp"
 
 #include <cmath>
@@ -18,35 +19,6 @@
 using namespace pgcn;
 
 namespace pgcn {
-// engine knobs (pgcn_debug_set): defaults and meaning at their definitions
-extern int g_train_ahead;           // host/gcn.cpp
-extern int g_split_rows;            // host/gcn.cpp
-extern int g_split_cols;            // host/gcn.cpp
-extern int g_fuse_epilogue;         // host/gcn.cpp
-extern int g_fuse_output;           // host/gcn.cpp
-extern int g_mm_side;               // host/gcn.cpp
-extern int g_eval_tail;             // host/gcn.cpp
-extern int g_peer_uncached;         // host/comm.cpp
-extern int g_tn_fold;               // host/gcn.cpp
-extern int g_fuse_finish;           // host/gcn.cpp
-extern int g_mask_per;              // host/gcn.cpp
-extern int g_mask_adam;             // host/gcn.cpp
-extern int g_mask_xstream;          // host/gcn.cpp
-extern int g_reassoc_small;         // host/gcn.cpp
-extern int g_defer_small_wgrad;     // host/module.cpp
-extern int g_eval_ax;               // host/gcn.cpp
-extern int g_epoch_graph;           // host/gcn.cpp
-extern long long g_lds_min_bytes;   // host/graph.cpp
-extern int g_lds_blocks;            // host/graph.cpp
-extern int g_xstream_ring;          // k_xstream_lds.hip
-extern int g_gs_split;              // host/graph.cpp
-extern int g_co_draw;               // host/gcn.cpp
-extern int g_sparse_dual;           // host/gcn.cpp
-extern int g_gs_item_iters;         // host/graph.cpp
-extern int g_gs_orig_cols;          // host/graph.cpp
-extern int g_gs16_gather;           // host/graph.cpp
-extern int g_parse_threads;         // host/data.cpp: pieces of the parallel text parse
-
 namespace {
 std::atomic<long long> g_path_hits[KP_COUNT];
 thread_local long long t_path_hits[KP_COUNT];  // the launching host thread's (loopback ranks)
@@ -155,7 +127,7 @@ const char *pgcn_status_string(int s) {
   }
 }
 
-int pgcn_version(void) { return 111; }
+int pgcn_version(void) { return 112; }
 
 // ---------------------------------------------------------------- graph + kernels
 int pgcn_graph_create(int n, const int *indptr, const int *indices, pgcn_graph **out) {
@@ -772,6 +744,10 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!g || !key) return PGCN_E_INVALID;
   const GCN &e = *g->g;
   const Comm *c = e.communicator();
+  if (!std::strncmp(key, "knob.", 5)) {  // the engine's snapshot, whatever was set since
+    const KnobRow *row = find_knob(key + 5);
+    return row ? e.knobs().*row->field : PGCN_E_INVALID;
+  }
   if (!std::strcmp(key, "world")) return c ? c->world() : 1;
   if (!std::strcmp(key, "rank")) return c ? c->rank() : 0;
   if (!std::strcmp(key, "comm"))
@@ -1056,105 +1032,28 @@ int pgcn_dataset_free(pgcn_dataset *ds) {
 
 // ---------------------------------------------------------------- diagnostics
 int pgcn_debug_set(const char *key, int value) {
-  if (!key) return PGCN_E_INVALID;
   // every key's value range is checked: an out-of-range value is refused, never reinterpreted
-  auto in = [&](int lo, int hi) { return value >= lo && value <= hi; };
-  if (!std::strcmp(key, "train_ahead")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_train_ahead = value;
-  } else if (!std::strcmp(key, "split_rows")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_split_rows = value;
-  } else if (!std::strcmp(key, "split_cols")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_split_cols = value;
-  } else if (!std::strcmp(key, "eval_ax")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_eval_ax = value;
-  } else if (!std::strcmp(key, "epoch_graph")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_epoch_graph = value;
-  } else if (!std::strcmp(key, "fuse_epilogue")) {
-    if (!in(0, 15)) return PGCN_E_INVALID;
-    pgcn::g_fuse_epilogue = value;
-  } else if (!std::strcmp(key, "fuse_output")) {
-    if (!in(0, 3)) return PGCN_E_INVALID;
-    pgcn::g_fuse_output = value;
-  } else if (!std::strcmp(key, "mm_side")) {
-    if (!in(0, 2)) return PGCN_E_INVALID;
-    pgcn::g_mm_side = value;
-  } else if (!std::strcmp(key, "eval_tail")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_eval_tail = value;
-  } else if (!std::strcmp(key, "mask_xstream")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_mask_xstream = value;
-  } else if (!std::strcmp(key, "mask_adam")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_mask_adam = value;
-  } else if (!std::strcmp(key, "defer_wgrad")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_defer_small_wgrad = value;
-  } else if (!std::strcmp(key, "reassoc_small")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_reassoc_small = value;
-  } else if (!std::strcmp(key, "csc_tree")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_csc_tree = value;
-  } else if (!std::strcmp(key, "mask_per")) {
-    if (!in(0, 2)) return PGCN_E_INVALID;
-    pgcn::g_mask_per = value;
-  } else if (!std::strcmp(key, "fuse_finish")) {
-    if (!in(0, 2)) return PGCN_E_INVALID;
-    pgcn::g_fuse_finish = value;
-  } else if (!std::strcmp(key, "tn_fold")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_tn_fold = value;
-  } else if (!std::strcmp(key, "ring_window")) {
-    if (value != 0 && value != 2 && value != 3) return PGCN_E_INVALID;
-    pgcn::g_ring_window = value;
-  } else if (!std::strcmp(key, "ring_pair")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_ring_pair = value;
-  } else if (!std::strcmp(key, "peer_uncached")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_peer_uncached = value;
-  } else if (!std::strcmp(key, "xstream_ring")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_xstream_ring = value;
-  } else if (!std::strcmp(key, "lds_min_kb")) {  // < 0: the default
-    pgcn::g_lds_min_bytes = value < 0 ? DevGraph::kLdsMinBytes : 1024LL * value;
-  } else if (!std::strcmp(key, "lds_blocks")) {
-    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16 &&
-        value != 32)
-      return PGCN_E_INVALID;
-    pgcn::g_lds_blocks = value;
-  } else if (!std::strcmp(key, "gs_orig_cols")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_gs_orig_cols = value;
-  } else if (!std::strcmp(key, "gs16_gather")) {
-    if (!in(0, 2)) return PGCN_E_INVALID;
-    pgcn::g_gs16_gather = value;
-  } else if (!std::strcmp(key, "sparse_dual")) {
-    if (!in(0, 1)) return PGCN_E_INVALID;
-    pgcn::g_sparse_dual = value;
-  } else if (!std::strcmp(key, "co_draw")) {
-    if (!in(0, 2)) return PGCN_E_INVALID;
-    pgcn::g_co_draw = value;
-  } else if (!std::strcmp(key, "gs_split")) {
-    if (!in(0, 3)) return PGCN_E_INVALID;
-    pgcn::g_gs_split = value;
-  } else if (!std::strcmp(key, "gs_item_iters")) {
-    if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16 && value != 32)
-      return PGCN_E_INVALID;
-    pgcn::g_gs_item_iters = value;
-  } else if (!std::strcmp(key, "parse_threads")) {
-    if (!in(0, 4096)) return PGCN_E_INVALID;
-    pgcn::g_parse_threads = value;
-  } else {
-    return PGCN_E_INVALID;
-  }
+  const KnobRow *row = key ? find_knob(key) : nullptr;
+  if (!row || !row->accepts(value)) return PGCN_E_INVALID;
+  process_knobs().*row->field = value;
   return PGCN_OK;
+}
+
+int pgcn_debug_knob(int index, const char **name, int *default_value) {
+  if (index < 0 || index >= kKnobCount) return PGCN_E_INVALID;
+  if (name) *name = kKnobTable[index].name;
+  if (default_value) *default_value = Knobs{}.*kKnobTable[index].field;
+  return PGCN_OK;
+}
+
+// the ring schedule a graph of this pattern created now would build (process_knobs())
+static LdsHost debug_ring_host(int n_rows, int n_cols, const std::vector<int> &ip,
+                               const std::vector<int> &ix) {
+  const Knobs &k = process_knobs();
+  const std::vector<int> cut = ring_cuts(n_cols, ix, lds_blocks(n_rows, n_cols, k));
+  return build_ring_host(
+      n_rows, n_cols, ip, ix, cut, lds_slots(n_rows, n_cols), k.ring_pair != 0,
+      ring_window_for(n_rows, n_cols, (long long)ix.size(), (int)cut.size() - 1, k));
 }
 
 // CPU check of the d = 16 ring schedule of a CSR pattern: builds it, walks it as the kernel
@@ -1169,10 +1068,7 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
     PGCN_CHECK(n_rows > 0 && n_cols > 0 && indptr && indices && window == kRingWindow,
                PGCN_E_INVALID, "lds_counts args");
     std::vector<int> ip(indptr, indptr + n_rows + 1), ix(indices, indices + indptr[n_rows]);
-    const std::vector<int> cut = ring_cuts(n_cols, ix, lds_blocks(n_rows, n_cols));
-    const LdsHost h = build_ring_host(
-        n_rows, n_cols, ip, ix, cut, lds_slots(n_rows, n_cols), -1,
-        ring_window_for(n_rows, n_cols, (long long)ix.size(), (int)cut.size() - 1));
+    const LdsHost h = debug_ring_host(n_rows, n_cols, ip, ix);
     n = (long long)h.counts.size();
     if (dst) std::copy(h.counts.begin(), h.counts.begin() + std::min(n, cap), dst);
     if (shape5) {
@@ -1192,10 +1088,7 @@ int pgcn_debug_lds_check(int n_rows, int n_cols, const int *indptr, const int *i
     PGCN_CHECK(n_rows > 0 && n_cols > 0 && indptr && indices && window == kRingWindow,
                PGCN_E_INVALID, "lds_check args");
     std::vector<int> ip(indptr, indptr + n_rows + 1), ix(indices, indices + indptr[n_rows]);
-    const std::vector<int> cut = ring_cuts(n_cols, ix, lds_blocks(n_rows, n_cols));
-    const LdsHost h = build_ring_host(
-        n_rows, n_cols, ip, ix, cut, lds_slots(n_rows, n_cols), -1,
-        ring_window_for(n_rows, n_cols, (long long)ix.size(), (int)cut.size() - 1));
+    const LdsHost h = debug_ring_host(n_rows, n_cols, ip, ix);
     std::vector<float> in((size_t)n_cols);
     uint64_t st[2] = {12345, 67890};
     for (auto &x : in) x = (float)((double)(xs_next(st) & 0xffffff) / (double)0x1000000 - 0.5);

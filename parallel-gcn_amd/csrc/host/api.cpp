@@ -294,7 +294,7 @@ void Context::freeze() {
   ctx.jump_table = jump_table.get();
   unsigned long long offset = glorot_draws;
   for (auto *d : dropouts) {
-    init_dropout_rng_range(*d->rng, seed, offset, 0, d->elems);
+    init_dropout_rng_range(*d->rng, seed, offset, 0, d->elems, ctx.knobs->mask_per);
     offset += (unsigned long long)d->elems;
   }
   frozen = true;

@@ -16,8 +16,6 @@
 
 namespace pgcn {
 
-int g_peer_uncached = 0;
-
 int Partition::owner(int node) const {
   return (int)(std::upper_bound(bounds.begin(), bounds.end(), node) - bounds.begin()) - 1;
 }
@@ -247,7 +245,7 @@ struct PeerBlob {  // what a rank publishes at construction
 }  // namespace
 
 PeerComm::PeerComm(int rank, int world, size_t slot_floats, AllGather ag, bool ipc,
-                   std::function<void()> host_order, bool solo)
+                   bool uncached, std::function<void()> host_order, bool solo)
     : Comm(rank, world), ag_(std::move(ag)), ipc_(ipc && !solo), solo_(solo),
       host_order_(std::move(host_order)) {
   PGCN_CHECK(world >= 1 && world <= kPeerMaxRanks && rank >= 0 && rank < world && (ag_ || solo),
@@ -258,7 +256,7 @@ PeerComm::PeerComm(int rank, int world, size_t slot_floats, AllGather ag, bool i
   // pushing workgroup; read after a system-scope acquire: peer_sync.hpp), or uncached
   // (peer_uncached); header: uncached (the flags and counters every rank polls and adds to)
   void *p = nullptr;
-  uncached_ = g_peer_uncached != 0 && !solo;
+  uncached_ = uncached && !solo;
   if (uncached_)
     PGCN_HIP(hipExtMallocWithFlags(&p, bytes_, hipDeviceMallocUncached));
   else

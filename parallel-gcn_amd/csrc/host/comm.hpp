@@ -20,11 +20,6 @@
 
 namespace pgcn {
 
-// "peer_uncached" (read at engine build): the peer exchange's receive slots in uncached device
-// memory (hipDeviceMallocUncached, MTYPE UC) instead of plain device memory -- no cache holds
-// a slot line on the receiver; the pushes are then write-through (0.3 TB/s on one GPU, r05)
-extern int g_peer_uncached;
-
 struct Partition {
   int world = 1, rank = 0;
   std::vector<int> bounds;  // world + 1 node boundaries
@@ -159,10 +154,11 @@ class PeerComm : public Comm {
   // host_order (in-process ranks): before a rank enqueues a wait, every rank has enqueued the
   // push it waits for -- ranks of one process may share hardware queues (GPU_MAX_HW_QUEUES),
   // where a wait ahead of a peer's push would block that push (a host rendezvous per wait)
+  // uncached: the receive slots in uncached device memory (the "peer_uncached" knob)
   // solo (timing only, tools/rank_epoch.py): rank `rank` of `world` with no peers -- every
   // peer's region is this rank's own, so the pushes, waits and sums run with this rank's
   // kernels and bytes (every store local), but the results are not the model's
-  PeerComm(int rank, int world, size_t slot_floats, AllGather ag, bool ipc,
+  PeerComm(int rank, int world, size_t slot_floats, AllGather ag, bool ipc, bool uncached,
            std::function<void()> host_order = nullptr, bool solo = false);
   ~PeerComm() override;
   void allreduce_sum(float *buf, size_t n, hipStream_t s) override;

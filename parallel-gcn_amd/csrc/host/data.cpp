@@ -73,7 +73,6 @@ Parser::Parser(GCNData *data, const std::string &name, const std::string &root)
       split_path_(root + "/data/" + name + ".split"),
       svm_path_(root + "/data/" + name + ".svmlight") {}
 
-int g_parse_threads = 0;  // "parse_threads": host threads of Parser::parse (0 = up to 16)
 
 namespace {
 
@@ -97,7 +96,8 @@ std::vector<size_t> line_pieces(const std::string &buf, int pieces) {
 }
 
 int parse_threads(size_t bytes) {
-  if (g_parse_threads > 0) return g_parse_threads;  // exactly this many pieces (tests)
+  const int forced = process_knobs().parse_threads;
+  if (forced > 0) return forced;  // exactly this many pieces (tests)
   int t = (int)std::thread::hardware_concurrency();
   t = std::max(1, std::min(t, 16));  // the GPU box grants 16 CPUs per GPU
   // pieces of at least 1 MB (small files: one piece, no threads)

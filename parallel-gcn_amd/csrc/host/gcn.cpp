@@ -13,84 +13,8 @@
 
 namespace pgcn {
 
-// "train_ahead" (pgcn_debug_set, read at engine build): eval's first-layer forward also
-// computes the next training forward's product (SparseMatmul, one pass over dense X)
-int g_train_ahead = 1;
-// "eval_ax" (read at engine build): eval's first layer as (Â X) W1 from Â X computed once
-// (Â and X are constants: exact algebra, fp32 rounding order differs)
-int g_eval_ax = 1;
-// "epoch_graph" (read per epoch_async): replay a captured per-epoch hipGraph when eligible;
-int g_epoch_graph = 0;  // measured no faster than eager launches (r01: GPU-bound epochs)
-// "split_rows" (read at each split switch): the output layer's GraphSum forward computes only
-// the current split's labelled rows.  Off by default: the reference's forward produces the
-// logits of every row, and so does the default engine (r02); on, rows outside the split keep
-// stale logits (get_var refuses them)
-int g_split_rows = 0;
-// "split_cols" (read at each split switch): the output layer's GraphSum backward keeps only the
-// edges from the training split's columns.  The loss gradient is exactly zero on every other
-// row, so the skipped terms are exact zeros: in.grad is the full gradient of every row
-int g_split_cols = 1;
-// "fuse_epilogue" (read at engine build), bits, all bit-identical to separate launches:
-//   1 (kFuseTails)    the ReLU / Dropout modules next to a GraphSum run in its final-write
-//                     epilogue (gs_epilogue.hpp);
-//   2 (kFusePrestage) ... and that epilogue also writes the next GraphSum's prescaled input
-//                     table, which then skips its prescale launch;
-//   4 (kFuseXstream)  the first layer's X-stream product applies the eval ReLU / writes the
-//                     first GraphSum's table;
-//   8 (kFuseMatmulTails) the Dropout / ReLU backward before a Matmul run in its input-grad
-//                     product's final write (k_xstream_nn: outputs of <= 16 columns; the
-//                     small graphs' second layer -- two launches fewer per epoch).
-int g_fuse_epilogue = kFuseTails | kFusePrestage | kFuseXstream | kFuseMatmulTails;
-// "fuse_output" (read at engine build): 0 = separate Matmul + loss; 1 = the output layer's
-// Matmul forward and input grad run inside the loss (launch_out_xent) when the Matmul produces
-// the logits (the reassociated order: GraphSum, then Matmul) from at most 16 columns
-// (bit-identical); 2 (default) = ... and its weight grad's block partials on graphs of >=
-// 65,536 rows or on an edge-cut rank (the same sums in another grouping); 3 = ... on any graph
-int g_fuse_output = 2;
-// "co_draw" (read at engine build): the hidden dropout's mask drawn in the input dropout's
-// launch (1: sparse X; 2: dense X too; bit-identical)
-int g_co_draw = 2;
-// "fuse_finish" (read per pass): one GPU, the loss kernel's last block sums the pass's
-// scalars and writes its results ring slot (XentFinal; one launch fewer per pass): 1 (default)
-// up to kFinishMaxBlocks loss blocks, 2 also above them with two levels of arrivals (reddit:
-// measured even, 615.2-616.0 vs 615.4 epochs/s -- the loss kernels' tails grew by what the
-// reduce launches cost, profiles/r06/x)
-int g_fuse_finish = 1;
-// "mask_adam" (read per epoch): one GPU, the next input mask drawn by the Adam launch
-int g_mask_adam = 1;
-// "mask_xstream" (read per epoch): dense X with eval_ax, one GPU -- the next input mask drawn
-// by eval's first-layer X-stream pass instead (GCN::mask_in_eval).  Off: bit-identical but
-// slower -- two drawing waves per CU (all the VGPR budget leaves beside the consumers) take
-// 202 us for what k_dropout_mask's 32 waves per CU draw in 63, so the pass doubles (reddit
-// 604-605 vs 617-619 epochs/s, profiles/r06/z2)
-int g_mask_xstream = 0;
-constexpr int kFinishMaxBlocks = 512, kFinishGroup = 64;
-// "tn_fold" (read per epoch): one GPU, the weight gradients' last reduction pass runs inside
-// the Adam launch (GCN::backward_pass; bit-identical)
-int g_tn_fold = 1;
-// "sparse_dual" (read per eval forward): sparse X with train_ahead: eval's first-layer product
-// also computes the next training forward's (k_spmm_csr<true>, one pass; bit-identical)
-int g_sparse_dual = 1;
-// "mm_side" (read at engine build): Matmul weight gradients on the side stream (ModuleContext)
-// on graphs of at least kMmSideRows rows; 2 = on every graph.  Off: r02 A/B on reddit-114M,
-// three runs each, 486.5 (on) vs 487.4 (off) epochs/s -- the LDS GraphSum holds every CU with
-// one workgroup, so the side kernels find no room to overlap; cora 5,957 vs 7,136 (the
-// stream hand-offs cost more than the ~7 us of kernels they hide)
-int g_mm_side = 0;
-constexpr int kMmSideRows = 65536;
-// "reassoc_small" (read at engine build): on graphs of fewer than kMmSideRows nodes the output
-// layer runs in the reassociated order (Â H) W even when the classes are no more than the last
-// hidden width (<= 16), so its Matmul runs inside the loss kernel: a small graph's epoch is
-// bound by its launches, not by the GraphSum's width (the fp32 order differs, like reddit's)
-int g_reassoc_small = 1;
-// "eval_tail" (read at engine build): the edge-cut eval pass's last exchange and output layer
-// on the (high-priority) comm stream beside the next epoch's mask draw and first-layer product
-// (ModuleContext::tail_stream; peer exchange between processes only; bit-identical).  Off: on
-// the solo timing form, where the push has no link time to hide, the overlapped kernels slow
-// each other -- W = 8 rank epoch 0.511-0.514 vs 0.489-0.495 ms (0.502-0.506 on the low-priority
-// side stream; profiles/r05/s).  An 8-GPU run with slow links may still gain (the eval push's
-// link time beside ~48 us of compute): `bench.py --knob eval_tail=1`
-int g_eval_tail = 0;
+constexpr int kFinishMaxBlocks = 512, kFinishGroup = 64;  // "fuse_finish"
+constexpr int kMmSideRows = 65536;                         // "mm_side", "reassoc_small"
 
 // ------------------------------------------------------------------------------------------
 // Adam (src/optim.cu:7-95; hpdga optim.cpp:16-35)
@@ -300,11 +224,6 @@ void build_dev_features(DevFeatures &feats, const int *fptr, const int *indices,
 // Chunk states of a dropout over global elements [elem_begin, elem_end) whose first training
 // forward draws stream positions offset + element (hpdga: one xorshift128+ draw per element,
 // module.cpp:208-219), each 64-element chunk's state jumped to from the seed state.
-// "mask_per" (read at engine build): 64-draw mask words per stored RNG state (1 or 2); 0 = by
-// size: 2 from kMaskPer2Chunks words on (reddit's input mask: half the period jumps, 68.3 ->
-// 65.2 us for both masks), else 1 (a W = 8 rank's input mask, 274 k words: twice the threads,
-// each chain half as long -- 17.3 -> 14.5 us, profiles/r06/o)
-int g_mask_per = 0;
 constexpr long long kMaskPer2Chunks = 1LL << 20;
 
 // The stored states of r (its range, chunks and `per` set) with the dropout's next draw of
@@ -329,13 +248,13 @@ static std::vector<uint64_t> dropout_states(const DropoutRng &r, const uint64_t 
 }
 
 void init_dropout_rng_range(DropoutRng &r, const uint64_t seed[2], unsigned long long offset,
-                            long long elem_begin, long long elem_end) {
+                            long long elem_begin, long long elem_end, int mask_per) {
   r.elem_begin = elem_begin;
   r.elem_end = elem_end;
   r.chunk_lo = r.elem_begin / kDropChunk;
   const long long chunk_hi = ceil_div(r.elem_end, kDropChunk);
   r.n_chunks = std::max(0LL, chunk_hi - r.chunk_lo);
-  r.per = g_mask_per ? g_mask_per : (r.n_chunks >= kMaskPer2Chunks ? 2 : 1);
+  r.per = mask_per ? mask_per : (r.n_chunks >= kMaskPer2Chunks ? 2 : 1);
   r.mask_base = r.elem_begin - kDropChunk * r.chunk_lo;
   const std::vector<uint64_t> st = dropout_states(r, seed, offset);
   r.states.allocate(st.size());
@@ -347,7 +266,8 @@ void init_dropout_rng_range(DropoutRng &r, const uint64_t seed[2], unsigned long
 
 GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, int device_,
          const DistSpec *dist)
-    : params(params_), adam_params(adam), device(device_) {
+    : knobs_(process_knobs()), params(params_), adam_params(adam), device(device_) {
+  ctx.knobs = &knobs_;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     throw Error(PGCN_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
@@ -401,16 +321,18 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
       if (params.layer_norm)  // the scale / shift gradients ride the same all-reduce
         for (int h : params.hidden_dims) wtotal += 2LL * h;
       const size_t cap = std::max((size_t)part.maxrows * ld, (size_t)wtotal);
+      const bool uncached = knobs_.peer_uncached != 0;
       if (dist->solo) {  // timing only: every peer is this rank (PeerComm's solo form)
-        comm = std::make_unique<PeerComm>(rank, world, cap, nullptr, false, nullptr, true);
+        comm = std::make_unique<PeerComm>(rank, world, cap, nullptr, false, uncached, nullptr,
+                                          true);
       } else if (dist->loopback) {
         auto grp = dist->loopback;
         comm = std::make_unique<PeerComm>(
             rank, world, cap,
             [grp, rank](const void *m, size_t b, void *all) { grp->allgather(rank, m, b, all); },
-            false, [grp, rank] { grp->barrier(rank); });
+            false, uncached, [grp, rank] { grp->barrier(rank); });
       } else {
-        comm = std::make_unique<PeerComm>(rank, world, cap, dist->allgather, true);
+        comm = std::make_unique<PeerComm>(rank, world, cap, dist->allgather, true, uncached);
       }
     } else {
       comm = std::make_unique<RcclComm>(rank, world, dist->unique_id);
@@ -465,10 +387,10 @@ void GCN::init_dropout_rng(const GCNData &data, long long glorot_draws) {
     auto r = std::make_shared<DropoutRng>();
     if (l == 0)
       init_dropout_rng_range(*r, seed, offset, data.feature_index.indptr[(size_t)first],
-                             data.feature_index.indptr[(size_t)last]);
+                             data.feature_index.indptr[(size_t)last], knobs_.mask_per);
     else
       init_dropout_rng_range(*r, seed, offset, (long long)first * dims[(size_t)l],
-                             (long long)last * dims[(size_t)l]);
+                             (long long)last * dims[(size_t)l], knobs_.mask_per);
     rngs.push_back(r);
     offset += (l == 0) ? (unsigned long long)nnz_x_global
                        : (unsigned long long)N * dims[(size_t)l];
@@ -547,7 +469,7 @@ void GCN::build(const GCNData &data) {
           }
         }
       auto gk = std::make_unique<DevGraph>(part.world * h, part.local_rows(), sp.data(), si.data(),
-                                           sv.data());
+                                           sv.data(), knobs_);
       gk->set_scales(std::move(rs), cs);
       chunk_graphs.push_back(std::move(gk));
     }
@@ -558,14 +480,14 @@ void GCN::build(const GCNData &data) {
   } else {
     std::vector<float> v = graph_coefs(N, data.graph.indptr.data(), data.graph.indices.data());
     graph = std::make_unique<DevGraph>(N, N, data.graph.indptr.data(), data.graph.indices.data(),
-                                       v.data());
+                                       v.data(), knobs_);
     const std::vector<float> sg = degree_scales(N, data.graph.indptr.data());
     graph->set_scales(sg, sg);
   }
   upload_features(data);
   // eval_ax (dense X): Â X's buffer now -- the modules built below read it -- and its sums at
   // the end of the build (build_eval_ax)
-  if (g_eval_ax && !params.attention && feats.dense && feats.cols >= 16 && (comm || graph)) {
+  if (knobs_.eval_ax && !params.attention && feats.dense && feats.cols >= 16 && (comm || graph)) {
     feats.ax.allocate(feats.x.size());
     feats.ax.zero();
   }
@@ -687,7 +609,7 @@ void GCN::build(const GCNData &data) {
   // the fused loss kernel's per-block W.grad partials of the output layer (fuse_output >= 2)
   ws = std::max(ws, tn_reduce_blocks_workspace(xent_blocks(prow), 16, 48));
   gemm_ws.allocate(ws / sizeof(float) + 64);
-  if (g_mm_side == 2 || (g_mm_side == 1 && rows >= kMmSideRows)) {
+  if (knobs_.mm_side == 2 || (knobs_.mm_side == 1 && rows >= kMmSideRows)) {
     // the side stream's Matmul weight gradients have a workspace of their own
     gemm_ws_side.allocate(ws / sizeof(float) + 64);
     ctx.mm_side = true;
@@ -695,7 +617,7 @@ void GCN::build(const GCNData &data) {
     ctx.mm_fork = Event::create();
     ctx.side_join = Event::create();
   }
-  ctx.train_ahead = g_train_ahead != 0;
+  ctx.train_ahead = knobs_.train_ahead != 0;
   ctx.xent_partials = xent_partials.get();
   ctx.xent_blocks = xent_blocks(prow);
   ctx.gemm_workspace = gemm_ws.get();
@@ -723,13 +645,13 @@ void GCN::build(const GCNData &data) {
     decays.push_back(false);
   }
   // (edge-cut: the tails run in k_gs_finish on the rank's rows after the reduce-scatter)
-  if (g_fuse_epilogue & kFuseTails) fuse_epilogues();
-  if (g_fuse_epilogue & kFuseMatmulTails) fuse_matmul_tails();
-  if (g_co_draw && dropouts_.size() >= 2 && (g_co_draw == 2 || !feats.dense) && dropouts_[0] &&
-      dropouts_[1])
+  if (knobs_.fuse_epilogue & kFuseTails) fuse_epilogues();
+  if (knobs_.fuse_epilogue & kFuseMatmulTails) fuse_matmul_tails();
+  if (knobs_.co_draw && dropouts_.size() >= 2 && (knobs_.co_draw == 2 || !feats.dense) &&
+      dropouts_[0] && dropouts_[1])
     const_cast<Dropout *>(dropouts_[0])->co_draw = dropouts_[1];
   // (multilabel: the output Matmul runs on its own, the `fuse_output 0` path)
-  if (g_fuse_output && !params.multilabel) fuse_output_layer();
+  if (knobs_.fuse_output && !params.multilabel) fuse_output_layer();
   optimizer = Adam(weights, decays, adam_params);
   prepare_graphs();
   build_eval_ax();
@@ -737,7 +659,7 @@ void GCN::build(const GCNData &data) {
   // ranks may share hardware queues, where a wait on one rank's side stream could sit ahead
   // of the push it waits for
   const auto *pc = dynamic_cast<const PeerComm *>(comm.get());
-  if (g_eval_tail && pc && !pc->host_ordered() && comm->world() > 1) {
+  if (knobs_.eval_tail && pc && !pc->host_ordered() && comm->world() > 1) {
     for (int i = 0; i < (int)modules.size(); i++)
       if (dynamic_cast<const GraphSum *>(modules[(size_t)i].get())) tail_gs = i;
     ctx.tail_fork = Event::create();
@@ -1014,7 +936,7 @@ void GCN::insert_last_layer() {
   auto drop = std::make_unique<Dropout>(prev, params.dropouts.back(), rngs[(size_t)L - 1], &ctx);
   dropouts_.push_back(drop.get());
   modules.push_back(std::move(drop));
-  const bool small = g_reassoc_small && hl <= 16 && part.bounds.back() < kMmSideRows;
+  const bool small = knobs_.reassoc_small && hl <= 16 && part.bounds.back() < kMmSideRows;
   if (params.reassociate_last && !params.attention && (hl < C || small) && graph_symmetric) {
     // out = Â (H W) computed as (Â H) W: the same product (Â is symmetric, so the backward
     // Â dOut W^T = Â (dOut W^T) and W.grad = H^T Â dOut = (Â H)^T dOut also match), but the
@@ -1068,7 +990,7 @@ void GCN::set_split(int split) {
   ctx.split_graph = nullptr;
   ctx.split_rows = nullptr;
   ctx.split_colgraph = nullptr;
-  if (g_split_rows && !comm && graph && !params.attention) {
+  if (knobs_.split_rows && !comm && graph && !params.attention) {
     if (!split_graphs[split]) {
       split_graphs[split] = graph->row_subset(split_rows_host[split]);
       split_rows_dev[split].allocate(std::max<size_t>(split_rows_host[split].size(), 1));
@@ -1079,7 +1001,7 @@ void GCN::set_split(int split) {
   }
   ctx.chunk_split_graphs.clear();
   ctx.chunk_split_rows.clear();
-  if (g_split_rows && comm && !chunk_graphs.empty()) {
+  if (knobs_.split_rows && comm && !chunk_graphs.empty()) {
     // edge-cut: the output layer's forward sums only the split's labelled rows of every RS
     // chunk (padded chunk row q*h + j = global node bounds[q] + k*h + j)
     if (chunk_split_graphs[split].empty()) {
@@ -1105,7 +1027,7 @@ void GCN::set_split(int split) {
     }
   }
   ctx.chunk_col_graphs.clear();
-  if (g_split_cols && comm && !chunk_graphs.empty() && split == 1 &&
+  if (knobs_.split_cols && comm && !chunk_graphs.empty() && split == 1 &&
       !split_rows_host[1].empty()) {  // backward follows training
     if (chunk_col_graphs.empty()) {
       for (auto &gk : chunk_graphs) chunk_col_graphs.push_back(gk->col_subset(split_rows_host[1]));
@@ -1114,7 +1036,7 @@ void GCN::set_split(int split) {
     }
     for (auto &cg : chunk_col_graphs) ctx.chunk_col_graphs.push_back(cg.get());
   }
-  if (g_split_cols && !comm && graph && split == 1 && !params.attention) {  // (after training)
+  if (knobs_.split_cols && !comm && graph && split == 1 && !params.attention) {  // (after training)
     if (!split_colgraphs[split]) split_colgraphs[split] = graph->col_subset(split_rows_host[split]);
     ctx.split_colgraph = split_colgraphs[split].get();
   }
@@ -1139,7 +1061,7 @@ void GCN::set_split(int split) {
 int GCN::mask_with_adam(MaskDraw out[2]) {
   // (not with epoch graphs: a capture after an eager epoch would find the mask drawn ahead and
   // record a forward without its draw)
-  if (!g_mask_adam || g_epoch_graph || comm || dropouts_.empty() || !dropouts_[0] ||
+  if (!knobs_.mask_adam || knobs_.epoch_graph || comm || dropouts_.empty() || !dropouts_[0] ||
       dropouts_[0]->variable() || optimizer.size() > (size_t)kAdamBatch || mask_in_eval())
     return 0;
   return dropouts_[0]->ahead_descs(out);
@@ -1151,7 +1073,7 @@ int GCN::mask_with_adam(MaskDraw out[2]) {
 // before it.  The same stream positions whenever they are drawn: bit-identical.  A training
 // epoch with no eval after it draws its next mask in its own forward, as without the knob.
 bool GCN::mask_in_eval() const {
-  return g_mask_xstream && !g_epoch_graph && !comm && feats.ax && !dropouts_.empty() &&
+  return knobs_.mask_xstream && !knobs_.epoch_graph && !comm && feats.ax && !dropouts_.empty() &&
          dropouts_[0] && !dropouts_[0]->variable();
 }
 
@@ -1167,9 +1089,9 @@ void GCN::arm_finish(int dst_offset, bool graph) {
   // r06 late (fuse_finish 2): above that, two levels -- the blocks arrive on one ticket per
   // group of kFinishGroup, the group's last block sums the group and arrives on the top ticket
   // (reddit: 57 groups of 64 instead of 3,641 adds on one address)
-  if (!g_fuse_finish || comm) return;
+  if (!knobs_.fuse_finish || comm) return;
   const bool two = ctx.xent_blocks > kFinishMaxBlocks;
-  if (two && g_fuse_finish < 2) return;
+  if (two && knobs_.fuse_finish < 2) return;
   const int groups = two ? (ctx.xent_blocks + kFinishGroup - 1) / kFinishGroup : 0;
   if (!fin_ticket || fin_blocks < ctx.xent_blocks) {
     fin_ticket.allocate(1);
@@ -1299,7 +1221,8 @@ struct GCN::FoldScope {
     // all-reduce push: GCN::backward_pass); in-process ranks and RCCL all-reduce finished
     // gradients
     const auto *pc = dynamic_cast<const PeerComm *>(g.comm.get());
-    if (!g_tn_fold || (g.comm && !(pc && !pc->host_ordered() && g.comm->world() > 1))) return;
+    if (!g.knobs_.tn_fold || (g.comm && !(pc && !pc->host_ordered() && g.comm->world() > 1)))
+      return;
     // the deferred passes' inputs: 64 first-pass groups of every weight's [K][16-padded]
     // gradient (reddit: 0.8 MB)
     if (!g.tn_pool) {
@@ -1379,9 +1302,10 @@ void GCN::enqueue_epoch(bool graph) {
 // events), and train-ahead over dense X without eval_ax (it swaps buffers on the host between
 // eval and the next training forward).
 bool GCN::graph_eligible() const {
-  if (!g_epoch_graph || !warm || comm || ctx.profile) return false;
+  if (!knobs_.epoch_graph || !warm || comm || ctx.profile) return false;
   if (ctx.train_ahead && feats.dense && feats.maskT && !feats.ax) return false;
-  if (ctx.train_ahead && !feats.dense && g_sparse_dual) return false;  // (the same host swaps)
+  // (the same host swaps)
+  if (ctx.train_ahead && !feats.dense && knobs_.sparse_dual) return false;
   return true;
 }
 

@@ -150,6 +150,8 @@ class GCN {
   void profile_read(double *ms, long long *calls, double *bytes);
   const Partition &partition() const { return part; }
   const GCNParams &get_params() const { return params; }
+  // the knobs this engine and its graphs were built with (pgcn_debug_set changes nothing here)
+  const Knobs &knobs() const { return knobs_; }
   const Comm *communicator() const { return comm.get(); }
   bool symmetric() const { return graph_symmetric; }
   long long epochs_run() const { return epoch_count; }
@@ -225,6 +227,7 @@ class GCN {
   void capture_epoch();
   void drop_epoch_graph();
 
+  const Knobs knobs_;
   GCNParams params;
   AdamParams adam_params;
   int device;

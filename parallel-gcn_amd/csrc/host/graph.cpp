@@ -97,8 +97,8 @@ std::vector<float> degree_scales(int n, const int *indptr) {
 }
 
 DevGraph::DevGraph(int n_rows, int n_cols, const int *indptr, const int *indices,
-                   const float *vals)
-    : n_rows_(n_rows), n_cols_(n_cols), nnz_(indptr[n_rows]), h_indptr_(indptr, indptr + n_rows + 1),
+                   const float *vals, const Knobs &knobs)
+    : n_rows_(n_rows), n_cols_(n_cols), nnz_(indptr[n_rows]), knobs_(knobs), h_indptr_(indptr, indptr + n_rows + 1),
       h_indices_(indices, indices + indptr[n_rows]), h_vals_(vals, vals + indptr[n_rows]) {
   indices_.allocate((size_t)nnz_ + 64);  // slack: unrolled loads never step past the end
   vals_.allocate((size_t)nnz_ + 64);
@@ -107,43 +107,6 @@ DevGraph::DevGraph(int n_rows, int n_cols, const int *indptr, const int *indices
   PGCN_HIP(hipMemset(indices_.get() + nnz_, 0, 64 * sizeof(int)));
   PGCN_HIP(hipMemset(vals_.get() + nnz_, 0, 64 * sizeof(float)));
 }
-
-// d = 16 feature tables above this byte count take the LDS GraphSum ("lds_min_kb"; the
-// plain path blocks its columns per XCD above DevGraph::kL2Budget: below it one XCD's 4 MB L2
-// holds the whole table).  The LDS path also wants rows to fill its workgroups (kLdsMinRows).
-// r02, the edge-cut engine's per-rank graphs of reddit-114M (tools/rank_graphsum.py, 118 k
-// padded rows): 3.7 MB table (4 ranks) LDS 0.123 vs plain 0.249 ms, 1.9 MB (8 ranks) 0.083 vs
-// 0.114 ms; 15 MB (1 rank) 0.33 vs 1.04 ms
-long long g_lds_min_bytes = DevGraph::kLdsMinBytes;
-
-
-// "gs_split" (read at schedule build), the rows of the plain unblocked path longer than one
-// work item: 0 = their items write slots that a combine launch sums; 1 = the last of a row's
-// items to finish sums them in the same launch (an arrival counter per row, the combine's
-// order: the same bits), on graphs of <= kSmallNnz slots (each arrival writes its XCD's L2
-// back: costly when many rows split -- pubmed_synth lost 4 % at 8-iteration items); 2 = on
-// those graphs, rows up to 8 items long stay one item (no slots; another summation order);
-// 3 = as 1, but rows of up to 8 workgroup-wide iterations are summed by one whole workgroup
-// (4 waves, an LDS reduce in wave order: no cross-workgroup hand-off; another summation
-// order), power-of-two row widths
-int g_gs_split = 3;
-// "gs_item_iters" (read at schedule build): group iterations per work item of the plain
-// unblocked path on graphs of <= kSmallNnz slots with gs_split 1 / 3 (32 elsewhere).  A small
-// graph's GraphSum lasts as long as its longest item (one index -> gather round trip per
-// iteration), so its long rows are cut short and summed in-kernel or by workgroup items.
-// 0 (default) = by shape with gs_split 3: the shortest of 2, 4, 8, 16, 32 that leaves at most
-// kWideCap workgroup items (r04 late: cora 224 rows at 2 iterations, 11.5k vs 11.1k epochs/s
-// at 8; pubmed_synth 3,215 rows at 2 lost 2 %, 1,321 at 4 gained 1 %: profiles/r04/ab_item_iters.txt)
-int g_gs_item_iters = 0;
-// "gs_orig_cols" (read per call): a column subset's unblocked plain GraphSum gathers the
-// input's own rows through the original column ids (1) instead of compacting them first (0)
-int g_gs_orig_cols = 1;
-// "gs16_gather" (read at schedule build): the blocked d = 16 path's kernel (GraphSchedule::
-// gather16): 0 = by shape -- the interleaved k_graphsum<4, 16> when a row's segment in a column
-// block averages under 16 slots (r05 late, one call: reddit-11.6M, ~12 slots, 341 vs 595 us;
-// reddit-114M, ~60 slots, k_graphsum16 1,016 vs 1,089 us; profiles/r05/y, z), 1 = k_graphsum16,
-// 2 = the interleaved kernel
-int g_gs16_gather = 0;
 
 int DevGraph::column_blocks(int dim) {
   const int vec = (dim + 3) / 4;
@@ -226,11 +189,12 @@ DevGraph::Sched &DevGraph::schedule(int vec) {
   std::vector<int4> wide;
   if (nbc == 1) {
     const bool small = nnz_ <= kSmallNnz;
-    const bool arrive = (g_gs_split == 1 || g_gs_split == 3) && small;
+    const bool arrive = (knobs_.gs_split == 1 || knobs_.gs_split == 3) && small;
     chunk = nb * 32;  // 32 group iterations per work item
-    const int wide_max = g_gs_split == 3 && small && (vec & (vec - 1)) == 0 ? 256 / vec * 8 : 0;
-    if (arrive && g_gs_item_iters > 0) {
-      chunk = nb * g_gs_item_iters;
+    const int wide_max =
+        knobs_.gs_split == 3 && small && (vec & (vec - 1)) == 0 ? 256 / vec * 8 : 0;
+    if (arrive && knobs_.gs_item_iters > 0) {
+      chunk = nb * knobs_.gs_item_iters;
     } else if (arrive) {
       int it = 2;
       for (; it < 32; it *= 2) {
@@ -243,7 +207,7 @@ DevGraph::Sched &DevGraph::schedule(int vec) {
       }
       chunk = nb * (wide_max ? it : 8);
     }
-    const int whole = g_gs_split == 2 && small ? 8 * chunk : chunk;
+    const int whole = knobs_.gs_split == 2 && small ? 8 * chunk : chunk;
     items.reserve((size_t)n_rows_ + (size_t)(nnz_ / chunk) + 1);
     for (int r = 0; r < n_rows_; r++) {
       const int b = h_indptr_[(size_t)r], e = h_indptr_[(size_t)r + 1];
@@ -306,7 +270,8 @@ DevGraph::Sched &DevGraph::schedule(int vec) {
   sp->s.vec = vec;
   if (nbc > 1 && vec == 4) {
     const bool short_segments = nnz_ < 16LL * kBlocks * std::max(n_rows_, 1);
-    sp->s.gather16 = g_gs16_gather == 2 || (g_gs16_gather == 0 && short_segments) ? 1 : 0;
+    sp->s.gather16 =
+        knobs_.gs16_gather == 2 || (knobs_.gs16_gather == 0 && short_segments) ? 1 : 0;
   }
   sp->s.chunk = chunk;
   sp->s.nbc = nbc;
@@ -362,7 +327,8 @@ std::unique_ptr<DevGraph> DevGraph::row_subset(const std::vector<int> &rows) con
     ix.insert(ix.end(), h_indices_.begin() + h_indptr_[(size_t)i], h_indices_.begin() + h_indptr_[(size_t)i + 1]);
     v.insert(v.end(), h_vals_.begin() + h_indptr_[(size_t)i], h_vals_.begin() + h_indptr_[(size_t)i + 1]);
   }
-  auto g = std::make_unique<DevGraph>((int)rows.size(), n_cols_, ip.data(), ix.data(), v.data());
+  auto g = std::make_unique<DevGraph>((int)rows.size(), n_cols_, ip.data(), ix.data(), v.data(),
+                                      knobs_);
   if (!h_row_scale_.empty()) {
     std::vector<float> rs(rows.size());
     for (size_t r = 0; r < rows.size(); r++) rs[r] = h_row_scale_[(size_t)rows[r]];
@@ -394,7 +360,7 @@ std::unique_ptr<DevGraph> DevGraph::col_subset(const std::vector<int> &cols) con
     v.push_back(0.0f);
   }
   auto g = std::make_unique<DevGraph>(n_rows_, std::max((int)cols.size(), 1), ip.data(), ix.data(),
-                                      v.data());
+                                      v.data(), knobs_);
   if (!h_col_scale_.empty() && !cols.empty()) {
     std::vector<float> cs(cols.size());
     for (size_t c = 0; c < cols.size(); c++) cs[c] = h_col_scale_[(size_t)cols[c]];
@@ -421,20 +387,14 @@ void DevGraph::set_scales(std::vector<float> row_scale, std::vector<float> col_s
   lds_.reset();
 }
 
-// "lds_blocks": column blocks of the LDS schedule; 0 = by shape (r01, reddit): 4 blocks when the
-// graph has about as many rows as columns (the full graph and its column subsets: one round of
-// 256 workgroups, half the partials; the same kernel time, combine 18 -> 11 us), 8 for a small
-// row subset (its 256 workgroups then stream half the table each: val rows 0.11 vs 0.22 ms)
-int g_lds_blocks = 0;
-
 int lds_slots(int n_rows, int n_cols) {
   (void)n_rows;
   (void)n_cols;
   return LDS_SLOTS;
 }
 
-int lds_blocks(int n_rows, int n_cols) {
-  if (g_lds_blocks) return g_lds_blocks;
+int lds_blocks(int n_rows, int n_cols, const Knobs &k) {
+  if (k.lds_blocks) return k.lds_blocks;
   const long long cap = (long long)LDS_CW * lds_slots(n_rows, n_cols);
   if ((double)n_rows >= 0.9 * (double)n_cols) {
     // square-ish: 4 blocks, or 8 when the rowset batches fill the chip only then and every
@@ -479,11 +439,13 @@ std::vector<int> column_cuts(int n_cols, const std::vector<int> &indices, int n_
 }
 
 void DevGraph::build_lds() {
-  if (lds_cut_.empty()) lds_cut_ = ring_cuts(n_cols_, h_indices_, lds_blocks(n_rows_, n_cols_));
+  if (lds_cut_.empty()) lds_cut_ = ring_cuts(n_cols_, h_indices_, lds_blocks(n_rows_, n_cols_, knobs_));
   auto L = std::make_unique<LdsSched>();
   LdsHost h = build_ring_host(
-      n_rows_, n_cols_, h_indptr_, h_indices_, lds_cut_, lds_slots(n_rows_, n_cols_), -1,
-      ring_window_for(n_rows_, n_cols_, (long long)h_indices_.size(), (int)lds_cut_.size() - 1));
+      n_rows_, n_cols_, h_indptr_, h_indices_, lds_cut_, lds_slots(n_rows_, n_cols_),
+      knobs_.ring_pair != 0,
+      ring_window_for(n_rows_, n_cols_, (long long)h_indices_.size(), (int)lds_cut_.size() - 1,
+                      knobs_));
   // + 2 KB slack: ring refills read whole 512-B chunks (up to 3) past a wave's last block
   L->entries.allocate(h.entries.size() / 4 + 256);
   L->entries.upload(reinterpret_cast<const uint2 *>(h.entries.data()), h.entries.size() / 4);
@@ -529,7 +491,8 @@ void DevGraph::prepare(int dim) {
 }
 
 bool DevGraph::uses_lds(int dim) const {
-  return dim >= 16 && !h_row_scale_.empty() && (double)n_cols_ * 64.0 > (double)g_lds_min_bytes &&
+  const long long min_bytes = knobs_.lds_min_kb < 0 ? kLdsMinBytes : 1024LL * knobs_.lds_min_kb;
+  return dim >= 16 && !h_row_scale_.empty() && (double)n_cols_ * 64.0 > (double)min_bytes &&
          n_rows_ >= kLdsMinRows;
 }
 
@@ -658,7 +621,7 @@ void DevGraph::graphsum(const float *in, int ld_in, float *out, int ld_out, int 
   const int vec = (dim + 3) / 4;
   Sched &sc = schedule(vec);
   const bool blocked = sc.s.nbc > 1;
-  const bool orig = col_map && !blocked && g_gs_orig_cols;
+  const bool orig = col_map && !blocked && knobs_.gs_orig_cols;
   if (col_map && !orig) {  // plain path of a column subset: compact the input rows first
     const size_t need = (size_t)n_cols_ * ld_in;
     if (col_in_.size() < need) col_in_.allocate(need);

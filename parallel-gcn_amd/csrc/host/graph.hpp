@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../kernels.hpp"
+#include "../knobs.hpp"
 #include "runtime.hpp"
 
 namespace pgcn {
@@ -55,9 +56,9 @@ struct LdsHost {
 // nnz-balanced column cuts (kGraphBlocks + 1 boundaries)
 std::vector<int> column_cuts(int n_cols, const std::vector<int> &indices,
                              int n_blocks = kGraphBlocks);
-// column blocks of the LDS GraphSum schedule of an n_rows x n_cols graph (XCD-affine), and
-// its rowsets per summing wave (ring_slots_ok; knob "lds_slots")
-int lds_blocks(int n_rows, int n_cols);
+// column blocks of the LDS GraphSum schedule of an n_rows x n_cols graph (XCD-affine;
+// k.lds_blocks, or by shape), and its rowsets per summing wave (ring_slots_ok)
+int lds_blocks(int n_rows, int n_cols, const Knobs &k);
 int lds_slots(int n_rows, int n_cols);
 // ring schedule (host/ring.cpp): block cuts on RING_SR multiples, the schedule, and its CPU
 // walk as the kernel consumes it: out[row] += sum of in[col] (throws on an inconsistent
@@ -65,21 +66,20 @@ int lds_slots(int n_rows, int n_cols);
 std::vector<int> ring_cuts(int n_cols, const std::vector<int> &indices, int n_blocks);
 // pair: rowsets 2p and 2p + 1 of a wave run the same step count per visit and their entry
 // blocks alternate in the stream (k_graphsum_ring<.., true>: both blocks' table reads in flight
-// under one wait); -1 = the "ring_pair" knob
-// window: slices a visit reads, 2 or 3 (ring_window_for)
+// under one wait; the "ring_pair" knob)
+// window: slices a visit reads, 2 or 3 (ring_window_for: k.ring_window, or by shape)
 LdsHost build_ring_host(int n_rows, int n_cols, const std::vector<int> &indptr,
                         const std::vector<int> &indices, const std::vector<int> &bcut,
-                        int ns = LDS_SLOTS, int pair = -1, int window = RING_W);
-extern int g_ring_pair;
-// "ring_window" (read at schedule build): 0 = by shape (ring_window_for), 2 or 3
-extern int g_ring_window;
-int ring_window_for(int n_rows, int n_cols, long long nnz, int n_blocks);
+                        int ns = LDS_SLOTS, bool pair = false, int window = RING_W);
+int ring_window_for(int n_rows, int n_cols, long long nnz, int n_blocks, const Knobs &k);
 void ring_emulate(const LdsHost &h, int n_rows, const float *in, double *out);
 
 class DevGraph {
  public:
-  // CSR with n_rows rows and column ids < n_cols; `vals` aligned with `indices`.
-  DevGraph(int n_rows, int n_cols, const int *indptr, const int *indices, const float *vals);
+  // CSR with n_rows rows and column ids < n_cols; `vals` aligned with `indices`.  Every schedule
+  // built later follows the graph's copy of `knobs` (its row_subset / col_subset graphs too)
+  DevGraph(int n_rows, int n_cols, const int *indptr, const int *indices, const float *vals,
+           const Knobs &knobs = process_knobs());
   int rows() const { return n_rows_; }
   int cols() const { return n_cols_; }
   long long nnz() const { return nnz_; }
@@ -139,8 +139,8 @@ class DevGraph {
 
   static constexpr int kBlocks = kGraphBlocks;   // one column block per XCD
   static constexpr double kL2Budget = 4.0e6;     // one XCD's L2: tables the plain kernel keeps whole
-  static constexpr long long kSmallNnz = 1 << 20;  // g_gs_split 1-3: the small-graph schedules
-  static constexpr int kWideCap = 1536;  // g_gs_item_iters 0: workgroup items (6 per CU) at most
+  static constexpr long long kSmallNnz = 1 << 20;  // gs_split 1-3: the small-graph schedules
+  static constexpr int kWideCap = 1536;  // gs_item_iters 0: workgroup items (6 per CU) at most
   static constexpr long long kLdsMinBytes = 1 << 20;  // d = 16 tables above: LDS GraphSum ...
   static constexpr int kLdsMinRows = 32768;           // ... when the rows fill its workgroups
 
@@ -188,6 +188,7 @@ class DevGraph {
   DeviceBuffer<int> orig_indices_;
   int n_rows_, n_cols_;
   long long nnz_;
+  const Knobs knobs_;
   std::vector<int> h_indptr_, h_indices_;
   std::vector<float> h_vals_;
   DeviceBuffer<int> indices_;  // plain layout

@@ -55,17 +55,7 @@ std::vector<float> Variable::to_host(int which) const {
   return out;
 }
 
-// "csc_tree" (read per launch): sparse X's W1.grad summed as a fixed tree over each feature's
-// entries (k_spmm_csc_tree) instead of hpdga's sequential scatter order (k_spmm_csc_bwd,
-// bit-exact); deterministic, the sums in another order.  Off: measured slower where it counts
-// (same box, 400 epochs, profiles/r06/k: citeseer 11.6-11.7k vs 12.1k epochs/s, pubmed_synth
-// 6.57-6.59k vs 7.06k, cora 10.7-12.4k vs 12.3k) -- the chain's one-wave tail is not what
-// bounds the launch
-int g_csc_tree = 0;
-// "defer_wgrad" (read per pass): a small graph's fused loss kernel writes the output layer's
-// W.grad block partials into the deferred-reduction pool (tn_fold), summed by the Adam launch
-int g_defer_small_wgrad = 1;
-// up to this many loss blocks (cora 43, citeseer 52): pubmed_synth's 309 partials per weight
+// "defer_wgrad": up to this many loss blocks (cora 43, citeseer 52): pubmed_synth's 309 partials per weight
 // element made the Adam launch's sum as long as the two launches it saved (7.73-7.74k vs
 // 7.78-7.80k epochs/s, profiles/r06/s)
 constexpr int kDeferWgradMaxBlocks = 128;
@@ -211,7 +201,7 @@ void SparseMatmul::forward(bool training, const Stream &s) const {
       // eval: out = relu(Â X W1) (GraphSum, then its fused ReLU; the Dropout after it is the
       // identity in eval), which the reassociated output layer's GraphSum reads next
       XsEpilogue e;
-      if ((g_fuse_epilogue & kFuseXstream) && consumer && consumer->fwd_relu) {
+      if ((ctx->knobs->fuse_epilogue & kFuseXstream) && consumer && consumer->fwd_relu) {
         e.relu = 1;
         consumer->fwd_relu->skip_forward = true;
         if (consumer->fwd_next)
@@ -250,7 +240,7 @@ void SparseMatmul::forward(bool training, const Stream &s) const {
     ahead_valid = false;
     return;
   }
-  if (!training && ctx->train_ahead && !x->dense && g_sparse_dual && !ahead_valid) {
+  if (!training && ctx->train_ahead && !x->dense && ctx->knobs->sparse_dual && !ahead_valid) {
     // sparse X: eval's X W1 and the next training forward's drop(X) W1 from one pass over X
     // (k_spmm_csr<true>; the next input mask -- and its co-drawn hidden mask -- drawn now)
     if (!ahead) {
@@ -295,7 +285,7 @@ void SparseMatmul::forward(bool training, const Stream &s) const {
     if (mask && !flat)
       launch_mask_nibbles(mask, base, x->cols, x->rows, x->cols, x->maskT.get(), s.get());
     XsEpilogue e;  // the first GraphSum's prescaled input, written beside c
-    if ((g_fuse_epilogue & kFuseXstream) && consumer && (training || !eval_out)) {
+    if ((ctx->knobs->fuse_epilogue & kFuseXstream) && consumer && (training || !eval_out)) {
       e.next_table = consumer->claim_forward_table(x->rows, c->ld, &e.next_scale);
       e.next_sr = RING_SR;
     }
@@ -335,7 +325,8 @@ void SparseMatmul::backward(const Stream &s) const {
   } else {
     launch_spmm_csc_bwd(x->cols, b->cols, c->ld, x->csc_ptr.get(), x->csc_row.get(),
                         x->csc_pos.get(), x->values.get(), mask, base, scale, c->dev_grad.get(),
-                        b->dev_grad.get(), s.get(), x->nnz, x->csc_order.get(), g_csc_tree != 0);
+                        b->dev_grad.get(), s.get(), x->nnz, x->csc_order.get(),
+                        ctx->knobs->csc_tree != 0);
   }
 }
 
@@ -383,7 +374,8 @@ DevGraph *GraphSum::backward_table_graph() const {
 
 float4 *GraphSum::claim_forward_table(int rows, int ld, const float **scale) const {
   DevGraph *g = forward_table_graph();
-  if (!g || !(g_fuse_epilogue & kFusePrestage) || dim != 16 || in->ld != 16 || ld != 16 || g->cols() != rows)
+  if (!g || !(ctx->knobs->fuse_epilogue & kFusePrestage) || dim != 16 || in->ld != 16 ||
+      ld != 16 || g->cols() != rows)
     return nullptr;
   float *t = g->ring_table(dim, scale);
   if (!t) return nullptr;
@@ -392,7 +384,7 @@ float4 *GraphSum::claim_forward_table(int rows, int ld, const float **scale) con
 }
 
 bool GraphSum::claim_backward_table(int rows, int ld, XentTable *t) const {
-  if (ctx->comm || !(g_fuse_epilogue & kFusePrestage) || dim != 16 || ld != 16 ||
+  if (ctx->comm || !(ctx->knobs->fuse_epilogue & kFusePrestage) || dim != 16 || ld != 16 ||
       out->ld != 16 || out->rows != rows)
     return false;
   DevGraph *g = backward_graph();
@@ -410,7 +402,7 @@ bool GraphSum::claim_backward_table(int rows, int ld, XentTable *t) const {
 }
 
 void GraphSum::stage_next(GsEpilogue &e, GraphSum *next, DevGraph *ng, bool fwd) const {
-  if (!next || !ng || !(g_fuse_epilogue & kFusePrestage)) return;
+  if (!next || !ng || !(ctx->knobs->fuse_epilogue & kFusePrestage)) return;
   const float *sc = nullptr;
   float *t = ng->ring_table(next->dim, &sc);
   if (!t) return;
@@ -954,9 +946,10 @@ void CrossEntropyLoss::forward(bool training, const Stream &s) const {
     const int nb = xent_blocks(logits->rows);
     float *dWp = nullptr;
     bool deferred = false;
+    const Knobs &kn = *ctx->knobs;
     // (an edge-cut rank's rows are a slice of a large graph: the block partials too)
-    if (training && g_fuse_output >= 2 &&
-        (g_fuse_output == 3 || logits->rows >= 65536 || ctx->comm) &&
+    if (training && kn.fuse_output >= 2 &&
+        (kn.fuse_output == 3 || logits->rows >= 65536 || ctx->comm) &&
         Wv.dev_grad && logits->ld <= 48 &&
         !ctx->mm_side &&
         tn_reduce_blocks_workspace(nb, fused->inner(), 48) <= ctx->gemm_workspace_bytes)
@@ -966,7 +959,7 @@ void CrossEntropyLoss::forward(bool training, const Stream &s) const {
     // of its own (k_xstream_tn before; the same sums in another grouping)
     // (tn_fold 0, or no room: the same one ordered pass as its own launch -- the same bits)
     bool one_pass = false;
-    if (training && !dWp && g_fuse_output >= 2 && g_defer_small_wgrad && !ctx->comm &&
+    if (training && !dWp && kn.fuse_output >= 2 && kn.defer_wgrad && !ctx->comm &&
         nb <= kDeferWgradMaxBlocks && Wv.dev_grad && logits->ld <= 48 && !ctx->mm_side) {
       dWp = tn_defer_blocks(nb, fused->inner(), num_classes, 48, Wv.dev_grad.get(), Wv.ld);
       deferred = dWp != nullptr;

@@ -80,7 +80,7 @@ struct DropoutRng {
   DeviceBuffer<uint64_t> mask_ahead;  // the next one, when drawn ahead (input dropout)
   long long chunk_lo = 0, n_chunks = 0;
   // 64-draw mask words per stored state (k_dropout_mask's PER; one state per 128 draws;
-  // "mask_per" knob, read at engine build)
+  // "mask_per" knob)
   int per = 2;
   long long elem_begin = 0, elem_end = 0;  // global element range of this rank
   long long mask_base = 0;                 // bit of local element 0 in `mask`
@@ -100,17 +100,13 @@ class GraphSum;
 class Dropout;
 class ResidualConnection;
 
-// "fuse_epilogue" bits (host/gcn.cpp g_fuse_epilogue) and "fuse_output" (g_fuse_output)
-constexpr int kFuseTails = 1, kFusePrestage = 2, kFuseXstream = 4, kFuseMatmulTails = 8;
-extern int g_fuse_epilogue;
-extern int g_fuse_output;
-extern int g_sparse_dual;
-
 // Shared per-GCN state the modules read (current split, comm, profiling, RNG table).
-extern int g_csc_tree;  // "csc_tree" (module.cpp)
-
 struct ModuleContext {
-  bool train_ahead = true;     // eval computes the next training forward's first product too
+  // the owning engine's snapshot (GCN), or the process table itself (the C++ API's context)
+  const Knobs *knobs = &process_knobs();
+  // eval computes the next training forward's first product too (an engine's
+  // knobs->train_ahead; off in the C++ API, whose caller decides what runs next)
+  bool train_ahead = true;
   // (measured and removed, r01/r02: drawing the next input mask on a side stream beside the
   // weight-gradient pass, the eval forward's X-stream product or its output layer -- the RNG
   // kernel and the pass beside it slow each other down, DESIGN.md §3 "Streams")
@@ -194,7 +190,7 @@ struct ModuleContext {
 void build_dev_features(DevFeatures &feats, const int *fptr, const int *indices,
                         const float *values, int first, int rows, int F, bool dense, int hidden0);
 void init_dropout_rng_range(DropoutRng &r, const uint64_t seed[2], unsigned long long offset,
-                            long long elem_begin, long long elem_end);
+                            long long elem_begin, long long elem_end, int mask_per);
 void glorot_fill(std::vector<float> &w, int in_size, int out_size, uint64_t s[2]);
 
 // include/module.cuh:33-43
@@ -266,7 +262,7 @@ class SparseMatmul : public Module {
   shared_ptr<Variable> eval_out;
   // the GraphSum reading c (training) / standing for eval_out (eval): the X-stream product's
   // epilogue writes that GraphSum's ring table (training) or applies its fused ReLU and
-  // writes the next GraphSum's table (eval), when g_fuse_epilogue & kFuseXstream
+  // writes the next GraphSum's table (eval), when fuse_epilogue & kFuseXstream
   const GraphSum *consumer = nullptr;
   void forward(bool training, const Stream &s) const override;
   void backward(const Stream &s) const override;

@@ -78,32 +78,22 @@ std::vector<int> ring_cuts(int n_cols, const std::vector<int> &indices, int n_bl
   return cut;
 }
 
-// "ring_pair" (read at schedule build): rowsets in lockstep pairs (build_ring_host)
-int g_ring_pair = 0;
-
-int g_ring_window = 0;
-
 // The window by shape: 3 (the reddit graph's), or 2 where a visit's work is too short to cover
 // the loader's one-slice-ahead LDS-DMA (~1.3 us per 32-KB slice): r06 tall edge-cut rank
 // graphs and sparse graphs, decided on the mean entry blocks a summing wave runs per visit
 // (about rows x (nnz / rows / slices + 1) / 64 per wave at 4-step blocks)
-int ring_window_for(int n_rows, int n_cols, long long nnz, int n_blocks) {
-  if (g_ring_window) return g_ring_window;
-  (void)n_rows;
-  (void)n_cols;
-  (void)nnz;
-  (void)n_blocks;
+int ring_window_for(int, int, long long, int, const Knobs &k) {  // (no shape takes 2 today)
+  if (k.ring_window) return k.ring_window;
   return RING_W;
 }
 
 LdsHost build_ring_host(int n_rows, int n_cols, const std::vector<int> &indptr,
                         const std::vector<int> &indices, const std::vector<int> &bcut, int ns,
-                        int pair_arg, int window) {
+                        bool pair, int window) {
   (void)n_cols;
   PGCN_CHECK(window == 2 || window == 3, PGCN_E_INVALID, "graphsum_ring: window 2 or 3");
   const int B = (int)bcut.size() - 1, SR = RING_SR, W = window, K = RING_K;
   const int CW = LDS_CW, NS = ns;
-  const bool pair = pair_arg < 0 ? g_ring_pair != 0 : pair_arg != 0;
   PGCN_CHECK(ring_slots_ok(ns), PGCN_E_INVALID, "graphsum_ring: rowsets per wave");
   PGCN_CHECK(B >= 1 && kCUs % B == 0, PGCN_E_INVALID, "graphsum_ring: column blocks");
   for (int b = 0; b < B; b++)

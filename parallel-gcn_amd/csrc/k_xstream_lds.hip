@@ -36,6 +36,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "knobs.hpp"
 #include "lds_dma.hpp"
 #include "mask_draw.hpp"
 
@@ -45,13 +46,11 @@
 
 namespace pgcn {
 
-// "xstream_ring": 1 = these kernels for the X-stream products where they apply (default),
-// 0 = the register-streamed k_xstream_nn / k_xstream_tn (the oracle-tested fallback of every
-// other width).  Measured and removed (r02): two groups in flight per loader wave with fewer
+// (The "xstream_ring" knob, knobs.hpp, picks these kernels or k_xstream_nn / k_xstream_tn.)
+// Measured and removed (r02): two groups in flight per loader wave with fewer
 // slots (r04 keeps two in flight at the same slot count, publishing group t-1 after group t's
 // DMAs are issued: xl_load), and a TN split in which every consumer takes a share of K of every group (173 vs 137
 // us on reddit: every consumer then waits on every group).
-int g_xstream_ring = 1;
 
 namespace {
 
@@ -620,7 +619,8 @@ static bool xl_pow2(float v) {
 // the shapes these kernels take: ten 64-column chunks (K in 577..640), rows packed at lda =
 // K rounded up to 4 (the group is contiguous), N <= 16
 bool xstream_ring_ok(int K, int lda) {
-  return g_xstream_ring && K > 64 * (XL_KC - 1) && K <= 64 * XL_KC && lda == (K + 3) / 4 * 4;
+  return process_knobs().xstream_ring && K > 64 * (XL_KC - 1) && K <= 64 * XL_KC &&
+         lda == (K + 3) / 4 * 4;
 }
 
 void launch_xstream_nn_ring(int M, int N, int K, const float *A, int lda, const float *B, int ldb,

@@ -41,11 +41,11 @@ struct GraphSchedule {
   const int4 *items = nullptr;
   const int *block_items = nullptr;  // nbc + 1 offsets into items
   const int4 *comb = nullptr;
-  // in-kernel combine (g_gs_split 1): the comb index of each slot, and one arrival counter per
+  // in-kernel combine (gs_split 1): the comb index of each slot, and one arrival counter per
   // comb row (zero between calls); the last item of a split row to finish sums its slots
   const int *slot_comb = nullptr;
   int *comb_ctr = nullptr;
-  // workgroup items (g_gs_split 3): rows one whole workgroup sums ({row, begin, end, -1}),
+  // workgroup items (gs_split 3): rows one whole workgroup sums ({row, begin, end, -1}),
   // taken by the launch's first n_wide workgroups
   int n_wide = 0;
   const int4 *wide = nullptr;
@@ -204,7 +204,7 @@ void launch_xstream_nn(int M, int N, int K, const float *A, int lda, const float
                        hipStream_t s, float *C2 = nullptr,  // C2: drop(X) W beside C = X W
                        const XsEpilogue *epi = nullptr, const XsMask *flat = nullptr);
 // k_xstream_lds.hip: the X-stream products with loader and MFMA waves split (the default
-// form, g_xstream_ring; the launchers above dispatch to them)
+// form, the "xstream_ring" knob; the launchers above dispatch to them)
 bool xstream_ring_ok(int K, int lda);
 void launch_xstream_nn_ring(int M, int N, int K, const float *A, int lda, const float *B, int ldb,
                             int trans_b, float *C, int ldc, const uint64_t *maskT, float a_scale,

@@ -268,7 +268,8 @@ def csr_reference(indptr, indices, vals, x, n_cols=None):
 
 
 # --------------------------------------------------------------------------- engine knobs
-# pgcn_debug_set defaults of the engine (include/pgcn.h; parallel-gcn_amd/csrc/host/gcn.cpp)
+# pgcn_debug_set defaults of the engine (include/pgcn.h; parallel-gcn_amd/csrc/knobs.hpp, whose
+# table test_cpu_host.py compares with this one through pgcn_debug_knob)
 ENGINE_DEFAULTS = {"train_ahead": 1, "split_rows": 0, "split_cols": 1, "eval_ax": 1,
                    "epoch_graph": 0, "fuse_epilogue": 15, "fuse_output": 2, "mm_side": 0,
                    "xstream_ring": 1, "lds_min_kb": -1, "lds_blocks": 0,

@@ -588,3 +588,21 @@ def test_debug_set_refuses_out_of_range_values(pgcn):
         assert lib.pgcn_debug_set(key.encode(), 0) < 0, key
     for key, val in helpers.ENGINE_DEFAULTS.items():
         assert lib.pgcn_debug_set(key.encode(), val) == 0, key
+
+
+def test_knob_table_matches_engine_defaults(pgcn):
+    """The library's knob table, enumerated through pgcn_debug_knob, has exactly the keys and
+    defaults of helpers.ENGINE_DEFAULTS; past its end the call returns PGCN_E_INVALID."""
+    import ctypes
+    table, i = {}, 0
+    while True:
+        name, default = ctypes.c_char_p(), ctypes.c_int()
+        st = pgcn.lib.pgcn_debug_knob(i, ctypes.byref(name), ctypes.byref(default))
+        if st != 0:
+            break
+        assert name.value.decode() not in table, name.value
+        table[name.value.decode()] = default.value
+        i += 1
+    assert st == -1 and pgcn.lib.pgcn_debug_knob(-1, None, None) == -1
+    assert pgcn.lib.pgcn_debug_knob(0, None, None) == 0
+    assert table == helpers.ENGINE_DEFAULTS

@@ -538,3 +538,56 @@ def test_rank_graphs_ring(pgcn, dim, blocks):
 def test_rank_graphs_ring_tall(pgcn):
     """Ranks 0 and 7 of 8 at n = 140000: rows >= 6 x cols, lds_blocks' 2-block rule."""
     run_rank_graphs(pgcn, RANK_RING_TALL, 1, (0, 7), 16, "gs_ring", "rank ring tall dim 16")
+
+
+# --------------------------------------------------------------------------- knob scope
+def _scoped_calls(pgcn, kw, create, dims, x, n_rows, calls_inside):
+    """A graph created inside knobs(**kw); its first GraphSum of every width in `dims` made
+    inside the block too, or only after it has closed."""
+    with contextlib.ExitStack() as st:
+        with helpers.knobs(pgcn, **kw):
+            g = st.enter_context(create())
+            if calls_inside:
+                return [gs_calls(pgcn, g, x, n_rows, dim) for dim in dims]
+        return [gs_calls(pgcn, g, x, n_rows, dim) for dim in dims]
+
+
+@contextlib.contextmanager
+def rank_graph(pgcn, gr, world, rank):
+    g, rows, cols = ctypes.c_void_p(), ctypes.c_int(), ctypes.c_int()
+    pgcn.check(pgcn.lib.pgcn_debug_rank_graph(
+        gr["n"], helpers.ptr(gr["indptr"]), helpers.ptr(gr["indices"]), world, rank, 1, 0,
+        ctypes.byref(g), ctypes.byref(rows), ctypes.byref(cols)), "rank_graph")
+    try:
+        yield g
+    finally:
+        pgcn.lib.pgcn_graph_destroy(g)
+
+
+@gpu
+def test_graph_keeps_the_knobs_it_was_created_with(pgcn):
+    """A graph builds the schedule of a width at its first GraphSum of that width, with the
+    knobs it was created under, whatever they are by then: created inside knobs(gs_split=0,
+    gs_item_iters=32) and first called after the block (dim 16 and dim 5), the ladder gives the
+    bits and the launches (the combine's) of the same calls made inside the block; and so does
+    a ring graph (RANK_RING's rank 0) created under lds_blocks=2."""
+    lad = ladder()
+    kw = dict(gs_split=0, gs_item_iters=32)
+    make = functools.partial(values_graph, pgcn, lad)
+    inside = _scoped_calls(pgcn, kw, make, (16, 5), lad["x"], lad["n"], True)
+    after = _scoped_calls(pgcn, kw, make, (16, 5), lad["x"], lad["n"], False)
+    for (bi, pi), (ba, pa), dim in zip(inside, after, (16, 5)):
+        assert pi["launches"] == 2 * CALLS and pi["gs_gather"] >= CALLS, (dim, pi)
+        assert pa == pi, (dim, pa, pi)
+        for x, y in zip(bi, ba):
+            assert same_bits(x, y), f"ladder dim {dim}: first call after the block differs"
+    gr = varied_graph(RANK_RING["n"], RANK_RING["hi"], RANK_RING["lo"])
+    bounds, maxrows = pgcn.partition_bounds(gr["indptr"], RANK_RING["world"])
+    xr, rows = gr["x"][:int(bounds[1])], RANK_RING["world"] * maxrows
+    make = functools.partial(rank_graph, pgcn, gr, RANK_RING["world"], 0)
+    (bi, pi), = _scoped_calls(pgcn, dict(lds_blocks=2), make, (16,), xr, rows, True)
+    (ba, pa), = _scoped_calls(pgcn, dict(lds_blocks=2), make, (16,), xr, rows, False)
+    assert pi["gs_ring"] >= CALLS and pi["gs_gather"] == 0, pi
+    assert pa == pi, (pa, pi)
+    for x, y in zip(bi, ba):
+        assert same_bits(x, y), "ring, lds_blocks 2: first call after the block differs"
