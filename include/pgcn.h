@@ -226,6 +226,40 @@ int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
                  int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
                  float *da /* [2][d]: dst, src */, void *workspace, void *stream);
 
+/* Several heads, and dropout on the attention weights.  Head h of `heads` owns columns [h dh,
+ * (h + 1) dh) of P, Z, G, dP, a_dst and a_src, dh = d / heads, and runs the formulas above on its
+ * slice with a softmax of its own: u, v are [n][heads], alpha [nnz][heads] (slot-major), the
+ * concatenated heads fill the d columns of Z.  With a mask (a training forward and its backward):
+ *   m'_s^h = bit (drop_base + s heads + h) of drop_mask ? drop_scale : 0
+ *   Z_i[h] = sum_row alpha_s^h m'_s^h P_j[h]
+ *   dx_s^h = alpha_s^h (m'_s^h G_i[h] . P_j[h] - G_i[h] . Z_i[h]) (x_s^h > 0 ? 1 : slope)
+ *   dP_j[h] = sum into column j of alpha_s^h m'_s^h G_i[h] + du_j^h a_dst[h] + dv_j^h a_src[h]
+ * drop_mask is a device bit array (bit b = word b / 64, bit b % 64: the triple the fused GraphSum
+ * entries take) or NULL for no dropout; alpha receives the weights BEFORE dropout (each head's
+ * sum to 1 per row) and is required with a mask.
+ * heads == 1: any d in 1..128, and without a mask exactly pgcn_gat_scores / _fwd / _bwd (their
+ * kernels, their bits); one head under an all-ones mask of scale 1 gives those bits too.
+ * heads > 1: heads divides d and dh is 4, 8, 16, 32, 64 or 128 -- a lane's float4 then belongs to
+ * one head and a head is an aligned power-of-two group of lanes; anything else is
+ * PGCN_E_INVALID before anything touches the device, like the checks of the entries above.
+ * Every head shares one pass over a row's or column's index and one load of each neighbour row:
+ * a call launches as many kernels as the single-head call on the same graph.  No float atomics;
+ * every summation order depends on the pattern, d and heads only.
+ * `workspace`: pgcn_gat_bwd_workspace_mh(g, d, heads) bytes (dx [nnz][heads], du, dv
+ * [n][heads], the partial sums); with heads == 1 it serves calls with and without a mask. */
+int pgcn_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
+                       const float *a_src, float *u /* [n][heads] */, float *v, void *stream);
+int pgcn_gat_fwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, float *Z, int ld_z, int d, int heads, const uint64_t *drop_mask,
+                    long long drop_base, float drop_scale,
+                    float *alpha /* [nnz][heads]; NULL only without a mask */, void *stream);
+size_t pgcn_gat_bwd_workspace_mh(const pgcn_graph *g, int d, int heads);
+int pgcn_gat_bwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                    int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                    int heads, const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                    float *da /* [2][d]: dst, src */, void *workspace, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -302,6 +336,21 @@ typedef struct {
   int hidden_dims[PGCN_MAX_LAYERS];      /* n_layers - 1 */
   float dropouts[PGCN_MAX_LAYERS];       /* n_layers */
   int epochs, early_stopping;
+  /* attention != 0 only (anything but 1 / 0 without it is PGCN_E_INVALID).  attention_heads = K
+   * (0 counts as 1): every HIDDEN attention layer runs K heads concatenated inside its width d_l
+   * -- head h owns columns [h dh, (h + 1) dh), dh = d_l / K, reads its own slice of a_dst / a_src
+   * and takes a softmax of its own (pgcn_gat_fwd_mh); no tensor changes shape.  K must divide
+   * every hidden width into dh of 4, 8, 16, 32, 64 or 128.  The output layer stays single-head.
+   * attention_dropout = p in [0, 1): in training, every attention layer (the output layer too)
+   * drops each normalised weight alpha_s^h with probability p and scales the kept ones by
+   * 1 / (1 - p) (kept iff draw >= int(p * RAND_MAX), the product in float, as every mask here).
+   * The draws come from the engine's xorshift stream: inside an epoch's block of draws they stand
+   * behind every existing Dropout's, layer by layer, nnz * K_l each (K_l = 1 on the output
+   * layer), element s * K_l + h for slot s (CSR order), head h -- so the other masks keep their
+   * offsets inside the epoch and only the period grows.  p == 0 draws nothing: heads 1 with p 0
+   * is the single-head attention engine bit for bit. */
+  int attention_heads;
+  float attention_dropout;
   float learning_rate, weight_decay, beta1, beta2, eps;
   /* != 0: graph attention layers -- every layer's GraphSum is replaced by a single-head additive
    * attention over the node's neighbours (pgcn_gat_fwd, LeakyReLU slope 0.2) on the adjacency
@@ -420,7 +469,9 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
  * the normalised variables -- always 0); "attention_layers" (layers whose aggregation is graph
  * attention, pgcn_params.attention: n_layers or 0; on such an engine "reassociated", "eval_ax_us"
- * and "graphsum_lds" are 0); "knob.<key>" (the value of that pgcn_debug_set key the engine was
+ * and "graphsum_lds" are 0); "attention_heads" (the heads of its hidden attention layers,
+ * pgcn_params.attention_heads; 1 without attention) and "attention_dropout_layers" (layers that
+ * drop attention weights in training: n_layers with attention_dropout > 0, else 0); "knob.<key>" (the value of that pgcn_debug_set key the engine was
  * built with).
  * Returns the value (>= 0) or PGCN_E_INVALID for an unknown key. */
 long long pgcn_gcn_query(pgcn_gcn *g, const char *key);
@@ -509,6 +560,15 @@ int pgcn_checkpoint_flags(const char *path);
  * engine's; a weights-only load crosses it as it crosses bit 1 (a file without the tensor leaves
  * the engine's alone, a plain engine ignores a file's). */
 #define PGCN_CKPT_ATTENTION 8
+/* Host-only: the heads and the attention dropout of the engine that saved the file.  An attention
+ * engine with attention_heads > 1 or attention_dropout > 0 writes a version-5 file: the
+ * version-4 header and flags (bit 3 set), then 16 bytes {u32 heads; f32 attention_dropout; u64 0}
+ * between the header and the payload, under the checksum; the payload is version 4's (no tensor
+ * changes shape).  Files of versions 1-4 give 1 and 0.  A flags-0 load refuses a file whose heads
+ * or dropout differ from the engine's -- a version-4 file into such an engine and the reverse
+ * included; a weights-only load crosses it.  pgcn_checkpoint_info and pgcn_checkpoint_flags
+ * accept version 5.  Validates as pgcn_checkpoint_info does. */
+int pgcn_checkpoint_attention(const char *path, int *heads, float *dropout);
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
@@ -664,7 +724,8 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * X-stream kernels), "xs_nn" / "xs_tn" (register-streamed X-stream kernels), "gs_ring" (LDS ring
  * GraphSum), "gs_gather" (gather GraphSum), "out_xent" (output layer fused into the loss),
  * "gemm_nn" / "gemm_tn" (general MFMA GEMMs), "gat_fwd" / "gat_bwd" (graph attention forward /
- * backward calls, pgcn_gat_fwd / pgcn_gat_bwd), "launches" (every kernel launch of the library).
+ * backward calls, pgcn_gat_fwd / pgcn_gat_bwd and their _mh forms), "gat_heads" (those of them
+ * with heads > 1), "launches" (every kernel launch of the library).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

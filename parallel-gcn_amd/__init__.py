@@ -42,6 +42,7 @@ class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("hidden_dims", c_int * MAX_LAYERS),
                 ("dropouts", c_float * MAX_LAYERS), ("epochs", c_int), ("early_stopping", c_int),
+                ("attention_heads", c_int), ("attention_dropout", c_float),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
                 ("beta2", c_float), ("eps", c_float), ("attention", c_int),
                 ("reassociate_last", c_int),
@@ -126,6 +127,14 @@ _sig("pgcn_gat_bwd_workspace", c_size_t, c_void_p, c_int)
 _sig("pgcn_gat_bwd", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
      c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
      c_void_p, c_void_p)
+_sig("pgcn_gat_scores_mh", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+     c_void_p, c_void_p, c_void_p)
+_sig("pgcn_gat_fwd_mh", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
+     c_int, c_int, c_int, c_void_p, c_ll, c_float, c_void_p, c_void_p)
+_sig("pgcn_gat_bwd_workspace_mh", c_size_t, c_void_p, c_int, c_int)
+_sig("pgcn_gat_bwd_mh", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
+     c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+     c_void_p, c_ll, c_float, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -164,6 +173,7 @@ _sig("pgcn_gcn_save", c_int, c_void_p, ctypes.c_char_p)
 _sig("pgcn_gcn_load", c_int, c_void_p, ctypes.c_char_p, c_int)
 _sig("pgcn_checkpoint_info", c_int, ctypes.c_char_p, P(c_ll))
 _sig("pgcn_checkpoint_flags", c_int, ctypes.c_char_p)
+_sig("pgcn_checkpoint_attention", c_int, ctypes.c_char_p, P(c_int), P(c_float))
 _sig("pgcn_gcn_predict", c_ll, c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -238,7 +248,8 @@ def _ptr(a):
 
 
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
-                "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "launches")
+                "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
+                "launches")
 
 
 def path_counts(reset=False, thread=False):
@@ -395,10 +406,11 @@ def f1_scores(counts):
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
-                multilabel=False, attention=False):
+                multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0):
     p = PgcnParams()
     lib.pgcn_params_default(ctypes.byref(p))
     p.attention = 1 if attention else 0
+    p.attention_heads, p.attention_dropout = attention_heads, attention_dropout
     p.multilabel = 1 if multilabel else 0
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
@@ -683,6 +695,15 @@ def checkpoint_flags(path):
     return st
 
 
+def checkpoint_attention(path):
+    """Host-only: (heads, attention dropout) of the engine that saved the file -- a version-5
+    file's extension; (1, 0.0) for versions 1-4.  PgcnError(PGCN_E_IO) for an invalid file."""
+    heads, p = c_int(), c_float()
+    check(lib.pgcn_checkpoint_attention(os.fsencode(path), ctypes.byref(heads), ctypes.byref(p)),
+          f"checkpoint_attention {path}")
+    return heads.value, p.value
+
+
 def comm_unique_id():
     buf = ctypes.create_string_buffer(128)
     check(lib.pgcn_comm_unique_id(buf), "comm_unique_id")
@@ -760,7 +781,8 @@ EXPORTED = [
     "pgcn_layernorm_fwd", "pgcn_layernorm_bwd_workspace", "pgcn_layernorm_bwd",
     "pgcn_debug_layernorm_fwd_tail",
     "pgcn_gat_scores", "pgcn_gat_fwd", "pgcn_gat_bwd_workspace", "pgcn_gat_bwd",
-    "pgcn_checkpoint_flags", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
+    "pgcn_gat_scores_mh", "pgcn_gat_fwd_mh", "pgcn_gat_bwd_workspace_mh", "pgcn_gat_bwd_mh",
+    "pgcn_checkpoint_flags", "pgcn_checkpoint_attention", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
     "pgcn_adam_step_size", "pgcn_params_default", "pgcn_gcn_create", "pgcn_comm_unique_id",
     "pgcn_gcn_create_dist", "pgcn_gcn_create_peer", "pgcn_loopback_create",
     "pgcn_loopback_destroy",

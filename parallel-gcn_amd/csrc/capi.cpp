@@ -25,7 +25,7 @@ thread_local long long t_path_hits[KP_COUNT];  // the launching host thread's (l
 const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",   "xs_tn",
                                           "gs_ring",    "gs_gather",  "out_xent", "gemm_nn",
                                           "gemm_tn",    "gemm_nn_w",  "gemm_tn_w", "gat_fwd",
-                                          "gat_bwd",    "launches"};
+                                          "gat_bwd",    "gat_heads",  "launches"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -75,6 +75,8 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.layer_norm = p->layer_norm != 0;
   q.multilabel = p->multilabel != 0;
   q.attention = p->attention != 0;
+  q.attention_heads = p->attention_heads == 0 ? 1 : p->attention_heads;
+  q.attention_dropout = p->attention_dropout;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -530,6 +532,78 @@ int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
   });
 }
 
+namespace {
+// the head rules of the _mh entries, after check_gat_dims
+void check_gat_heads(int d, int heads) {
+  PGCN_CHECK(heads >= 1 && heads <= kGatMaxHeads, PGCN_E_INVALID, "gat: 1 <= heads <= 32");
+  PGCN_CHECK(gat_heads_ok(d, heads), PGCN_E_INVALID,
+             "gat: heads must divide d into widths of 4, 8, 16, 32, 64 or 128");
+}
+}  // namespace
+
+int pgcn_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
+                       const float *a_src, float *u, float *v, void *stream) {
+  return guarded([&] {
+    check_gat_dims(n, d, {ld_p});
+    check_gat_heads(d, heads);
+    PGCN_CHECK(n == 0 || (P && a_dst && a_src && u && v && aligned16(P)), PGCN_E_INVALID,
+               "gat_scores: null or misaligned argument");
+    if (n == 0) return;
+    check_device();
+    launch_gat_scores_mh(P, ld_p, n, d, heads, a_dst, a_src, u, v, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_gat_fwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, float *Z, int ld_z, int d, int heads, const uint64_t *drop_mask,
+                    long long drop_base, float drop_scale, float *alpha, void *stream) {
+  return guarded([&] {
+    check_gat_dims(0, d, {ld_p, ld_z});
+    check_gat_heads(d, heads);
+    PGCN_CHECK(!drop_mask || (alpha && drop_base >= 0), PGCN_E_INVALID,
+               "gat_fwd: a mask needs alpha (a training forward) and drop_base >= 0");
+    PGCN_CHECK(g && g->g && P && u && v && Z && aligned16(P) && aligned16(Z), PGCN_E_INVALID,
+               "gat_fwd: null or misaligned argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_fwd: square pattern");
+    check_device();
+    launch_gat_fwd_mh(g->g->gat_pattern(), P, ld_p, u, v, slope, Z, ld_z, d, heads, drop_mask,
+                      drop_base, drop_scale, alpha, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+size_t pgcn_gat_bwd_workspace_mh(const pgcn_graph *g, int d, int heads) {
+  if (!g || !g->g || heads > kGatMaxHeads || !gat_heads_ok(d, heads) ||
+      g->g->rows() != g->g->cols())
+    return 0;
+  size_t bytes = 0;
+  (void)guarded([&] { bytes = gat_bwd_workspace_mh(g->g->gat_pattern(), d, heads); });
+  return bytes;
+}
+
+int pgcn_gat_bwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                    int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                    int heads, const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                    float *da, void *workspace, void *stream) {
+  return guarded([&] {
+    check_gat_dims(0, d, {ld_p, ld_z, ld_g, ld_dp});
+    check_gat_heads(d, heads);
+    PGCN_CHECK(!drop_mask || drop_base >= 0, PGCN_E_INVALID, "gat_bwd: drop_base >= 0");
+    PGCN_CHECK(g && g->g && P && u && v && alpha && Z && G && a_dst && a_src && dP && da &&
+                   workspace && aligned16(P) && aligned16(Z) && aligned16(G) && aligned16(dP) &&
+                   aligned16(workspace),
+               PGCN_E_INVALID, "gat_bwd: null or misaligned argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_bwd: square pattern");
+    check_device();
+    launch_gat_bwd_mh(g->g->gat_pattern(), P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst,
+                      a_src, dP, ld_dp, d, heads, drop_mask, drop_base, drop_scale, da, workspace,
+                      as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -624,6 +698,8 @@ void pgcn_params_default(pgcn_params *p) {
   p->dropouts[1] = 0.5f;
   p->epochs = 100;
   p->early_stopping = 0;
+  p->attention_heads = 1;
+  p->attention_dropout = 0.0f;
   p->learning_rate = 0.01f;
   p->weight_decay = 5e-4f;
   p->beta1 = 0.9f;
@@ -773,6 +849,8 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   }
   if (!std::strcmp(key, "norm_layers")) return e.norm_layers();
   if (!std::strcmp(key, "attention_layers")) return e.attention_layers();
+  if (!std::strcmp(key, "attention_heads")) return e.attention_heads();
+  if (!std::strcmp(key, "attention_dropout_layers")) return e.attention_dropout_layers();
   if (!std::strcmp(key, "multilabel")) return e.get_params().multilabel ? 1 : 0;
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
@@ -872,6 +950,14 @@ int pgcn_checkpoint_flags(const char *path) {
     flags = (int)read_checkpoint(path).flags;
   });
   return st == PGCN_OK ? flags : st;
+}
+int pgcn_checkpoint_attention(const char *path, int *heads, float *dropout) {
+  return guarded([&] {
+    PGCN_CHECK(path && heads && dropout, PGCN_E_INVALID, "checkpoint_attention args");
+    const Checkpoint ck = read_checkpoint(path);
+    *heads = ck.heads;
+    *dropout = ck.attention_dropout;
+  });
 }
 int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }
 long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs) {

@@ -25,8 +25,24 @@ struct CkHeader {
 };
 static_assert(sizeof(CkHeader) == 216, "checkpoint header layout");
 
+// version 5: between the header and the payload
+struct CkHeadsExt {
+  uint32_t heads;
+  float attention_dropout;
+  uint64_t zero;
+};
+static_assert(sizeof(CkHeadsExt) == 16, "checkpoint extension layout");
+
+CkHeadsExt heads_ext(const Checkpoint &ck) {
+  return CkHeadsExt{(uint32_t)ck.heads, ck.attention_dropout, 0};
+}
+
 uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
   uint64_t x = fnv1a(kFnvBasis, &h, offsetof(CkHeader, checksum));
+  if (h.version == (uint32_t)kCheckpointVersionHeads) {
+    const CkHeadsExt e = heads_ext(ck);
+    x = fnv1a(x, &e, sizeof e);
+  }
   for (const auto *vec : {&ck.results, &ck.w, &ck.m, &ck.v})
     x = fnv1a(x, vec->data(), vec->size() * sizeof(float));
   return x;
@@ -68,7 +84,8 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
   if (version == (uint32_t)kCheckpointVersionLayerNormMultilabel)
     return (flags & kCheckpointLayerNorm) && (flags & kCheckpointMultilabel) &&
            (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm)) == 0;
-  if (version == (uint32_t)kCheckpointVersionAttention)
+  if (version == (uint32_t)kCheckpointVersionAttention ||
+      version == (uint32_t)kCheckpointVersionHeads)
     return (flags & kCheckpointAttention) &&
            (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm | kCheckpointAttention)) == 0;
   return false;
@@ -78,6 +95,18 @@ long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags) {
   return weight_count(dims, n_layers) +
          ((flags & kCheckpointLayerNorm) ? norm_count_of(dims, n_layers) : 0) +
          ((flags & kCheckpointAttention) ? attn_count_of(dims, n_layers) : 0);
+}
+
+// the extension's values against the file's version and hidden dims (the engine's own rules)
+bool heads_ok(uint32_t version, const int32_t *dims, int n_layers, long long heads, float p) {
+  if (version != (uint32_t)kCheckpointVersionHeads) return heads == 1 && p == 0.0f;
+  if (heads < 1 || heads > 32 || !(p >= 0.0f && p < 1.0f) || (heads == 1 && p == 0.0f))
+    return false;
+  for (int l = 1; heads > 1 && l < n_layers; l++) {
+    const long long dh = dims[l] / heads;
+    if (dims[l] % heads != 0 || dh < 4 || dh > 128 || (dh & (dh - 1)) != 0) return false;
+  }
+  return true;
 }
 }  // namespace
 
@@ -107,11 +136,17 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   h.n_weights = (int64_t)ck.w.size();
   PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags), PGCN_E_INVALID,
              "checkpoint: weight count does not match the layer dims");
+  PGCN_CHECK(heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout), PGCN_E_INVALID,
+             "checkpoint: heads / attention dropout do not match the file's version");
+  const CkHeadsExt ext = heads_ext(ck);
+  const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads;
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
   std::FILE *f = std::fopen(tmp.c_str(), "wb");
   if (!f) throw Error(PGCN_E_IO, "checkpoint: cannot write " + tmp);
-  bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1 && write_floats(f, ck.results) &&
+  bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1 &&
+            (!with_ext || std::fwrite(&ext, sizeof(ext), 1, f) == 1) &&
+            write_floats(f, ck.results) &&
             write_floats(f, ck.w) && write_floats(f, ck.m) && write_floats(f, ck.v);
   ok = (std::fclose(f) == 0) && ok;
   if (ok) ok = std::rename(tmp.c_str(), path.c_str()) == 0;  // readers never see a partial file
@@ -134,6 +169,13 @@ Checkpoint read_checkpoint(const std::string &path) {
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
        h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
        h.n_weights == expected_weights(h.dims, L, h.flags) && h.n_weights < (1LL << 31);
+  if (ok && h.version == (uint32_t)kCheckpointVersionHeads) {
+    CkHeadsExt e{};
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.heads <= 32;
+    ck.heads = (int)e.heads;
+    ck.attention_dropout = e.attention_dropout;
+  }
+  ok = ok && heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout);
   ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
        read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);
   ok = ok && std::fgetc(f) == EOF;  // nothing trailing

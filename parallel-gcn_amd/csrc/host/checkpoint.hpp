@@ -24,7 +24,16 @@
 // attention tensor (per layer a_dst then a_src, 2 * (sum of the hidden dims + output dim) floats)
 // last, behind the scale / shift tensor when bit 1 is set.  Every other engine keeps writing
 // versions 1-3 byte for byte; there bit 3 stays unknown.
-// checksum = FNV-1a 64 of the header's bytes before it, continued over the payload.
+// Version 5 = saved by an attention engine with several heads or attention dropout
+// (pgcn_params.attention_heads > 1 or attention_dropout > 0): the version-4 header and flags
+// (bit 3 set), then a 16-byte extension between the header and the payload,
+//   extension  u32 heads; f32 attention_dropout; u64 0
+// with heads in [1, 32] dividing every hidden dim into head widths of 4 .. 128 (a power of two),
+// attention_dropout in [0, 1), not both at their defaults (1 and 0: that engine writes version
+// 4), and the last word 0.  The tensors keep their shapes, so the payload is version 4's.  Every
+// other engine keeps writing versions 1-4 byte for byte.
+// checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (version
+// 5) and the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
 // stored and the file does not depend on the world size.  Nothing newer than the reference:
@@ -44,6 +53,7 @@ constexpr unsigned kCheckpointMultilabel = 4u;  // header flags, bit 2 (versions
 constexpr int kCheckpointVersionLayerNormMultilabel = 3;  // version 2's layout with bits 1 and 2
 constexpr unsigned kCheckpointAttention = 8u;  // header flags, bit 3 (version 4 only)
 constexpr int kCheckpointVersionAttention = 4;  // bits 0-3 known, bit 3 set
+constexpr int kCheckpointVersionHeads = 5;  // version 4 + the {heads, attention_dropout} extension
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -55,6 +65,9 @@ struct Checkpoint {
   std::vector<float> dropouts;  // n_layers
   unsigned seed = 0;
   unsigned flags = 0;  // kCheckpoint* bits
+  // version 5's extension; 1 and 0 in every other version
+  int heads = 1;
+  float attention_dropout = 0.0f;
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

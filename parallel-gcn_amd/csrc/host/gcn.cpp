@@ -295,6 +295,16 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
     for (int h : params.hidden_dims)
       PGCN_CHECK(h <= kGatMaxWidth, PGCN_E_INVALID, "attention: hidden dims up to 128");
   }
+  PGCN_CHECK(params.attention_heads >= 1 && params.attention_heads <= kGatMaxHeads,
+             PGCN_E_INVALID, "attention_heads must be in [1,32]");
+  PGCN_CHECK(params.attention_dropout >= 0.0f && params.attention_dropout < 1.0f, PGCN_E_INVALID,
+             "attention_dropout must be in [0,1)");
+  PGCN_CHECK(params.attention || (params.attention_heads == 1 && params.attention_dropout == 0.0f),
+             PGCN_E_INVALID, "attention_heads / attention_dropout need attention != 0");
+  for (int h : params.hidden_dims)
+    PGCN_CHECK(gat_heads_ok(std::min(h, kGatMaxWidth), params.attention_heads), PGCN_E_INVALID,
+               "attention_heads must divide every hidden width into head widths of 4, 8, 16, 32, "
+               "64 or 128");
   int lo_prio = 0, hi_prio = 0;
   PGCN_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
   stream = Stream::create(hi_prio);  // the reference uses High priority streams
@@ -369,6 +379,12 @@ void GCN::init_dropout_rng(const GCNData &data, long long glorot_draws) {
   // draws per training epoch: the input dropout (nnz_X) then each hidden dropout (N*h_l)
   unsigned long long period = (unsigned long long)nnz_x_global;
   for (int l = 1; l < L; l++) period += (unsigned long long)N * dims[(size_t)l];
+  // ... then (attention_dropout > 0) each attention layer's weights, nnz * K_l: behind every
+  // Dropout's draws, so those keep their offsets inside the epoch and only the period grows
+  const bool attn_drop = params.attention && params.attention_dropout > 0.0f;
+  const unsigned long long nnz_a = (unsigned long long)data.graph.indices.size();
+  if (attn_drop)
+    for (int l = 0; l < L; l++) period += nnz_a * (unsigned long long)layer_heads(l);
   draw_period = period;
   this->glorot_draws = glorot_draws;
   std::vector<uint64_t> table(16 * 256 * 2);
@@ -395,6 +411,13 @@ void GCN::init_dropout_rng(const GCNData &data, long long glorot_draws) {
     offset += (l == 0) ? (unsigned long long)nnz_x_global
                        : (unsigned long long)N * dims[(size_t)l];
   }
+  for (int l = 0; attn_drop && l < L; l++) {  // (single GPU: the whole range)
+    auto r = std::make_shared<DropoutRng>();
+    const unsigned long long count = nnz_a * (unsigned long long)layer_heads(l);
+    init_dropout_rng_range(*r, seed, offset, 0, (long long)count, knobs_.mask_per);
+    attn_rngs.push_back(r);
+    offset += count;
+  }
 }
 
 // The chunk states of every dropout as after `epochs` training forwards (each consumes exactly
@@ -414,6 +437,13 @@ void GCN::reseed_dropout(long long epochs) {
     offset += (unsigned long long)(l == 0 ? nnz_x_global
                                           : (long long)params.num_nodes *
                                                 params.hidden_dims[(size_t)l - 1]);
+  }
+  for (const auto &rp : attn_rngs) {  // the attention masks' ranges, behind them
+    DropoutRng &r = *rp;
+    const std::vector<uint64_t> st = dropout_states(r, seed, offset);
+    PGCN_CHECK(st.size() == r.states.size(), PGCN_E_INVALID, "dropout states changed size");
+    r.states.upload(st);
+    offset += (unsigned long long)r.elem_end;
   }
   draw_epochs = epochs;
 }
@@ -888,8 +918,9 @@ void GCN::insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<
   long long off = 0;
   for (int l = 0; l < layer; l++)
     off += 2LL * (l == L - 1 ? params.output_dim : params.hidden_dims[(size_t)l]);
-  modules.push_back(
-      std::make_unique<GraphAttention>(var1, var2, graph.get(), dim, attn_var, off));
+  modules.push_back(std::make_unique<GraphAttention>(
+      var1, var2, graph.get(), dim, attn_var, off, layer_heads(layer), params.attention_dropout,
+      attn_rngs.empty() ? nullptr : attn_rngs[(size_t)layer], &ctx));
 }
 
 // layer_norm: the LayerNorm of hidden layer `layer` on its var2, right behind its GraphSum (and
@@ -1604,6 +1635,11 @@ void GCN::save(const std::string &path) {
   if (attn_var) {  // version 4: the attention tensor last
     ck.flags |= kCheckpointAttention;
     ck.version = kCheckpointVersionAttention;
+    if (params.attention_heads > 1 || params.attention_dropout > 0.0f) {  // version 5
+      ck.version = kCheckpointVersionHeads;
+      ck.heads = params.attention_heads;
+      ck.attention_dropout = params.attention_dropout;
+    }
   }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
@@ -1630,7 +1666,11 @@ void GCN::load(const std::string &path, int flags) {
     same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty() &&
            !(ck.flags & kCheckpointLayerNorm) == !norm_var &&
            !(ck.flags & kCheckpointMultilabel) == !params.multilabel &&
-           !(ck.flags & kCheckpointAttention) == !attn_var;
+           !(ck.flags & kCheckpointAttention) == !attn_var &&
+           // (versions 1-4 read as 1 head, no attention dropout; a weights-only load crosses
+           // this too: the tensors have the same shapes)
+           ck.heads == params.attention_heads &&
+           ck.attention_dropout == params.attention_dropout;
     for (int l = 0; same && l < L; l++) same = ck.dropouts[(size_t)l] == params.dropouts[(size_t)l];
   }
   PGCN_CHECK(same, PGCN_E_INVALID, "load: the checkpoint is for another model");

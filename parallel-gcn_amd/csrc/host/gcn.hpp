@@ -49,6 +49,11 @@ struct GCNParams {
   // every layer's GraphSum is a GraphAttention (module.hpp) on the pattern as loaded; its
   // attention vectors are one more weight (no decay), the last of all.  Single GPU, widths <= 128
   bool attention = false;
+  // ... its hidden layers with this many heads concatenated inside their widths (the output
+  // layer keeps one), and dropout on every attention layer's normalised weights (p > 0: one
+  // DropoutRng per layer behind the Dropout modules' in the epoch's draws, init_dropout_rng)
+  int attention_heads = 1;
+  float attention_dropout = 0.0f;
 };
 
 struct AdamParams {
@@ -167,6 +172,9 @@ class GCN {
   int fused_residuals() const;
   int norm_layers() const { return (int)norms_.size(); }
   int attention_layers() const { return attn_var ? L : 0; }
+  // the heads of its hidden layers, and the layers that drop attention weights in training
+  int attention_heads() const { return attn_var ? params.attention_heads : 1; }
+  int attention_dropout_layers() const { return (int)attn_rngs.size(); }
   // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
   int fused_norm_tails() const;
   // diagnostics (syncs): non-zero elements in the edge-cut padding rows of the variables the
@@ -274,6 +282,10 @@ class GCN {
   std::vector<shared_ptr<Variable>> weights;
   std::vector<bool> decays;
   std::vector<shared_ptr<DropoutRng>> rngs;  // [0] input, then one per hidden layer
+  // attention_dropout > 0: one per attention layer (nnz * K_l weights), behind rngs in the epoch
+  std::vector<shared_ptr<DropoutRng>> attn_rngs;
+  // the heads of layer l's attention: the output layer keeps one
+  int layer_heads(int l) const { return l == L - 1 ? 1 : params.attention_heads; }
   std::vector<const Dropout *> dropouts_;
   Adam optimizer;
   DeviceBuffer<float> tn_pool;  // tn_fold: the deferred reduction passes' inputs

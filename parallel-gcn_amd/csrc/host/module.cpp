@@ -688,28 +688,41 @@ void GraphSum::backward(const Stream &s) const {
 // ------------------------------------------------------------------------------------------
 GraphAttention::GraphAttention(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
                                DevGraph *graph_, int dim_, shared_ptr<Variable> attn_,
-                               long long offset_)
+                               long long offset_, int heads_, float p_,
+                               shared_ptr<DropoutRng> rng_, ModuleContext *ctx_)
     : in(std::move(in_)), out(std::move(out_)), attn(std::move(attn_)), graph(graph_), dim(dim_),
-      offset(offset_) {
+      offset(offset_), heads(heads_), p(p_), rng(std::move(rng_)), ctx(ctx_) {
   PGCN_CHECK(in && out && attn && graph && dim >= 1 && dim <= kGatMaxWidth && in->cols == dim &&
                  out->cols == dim && graph->rows() == graph->cols() && in->rows >= graph->rows() &&
                  out->rows >= graph->rows() && offset >= 0 && offset + 2LL * dim <= attn->size,
              PGCN_E_INVALID, "attention: widths up to 128 on a square pattern");
-  const GatPattern &p = graph->gat_pattern();  // (host build and upload: now, not in an epoch)
-  u.allocate((size_t)std::max(p.n, 1));
-  v.allocate((size_t)std::max(p.n, 1));
-  alpha.allocate((size_t)std::max<long long>(p.nnz, 1));
-  ws.allocate(std::max<size_t>(gat_bwd_workspace(p, dim) / sizeof(float), 4));
-  z.allocate((size_t)std::max(p.n, 1) * out->ld);
+  PGCN_CHECK(gat_heads_ok(dim, heads) && heads <= kGatMaxHeads, PGCN_E_INVALID,
+             "attention: heads must divide the width into head widths of 4, 8, 16, 32, 64 or 128");
+  PGCN_CHECK(p >= 0.0f && p < 1.0f && (p > 0.0f) == (rng != nullptr) && (!rng || ctx),
+             PGCN_E_INVALID, "attention: dropout in [0, 1), with its mask stream");
+  const GatPattern &g = graph->gat_pattern();  // (host build and upload: now, not in an epoch)
+  PGCN_CHECK(!rng || (rng->elem_begin == 0 && rng->elem_end == g.nnz * heads), PGCN_E_INVALID,
+             "attention: the mask stream covers nnz * heads weights");
+  u.allocate((size_t)std::max(g.n, 1) * heads);
+  v.allocate((size_t)std::max(g.n, 1) * heads);
+  alpha.allocate((size_t)std::max<long long>(g.nnz, 1) * heads);
+  ws.allocate(std::max<size_t>(gat_bwd_workspace_mh(g, dim, heads) / sizeof(float), 4));
+  z.allocate((size_t)std::max(g.n, 1) * out->ld);
   for (const auto *b : {&u, &v, &alpha, &ws, &z}) b->zero();
 }
 
 void GraphAttention::forward(bool training, const Stream &s) const {
   const GatPattern &p = graph->gat_pattern();
   const float *a = attn->dev_data.get() + offset;
-  launch_gat_scores(in->dev_data.get(), in->ld, p.n, dim, a, a + dim, u.get(), v.get(), s.get());
-  launch_gat_fwd(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, out->dev_data.get(),
-                 out->ld, dim, training ? alpha.get() : nullptr, s.get());
+  const bool drop = training && rng;
+  if (drop)  // this epoch's mask of the layer: the stream moves on by one period per draw
+    launch_dropout_mask(rng->states.get(), rng->n_chunks, 64 * rng->chunk_lo, rng->elem_end,
+                        this->p, rng->mask.get(), ctx->jump_table, s.get(), 0, rng->per);
+  launch_gat_scores_mh(in->dev_data.get(), in->ld, p.n, dim, heads, a, a + dim, u.get(), v.get(),
+                       s.get());
+  launch_gat_fwd_mh(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, out->dev_data.get(),
+                    out->ld, dim, heads, drop ? rng->mask.get() : nullptr, drop ? rng->mask_base : 0,
+                    scale(), training ? alpha.get() : nullptr, s.get());
   if (training && p.n > 0)
     PGCN_HIP(hipMemcpyAsync(z.get(), out->dev_data.get(), sizeof(float) * (size_t)p.n * out->ld,
                             hipMemcpyDeviceToDevice, s.get()));
@@ -721,9 +734,11 @@ void GraphAttention::backward(const Stream &s) const {
   const float *a = attn->dev_data.get() + offset;
   // (a residual layer's out.grad stays unmasked: its ReLU backward wrote dev_grad_z)
   const float *g = out->dev_grad_z ? out->dev_grad_z.get() : out->dev_grad.get();
-  launch_gat_bwd(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, alpha.get(), z.get(),
-                 out->ld, g, out->ld, a, a + dim, in->dev_grad.get(), in->ld,
-                 dim, attn->dev_grad.get() + offset, ws.get(), s.get());
+  // (the mask of the training forward this backward belongs to)
+  launch_gat_bwd_mh(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, alpha.get(), z.get(),
+                    out->ld, g, out->ld, a, a + dim, in->dev_grad.get(), in->ld, dim, heads,
+                    rng ? rng->mask.get() : nullptr, rng ? rng->mask_base : 0, scale(),
+                    attn->dev_grad.get() + offset, ws.get(), s.get());
 }
 
 // ------------------------------------------------------------------------------------------

@@ -348,22 +348,36 @@ class GraphSum : public Module {
 // only.  It owns u, v, alpha, the backward's workspace (dx per slot, du, dv, partials) and a copy
 // of Z as the training forward wrote it: the modules behind it (LayerNorm, ReLU, the residual add,
 // Dropout, the loss's max shift) rewrite `out` in place, and the backward needs G_i . Z_i.
+// `heads` heads are concatenated inside dim (head h: columns [h dim / heads, ...), its slice of
+// a_dst / a_src; u, v [n][heads], alpha [nnz][heads]).  With `rng` (attention dropout p > 0; its
+// range is the nnz * heads weights, element s * heads + h) a training forward draws the layer's
+// mask itself, one launch on its own stream right before its kernels -- never ahead, never with
+// another module's draw -- and the forward and the backward apply it with scale 1 / (1 - p);
+// alpha keeps the weights before dropout.  heads == 1 without rng: the single-head kernels.
 class GraphAttention : public Module {
   shared_ptr<Variable> in, out, attn;
   DevGraph *graph;
   int dim;
   long long offset;
+  int heads;
+  float p;
+  shared_ptr<DropoutRng> rng;
+  ModuleContext *ctx;
   DeviceBuffer<float> u, v, alpha, ws, z;
 
  public:
   static constexpr float kSlope = 0.2f;
   GraphAttention(shared_ptr<Variable> in_, shared_ptr<Variable> out_, DevGraph *graph_, int dim_,
-                 shared_ptr<Variable> attn_, long long offset_);
+                 shared_ptr<Variable> attn_, long long offset_, int heads_ = 1, float p_ = 0.0f,
+                 shared_ptr<DropoutRng> rng_ = nullptr, ModuleContext *ctx_ = nullptr);
   void forward(bool training, const Stream &s) const override;
   void backward(const Stream &s) const override;
   const Variable *input() const { return in.get(); }
   const Variable *output() const { return out.get(); }
   int width() const { return dim; }
+  int head_count() const { return heads; }
+  const DropoutRng *mask_state() const { return rng.get(); }
+  float scale() const { return 1.0f / (1.0f - p); }
 };
 
 // include/module.cuh:90-99

@@ -21,6 +21,9 @@
 //   summed from dx by the column pass (the wave of column i).
 // da_dst / da_src go through per-workgroup partials and one reducing launch (the shape of
 // k_layernorm_bwd).  Every order depends on the pattern and d only: bit-reproducible.
+//
+// Several heads inside d and dropout on the attention weights are the *_mh kernels in the second
+// half of this file: the same passes with a head axis (their layout is described there).
 #include <algorithm>
 
 #include "common.hpp"
@@ -529,6 +532,527 @@ void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *
                  du, dv, col_ws);
   const int nb = gat_da_blocks(g.n, d), ldp = (d + 3) / 4 * 4;
   GAT_DISPATCH(k_gat_da, dim3((unsigned)nb), s, P, ld_p, g.n, d, du, dv, partial, ldp);
+  PGCN_LAUNCH(k_gat_da_reduce, dim3((unsigned)ceil_div(2 * ldp, kGatThreads)), dim3(kGatThreads),
+              0, s, partial, nb, ldp, d, da);
+}
+
+// ---- several heads, dropout on the attention weights ------------------------------------------
+// Head h owns columns [h dh, (h + 1) dh) with dh = d / K in {4 .. 128}: the hl = dh / 4 lanes
+// [h hl, (h + 1) hl) of every GL-lane neighbour group, so a lane's float4 belongs to one head
+// and the dot products (u, v, t, c) are butterflies over the lane offsets below hl.  u, v are
+// [n][K], alpha, dx and the mask bits [nnz][K].  A row's per-head maximum and exponent sum are
+// taken in the gather layout (group q over slots q, q + 64 / GL, ..., then the offsets GL .. 32):
+// one pass over the row's index serves every head.  A segment's partial is {max[32], sum[32],
+// row[128]} (forward) / {dv[32], -, row[128]} (column pass).
+// ONE = a single head over any d in 1..128 (the output layer under attention dropout): the
+// single-head kernels' statements and summation orders with the mask factor put in, so an
+// all-ones mask of scale 1 gives their bits.
+namespace {
+struct GatDrop {
+  const uint64_t *mask;  // bit base + s K + h: the weight of slot s, head h is kept; null: all
+  long long base;
+  float scale;
+};
+
+// the factor m'_s^h: 1 without a mask
+__device__ __forceinline__ float drop_factor(const GatDrop &dr, long long e) {
+  if (!dr.mask) return 1.0f;
+  const long long b = dr.base + e;
+  return (dr.mask[b >> 6] >> (b & 63)) & 1ull ? dr.scale : 0.0f;
+}
+
+// sum over the hl lanes of a head (hl a power of two <= GL; ONE: the whole group, group_sum's
+// order)
+template <int GL, bool ONE>
+__device__ __forceinline__ float head_sum(float v, int hl) {
+  if constexpr (ONE) return group_sum<GL>(v);
+  for (int off = hl >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <int GL>
+__device__ __forceinline__ float across_groups_max(float v) {
+#pragma unroll
+  for (int off = GL; off < 64; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// a lane's place: its head (clamped on the idle lanes past column d, which store nothing) and
+// whether it writes its head's scalars
+template <int GL, bool ONE>
+struct HeadLane {
+  int q, li, c0, hd;
+  bool lead;
+  __device__ HeadLane(int lane, int d, int K, int hl) {
+    q = lane / GL;
+    li = lane % GL;
+    c0 = 4 * li;
+    hd = ONE ? 0 : min(li / hl, K - 1);
+    lead = ONE ? li == 0 : (li % hl == 0 && c0 < d);
+  }
+};
+
+// this lane's head over slots [b, e) of row i's index list: the score maximum and the sum of
+// exp(score - max); every lane of the wave takes part
+template <int GL, bool ONE>
+__device__ __forceinline__ void slot_stats_mh(const int *__restrict__ idx,
+                                              const float *__restrict__ v, int K, int hd, float ui,
+                                              float slope, int b, int e, int lane, float *m,
+                                              float *s) {
+  if constexpr (ONE) {
+    slot_stats(idx, v, ui, slope, b, e, lane, m, s);
+  } else {
+    constexpr int NB = kWave / GL;
+    const int q = lane / GL;
+    float mx = -INFINITY;
+    for (int k = b + q; k < e; k += NB)
+      mx = fmaxf(mx, leaky(ui + v[(long long)idx[k] * K + hd], slope));
+    mx = across_groups_max<GL>(mx);
+    float sm = 0.0f;
+    for (int k = b + q; k < e; k += NB)
+      sm += expf(leaky(ui + v[(long long)idx[k] * K + hd], slope) - mx);
+    *m = mx;
+    *s = across_groups<GL>(sm);
+  }
+}
+
+// slot_gather with the head's own {ui, m, s} per lane and the mask factor on the summed weight;
+// alpha (or null) takes the weight before dropout
+template <int GL, bool ONE>
+__device__ __forceinline__ float4 slot_gather_mh(const float *__restrict__ P, int ld_p, int d,
+                                                 const int *__restrict__ idx,
+                                                 const float *__restrict__ v, int K,
+                                                 const HeadLane<GL, ONE> &hl, float ui, float slope,
+                                                 int b, int e, float m, float s, float *alpha,
+                                                 const GatDrop &dr) {
+  constexpr int NB = kWave / GL;
+  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 2
+  for (int k = b + hl.q; k < e; k += NB) {
+    const int j = idx[k];
+    const long long eh = (long long)k * K + hl.hd;
+    const float w = expf(leaky(ui + v[(long long)j * K + hl.hd], slope) - m) / s;
+    if (alpha && hl.lead) alpha[eh] = w;
+    axpy4(acc, dr.mask ? w * drop_factor(dr, eh) : w,
+          row4(P + (long long)j * ld_p, hl.c0, d, hl.c0 < d));
+  }
+  return across_groups4<GL>(acc);
+}
+}  // namespace
+
+// u[i][h] = P_i[h] . a_dst[h], v[i][h] = P_i[h] . a_src[h]
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_scores_mh(
+    const float *__restrict__ P, int ld_p, int n, int d, int K, int hl,
+    const float *__restrict__ a_dst, const float *__restrict__ a_src, float *__restrict__ u,
+    float *__restrict__ v) {
+  constexpr int RPB = kGatThreads / GL;
+  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
+  const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
+  for (long long base = (long long)blockIdx.x * RPB; base < n; base += (long long)gridDim.x * RPB) {
+    const long long r = base + grp;
+    const bool live = r < n;
+    const float4 p = row4(P + r * ld_p, c0, d, live && c0 < d);
+    const float su = head_sum<GL, false>(dot4(p, ad), hl);
+    const float sv = head_sum<GL, false>(dot4(p, as), hl);
+    if (live && c0 < d && li % hl == 0) {
+      u[r * K + li / hl] = su;
+      v[r * K + li / hl] = sv;
+    }
+  }
+}
+
+template <int GL, bool ONE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_mh(
+    const GatPattern g, const float *__restrict__ P, int ld_p, const float *__restrict__ u,
+    const float *__restrict__ v, float slope, float *__restrict__ Z, int ld_z, int d, int K,
+    int hlanes, float *__restrict__ alpha, const GatDrop dr) {
+  const int lane = threadIdx.x % kWave;
+  const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
+  const int c0 = hl.c0;
+  const long long items = (long long)g.n + g.n_row_segs;
+  for (long long it = first_item(); it < items; it += item_stride()) {
+    if (it < g.n) {
+      const int i = (int)it, b = g.indptr[i], e = g.indptr[i + 1];
+      if (e - b > kGatSeg) continue;
+      float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (e > b) {
+        const float ui = u[(long long)i * K + hl.hd];
+        float m, s;
+        slot_stats_mh<GL, ONE>(g.indices, v, K, hl.hd, ui, slope, b, e, lane, &m, &s);
+        z = slot_gather_mh<GL, ONE>(P, ld_p, d, g.indices, v, K, hl, ui, slope, b, e, m, s, alpha,
+                                    dr);
+      }
+      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
+    } else {
+      const long long t = it - g.n;
+      const int4 sg = g.row_segs[t];
+      const float ui = u[(long long)sg.x * K + hl.hd];
+      float m, s;
+      slot_stats_mh<GL, ONE>(g.indices, v, K, hl.hd, ui, slope, sg.y, sg.z, lane, &m, &s);
+      const float4 z = slot_gather_mh<GL, ONE>(P, ld_p, d, g.indices, v, K, hl, ui, slope, sg.y,
+                                               sg.z, m, 1.0f, nullptr, dr);
+      float *ws = g.row_ws + t * kGatWsStrideMh;
+      if (lane < GL && hl.lead) {
+        ws[hl.hd] = m;
+        ws[kGatMaxHeads + hl.hd] = s;
+      }
+      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 2 * kGatMaxHeads + c0) = z;
+    }
+  }
+}
+
+template <int GL, bool ONE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_merge_mh(
+    const GatPattern g, const float *__restrict__ u, const float *__restrict__ v, float slope,
+    float *__restrict__ Z, int ld_z, int d, int K, int hlanes, float *__restrict__ alpha) {
+  constexpr int NB = kWave / GL;
+  const int lane = threadIdx.x % kWave;
+  const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
+  const int c0 = hl.c0;
+  for (long long t = first_item(); t < g.n_row_segs; t += item_stride()) {
+    const int4 sg = g.row_segs[t];
+    const int i = sg.x, first = sg.w;
+    const int nseg = (g.indptr[i + 1] - g.indptr[i] + kGatSeg - 1) / kGatSeg;
+    const float *ws = g.row_ws + (long long)first * kGatWsStrideMh + hl.hd;
+    float m = -INFINITY;
+    for (int k = 0; k < nseg; k++) m = fmaxf(m, ws[(long long)k * kGatWsStrideMh]);
+    float s = 0.0f;
+    for (int k = 0; k < nseg; k++)
+      s += ws[(long long)k * kGatWsStrideMh + kGatMaxHeads] *
+           expf(ws[(long long)k * kGatWsStrideMh] - m);
+    if (alpha) {
+      const float ui = u[(long long)i * K + hl.hd];
+      if constexpr (ONE) {
+        for (int k = sg.y + lane; k < sg.z; k += kWave)
+          alpha[k] = expf(leaky(ui + v[g.indices[k]], slope) - m) / s;
+      } else {
+        for (int k = sg.y + hl.q; k < sg.z; k += NB)
+          if (hl.lead)
+            alpha[(long long)k * K + hl.hd] =
+                expf(leaky(ui + v[(long long)g.indices[k] * K + hl.hd], slope) - m) / s;
+      }
+    }
+    if (t == first && lane < GL && c0 < d) {
+      float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      for (int k = 0; k < nseg; k++) {
+        const float *w = ws + (long long)k * kGatWsStrideMh;
+        axpy4(z, expf(w[0] - m),
+              *reinterpret_cast<const float4 *>(w - hl.hd + 2 * kGatMaxHeads + c0));
+      }
+      z.x /= s;
+      z.y /= s;
+      z.z /= s;
+      z.w /= s;
+      *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
+    }
+  }
+}
+
+// dx_s^h = alpha_s^h (m'_s^h G_i[h] . P_j[h] - G_i[h] . Z_i[h]) leaky'(u_i^h + v_j^h)
+template <int GL, bool ONE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_rows_mh(
+    const GatPattern g, const float *__restrict__ P, int ld_p, const float *__restrict__ u,
+    const float *__restrict__ v, float slope, const float *__restrict__ alpha,
+    const float *__restrict__ Z, int ld_z, const float *__restrict__ G, int ld_g, int d, int K,
+    int hlanes, const GatDrop dr, float *__restrict__ dx) {
+  constexpr int NB = kWave / GL;
+  const int lane = threadIdx.x % kWave;
+  const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
+  const int c0 = hl.c0;
+  const long long items = (long long)g.n + g.n_row_segs;
+  for (long long it = first_item(); it < items; it += item_stride()) {
+    int i, b, e;
+    if (it < g.n) {
+      i = (int)it;
+      b = g.indptr[i];
+      e = g.indptr[i + 1];
+      if (e - b > kGatSeg) continue;
+    } else {
+      const int4 sg = g.row_segs[it - g.n];
+      i = sg.x;
+      b = sg.y;
+      e = sg.z;
+    }
+    if (e <= b) continue;
+    const float4 gi = row4(G + (long long)i * ld_g, c0, d, c0 < d);
+    const float4 zi = row4(Z + (long long)i * ld_z, c0, d, c0 < d);
+    const float c = head_sum<GL, ONE>(dot4(gi, zi), hlanes), ui = u[(long long)i * K + hl.hd];
+    // (the same trip count for every group: the head sums run under uniform control flow)
+    for (int k0 = b; k0 < e; k0 += NB) {
+      const int k = k0 + hl.q;
+      const bool on = k < e;
+      const int j = on ? g.indices[k] : i;
+      float t = head_sum<GL, ONE>(
+          dot4(gi, row4(P + (long long)j * ld_p, c0, d, on && c0 < d)), hlanes);
+      if (on && hl.lead) {
+        const long long eh = (long long)k * K + hl.hd;
+        if (dr.mask) t = drop_factor(dr, eh) * t;
+        dx[eh] = alpha[eh] * (t - c) * (ui + v[(long long)j * K + hl.hd] > 0.0f ? 1.0f : slope);
+      }
+    }
+  }
+}
+
+// col_gather per head: acc = sum alpha_s^h m'_s^h G_row[h], dv^h = sum dx_s^h
+template <int GL, bool ONE>
+__device__ __forceinline__ float4 col_gather_mh(const GatPattern &g,
+                                                const float *__restrict__ alpha,
+                                                const float *__restrict__ dx,
+                                                const float *__restrict__ G, int ld_g, int d, int K,
+                                                const HeadLane<GL, ONE> &hl, const GatDrop &dr,
+                                                int b, int e, float *dv_out) {
+  constexpr int NB = kWave / GL;
+  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float dv = 0.0f;
+#pragma unroll 2
+  for (int o = b + hl.q; o < e; o += NB) {
+    const int r = g.csc_row[o];
+    const long long eh = (long long)g.csc_pos[o] * K + hl.hd;
+    axpy4(acc, dr.mask ? alpha[eh] * drop_factor(dr, eh) : alpha[eh],
+          row4(G + (long long)r * ld_g, hl.c0, d, hl.c0 < d));
+    dv += dx[eh];
+  }
+  *dv_out = across_groups<GL>(dv);
+  return across_groups4<GL>(acc);
+}
+
+// the final write of column j: du_j^h from row j's dx, then dP_j = acc + du a_dst + dv a_src
+template <int GL, bool ONE>
+__device__ __forceinline__ void col_finish_mh(const GatPattern &g, int j, float4 acc, float dv,
+                                              const float *__restrict__ dx,
+                                              const float *__restrict__ a_dst,
+                                              const float *__restrict__ a_src, int d, int K,
+                                              const HeadLane<GL, ONE> &hl,
+                                              float *__restrict__ dP, int ld_dp,
+                                              float *__restrict__ du_out,
+                                              float *__restrict__ dv_out, int lane) {
+  constexpr int NB = kWave / GL;
+  const int c0 = hl.c0;
+  float du = 0.0f;
+  if constexpr (ONE) {
+    for (int k = g.indptr[j] + lane; k < g.indptr[j + 1]; k += kWave) du += dx[k];
+    du = wave_sum(du);
+  } else {
+    for (int k = g.indptr[j] + hl.q; k < g.indptr[j + 1]; k += NB) du += dx[(long long)k * K + hl.hd];
+    du = across_groups<GL>(du);
+  }
+  if (lane < GL && hl.lead) {
+    du_out[(long long)j * K + hl.hd] = du;
+    dv_out[(long long)j * K + hl.hd] = dv;
+  }
+  if (lane < GL && c0 < d) {
+    const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
+    float4 o;
+    o.x = (acc.x + du * ad.x) + dv * as.x;
+    o.y = (acc.y + du * ad.y) + dv * as.y;
+    o.z = (acc.z + du * ad.z) + dv * as.z;
+    o.w = (acc.w + du * ad.w) + dv * as.w;
+    *reinterpret_cast<float4 *>(dP + (long long)j * ld_dp + c0) = o;
+  }
+}
+
+template <int GL, bool ONE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_cols_mh(
+    const GatPattern g, const float *__restrict__ alpha, const float *__restrict__ dx,
+    const float *__restrict__ G, int ld_g, const float *__restrict__ a_dst,
+    const float *__restrict__ a_src, int d, int K, int hlanes, const GatDrop dr,
+    float *__restrict__ dP, int ld_dp, float *__restrict__ du, float *__restrict__ dv,
+    float *__restrict__ col_ws) {
+  const int lane = threadIdx.x % kWave;
+  const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
+  const int c0 = hl.c0;
+  const long long items = (long long)g.n + g.n_col_segs;
+  for (long long it = first_item(); it < items; it += item_stride()) {
+    if (it < g.n) {
+      const int j = (int)it, b = g.csc_ptr[j], e = g.csc_ptr[j + 1];
+      if (e - b > kGatSeg) continue;
+      float dvj;
+      const float4 acc = col_gather_mh<GL, ONE>(g, alpha, dx, G, ld_g, d, K, hl, dr, b, e, &dvj);
+      col_finish_mh<GL, ONE>(g, j, acc, dvj, dx, a_dst, a_src, d, K, hl, dP, ld_dp, du, dv, lane);
+    } else {
+      const long long t = it - g.n;
+      const int4 sg = g.col_segs[t];
+      float dvj;
+      const float4 acc =
+          col_gather_mh<GL, ONE>(g, alpha, dx, G, ld_g, d, K, hl, dr, sg.y, sg.z, &dvj);
+      float *ws = col_ws + t * kGatWsStrideMh;
+      if (lane < GL && hl.lead) ws[hl.hd] = dvj;
+      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 2 * kGatMaxHeads + c0) = acc;
+    }
+  }
+}
+
+template <int GL, bool ONE>
+__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_colmerge_mh(
+    const GatPattern g, const float *__restrict__ dx, const float *__restrict__ a_dst,
+    const float *__restrict__ a_src, int d, int K, int hlanes, float *__restrict__ dP, int ld_dp,
+    float *__restrict__ du, float *__restrict__ dv, const float *__restrict__ col_ws) {
+  const int lane = threadIdx.x % kWave;
+  const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
+  const int c0 = hl.c0;
+  for (long long t = first_item(); t < g.n_long_cols; t += item_stride()) {
+    const int j = g.long_cols[t].x, first = g.long_cols[t].y;
+    const int nseg = (g.csc_ptr[j + 1] - g.csc_ptr[j] + kGatSeg - 1) / kGatSeg;
+    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float dvj = 0.0f;
+    for (int k = 0; k < nseg; k++) {
+      const float *w = col_ws + (long long)(first + k) * kGatWsStrideMh;
+      dvj += w[hl.hd];
+      if (c0 < d) {
+        const float4 p = *reinterpret_cast<const float4 *>(w + 2 * kGatMaxHeads + c0);
+        acc.x += p.x;
+        acc.y += p.y;
+        acc.z += p.z;
+        acc.w += p.w;
+      }
+    }
+    col_finish_mh<GL, ONE>(g, j, acc, dvj, dx, a_dst, a_src, d, K, hl, dP, ld_dp, du, dv, lane);
+  }
+}
+
+// k_gat_da with a lane's own head of du, dv [n][K]
+template <int GL>
+__global__ __launch_bounds__(kGatThreads) void k_gat_da_mh(
+    const float *__restrict__ P, int ld_p, int n, int d, int K, int hlanes,
+    const float *__restrict__ du, const float *__restrict__ dv, float *__restrict__ partial,
+    int ldp) {
+  constexpr int RPB = kGatThreads / GL;
+  constexpr int W = GL * 4;
+  __shared__ __align__(16) float sh[RPB * 2 * W];
+  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
+  const int hd = min(li / hlanes, K - 1);
+  float4 ad = make_float4(0.0f, 0.0f, 0.0f, 0.0f), as = ad;
+  for (long long r = (long long)blockIdx.x * RPB + grp; r < n; r += (long long)gridDim.x * RPB) {
+    const float4 p = row4(P + r * ld_p, c0, d, c0 < d);
+    axpy4(ad, du[r * K + hd], p);
+    axpy4(as, dv[r * K + hd], p);
+  }
+  *reinterpret_cast<float4 *>(&sh[(grp * 2 + 0) * W + c0]) = ad;
+  *reinterpret_cast<float4 *>(&sh[(grp * 2 + 1) * W + c0]) = as;
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * W; i += kGatThreads) {
+    const int c = i % W;
+    if (c >= ldp) continue;
+    float s = 0.0f;
+    for (int q = 0; q < RPB; q++) s += sh[q * 2 * W + i];
+    partial[((long long)blockIdx.x * 2 + i / W) * ldp + c] = s;
+  }
+}
+
+// K > 1: the gather kernels' <GL, false>; one head under a mask: <GL, true>
+#define GAT_DISPATCH_ONE(KERNEL, ONE, grid, s, ...)                                              \
+  do {                                                                                           \
+    switch (gat_gl(d)) {                                                                         \
+      case 1: PGCN_LAUNCH((KERNEL<1, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 2: PGCN_LAUNCH((KERNEL<2, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 4: PGCN_LAUNCH((KERNEL<4, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 8: PGCN_LAUNCH((KERNEL<8, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
+      case 16: PGCN_LAUNCH((KERNEL<16, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
+      default: PGCN_LAUNCH((KERNEL<32, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
+    }                                                                                            \
+  } while (0)
+#define GAT_DISPATCH_MH(KERNEL, grid, s, ...)                 \
+  do {                                                        \
+    if (heads > 1)                                            \
+      GAT_DISPATCH_ONE(KERNEL, false, grid, s, __VA_ARGS__);  \
+    else                                                      \
+      GAT_DISPATCH_ONE(KERNEL, true, grid, s, __VA_ARGS__);   \
+  } while (0)
+
+bool gat_heads_ok(int d, int heads) {
+  if (d < 1 || d > kGatMaxWidth || heads < 1) return false;
+  if (heads == 1) return true;
+  if (d % heads != 0) return false;
+  const int dh = d / heads;
+  return dh >= 4 && dh <= kGatMaxWidth && (dh & (dh - 1)) == 0;
+}
+
+// lanes per head: dh / 4 (one head: the whole group)
+static int gat_head_lanes(int d, int heads) { return heads > 1 ? d / heads / 4 : gat_gl(d); }
+
+void launch_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
+                          const float *a_src, float *u, float *v, hipStream_t s) {
+  PGCN_CHECK(gat_heads_ok(d, heads) && n >= 0, PGCN_E_INVALID,
+             "gat_scores: 1 <= d <= 128, heads dividing d into widths of 4 .. 128 (a power of two)");
+  if (heads == 1) return launch_gat_scores(P, ld_p, n, d, a_dst, a_src, u, v, s);
+  if (n == 0) return;
+  const dim3 grid((unsigned)std::min<long long>(ceil_div(n, kGatThreads / gat_gl(d)),
+                                                kGatMaxBlocks));
+  GAT_DISPATCH(k_gat_scores_mh, grid, s, P, ld_p, n, d, heads, gat_head_lanes(d, heads), a_dst,
+               a_src, u, v);
+}
+
+void launch_gat_fwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
+                       const float *v, float slope, float *Z, int ld_z, int d, int heads,
+                       const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                       float *alpha, hipStream_t s) {
+  PGCN_CHECK(gat_heads_ok(d, heads) && g.n >= 0, PGCN_E_INVALID,
+             "gat_fwd: 1 <= d <= 128, heads dividing d into widths of 4 .. 128 (a power of two)");
+  if (heads == 1 && !drop_mask) return launch_gat_fwd(g, P, ld_p, u, v, slope, Z, ld_z, d, alpha, s);
+  if (g.n == 0) return;
+  note_path(KP_GAT_FWD);
+  if (heads > 1) note_path(KP_GAT_HEADS);
+  const int hl = gat_head_lanes(d, heads);
+  const GatDrop dr{drop_mask, drop_base, drop_scale};
+  GAT_DISPATCH_MH(k_gat_fwd_mh, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v,
+                  slope, Z, ld_z, d, heads, hl, alpha, dr);
+  if (g.n_row_segs > 0)
+    GAT_DISPATCH_MH(k_gat_fwd_merge_mh, gat_grid(g.n_row_segs), s, g, u, v, slope, Z, ld_z, d,
+                    heads, hl, alpha);
+}
+
+namespace {
+// the layout of the _mh entries: serves one head with and without a mask
+GatBwdWs gat_bwd_layout_mh(const GatPattern &g, int d, int heads) {
+  GatBwdWs w;
+  w.dx = 0;
+  w.du = w.dx + up4((size_t)g.nnz * heads);
+  w.dv = w.du + up4((size_t)g.n * heads);
+  w.col_ws = w.dv + up4((size_t)g.n * heads);
+  w.part = w.col_ws + (size_t)g.n_col_segs * kGatWsStrideMh;
+  w.floats = w.part + (size_t)gat_da_blocks(g.n, d) * 2 * (size_t)((d + 3) / 4 * 4);
+  return w;
+}
+}  // namespace
+
+size_t gat_bwd_workspace_mh(const GatPattern &g, int d, int heads) {
+  if (g.n <= 0 || !gat_heads_ok(d, heads)) return 0;
+  return gat_bwd_layout_mh(g, d, heads).floats * sizeof(float);
+}
+
+void launch_gat_bwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
+                       const float *v, float slope, const float *alpha, const float *Z, int ld_z,
+                       const float *G, int ld_g, const float *a_dst, const float *a_src, float *dP,
+                       int ld_dp, int d, int heads, const uint64_t *drop_mask, long long drop_base,
+                       float drop_scale, float *da, void *workspace, hipStream_t s) {
+  PGCN_CHECK(gat_heads_ok(d, heads) && g.n >= 0, PGCN_E_INVALID,
+             "gat_bwd: 1 <= d <= 128, heads dividing d into widths of 4 .. 128 (a power of two)");
+  if (heads == 1 && !drop_mask)
+    return launch_gat_bwd(g, P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst, a_src, dP,
+                          ld_dp, d, da, workspace, s);
+  if (g.n == 0) return;
+  note_path(KP_GAT_BWD);
+  if (heads > 1) note_path(KP_GAT_HEADS);
+  const GatBwdWs w = gat_bwd_layout_mh(g, d, heads);
+  float *ws = static_cast<float *>(workspace);
+  float *dx = ws + w.dx, *du = ws + w.du, *dv = ws + w.dv, *col_ws = ws + w.col_ws;
+  float *partial = ws + w.part;
+  const int hl = gat_head_lanes(d, heads);
+  const GatDrop dr{drop_mask, drop_base, drop_scale};
+  GAT_DISPATCH_MH(k_gat_bwd_rows_mh, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v,
+                  slope, alpha, Z, ld_z, G, ld_g, d, heads, hl, dr, dx);
+  GAT_DISPATCH_MH(k_gat_bwd_cols_mh, gat_grid((long long)g.n + g.n_col_segs), s, g, alpha, dx, G,
+                  ld_g, a_dst, a_src, d, heads, hl, dr, dP, ld_dp, du, dv, col_ws);
+  if (g.n_long_cols > 0)
+    GAT_DISPATCH_MH(k_gat_bwd_colmerge_mh, gat_grid(g.n_long_cols), s, g, dx, a_dst, a_src, d,
+                    heads, hl, dP, ld_dp, du, dv, col_ws);
+  const int nb = gat_da_blocks(g.n, d), ldp = (d + 3) / 4 * 4;
+  if (heads > 1)
+    GAT_DISPATCH(k_gat_da_mh, dim3((unsigned)nb), s, P, ld_p, g.n, d, heads, hl, du, dv, partial,
+                 ldp);
+  else
+    GAT_DISPATCH(k_gat_da, dim3((unsigned)nb), s, P, ld_p, g.n, d, du, dv, partial, ldp);
   PGCN_LAUNCH(k_gat_da_reduce, dim3((unsigned)ceil_div(2 * ldp, kGatThreads)), dim3(kGatThreads),
               0, s, partial, nb, ldp, d, da);
 }

@@ -14,7 +14,7 @@ namespace pgcn {
 // which kernels a configuration took
 enum KernelPath {
   KP_XS_NN_RING, KP_XS_TN_RING, KP_XS_NN, KP_XS_TN, KP_GS_RING, KP_GS_GATHER, KP_OUT_XENT,
-  KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_LAUNCHES, KP_COUNT
+  KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS, KP_LAUNCHES, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -371,7 +371,7 @@ struct GatPattern {
   int n_row_segs = 0, n_col_segs = 0, n_long_cols = 0;
   const int4 *row_segs = nullptr, *col_segs = nullptr;
   const int2 *long_cols = nullptr;  // {column, its first segment}
-  float *row_ws = nullptr;          // forward: [n_row_segs][kGatWsStride]
+  float *row_ws = nullptr;          // forward: [n_row_segs][kGatWsStrideMh] (one head: kGatWsStride)
 };
 void launch_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
                        const float *a_src, float *u, float *v, hipStream_t s);
@@ -387,6 +387,30 @@ void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *
                     float slope, const float *alpha, const float *Z, int ld_z, const float *G,
                     int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
                     float *da, void *workspace, hipStream_t s);
+// Several heads and dropout on the attention weights: head h of `heads` owns columns [h dh,
+// (h + 1) dh), dh = d / heads in {4, 8, .., 128} (gat_heads_ok; one head: any d in 1..128), and
+// runs the formulas above on its slice: u, v [n][heads], alpha [nnz][heads].  drop_mask (or
+// null): bit drop_base + s heads + h keeps the weight of slot s, head h, times drop_scale in Z
+// and in the backward; alpha receives the weights before dropout.  One launch serves every
+// head; heads == 1 without a mask is the single-head launch above.
+constexpr int kGatMaxHeads = kGatMaxWidth / 4;
+// a segment's partial there: {max[32], sum[32], row[128]}; the column pass's {dv[32], -, row}
+constexpr int kGatWsStrideMh = 2 * kGatMaxHeads + kGatMaxWidth;
+bool gat_heads_ok(int d, int heads);
+void launch_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
+                          const float *a_src, float *u, float *v, hipStream_t s);
+void launch_gat_fwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
+                       const float *v, float slope, float *Z, int ld_z, int d, int heads,
+                       const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                       float *alpha, hipStream_t s);
+// dx [nnz][heads], du, dv [n][heads], the segment partials, the da partials (one head: enough
+// for a call with a mask and for one without)
+size_t gat_bwd_workspace_mh(const GatPattern &g, int d, int heads);
+void launch_gat_bwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
+                       const float *v, float slope, const float *alpha, const float *Z, int ld_z,
+                       const float *G, int ld_g, const float *a_dst, const float *a_src, float *dP,
+                       int ld_dp, int d, int heads, const uint64_t *drop_mask, long long drop_base,
+                       float drop_scale, float *da, void *workspace, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

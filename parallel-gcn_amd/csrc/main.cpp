@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -17,7 +17,10 @@
 // the epoch lines' accuracy column is the Hamming accuracy, and predict= writes `node id id ...`
 // (the classes with a positive logit) per node.
 // attention=1 (command line or parameter file): graph attention layers in the GraphSums' place,
-// pgcn_params.attention.
+// pgcn_params.attention; heads=<K> runs its hidden layers with K heads concatenated inside their
+// widths and attn_dropout=<p> drops attention weights in training (pgcn_params.attention_heads /
+// attention_dropout; `gcn-par cora attention=1 heads=8 attn_dropout=0.6` with hidden_dims=64 is
+// the published GAT), both also keys of the parameter file.
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +73,8 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "layer_norm") p->layer_norm = std::atoi(v.c_str());
     else if (k == "attention") p->attention = std::atoi(v.c_str());
     else if (k == "multilabel") p->multilabel = std::atoi(v.c_str());
+    else if (k == "heads") p->attention_heads = std::atoi(v.c_str());
+    else if (k == "attn_dropout") p->attention_dropout = std::strtof(v.c_str(), nullptr);
   }
   return true;
 }
@@ -84,7 +89,8 @@ int main(int argc, char **argv) {
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
   std::string load, save, predict;
-  int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1;
+  int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
+  float attn_dropout = -1.0f;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -98,6 +104,9 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "layer_norm=", 11)) layer_norm = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "multilabel=", 11)) multilabel = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "attention=", 10)) attention = std::atoi(argv[i] + 10);
+    if (!std::strncmp(argv[i], "heads=", 6)) heads = std::atoi(argv[i] + 6);
+    if (!std::strncmp(argv[i], "attn_dropout=", 13))
+      attn_dropout = std::strtof(argv[i] + 13, nullptr);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -110,6 +119,8 @@ int main(int argc, char **argv) {
   if (layer_norm >= 0) p.layer_norm = layer_norm;
   if (multilabel >= 0) p.multilabel = multilabel;
   if (attention >= 0) p.attention = attention;
+  if (heads >= 0) p.attention_heads = heads;
+  if (attn_dropout >= 0.0f) p.attention_dropout = attn_dropout;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
