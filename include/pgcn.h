@@ -260,6 +260,45 @@ int pgcn_gat_bwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *
                     int heads, const uint64_t *drop_mask, long long drop_base, float drop_scale,
                     float *da /* [2][d]: dst, src */, void *workspace, void *stream);
 
+/* --- GraphSAGE aggregators over the CSR slots of a square pattern (k_sage.hip) ---------------
+ * Max (new kernels).  `g` comes from pgcn_graph_create* with a square pattern; its values are
+ * not used, and nnz must fit an int.  Slot s = (i, j) is global position s of `indices`.
+ *   pgcn_agg_max_fwd: out_i[c] = add_i[c] + max over row i's slots of in_j[c] -- the maximum is
+ *     exact and the add is one fp32 add (add == NULL: the maximum itself).  arg_i[c] (arg may be
+ *     NULL: an inference call) is the slot whose in_j[c] is that maximum.  A candidate replaces
+ *     the incumbent only when strictly greater (the project's tie rule), so among equal values --
+ *     -0.0 and +0.0 are equal -- the LOWEST slot wins, however the slots are dealt to lanes.  A row
+ *     without a slot: out_i = add_i (or 0), arg_i = -1.  Inputs are taken as finite.
+ *   pgcn_agg_max_bwd: with G [n][ld_g] = dLoss/dout and the forward's arg, din_j[c] = sum over
+ *     the slots s = (i, j) into column j with arg_i[c] == s of G_i[c]: every gradient element
+ *     goes to the one slot that won.  The sum walks the transposed index in CSR order (the
+ *     pattern need not be symmetric); a column without incoming slots gives a zero row.  The
+ *     gradient of `add` is G itself.
+ * 1 <= d <= 128; every ld a multiple of 4 and >= d, rows 16-byte aligned.  The float4s / int4s
+ * covering [0, round_up4(d)) of out, arg and din are written -- 0 (arg: -1) from column d on --
+ * and columns beyond them are left alone; padding columns of in, add, G and arg may hold
+ * anything and never reach a result.  Anything else is PGCN_E_INVALID before anything touches
+ * the device.  The calls are asynchronous and allocate nothing -- a graph's first call builds
+ * and uploads its transposed index and segment lists and allocates the segment partials of its
+ * rows / columns longer than 512 slots, which live in the graph, so two calls on one graph must
+ * not overlap -- and may be captured after it.  No float atomics: every order depends on the
+ * pattern and d only, so two calls give the same bits.
+ * Mean (no new kernel): pgcn_graph_create_mean builds the graph whose pgcn_graphsum is the mean
+ * forward (transpose = 0: the pattern with 1 / len_i on every slot of row i, out_i = (1 / len_i)
+ * sum in_j) or backward (transpose = 1: the transposed pattern, host side as
+ * pgcn_csr_transpose orders it, whose slot (j, i) carries 1 / len_i: out_j = sum over the slots
+ * into column j of in_i / len_i).  1 / len_i is one 1.0f / (float)len_i, len_i the CSR row
+ * length as given.  The values factor into (row scale, column scale) = (1 / len, 1) resp.
+ * (1, 1 / len), so pgcn_graphsum takes whatever kernel the width and size select, the LDS ring
+ * schedule included. */
+int pgcn_graph_create_mean(int n_nodes, const int *indptr, const int *indices, int transpose,
+                           pgcn_graph **out);
+int pgcn_agg_max_fwd(const pgcn_graph *g, const float *in, int ld_in, int d,
+                     const float *add /* [n][ld_add] or NULL */, int ld_add, float *out,
+                     int ld_out, int *arg /* [n][ld_arg] or NULL */, int ld_arg, void *stream);
+int pgcn_agg_max_bwd(const pgcn_graph *g, const float *G, int ld_g, const int *arg, int ld_arg,
+                     int d, float *din, int ld_din, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -335,6 +374,24 @@ typedef struct {
   int n_layers;                          /* >= 2 */
   int hidden_dims[PGCN_MAX_LAYERS];      /* n_layers - 1 */
   float dropouts[PGCN_MAX_LAYERS];       /* n_layers */
+  /* GraphSAGE layers.  aggregator: 0 = GCN's Â (the engine as it was, bit for bit), 1 = mean,
+   * 2 = max; root_weight: 0 / 1, 1 only with aggregator != 0.  With H the layer's input as it
+   * reads it (after its Dropout in training) and d_l its output width:
+   *   root_weight 1: W_l is [d_in][2 d_l]; P = H W_l; R = P[:, 0:d_l], Q = P[:, d_l:2 d_l]
+   *   root_weight 0: W_l is [d_in][d_l] as before; Q = H W_l, R absent
+   *   mean: Z_i = R_i + (1 / len_i) sum over row i's slots of Q_j   (pgcn_graph_create_mean)
+   *   max:  Z_i[c] = R_i[c] + max over row i's slots of Q_j[c]      (pgcn_agg_max_fwd)
+   * on the adjacency pattern as loaded -- directed patterns included, len_i the CSR row length
+   * with the self loop and duplicated edges as the pattern has them; the Â coefficients are not
+   * used.  A row without a slot gives Z_i = R_i (or 0).  Behind Z a hidden layer goes on as
+   * before ([LayerNorm] -> ReLU -> [Residual] -> Dropout) and the output layer is Z itself.  The
+   * wider weight is drawn like any weight of its shape (Glorot with fan-out 2 d_l, one draw per
+   * element, the dropout streams after the last draw); variable var1 of a layer is then
+   * [rows][2 d_l], root half first.  No reassociated output layer, no Â X precompute, no
+   * output-row restriction, the loss unfused.  Hidden widths and output_dim up to 128; not with
+   * attention; single GPU only (the edge-cut creators return PGCN_E_INVALID: the mean could be
+   * partitioned, the max needs a max / arg exchange). */
+  int aggregator, root_weight;
   int epochs, early_stopping;
   /* attention != 0 only (anything but 1 / 0 without it is PGCN_E_INVALID).  attention_heads = K
    * (0 counts as 1): every HIDDEN attention layer runs K heads concatenated inside its width d_l
@@ -569,6 +626,19 @@ int pgcn_checkpoint_flags(const char *path);
  * included; a weights-only load crosses it.  pgcn_checkpoint_info and pgcn_checkpoint_flags
  * accept version 5.  Validates as pgcn_checkpoint_info does. */
 int pgcn_checkpoint_attention(const char *path, int *heads, float *dropout);
+/* flags bit 4: saved by a GraphSAGE engine (pgcn_params.aggregator != 0).  Such an engine writes
+ * a version-6 file: the header with bit 4 set (bits 0-2 known, bit 3 never: no attention), then
+ * 16 bytes {u32 aggregator; u32 root_weight; u64 0} where version 5 has its block, under the
+ * checksum, then the payload.  With root_weight 1 every layer weight is [d_in][2 d_l], so
+ * n_weights and the w / m / v tensors are that much longer; the scale / shift tensor follows as in
+ * version 2.  Every other engine keeps writing versions 1-5 byte for byte.
+ * pgcn_checkpoint_sage is host-only and validates as pgcn_checkpoint_info does: the aggregator
+ * and the root weight of the engine that saved the file; versions 1-5 give 0 and 0.  A flags-0
+ * load refuses a file whose aggregator or root weight differs from the engine's; a weights-only
+ * load crosses the aggregator whenever the tensor shapes agree (the same root_weight) and refuses
+ * otherwise.  pgcn_checkpoint_info and pgcn_checkpoint_flags accept version 6. */
+#define PGCN_CKPT_SAGE 16
+int pgcn_checkpoint_sage(const char *path, int *aggregator, int *root_weight);
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever

@@ -41,7 +41,8 @@ P = ctypes.POINTER
 class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("hidden_dims", c_int * MAX_LAYERS),
-                ("dropouts", c_float * MAX_LAYERS), ("epochs", c_int), ("early_stopping", c_int),
+                ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
+                ("root_weight", c_int), ("epochs", c_int), ("early_stopping", c_int),
                 ("attention_heads", c_int), ("attention_dropout", c_float),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
                 ("beta2", c_float), ("eps", c_float), ("attention", c_int),
@@ -135,6 +136,11 @@ _sig("pgcn_gat_bwd_workspace_mh", c_size_t, c_void_p, c_int, c_int)
 _sig("pgcn_gat_bwd_mh", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
      c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
      c_void_p, c_ll, c_float, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_graph_create_mean", c_int, c_int, c_void_p, c_void_p, c_int, P(c_void_p))
+_sig("pgcn_agg_max_fwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+     c_void_p, c_int, c_void_p)
+_sig("pgcn_agg_max_bwd", c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+     c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -174,6 +180,7 @@ _sig("pgcn_gcn_load", c_int, c_void_p, ctypes.c_char_p, c_int)
 _sig("pgcn_checkpoint_info", c_int, ctypes.c_char_p, P(c_ll))
 _sig("pgcn_checkpoint_flags", c_int, ctypes.c_char_p)
 _sig("pgcn_checkpoint_attention", c_int, ctypes.c_char_p, P(c_int), P(c_float))
+_sig("pgcn_checkpoint_sage", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_gcn_predict", c_ll, c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -403,12 +410,26 @@ def f1_scores(counts):
     return (float(2 * tp.sum() / tot) if tot > 0 else 0.0), float(per.mean())
 
 
+AGGREGATORS = {None: 0, "mean": 1, "max": 2}
+
+
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
-                multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0):
+                multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
+                aggregator=None, root_weight=False):
+    """aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
+    own row through its own half of a [d_in][2 d_l] weight (with an aggregator only)."""
+    if aggregator not in AGGREGATORS:
+        raise ValueError(f"aggregator must be one of {sorted(k for k in AGGREGATORS if k)} or None")
+    if root_weight and not AGGREGATORS[aggregator]:
+        raise ValueError("root_weight needs aggregator='mean' or 'max'")
+    if attention and AGGREGATORS[aggregator]:
+        raise ValueError("an aggregator cannot be combined with attention")
     p = PgcnParams()
     lib.pgcn_params_default(ctypes.byref(p))
+    p.aggregator = AGGREGATORS[aggregator]
+    p.root_weight = 1 if root_weight else 0
     p.attention = 1 if attention else 0
     p.attention_heads, p.attention_dropout = attention_heads, attention_dropout
     p.multilabel = 1 if multilabel else 0
@@ -683,6 +704,7 @@ CKPT_RESIDUAL = 1
 CKPT_LAYERNORM = 2  # version-2 files: the scale / shift tensor behind the layer weights
 CKPT_MULTILABEL = 4  # saved by a multi-label engine (no payload change)
 CKPT_ATTENTION = 8  # version-4 files: the attention tensor last in the payloads
+CKPT_SAGE = 16  # version-6 files: a GraphSAGE engine's, with the {aggregator, root_weight} block
 
 
 def checkpoint_flags(path):
@@ -702,6 +724,15 @@ def checkpoint_attention(path):
     check(lib.pgcn_checkpoint_attention(os.fsencode(path), ctypes.byref(heads), ctypes.byref(p)),
           f"checkpoint_attention {path}")
     return heads.value, p.value
+
+
+def checkpoint_sage(path):
+    """Host-only: (aggregator, root_weight) of the engine that saved the file -- a version-6
+    file's block; (0, 0) for versions 1-5.  PgcnError(PGCN_E_IO) for an invalid file."""
+    agg, root = c_int(), c_int()
+    check(lib.pgcn_checkpoint_sage(os.fsencode(path), ctypes.byref(agg), ctypes.byref(root)),
+          f"checkpoint_sage {path}")
+    return agg.value, root.value
 
 
 def comm_unique_id():
@@ -782,7 +813,8 @@ EXPORTED = [
     "pgcn_debug_layernorm_fwd_tail",
     "pgcn_gat_scores", "pgcn_gat_fwd", "pgcn_gat_bwd_workspace", "pgcn_gat_bwd",
     "pgcn_gat_scores_mh", "pgcn_gat_fwd_mh", "pgcn_gat_bwd_workspace_mh", "pgcn_gat_bwd_mh",
-    "pgcn_checkpoint_flags", "pgcn_checkpoint_attention", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
+    "pgcn_graph_create_mean", "pgcn_agg_max_fwd", "pgcn_agg_max_bwd",
+    "pgcn_checkpoint_flags", "pgcn_checkpoint_attention", "pgcn_checkpoint_sage", "pgcn_xent_blocks", "pgcn_xent_fwd", "pgcn_finalize", "pgcn_adam",
     "pgcn_adam_step_size", "pgcn_params_default", "pgcn_gcn_create", "pgcn_comm_unique_id",
     "pgcn_gcn_create_dist", "pgcn_gcn_create_peer", "pgcn_loopback_create",
     "pgcn_loopback_destroy",

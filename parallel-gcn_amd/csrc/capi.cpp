@@ -1,5 +1,6 @@
 // parallel-gcn_amd/csrc/capi.cpp -- the extern "C" boundary declared in include/pgcn.h.
 #include <atomic>
+#include <climits>
 #include <cstring>
 #include <memory>
 
@@ -53,10 +54,14 @@ void check_device() {
     throw Error(PGCN_E_NODEVICE, "no HIP device visible: the engine has no CPU fallback");
 }
 
-// the edge-cut creators: a row's softmax needs all its columns
-void refuse_attention(const pgcn_params *p) {
+// the edge-cut creators: attention (a row's softmax needs all its columns) and the SAGE
+// aggregators run on one GPU only
+void refuse_single_gpu_only(const pgcn_params *p) {
   PGCN_CHECK(!p->attention, PGCN_E_INVALID,
              "attention: single GPU only (edge-cut attention is not supported)");
+  // (the mean is linear and could be partitioned; the max needs a max / arg exchange)
+  PGCN_CHECK(!p->aggregator && !p->root_weight, PGCN_E_INVALID,
+             "aggregator: single GPU only (edge-cut SAGE layers are not supported)");
 }
 
 GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
@@ -77,6 +82,10 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.attention = p->attention != 0;
   q.attention_heads = p->attention_heads == 0 ? 1 : p->attention_heads;
   q.attention_dropout = p->attention_dropout;
+  PGCN_CHECK(p->root_weight == 0 || p->root_weight == 1, PGCN_E_INVALID,
+             "root_weight must be 0 or 1");
+  q.aggregator = p->aggregator;
+  q.root_weight = p->root_weight != 0;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -604,6 +613,67 @@ int pgcn_gat_bwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *
   });
 }
 
+int pgcn_graph_create_mean(int n, const int *indptr, const int *indices, int transpose,
+                           pgcn_graph **out) {
+  return guarded([&] {
+    PGCN_CHECK(n > 0 && indptr && indices && out && (transpose == 0 || transpose == 1),
+               PGCN_E_INVALID, "graph_create_mean args");
+    PGCN_CHECK(indptr[0] == 0 && indptr[n] >= 0, PGCN_E_INVALID, "graph_create_mean: indptr");
+    for (int i = 0; i < n; i++)
+      PGCN_CHECK(indptr[i + 1] >= indptr[i], PGCN_E_INVALID, "graph_create_mean: indptr order");
+    const int nnz = indptr[n];
+    for (int k = 0; k < nnz; k++)
+      PGCN_CHECK(indices[k] >= 0 && indices[k] < n, PGCN_E_INVALID,
+                 "graph_create_mean: column id out of range");
+    check_device();
+    auto h = std::make_unique<pgcn_graph>();
+    h->g = make_mean_graph(n, indptr, indices, transpose != 0);
+    *out = h.release();
+  });
+}
+
+namespace {
+void check_sage_dims(int d, std::initializer_list<int> lds) {
+  PGCN_CHECK(d >= 1 && d <= kSageMaxWidth, PGCN_E_INVALID, "agg_max: 1 <= d <= 128");
+  for (int ld : lds) PGCN_CHECK(ln_ld_ok(ld, d), PGCN_E_INVALID, "agg_max: ld % 4 == 0, ld >= d");
+}
+}  // namespace
+
+int pgcn_agg_max_fwd(const pgcn_graph *g, const float *in, int ld_in, int d, const float *add,
+                     int ld_add, float *out, int ld_out, int *arg, int ld_arg, void *stream) {
+  return guarded([&] {
+    check_sage_dims(d, {ld_in, ld_out});
+    if (add) check_sage_dims(d, {ld_add});
+    if (arg) check_sage_dims(d, {ld_arg});
+    PGCN_CHECK(g && g->g && in && out && aligned16(in) && aligned16(out) && aligned16(add) &&
+                   aligned16(arg),
+               PGCN_E_INVALID, "agg_max_fwd: null or misaligned argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols() && g->g->nnz() <= INT_MAX, PGCN_E_INVALID,
+               "agg_max_fwd: square pattern, nnz within an int");
+    check_device();
+    const GatPattern &p = g->g->gat_pattern();
+    launch_agg_max_fwd(p, g->g->sage_ws(), in, ld_in, d, add, ld_add, out, ld_out, arg, ld_arg,
+                       as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_agg_max_bwd(const pgcn_graph *g, const float *G, int ld_g, const int *arg, int ld_arg,
+                     int d, float *din, int ld_din, void *stream) {
+  return guarded([&] {
+    check_sage_dims(d, {ld_g, ld_arg, ld_din});
+    PGCN_CHECK(g && g->g && G && arg && din && aligned16(G) && aligned16(arg) && aligned16(din),
+               PGCN_E_INVALID, "agg_max_bwd: null or misaligned argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols() && g->g->nnz() <= INT_MAX, PGCN_E_INVALID,
+               "agg_max_bwd: square pattern, nnz within an int");
+    check_device();
+    const GatPattern &p = g->g->gat_pattern();
+    launch_agg_max_bwd(p, g->g->sage_ws(), G, ld_g, arg, ld_arg, d, din, ld_din,
+                       as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -696,6 +766,8 @@ void pgcn_params_default(pgcn_params *p) {
   p->hidden_dims[0] = 16;
   p->dropouts[0] = 0.5f;
   p->dropouts[1] = 0.5f;
+  p->aggregator = 0;
+  p->root_weight = 0;
   p->epochs = 100;
   p->early_stopping = 0;
   p->attention_heads = 1;
@@ -732,7 +804,7 @@ int pgcn_gcn_create_dist(const pgcn_params *p, const pgcn_data *d, int device, i
                          int world, const void *uid, pgcn_gcn **out) {
   return guarded([&] {
     PGCN_CHECK(p && d && out && uid, PGCN_E_INVALID, "gcn_create_dist args");
-    refuse_attention(p);
+    refuse_single_gpu_only(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -751,7 +823,7 @@ int pgcn_gcn_create_peer(const pgcn_params *p, const pgcn_data *d, int device, i
     PGCN_CHECK(p && d && out && allgather && world >= 1 && world <= kPeerMaxRanks && rank >= 0 &&
                    rank < world,
                PGCN_E_INVALID, "gcn_create_peer args");
-    refuse_attention(p);
+    refuse_single_gpu_only(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -772,7 +844,7 @@ int pgcn_debug_gcn_create_solo(const pgcn_params *p, const pgcn_data *d, int dev
   return guarded([&] {
     PGCN_CHECK(p && d && out && world >= 1 && rank >= 0 && rank < world, PGCN_E_INVALID,
                "gcn_create_solo args");
-    refuse_attention(p);
+    refuse_single_gpu_only(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -803,7 +875,7 @@ int pgcn_gcn_create_loopback(const pgcn_params *p, const pgcn_data *d, int devic
                              pgcn_loopback *group, pgcn_gcn **out) {
   return guarded([&] {
     PGCN_CHECK(p && d && out && group && group->g, PGCN_E_INVALID, "gcn_create_loopback args");
-    refuse_attention(p);
+    refuse_single_gpu_only(p);
     check_device();
     GCNData data = to_data(d, p);
     DistSpec ds;
@@ -851,6 +923,8 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "attention_layers")) return e.attention_layers();
   if (!std::strcmp(key, "attention_heads")) return e.attention_heads();
   if (!std::strcmp(key, "attention_dropout_layers")) return e.attention_dropout_layers();
+  if (!std::strcmp(key, "aggregator")) return e.aggregator();
+  if (!std::strcmp(key, "root_weight")) return e.root_weight() ? 1 : 0;
   if (!std::strcmp(key, "multilabel")) return e.get_params().multilabel ? 1 : 0;
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
@@ -957,6 +1031,14 @@ int pgcn_checkpoint_attention(const char *path, int *heads, float *dropout) {
     const Checkpoint ck = read_checkpoint(path);
     *heads = ck.heads;
     *dropout = ck.attention_dropout;
+  });
+}
+int pgcn_checkpoint_sage(const char *path, int *aggregator, int *root_weight) {
+  return guarded([&] {
+    PGCN_CHECK(path && aggregator && root_weight, PGCN_E_INVALID, "checkpoint_sage args");
+    const Checkpoint ck = read_checkpoint(path);
+    *aggregator = ck.aggregator;
+    *root_weight = ck.root_weight;
   });
 }
 int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }

@@ -37,10 +37,25 @@ CkHeadsExt heads_ext(const Checkpoint &ck) {
   return CkHeadsExt{(uint32_t)ck.heads, ck.attention_dropout, 0};
 }
 
+// version 6: in the same place
+struct CkSageExt {
+  uint32_t aggregator, root_weight;
+  uint64_t zero;
+};
+static_assert(sizeof(CkSageExt) == 16, "checkpoint extension layout");
+
+CkSageExt sage_ext(const Checkpoint &ck) {
+  return CkSageExt{(uint32_t)ck.aggregator, (uint32_t)ck.root_weight, 0};
+}
+
 uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
   uint64_t x = fnv1a(kFnvBasis, &h, offsetof(CkHeader, checksum));
   if (h.version == (uint32_t)kCheckpointVersionHeads) {
     const CkHeadsExt e = heads_ext(ck);
+    x = fnv1a(x, &e, sizeof e);
+  }
+  if (h.version == (uint32_t)kCheckpointVersionSage) {
+    const CkSageExt e = sage_ext(ck);
     x = fnv1a(x, &e, sizeof e);
   }
   for (const auto *vec : {&ck.results, &ck.w, &ck.m, &ck.v})
@@ -57,9 +72,9 @@ bool read_floats(std::FILE *f, std::vector<float> &v, long long n) {
   return n == 0 || std::fread(v.data(), sizeof(float), (size_t)n, f) == (size_t)n;
 }
 
-long long weight_count(const int32_t *dims, int n_layers) {
+long long weight_count(const int32_t *dims, int n_layers, int root_weight = 0) {
   long long n = 0;
-  for (int l = 0; l < n_layers; l++) n += (long long)dims[l] * dims[l + 1];
+  for (int l = 0; l < n_layers; l++) n += (long long)dims[l] * dims[l + 1] * (root_weight ? 2 : 1);
   return n;
 }
 
@@ -88,11 +103,15 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
       version == (uint32_t)kCheckpointVersionHeads)
     return (flags & kCheckpointAttention) &&
            (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm | kCheckpointAttention)) == 0;
+  if (version == (uint32_t)kCheckpointVersionSage)
+    return (flags & kCheckpointSage) &&
+           (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm | kCheckpointSage)) == 0;
   return false;
 }
 
-long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags) {
-  return weight_count(dims, n_layers) +
+long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags,
+                           int root_weight = 0) {
+  return weight_count(dims, n_layers, root_weight) +
          ((flags & kCheckpointLayerNorm) ? norm_count_of(dims, n_layers) : 0) +
          ((flags & kCheckpointAttention) ? attn_count_of(dims, n_layers) : 0);
 }
@@ -106,6 +125,16 @@ bool heads_ok(uint32_t version, const int32_t *dims, int n_layers, long long hea
     const long long dh = dims[l] / heads;
     if (dims[l] % heads != 0 || dh < 4 || dh > 128 || (dh & (dh - 1)) != 0) return false;
   }
+  return true;
+}
+
+// version 6's block against the file's version (the engine's own rules)
+bool sage_ok(uint32_t version, const int32_t *dims, int n_layers, long long aggregator,
+             long long root_weight) {
+  if (version != (uint32_t)kCheckpointVersionSage) return aggregator == 0 && root_weight == 0;
+  if (aggregator < 1 || aggregator > 2 || root_weight < 0 || root_weight > 1) return false;
+  for (int l = 1; l <= n_layers; l++)
+    if (dims[l] > 128) return false;
   return true;
 }
 }  // namespace
@@ -134,18 +163,23 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   h.epochs = ck.epochs;
   h.n_results = (int64_t)(ck.results.size() / 4);
   h.n_weights = (int64_t)ck.w.size();
-  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags), PGCN_E_INVALID,
+  PGCN_CHECK(sage_ok(h.version, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
+             "checkpoint: aggregator / root weight do not match the file's version");
+  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: weight count does not match the layer dims");
   PGCN_CHECK(heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout), PGCN_E_INVALID,
              "checkpoint: heads / attention dropout do not match the file's version");
   const CkHeadsExt ext = heads_ext(ck);
   const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads;
+  const CkSageExt sext = sage_ext(ck);
+  const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage;
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
   std::FILE *f = std::fopen(tmp.c_str(), "wb");
   if (!f) throw Error(PGCN_E_IO, "checkpoint: cannot write " + tmp);
   bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1 &&
             (!with_ext || std::fwrite(&ext, sizeof(ext), 1, f) == 1) &&
+            (!with_sage || std::fwrite(&sext, sizeof(sext), 1, f) == 1) &&
             write_floats(f, ck.results) &&
             write_floats(f, ck.w) && write_floats(f, ck.m) && write_floats(f, ck.v);
   ok = (std::fclose(f) == 0) && ok;
@@ -168,14 +202,23 @@ Checkpoint read_checkpoint(const std::string &path) {
   for (int l = 0; ok && l <= L; l++) ok = h.dims[l] > 0 && h.dims[l] <= (1 << 24);
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
        h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
-       h.n_weights == expected_weights(h.dims, L, h.flags) && h.n_weights < (1LL << 31);
+       h.n_weights < (1LL << 31);
   if (ok && h.version == (uint32_t)kCheckpointVersionHeads) {
     CkHeadsExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.heads <= 32;
     ck.heads = (int)e.heads;
     ck.attention_dropout = e.attention_dropout;
   }
-  ok = ok && heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout);
+  if (ok && h.version == (uint32_t)kCheckpointVersionSage) {
+    CkSageExt e{};
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.aggregator <= 2 &&
+         e.root_weight <= 1;
+    ck.aggregator = (int)e.aggregator;
+    ck.root_weight = (int)e.root_weight;
+  }
+  ok = ok && heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout) &&
+       sage_ok(h.version, h.dims, L, ck.aggregator, ck.root_weight) &&
+       h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight);
   ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
        read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);
   ok = ok && std::fgetc(f) == EOF;  // nothing trailing

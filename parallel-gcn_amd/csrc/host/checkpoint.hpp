@@ -32,8 +32,14 @@
 // attention_dropout in [0, 1), not both at their defaults (1 and 0: that engine writes version
 // 4), and the last word 0.  The tensors keep their shapes, so the payload is version 4's.  Every
 // other engine keeps writing versions 1-4 byte for byte.
-// checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (version
-// 5) and the payload.
+// Version 6 = saved by a GraphSAGE engine (pgcn_params.aggregator != 0): flags bit 4 always set,
+// bits 0-2 known, bit 3 unknown (no attention), and a 16-byte block where version 5 has its own,
+//   block  u32 aggregator (1 mean, 2 max); u32 root_weight (0 / 1); u64 0
+// With root_weight 1 every layer weight is [d_in][2 d_l] (the root half first), so n_weights and
+// the w / m / v payloads count 2 * dims[l] * dims[l + 1] per layer; the scale / shift tensor
+// follows as in version 2.  Every other engine keeps writing versions 1-5 byte for byte.
+// checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (versions
+// 5 and 6) and the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
 // stored and the file does not depend on the world size.  Nothing newer than the reference:
@@ -54,6 +60,8 @@ constexpr int kCheckpointVersionLayerNormMultilabel = 3;  // version 2's layout 
 constexpr unsigned kCheckpointAttention = 8u;  // header flags, bit 3 (version 4 only)
 constexpr int kCheckpointVersionAttention = 4;  // bits 0-3 known, bit 3 set
 constexpr int kCheckpointVersionHeads = 5;  // version 4 + the {heads, attention_dropout} extension
+constexpr unsigned kCheckpointSage = 16u;  // header flags, bit 4 (version 6 only)
+constexpr int kCheckpointVersionSage = 6;  // bits 0-2 and 4 known, bit 4 set, + its block
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -68,6 +76,8 @@ struct Checkpoint {
   // version 5's extension; 1 and 0 in every other version
   int heads = 1;
   float attention_dropout = 0.0f;
+  // version 6's block; 0 and 0 in every other version
+  int aggregator = 0, root_weight = 0;
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

@@ -305,6 +305,19 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
     PGCN_CHECK(gat_heads_ok(std::min(h, kGatMaxWidth), params.attention_heads), PGCN_E_INVALID,
                "attention_heads must divide every hidden width into head widths of 4, 8, 16, 32, "
                "64 or 128");
+  PGCN_CHECK(params.aggregator >= 0 && params.aggregator <= 2, PGCN_E_INVALID,
+             "aggregator must be 0 (GCN), 1 (mean) or 2 (max)");
+  PGCN_CHECK(params.aggregator != 0 || !params.root_weight, PGCN_E_INVALID,
+             "root_weight needs aggregator != 0");
+  if (params.aggregator != 0) {
+    PGCN_CHECK(!params.attention, PGCN_E_INVALID, "aggregator != 0 cannot be combined with attention");
+    PGCN_CHECK(!dist, PGCN_E_INVALID,
+               "aggregator != 0: single GPU only (edge-cut SAGE layers are not supported)");
+    for (int h : params.hidden_dims)
+      PGCN_CHECK(h <= kSageMaxWidth, PGCN_E_INVALID, "aggregator != 0: hidden dims up to 128");
+    PGCN_CHECK(params.output_dim <= kSageMaxWidth, PGCN_E_INVALID,
+               "aggregator != 0: output_dim up to 128");
+  }
   int lo_prio = 0, hi_prio = 0;
   PGCN_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
   stream = Stream::create(hi_prio);  // the reference uses High priority streams
@@ -367,7 +380,7 @@ void GCN::upload_features(const GCNData &data) {
   nnz_x_global = fptr[(size_t)params.num_nodes];
   build_dev_features(feats, fptr.data(), data.feature_index.indices.data(),
                      data.feature_value.data(), part.first(), part.local_rows(), params.input_dim,
-                     features_dense(data), params.hidden_dims.front());
+                     features_dense(data), weight_cols(params.hidden_dims.front()));
 }
 
 void GCN::init_dropout_rng(const GCNData &data, long long glorot_draws) {
@@ -513,11 +526,17 @@ void GCN::build(const GCNData &data) {
                                        v.data(), knobs_);
     const std::vector<float> sg = degree_scales(N, data.graph.indptr.data());
     graph->set_scales(sg, sg);
+    if (params.aggregator == 1) {  // the mean aggregator's two GraphSums (every layer's)
+      mean_fwd_graph = make_mean_graph(N, data.graph.indptr.data(), data.graph.indices.data(),
+                                       false, knobs_);
+      mean_bwd_graph = make_mean_graph(N, data.graph.indptr.data(), data.graph.indices.data(),
+                                       true, knobs_);
+    }
   }
   upload_features(data);
   // eval_ax (dense X): Â X's buffer now -- the modules built below read it -- and its sums at
   // the end of the build (build_eval_ax)
-  if (knobs_.eval_ax && !params.attention && feats.dense && feats.cols >= 16 && (comm || graph)) {
+  if (knobs_.eval_ax && !custom_aggregation() && feats.dense && feats.cols >= 16 && (comm || graph)) {
     feats.ax.allocate(feats.x.size());
     feats.ax.zero();
   }
@@ -573,7 +592,9 @@ void GCN::build(const GCNData &data) {
   for (int h : params.hidden_dims) dims.push_back(h);
   dims.push_back(params.output_dim);
   long long wtotal = 0;
-  for (int l = 0; l < L; l++) wtotal += (long long)dims[(size_t)l] * dims[(size_t)l + 1];
+  // (root_weight: W_l is [d_in][2 d_l], the root half first -- glorot's fan-out is 2 d_l)
+  for (int l = 0; l < L; l++)
+    wtotal += (long long)dims[(size_t)l] * weight_cols(dims[(size_t)l + 1]);
   long long ntotal = 0;  // layer_norm: gamma and beta of every hidden layer, behind the weights
   if (params.layer_norm)
     for (int h : params.hidden_dims) ntotal += 2LL * h;
@@ -588,9 +609,10 @@ void GCN::build(const GCNData &data) {
   long long woff = 0;
   std::vector<std::vector<float>> winit;
   for (int l = 0; l < L; l++) {
-    auto w = std::make_shared<Variable>(dims[(size_t)l], dims[(size_t)l + 1], false);
+    const int wc = weight_cols(dims[(size_t)l + 1]);
+    auto w = std::make_shared<Variable>(dims[(size_t)l], wc, false);
     std::vector<float> h((size_t)w->size);
-    glorot_host(h, dims[(size_t)l], dims[(size_t)l + 1], rs);
+    glorot_host(h, dims[(size_t)l], wc, rs);
     w->dev_data.upload(h);
     w->dev_grad = grad_arena.slice((size_t)woff, (size_t)w->size);
     woff += w->size;
@@ -635,7 +657,7 @@ void GCN::build(const GCNData &data) {
   pinned = PinnedBuffer<float>(8);
   size_t ws = 0;
   for (int l = 0; l < L; l++)
-    ws = std::max(ws, gemm_tn_workspace(rows, dims[(size_t)l + 1], dims[(size_t)l]));
+    ws = std::max(ws, gemm_tn_workspace(rows, weight_cols(dims[(size_t)l + 1]), dims[(size_t)l]));
   // the fused loss kernel's per-block W.grad partials of the output layer (fuse_output >= 2)
   ws = std::max(ws, tn_reduce_blocks_workspace(xent_blocks(prow), 16, 48));
   gemm_ws.allocate(ws / sizeof(float) + 64);
@@ -886,7 +908,8 @@ void GCN::insert_first_layer() {
   const Dropout *dptr = drop.get();
   dropouts_.push_back(dptr);
   modules.push_back(std::move(drop));
-  auto var1 = std::make_shared<Variable>(prow, h, true, round_up4(h));
+  const int wc = weight_cols(h);
+  auto var1 = std::make_shared<Variable>(prow, wc, true, round_up4(wc));
   variables.push_back(var1);
   variables.push_back(weights[0]);
   auto sm = std::make_unique<SparseMatmul>(&feats, weights[0], var1, dptr, &ctx);
@@ -894,7 +917,7 @@ void GCN::insert_first_layer() {
   modules.push_back(std::move(sm));
   auto var2 = std::make_shared<Variable>(prow, h, true, round_up4(h));
   variables.push_back(var2);
-  if (params.attention) {  // (no consumer, no eval_ax: SparseMatmul's plain products)
+  if (custom_aggregation()) {  // (no consumer, no eval_ax: SparseMatmul's plain products)
     insert_aggregation(var1, var2, h, 0, false);
   } else {
     auto gs = std::make_unique<GraphSum>(var1, var2, graph.get(), h, &ctx);
@@ -911,6 +934,12 @@ void GCN::insert_first_layer() {
 
 void GCN::insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,
                              int dim, int layer, bool last) {
+  if (params.aggregator != 0) {
+    modules.push_back(std::make_unique<SageAggregate>(var1, var2, graph.get(), mean_fwd_graph.get(),
+                                                      mean_bwd_graph.get(), dim, params.aggregator,
+                                                      params.root_weight));
+    return;
+  }
   if (!attn_var) {
     modules.push_back(std::make_unique<GraphSum>(var1, var2, graph.get(), dim, &ctx, last));
     return;
@@ -941,11 +970,12 @@ void GCN::insert_layer(int in_dim, int out_dim, float dropout, int layer) {
   auto drop = std::make_unique<Dropout>(prev, dropout, rngs[(size_t)layer], &ctx);
   dropouts_.push_back(drop.get());
   modules.push_back(std::move(drop));
-  auto var1 = std::make_shared<Variable>(prow, out_dim, true, round_up4(out_dim));
+  const int wc = weight_cols(out_dim);
+  auto var1 = std::make_shared<Variable>(prow, wc, true, round_up4(wc));
   variables.push_back(var1);
   variables.push_back(weights[(size_t)layer]);
   modules.push_back(std::make_unique<Matmul>(prev, weights[(size_t)layer], var1,
-                                             part.local_rows(), in_dim, out_dim, &ctx));
+                                             part.local_rows(), in_dim, wc, &ctx));
   auto var2 = std::make_shared<Variable>(prow, out_dim, true, round_up4(out_dim));
   variables.push_back(var2);
   insert_aggregation(var1, var2, out_dim, layer, false);
@@ -968,7 +998,7 @@ void GCN::insert_last_layer() {
   dropouts_.push_back(drop.get());
   modules.push_back(std::move(drop));
   const bool small = knobs_.reassoc_small && hl <= 16 && part.bounds.back() < kMmSideRows;
-  if (params.reassociate_last && !params.attention && (hl < C || small) && graph_symmetric) {
+  if (params.reassociate_last && !custom_aggregation() && (hl < C || small) && graph_symmetric) {
     // out = Â (H W) computed as (Â H) W: the same product (Â is symmetric, so the backward
     // Â dOut W^T = Â (dOut W^T) and W.grad = H^T Â dOut = (Â H)^T dOut also match), but the
     // GraphSum gathers rows of width hl instead of C.  Only the fp32 rounding order differs.
@@ -998,13 +1028,14 @@ void GCN::insert_last_layer() {
     }
     return;
   }
-  auto var1 = std::make_shared<Variable>(prow, C, true, round_up4(C));
+  const int wc = weight_cols(C);
+  auto var1 = std::make_shared<Variable>(prow, wc, true, round_up4(wc));
   variables.push_back(var1);
   variables.push_back(weights.back());
   modules.push_back(std::make_unique<Matmul>(prev, weights.back(), var1, part.local_rows(), hl,
-                                             C, &ctx));
+                                             wc, &ctx));
   auto out = std::make_shared<Variable>(prow, C, true, round_up4(C));
-  if (!params.attention) restricted_vars.push_back((int)variables.size());
+  if (!custom_aggregation()) restricted_vars.push_back((int)variables.size());
   variables.push_back(out);
   insert_aggregation(var1, out, C, L - 1, true);
   if (params.multilabel) modules.push_back(std::make_unique<BCEWithLogitsLoss>(out, C, &ctx));
@@ -1021,7 +1052,7 @@ void GCN::set_split(int split) {
   ctx.split_graph = nullptr;
   ctx.split_rows = nullptr;
   ctx.split_colgraph = nullptr;
-  if (knobs_.split_rows && !comm && graph && !params.attention) {
+  if (knobs_.split_rows && !comm && graph && !custom_aggregation()) {
     if (!split_graphs[split]) {
       split_graphs[split] = graph->row_subset(split_rows_host[split]);
       split_rows_dev[split].allocate(std::max<size_t>(split_rows_host[split].size(), 1));
@@ -1067,7 +1098,7 @@ void GCN::set_split(int split) {
     }
     for (auto &cg : chunk_col_graphs) ctx.chunk_col_graphs.push_back(cg.get());
   }
-  if (knobs_.split_cols && !comm && graph && split == 1 && !params.attention) {  // (after training)
+  if (knobs_.split_cols && !comm && graph && split == 1 && !custom_aggregation()) {  // (after training)
     if (!split_colgraphs[split]) split_colgraphs[split] = graph->col_subset(split_rows_host[split]);
     ctx.split_colgraph = split_colgraphs[split].get();
   }
@@ -1547,7 +1578,8 @@ int GCN::fused_residuals() const {
 }
 
 bool GCN::graphsum_lds() const {
-  if (attn_var) return false;  // no GraphSum runs
+  if (attn_var || params.aggregator == 2) return false;  // no GraphSum runs
+  if (mean_fwd_graph) return mean_fwd_graph->uses_lds(16);
   if (graph) return graph->uses_lds(16);
   return !chunk_graphs.empty() && chunk_graphs.front()->uses_lds(16);
 }
@@ -1641,6 +1673,12 @@ void GCN::save(const std::string &path) {
       ck.attention_dropout = params.attention_dropout;
     }
   }
+  if (params.aggregator != 0) {  // version 6: its block, and W_l [d_in][2 d_l] under root_weight
+    ck.flags |= kCheckpointSage;
+    ck.version = kCheckpointVersionSage;
+    ck.aggregator = params.aggregator;
+    ck.root_weight = params.root_weight ? 1 : 0;
+  }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1660,6 +1698,10 @@ void GCN::load(const std::string &path, int flags) {
               ck.dims.front() == params.input_dim && ck.dims.back() == params.output_dim;
   for (int l = 0; same && l + 1 < L; l++)
     same = ck.dims[(size_t)l + 1] == params.hidden_dims[(size_t)l];
+  // (a weights-only load crosses the aggregator wherever the tensor shapes agree: the root weight
+  // alone decides them)
+  same = same && ck.root_weight == (params.root_weight ? 1 : 0);
+  if (same && resume) same = ck.aggregator == params.aggregator;
   if (same && resume) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
     // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)

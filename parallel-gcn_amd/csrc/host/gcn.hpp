@@ -54,6 +54,12 @@ struct GCNParams {
   // DropoutRng per layer behind the Dropout modules' in the epoch's draws, init_dropout_rng)
   int attention_heads = 1;
   float attention_dropout = 0.0f;
+  // GraphSAGE: every layer's GraphSum is a SageAggregate (module.hpp) on the pattern as loaded,
+  // 1 = the mean over a row's slots (GraphSum kernels on 1 / len values), 2 = the element-wise
+  // max (k_sage.hip); with root_weight every W_l is [d_in][2 d_l] and the layer's own row enters
+  // through the first d_l columns of H W_l.  Single GPU, widths <= 128
+  int aggregator = 0;
+  bool root_weight = false;
 };
 
 struct AdamParams {
@@ -175,6 +181,8 @@ class GCN {
   // the heads of its hidden layers, and the layers that drop attention weights in training
   int attention_heads() const { return attn_var ? params.attention_heads : 1; }
   int attention_dropout_layers() const { return (int)attn_rngs.size(); }
+  int aggregator() const { return params.aggregator; }
+  bool root_weight() const { return params.root_weight; }
   // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
   int fused_norm_tails() const;
   // diagnostics (syncs): non-zero elements in the edge-cut padding rows of the variables the
@@ -213,7 +221,15 @@ class GCN {
   // attention: per layer a_dst_l[d_l] then a_src_l[d_l] (d_l the layer's output width), one
   // tensor, the last of `weights` and of `variables` (behind norm_var); null without attention
   shared_ptr<Variable> attn_var;
-  // the layer's aggregation from var1 to var2: a GraphSum, or a GraphAttention on attn_var
+  // aggregator 1: the mean graphs every SageAggregate sums over (pgcn_graph_create_mean's two)
+  std::unique_ptr<DevGraph> mean_fwd_graph, mean_bwd_graph;
+  // layer l's weight has this many columns: 2 d_l under root_weight
+  int weight_cols(int d) const { return params.root_weight ? 2 * d : d; }
+  // an engine whose aggregation is not a GraphSum module: no reassociated output layer, no Â X
+  // precompute, no output-row restriction, the loss unfused
+  bool custom_aggregation() const { return params.attention || params.aggregator != 0; }
+  // the layer's aggregation from var1 to var2: a GraphSum, a GraphAttention on attn_var or a
+  // SageAggregate
   void insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,
                           int dim, int layer, bool last);
   int fused_tails_ = 0;  // GraphSum epilogues carrying ReLU / Dropout work (forward + backward)

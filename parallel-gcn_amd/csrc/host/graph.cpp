@@ -705,6 +705,53 @@ const GatPattern &DevGraph::gat_pattern() {
   return gat_->p;
 }
 
+std::unique_ptr<DevGraph> make_mean_graph(int n, const int *indptr, const int *indices,
+                                          bool transpose, const Knobs &knobs) {
+  const int nnz = indptr[n];
+  std::vector<float> inv((size_t)n, 0.0f), one((size_t)n, 1.0f);
+  for (int i = 0; i < n; i++)
+    if (indptr[i + 1] > indptr[i]) inv[(size_t)i] = 1.0f / (float)(indptr[i + 1] - indptr[i]);
+  std::vector<float> vals((size_t)std::max(nnz, 1));
+  std::unique_ptr<DevGraph> g;
+  if (!transpose) {
+    for (int i = 0; i < n; i++)
+      for (int k = indptr[i]; k < indptr[i + 1]; k++) vals[(size_t)k] = inv[(size_t)i];
+    g = std::make_unique<DevGraph>(n, n, indptr, indices, vals.data(), knobs);
+    g->set_scales(std::move(inv), std::move(one));
+    return g;
+  }
+  std::vector<int> tptr((size_t)n + 1, 0), trow((size_t)std::max(nnz, 1));
+  for (int k = 0; k < nnz; k++) tptr[(size_t)indices[k] + 1]++;
+  for (int j = 0; j < n; j++) tptr[(size_t)j + 1] += tptr[(size_t)j];
+  std::vector<int> fill(tptr.begin(), tptr.end() - 1);
+  for (int i = 0; i < n; i++)
+    for (int k = indptr[i]; k < indptr[i + 1]; k++) {
+      const int o = fill[(size_t)indices[k]]++;
+      trow[(size_t)o] = i;
+      vals[(size_t)o] = inv[(size_t)i];
+    }
+  g = std::make_unique<DevGraph>(n, n, tptr.data(), trow.data(), vals.data(), knobs);
+  g->set_scales(std::move(one), std::move(inv));
+  return g;
+}
+
+const SageWs &DevGraph::sage_ws() {
+  if (sage_) return sage_->w;
+  const GatPattern &p = gat_pattern();
+  auto s = std::make_unique<SageDev>();
+  s->row_val.allocate(std::max<size_t>((size_t)p.n_row_segs * kSageWsStride, 4));
+  s->row_arg.allocate(std::max<size_t>((size_t)p.n_row_segs * kSageWsStride, 4));
+  s->col_ws.allocate(std::max<size_t>((size_t)p.n_col_segs * kSageWsStride, 4));
+  s->row_val.zero();
+  s->row_arg.zero();
+  s->col_ws.zero();
+  s->w.row_val = s->row_val.get();
+  s->w.row_arg = s->row_arg.get();
+  s->w.col_ws = s->col_ws.get();
+  sage_ = std::move(s);
+  return sage_->w;
+}
+
 double DevGraph::algorithmic_bytes(int dim) const {
   // 4(N+1) indptr + 8 nnz (index + value) + 4 N_in d (read) + 4 N d (write)
   return 4.0 * (n_rows_ + 1) + 8.0 * (double)nnz_ + 4.0 * (double)n_cols_ * dim +

@@ -74,6 +74,15 @@ LdsHost build_ring_host(int n_rows, int n_cols, const std::vector<int> &indptr,
 int ring_window_for(int n_rows, int n_cols, long long nnz, int n_blocks, const Knobs &k);
 void ring_emulate(const LdsHost &h, int n_rows, const float *in, double *out);
 
+class DevGraph;
+// GraphSAGE's mean aggregator as a GraphSum (square pattern, validated by the caller): the
+// pattern with 1 / len_i on every slot of row i and scales (1 / len, 1), or (transpose) the
+// transposed pattern -- column j's slots in CSR order as row j -- whose slot (j, i) carries
+// 1 / len_i, scales (1, 1 / len).  1 / len_i is one 1.0f / (float)len_i; a row without a slot
+// scales nothing.
+std::unique_ptr<DevGraph> make_mean_graph(int n, const int *indptr, const int *indices,
+                                          bool transpose, const Knobs &knobs = process_knobs());
+
 class DevGraph {
  public:
   // CSR with n_rows rows and column ids < n_cols; `vals` aligned with `indices`.  Every schedule
@@ -125,6 +134,9 @@ class DevGraph {
   // never runs attention allocates none of it.  The forward's segment partials live here too, so
   // two attention forwards on one graph must not overlap.
   const GatPattern &gat_pattern();
+  // The max aggregator's segment partials (k_sage.hip), allocated at the first call on top of
+  // gat_pattern(): two max aggregations on one graph must not overlap.
+  const SageWs &sage_ws();
 
   // Enables the d = 16 LDS path (k_graphsum_ring): out_i = row_scale_i * sum_j col_scale_j
   // in_j over the CSR pattern, i.e. vals_ij = row_scale_i * col_scale_j.
@@ -174,6 +186,12 @@ class DevGraph {
     DeviceBuffer<float> row_ws;
   };
   std::unique_ptr<GatDev> gat_;
+  struct SageDev {
+    SageWs w;
+    DeviceBuffer<float> row_val, col_ws;
+    DeviceBuffer<int> row_arg;
+  };
+  std::unique_ptr<SageDev> sage_;
   DevGraph *table_owner_ = nullptr;  // share_tables: the graph whose table buffers this one reads
   float *table_scratch();            // the one-pass table (own or the owner's)
   float *table_wide(size_t floats);  // the multi-pass tables (own or the owner's), >= floats

@@ -742,6 +742,77 @@ void GraphAttention::backward(const Stream &s) const {
 }
 
 // ------------------------------------------------------------------------------------------
+// SageAggregate (k_sage.hip; the mean on DevGraph::graphsum)
+// ------------------------------------------------------------------------------------------
+SageAggregate::SageAggregate(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
+                             DevGraph *graph_, DevGraph *mean_fwd_, DevGraph *mean_bwd_, int dim_,
+                             int aggregator_, bool root_)
+    : in(std::move(in_)), out(std::move(out_)), graph(graph_), mean_fwd(mean_fwd_),
+      mean_bwd(mean_bwd_), dim(dim_), aggregator(aggregator_), root(root_),
+      ld_s((dim_ + 3) / 4 * 4) {
+  PGCN_CHECK(in && out && graph && dim >= 1 && dim <= kSageMaxWidth &&
+                 in->cols == (root ? 2 : 1) * dim && out->cols == dim &&
+                 graph->rows() == graph->cols() && in->rows >= graph->rows() &&
+                 out->rows >= graph->rows() && in->ld % 4 == 0 && out->ld % 4 == 0,
+             PGCN_E_INVALID, "sage: widths up to 128 on a square pattern");
+  PGCN_CHECK(aggregator == 2 || (aggregator == 1 && mean_fwd && mean_bwd &&
+                                 mean_fwd->rows() == graph->rows() &&
+                                 mean_bwd->rows() == graph->rows()),
+             PGCN_E_INVALID, "sage: aggregator 1 (mean, with its two graphs) or 2 (max)");
+  const size_t n = (size_t)std::max(graph->rows(), 1);
+  if (aggregator == 2) {  // (host build and upload: now, not in an epoch)
+    graph->sage_ws();
+    arg.allocate(n * ld_s);
+    arg.zero();
+  } else {
+    mean_fwd->prepare(dim);
+    mean_bwd->prepare(dim);
+  }
+  if (staged()) {  // (the padding columns stay zero: the copies write [0, dim) only)
+    q.allocate(n * ld_s);
+    dq.allocate(n * ld_s);
+    q.zero();
+    dq.zero();
+  }
+}
+
+void SageAggregate::forward(bool training, const Stream &s) const {
+  const int n = graph->rows();
+  const float *P = in->dev_data.get(), *R = root ? P : nullptr;
+  const float *Q = root ? P + dim : P;
+  int ld_q = in->ld;
+  if (staged()) {
+    launch_copy_cols(Q, in->ld, q.get(), ld_s, n, dim, false, s.get());
+    Q = q.get();
+    ld_q = ld_s;
+  }
+  if (aggregator == 2) {
+    launch_agg_max_fwd(graph->gat_pattern(), graph->sage_ws(), Q, ld_q, dim, R, in->ld,
+                       out->dev_data.get(), out->ld, training ? arg.get() : nullptr, ld_s, s.get());
+    return;
+  }
+  mean_fwd->graphsum(Q, ld_q, out->dev_data.get(), out->ld, dim, s.get());
+  if (R) launch_copy_cols(R, in->ld, out->dev_data.get(), out->ld, n, dim, true, s.get());
+}
+
+void SageAggregate::backward(const Stream &s) const {
+  if (!in->dev_grad || !out->dev_grad) return;
+  const int n = graph->rows();
+  // (a residual layer's out.grad stays unmasked: its ReLU backward wrote dev_grad_z)
+  const float *g = out->dev_grad_z ? out->dev_grad_z.get() : out->dev_grad.get();
+  float *din = in->dev_grad.get();
+  float *dQ = staged() ? dq.get() : root ? din + dim : din;
+  const int ld_dq = staged() ? ld_s : in->ld;
+  if (aggregator == 2)
+    launch_agg_max_bwd(graph->gat_pattern(), graph->sage_ws(), g, out->ld, arg.get(), ld_s, dim,
+                       dQ, ld_dq, s.get());
+  else
+    mean_bwd->graphsum(g, out->ld, dQ, ld_dq, dim, s.get());
+  if (staged()) launch_copy_cols(dQ, ld_s, din + dim, in->ld, n, dim, false, s.get());
+  if (root) launch_copy_cols(g, out->ld, din, in->ld, n, dim, false, s.get());
+}
+
+// ------------------------------------------------------------------------------------------
 // ReLU (src/module.cu:215-265)
 // ------------------------------------------------------------------------------------------
 ReLU::ReLU(shared_ptr<Variable> in_) : in(std::move(in_)) {

@@ -380,6 +380,36 @@ class GraphAttention : public Module {
   float scale() const { return 1.0f / (1.0f - p); }
 };
 
+// GraphSAGE aggregation in GraphSum's place (the reference has none).  `in` is the layer's H W:
+// [rows][dim] (no root weight: Q = in) or [rows][2 dim] (root weight: R = in[:, 0:dim], Q =
+// in[:, dim:2 dim]); out_i = R_i + aggr over row i's slots of Q_j on the pattern as loaded.
+//   mean (aggregator 1): `mean_fwd` / `mean_bwd` are the engine's two make_mean_graph graphs;
+//     the forward is mean_fwd's graphsum (whatever kernel DevGraph picks) and one strided add of
+//     R, the backward mean_bwd's graphsum of out.grad.
+//   max (aggregator 2): launch_agg_max_fwd adds R in its final write and a training forward
+//     keeps the winning slots in `arg` (owned here) for launch_agg_max_bwd.
+// The backward reads out->dev_grad_z when that buffer exists (a residual layer), else
+// out->dev_grad, and writes in->dev_grad whole: dR = that gradient (one strided copy), dQ beside
+// it.  When dim is no multiple of 4 (an output layer) the Q half of `in` does not start on the
+// 16-byte grid: Q and dQ then pass through the staging buffers `q` / `dq` (one strided copy each
+// way).  Single GPU only.
+class SageAggregate : public Module {
+  shared_ptr<Variable> in, out;
+  DevGraph *graph, *mean_fwd, *mean_bwd;
+  int dim, aggregator;
+  bool root;
+  DeviceBuffer<int> arg;
+  DeviceBuffer<float> q, dq;
+  int ld_s;  // the stride of arg, q and dq: round_up4(dim)
+  bool staged() const { return root && dim % 4 != 0; }
+
+ public:
+  SageAggregate(shared_ptr<Variable> in_, shared_ptr<Variable> out_, DevGraph *graph_,
+                DevGraph *mean_fwd_, DevGraph *mean_bwd_, int dim_, int aggregator_, bool root_);
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+};
+
 // include/module.cuh:90-99
 class ReLU : public Module {
   shared_ptr<Variable> in;

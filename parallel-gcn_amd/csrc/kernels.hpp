@@ -411,6 +411,32 @@ void launch_gat_bwd_mh(const GatPattern &g, const float *P, int ld_p, const floa
                        const float *G, int ld_g, const float *a_dst, const float *a_src, float *dP,
                        int ld_dp, int d, int heads, const uint64_t *drop_mask, long long drop_base,
                        float drop_scale, float *da, void *workspace, hipStream_t s);
+// ---- GraphSAGE's max aggregator over the same pattern (k_sage.hip) ----------------------------
+// out_i[c] = add_i[c] + max over row i's slots of in_j[c] (one add; `add` null: the maximum),
+// arg_i[c] (or null) the global CSR slot that won: a candidate replaces the incumbent only when
+// strictly greater, so the lowest slot of equal values wins.  An empty row: out = add (or 0),
+// arg = -1.  The widths, strides and padding rules of the attention kernels; arg's [d,
+// round_up4(d)) is -1.  Inputs are taken as finite.  Rows / columns longer than kGatSeg slots
+// leave their segments' partials in `ws` (DevGraph::sage_ws: two calls on one graph must not
+// overlap).  nnz must fit an int.
+constexpr int kSageMaxWidth = kGatMaxWidth;
+constexpr int kSageWsStride = kSageMaxWidth;
+struct SageWs {
+  float *row_val = nullptr;  // forward: [n_row_segs][kSageWsStride] the segments' maxima ...
+  int *row_arg = nullptr;    // ... and their slots
+  float *col_ws = nullptr;   // backward: [n_col_segs][kSageWsStride] the segments' partial rows
+};
+void launch_agg_max_fwd(const GatPattern &g, const SageWs &ws, const float *in, int ld_in, int d,
+                        const float *add, int ld_add, float *out, int ld_out, int *arg,
+                        int ld_arg, hipStream_t s);
+// din_j[c] = sum over the slots s = (i, j) into column j with arg_i[c] == s of G_i[c], in the
+// transposed index's order (no float atomics); a column without incoming slots: a zero row
+void launch_agg_max_bwd(const GatPattern &g, const SageWs &ws, const float *G, int ld_g,
+                        const int *arg, int ld_arg, int d, float *din, int ld_din, hipStream_t s);
+// dst[i][c] = src[i][c] (add: dst[i][c] + src[i][c]) for c < cols of n rows, any strides and
+// alignment: the root half of a SAGE layer in and out of its [n][2 d] variable
+void launch_copy_cols(const float *src, int ld_src, float *dst, int ld_dst, int n, int cols,
+                      bool add, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

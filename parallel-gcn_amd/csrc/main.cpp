@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -21,6 +21,9 @@
 // widths and attn_dropout=<p> drops attention weights in training (pgcn_params.attention_heads /
 // attention_dropout; `gcn-par cora attention=1 heads=8 attn_dropout=0.6` with hidden_dims=64 is
 // the published GAT), both also keys of the parameter file.
+// aggregator=mean|max (or 1|2) [root_weight=1] (command line or parameter file): GraphSAGE layers
+// in the GraphSums' place, pgcn_params.aggregator / root_weight; `gcn-par cora aggregator=max
+// root_weight=1` trains the max-pooling variant with a self term.
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +37,16 @@
 static void trim(std::string &s) {
   size_t a = s.find_first_not_of(" \t\r\n"), b = s.find_last_not_of(" \t\r\n");
   s = a == std::string::npos ? "" : s.substr(a, b - a + 1);
+}
+
+// aggregator=: mean / max by name or 0 / 1 / 2; anything else is left for the engine to refuse
+static int aggregator_id(const std::string &v) {
+  if (v == "mean") return 1;
+  if (v == "max") return 2;
+  if (v == "gcn" || v == "none") return 0;
+  char *end = nullptr;
+  const long x = std::strtol(v.c_str(), &end, 10);
+  return (end && *end == '\0' && !v.empty()) ? (int)x : -1;
 }
 
 static bool load_params(const char *path, pgcn_params *p) {
@@ -75,6 +88,8 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "multilabel") p->multilabel = std::atoi(v.c_str());
     else if (k == "heads") p->attention_heads = std::atoi(v.c_str());
     else if (k == "attn_dropout") p->attention_dropout = std::strtof(v.c_str(), nullptr);
+    else if (k == "aggregator") p->aggregator = aggregator_id(v);
+    else if (k == "root_weight") p->root_weight = std::atoi(v.c_str());
   }
   return true;
 }
@@ -91,6 +106,8 @@ int main(int argc, char **argv) {
   std::string load, save, predict;
   int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
+  int root_weight = -1;
+  std::string aggregator;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -107,6 +124,8 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "heads=", 6)) heads = std::atoi(argv[i] + 6);
     if (!std::strncmp(argv[i], "attn_dropout=", 13))
       attn_dropout = std::strtof(argv[i] + 13, nullptr);
+    if (!std::strncmp(argv[i], "aggregator=", 11)) aggregator = argv[i] + 11;
+    if (!std::strncmp(argv[i], "root_weight=", 12)) root_weight = std::atoi(argv[i] + 12);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -121,6 +140,8 @@ int main(int argc, char **argv) {
   if (attention >= 0) p.attention = attention;
   if (heads >= 0) p.attention_heads = heads;
   if (attn_dropout >= 0.0f) p.attention_dropout = attn_dropout;
+  if (!aggregator.empty()) p.aggregator = aggregator_id(aggregator);
+  if (root_weight >= 0) p.root_weight = root_weight;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
