@@ -200,7 +200,11 @@ int pgcn_debug_layernorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, 
  *     slots into column j; dP_j = sum over the slots into j of alpha_s G_i + du_j a_dst + dv_j
  *     a_src; da [2][d] = {sum du_i P_i, sum dv_j P_j} (a_dst's gradient, then a_src's).
  *     `workspace`: pgcn_gat_bwd_workspace(g, d) bytes, 16-byte aligned (dx per slot, du, dv and
- *     the partial sums).  d is passed (after ld_dp): the widths cannot be told from the strides.
+ *     the partial sums): the value of pgcn_gat_bwd_workspace_mh(g, d, 1), whose long columns'
+ *     segment partials are 192 floats each.  d is passed (after ld_dp): the widths cannot be
+ *     told from the strides.
+ * These three entries are the _mh entries below at heads = 1 without a mask, behind their own
+ * argument checks: one set of kernels serves both.
  * 1 <= d <= 128; every ld a multiple of 4 and >= d; every row 16-byte aligned.  The float4s
  * covering columns [0, round_up4(d)) of Z and dP are written, zero from column d on; columns
  * beyond them are left alone.  Padding columns of P, Z and G are never read into the result.
@@ -237,8 +241,9 @@ int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
  * drop_mask is a device bit array (bit b = word b / 64, bit b % 64: the triple the fused GraphSum
  * entries take) or NULL for no dropout; alpha receives the weights BEFORE dropout (each head's
  * sum to 1 per row) and is required with a mask.
- * heads == 1: any d in 1..128, and without a mask exactly pgcn_gat_scores / _fwd / _bwd (their
- * kernels, their bits); one head under an all-ones mask of scale 1 gives those bits too.
+ * heads == 1: any d in 1..128; without a mask this is what pgcn_gat_scores / _fwd / _bwd run
+ * (the same kernels, the same bits); one head under an all-ones mask of scale 1 gives those bits
+ * too.
  * heads > 1: heads divides d and dh is 4, 8, 16, 32, 64 or 128 -- a lane's float4 then belongs to
  * one head and a head is an aligned power-of-two group of lanes; anything else is
  * PGCN_E_INVALID before anything touches the device, like the checks of the entries above.
@@ -246,7 +251,7 @@ int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
  * a call launches as many kernels as the single-head call on the same graph.  No float atomics;
  * every summation order depends on the pattern, d and heads only.
  * `workspace`: pgcn_gat_bwd_workspace_mh(g, d, heads) bytes (dx [nnz][heads], du, dv
- * [n][heads], the partial sums); with heads == 1 it serves calls with and without a mask. */
+ * [n][heads], the partial sums); it does not depend on whether a mask is passed. */
 int pgcn_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
                        const float *a_src, float *u /* [n][heads] */, float *v, void *stream);
 int pgcn_gat_fwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *u, const float *v,

@@ -497,7 +497,7 @@ int pgcn_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
                "gat_scores: null or misaligned argument");
     if (n == 0) return;
     check_device();
-    launch_gat_scores(P, ld_p, n, d, a_dst, a_src, u, v, as_stream(stream));
+    launch_gat_scores(P, ld_p, n, d, 1, a_dst, a_src, u, v, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }
@@ -510,8 +510,8 @@ int pgcn_gat_fwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
                "gat_fwd: null or misaligned argument");
     PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_fwd: square pattern");
     check_device();
-    launch_gat_fwd(g->g->gat_pattern(), P, ld_p, u, v, slope, Z, ld_z, d, alpha,
-                   as_stream(stream));
+    launch_gat_fwd(g->g->gat_pattern(), P, ld_p, u, v, slope, Z, ld_z, d, 1, nullptr, 0, 1.0f,
+                   alpha, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }
@@ -519,7 +519,7 @@ int pgcn_gat_fwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
 size_t pgcn_gat_bwd_workspace(const pgcn_graph *g, int d) {
   if (!g || !g->g || d < 1 || d > kGatMaxWidth || g->g->rows() != g->g->cols()) return 0;
   size_t bytes = 0;
-  (void)guarded([&] { bytes = gat_bwd_workspace(g->g->gat_pattern(), d); });
+  (void)guarded([&] { bytes = gat_bwd_workspace(g->g->gat_pattern(), d, 1); });
   return bytes;
 }
 
@@ -536,7 +536,7 @@ int pgcn_gat_bwd(const pgcn_graph *g, const float *P, int ld_p, const float *u, 
     PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_bwd: square pattern");
     check_device();
     launch_gat_bwd(g->g->gat_pattern(), P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst,
-                   a_src, dP, ld_dp, d, da, workspace, as_stream(stream));
+                   a_src, dP, ld_dp, d, 1, nullptr, 0, 1.0f, da, workspace, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }
@@ -559,7 +559,7 @@ int pgcn_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const 
                "gat_scores: null or misaligned argument");
     if (n == 0) return;
     check_device();
-    launch_gat_scores_mh(P, ld_p, n, d, heads, a_dst, a_src, u, v, as_stream(stream));
+    launch_gat_scores(P, ld_p, n, d, heads, a_dst, a_src, u, v, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }
@@ -576,8 +576,8 @@ int pgcn_gat_fwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *
                "gat_fwd: null or misaligned argument");
     PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_fwd: square pattern");
     check_device();
-    launch_gat_fwd_mh(g->g->gat_pattern(), P, ld_p, u, v, slope, Z, ld_z, d, heads, drop_mask,
-                      drop_base, drop_scale, alpha, as_stream(stream));
+    launch_gat_fwd(g->g->gat_pattern(), P, ld_p, u, v, slope, Z, ld_z, d, heads, drop_mask,
+                   drop_base, drop_scale, alpha, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }
@@ -587,7 +587,7 @@ size_t pgcn_gat_bwd_workspace_mh(const pgcn_graph *g, int d, int heads) {
       g->g->rows() != g->g->cols())
     return 0;
   size_t bytes = 0;
-  (void)guarded([&] { bytes = gat_bwd_workspace_mh(g->g->gat_pattern(), d, heads); });
+  (void)guarded([&] { bytes = gat_bwd_workspace(g->g->gat_pattern(), d, heads); });
   return bytes;
 }
 
@@ -606,9 +606,9 @@ int pgcn_gat_bwd_mh(const pgcn_graph *g, const float *P, int ld_p, const float *
                PGCN_E_INVALID, "gat_bwd: null or misaligned argument");
     PGCN_CHECK(g->g->rows() == g->g->cols(), PGCN_E_INVALID, "gat_bwd: square pattern");
     check_device();
-    launch_gat_bwd_mh(g->g->gat_pattern(), P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst,
-                      a_src, dP, ld_dp, d, heads, drop_mask, drop_base, drop_scale, da, workspace,
-                      as_stream(stream));
+    launch_gat_bwd(g->g->gat_pattern(), P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst,
+                   a_src, dP, ld_dp, d, heads, drop_mask, drop_base, drop_scale, da, workspace,
+                   as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }

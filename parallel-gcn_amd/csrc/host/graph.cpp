@@ -684,7 +684,7 @@ const GatPattern &DevGraph::gat_pattern() {
   up(g->row_segs, rsegs);
   up(g->col_segs, csegs);
   up(g->long_cols, lcols);
-  g->row_ws.allocate(std::max<size_t>(rsegs.size() * kGatWsStrideMh, 4));
+  g->row_ws.allocate(std::max<size_t>(rsegs.size() * kGatWsStride, 4));
   g->row_ws.zero();
   GatPattern &p = g->p;
   p.n = n;

@@ -706,7 +706,7 @@ GraphAttention::GraphAttention(shared_ptr<Variable> in_, shared_ptr<Variable> ou
   u.allocate((size_t)std::max(g.n, 1) * heads);
   v.allocate((size_t)std::max(g.n, 1) * heads);
   alpha.allocate((size_t)std::max<long long>(g.nnz, 1) * heads);
-  ws.allocate(std::max<size_t>(gat_bwd_workspace_mh(g, dim, heads) / sizeof(float), 4));
+  ws.allocate(std::max<size_t>(gat_bwd_workspace(g, dim, heads) / sizeof(float), 4));
   z.allocate((size_t)std::max(g.n, 1) * out->ld);
   for (const auto *b : {&u, &v, &alpha, &ws, &z}) b->zero();
 }
@@ -718,11 +718,11 @@ void GraphAttention::forward(bool training, const Stream &s) const {
   if (drop)  // this epoch's mask of the layer: the stream moves on by one period per draw
     launch_dropout_mask(rng->states.get(), rng->n_chunks, 64 * rng->chunk_lo, rng->elem_end,
                         this->p, rng->mask.get(), ctx->jump_table, s.get(), 0, rng->per);
-  launch_gat_scores_mh(in->dev_data.get(), in->ld, p.n, dim, heads, a, a + dim, u.get(), v.get(),
-                       s.get());
-  launch_gat_fwd_mh(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, out->dev_data.get(),
-                    out->ld, dim, heads, drop ? rng->mask.get() : nullptr, drop ? rng->mask_base : 0,
-                    scale(), training ? alpha.get() : nullptr, s.get());
+  launch_gat_scores(in->dev_data.get(), in->ld, p.n, dim, heads, a, a + dim, u.get(), v.get(),
+                    s.get());
+  launch_gat_fwd(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, out->dev_data.get(),
+                 out->ld, dim, heads, drop ? rng->mask.get() : nullptr, drop ? rng->mask_base : 0,
+                 scale(), training ? alpha.get() : nullptr, s.get());
   if (training && p.n > 0)
     PGCN_HIP(hipMemcpyAsync(z.get(), out->dev_data.get(), sizeof(float) * (size_t)p.n * out->ld,
                             hipMemcpyDeviceToDevice, s.get()));
@@ -735,10 +735,10 @@ void GraphAttention::backward(const Stream &s) const {
   // (a residual layer's out.grad stays unmasked: its ReLU backward wrote dev_grad_z)
   const float *g = out->dev_grad_z ? out->dev_grad_z.get() : out->dev_grad.get();
   // (the mask of the training forward this backward belongs to)
-  launch_gat_bwd_mh(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, alpha.get(), z.get(),
-                    out->ld, g, out->ld, a, a + dim, in->dev_grad.get(), in->ld, dim, heads,
-                    rng ? rng->mask.get() : nullptr, rng ? rng->mask_base : 0, scale(),
-                    attn->dev_grad.get() + offset, ws.get(), s.get());
+  launch_gat_bwd(p, in->dev_data.get(), in->ld, u.get(), v.get(), kSlope, alpha.get(), z.get(),
+                 out->ld, g, out->ld, a, a + dim, in->dev_grad.get(), in->ld, dim, heads,
+                 rng ? rng->mask.get() : nullptr, rng ? rng->mask_base : 0, scale(),
+                 attn->dev_grad.get() + offset, ws.get(), s.get());
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,42 +1,47 @@
-// parallel-gcn_amd/csrc/k_gat.hip -- single-head additive graph attention over the CSR slots of
-// a square pattern, for gfx950 (GAT; the reference has no such module): the per-row softmax of
-// the slot scores fused with the weighted row gather, and its backward without float atomics.
+// parallel-gcn_amd/csrc/k_gat.hip -- additive graph attention over the CSR slots of a square
+// pattern, for gfx950 (GAT; the reference has no such module): K heads inside the width d, the
+// per-row, per-head softmax of the slot scores fused with the weighted row gather, dropout on the
+// attention weights, and the backward without float atomics.
 //
 // Layout (every gather kernel): one wave per work item -- a row (forward, backward row pass) or
-// a column of the transposed index (backward column pass).  The wave is cut into 64 / GL
-// neighbour groups of GL lanes, lane li of a group holding the float4 at column 4 * li of its
-// neighbour's row, so 64 / GL neighbours are in flight per step (16 at d <= 16):
-//   d <= 4: GL 1 | <= 8: 2 | <= 16: 4 | <= 32: 8 | <= 64: 16 | <= 128: 32
-// Group q takes slots q, q + 64 / GL, ... of the item; the groups' sums meet in xor butterflies
-// over the lane offsets GL .. 32 (every lane ends with the same bits).  Scalars of a row (its
-// score maximum and exponent sum, du_i) are summed one slot per lane, then over the wave.
+// a column of the transposed index (backward column pass) -- cut into 64 / GL neighbour groups
+// of GL lanes as slot_items.hpp describes, so 64 / GL neighbours are in flight per step (16 at
+// d <= 16).  Head h owns columns [h dh, (h + 1) dh) with dh = d / K in {4 .. 128}: the hl = dh / 4
+// lanes [h hl, (h + 1) hl) of every group, so a lane's float4 belongs to one head and the dot
+// products (u, v, t, c) are butterflies over the lane offsets below hl.  u, v are [n][K], alpha,
+// dx and the mask bits [nnz][K].  A row's per-head score maximum and exponent sum are taken in
+// the gather layout (group q over slots q, q + 64 / GL, ..., then the offsets GL .. 32): one pass
+// over the row's index serves every head.  The groups' sums meet in xor butterflies over the
+// lane offsets GL .. 32 (every lane ends with the same bits).
+// ONE = a single head over any d in 1 .. 128 (K = 1, hl = GL): the dot products are butterflies
+// over the whole group with their offsets known at compile time, and a row's scalars (its score
+// maximum and exponent sum, du_i) are summed one slot per lane, then over the wave.
 //
 // Items longer than kGatSeg slots (hub rows and hub columns of a power-law graph) are cut into
 // kGatSeg-slot segments, each summed by a wave of its own in the same launch as the short items:
-//   forward: a segment leaves {its max, its exponent sum, its unnormalised partial row}; a second
+//   forward: a segment leaves {max[32], sum[32], its unnormalised partial row[128]}; a second
 //   launch merges a row's segments in segment order (every segment's wave: the row's max and sum,
 //   then its own alpha; the first segment's wave also Z);
-//   backward column pass: a segment leaves {its dv, its partial dP row}; a second launch sums a
-//   column's segments in order.  The backward row pass needs no merge: dx is per slot, and du_i is
-//   summed from dx by the column pass (the wave of column i).
+//   backward column pass: a segment leaves {dv[32], -, its partial dP row[128]}; a second launch
+//   sums a column's segments in order.  The backward row pass needs no merge: dx is per slot, and
+//   du_i is summed from dx by the column pass (the wave of column i).
 // da_dst / da_src go through per-workgroup partials and one reducing launch (the shape of
-// k_layernorm_bwd).  Every order depends on the pattern and d only: bit-reproducible.
+// k_layernorm_bwd).  Every order depends on the pattern, d and K only: bit-reproducible.
 //
-// Several heads inside d and dropout on the attention weights are the *_mh kernels in the second
-// half of this file: the same passes with a head axis (their layout is described there).
+// Dropout: the weight of slot s, head h is kept when bit base + s K + h of the mask is set, times
+// the scale in Z and in the backward; alpha holds the weights before dropout.  A null mask skips
+// the factor (not a multiplication by one), so it costs nothing where there is no dropout.
 #include <algorithm>
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "slot_items.hpp"
 
 #pragma clang fp contract(off)
 
 namespace pgcn {
 
 namespace {
-constexpr int kGatThreads = 256;  // 4 waves: 4 items per workgroup step
-constexpr int kGatWaves = kGatThreads / kWave;
-constexpr int kGatMaxBlocks = 32 * kCUs;
 constexpr int kGatDaBlocks = 256;  // da partials: one reducing chain of <= 256 per element
 
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.0f ? x : slope * x; }
@@ -53,18 +58,22 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// sum over the GL lanes of a group (offsets below GL) / over the groups of a wave (GL and above)
-template <int GL>
-__device__ __forceinline__ float group_sum(float v) {
+// sum over the hl lanes of a head (hl a power of two <= GL; ONE: the whole group)
+template <int GL, bool ONE>
+__device__ __forceinline__ float head_sum(float v, int hl) {
+  if constexpr (ONE) {
 #pragma unroll
-  for (int off = GL / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    for (int off = GL / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  } else {
+    for (int off = hl >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  }
   return v;
 }
 
 template <int GL>
-__device__ __forceinline__ float across_groups(float v) {
+__device__ __forceinline__ float across_groups_max(float v) {
 #pragma unroll
-  for (int off = GL; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+  for (int off = GL; off < 64; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
 }
 
@@ -75,19 +84,6 @@ __device__ __forceinline__ float4 across_groups4(float4 a) {
   a.z = across_groups<GL>(a.z);
   a.w = across_groups<GL>(a.w);
   return a;
-}
-
-// the float4 at columns c0 .. c0 + 3 of a row of logical width d: columns >= d read as zero
-// (the padding may hold anything)
-__device__ __forceinline__ float4 row4(const float *p, int c0, int d, bool on) {
-  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (on) {
-    v = *reinterpret_cast<const float4 *>(p + c0);
-    if (c0 + 1 >= d) v.y = 0.0f;
-    if (c0 + 2 >= d) v.z = 0.0f;
-    if (c0 + 3 >= d) v.w = 0.0f;
-  }
-  return v;
 }
 
 __device__ __forceinline__ float4 cols4(const float *p, int c0, int d) {
@@ -110,444 +106,6 @@ __device__ __forceinline__ void axpy4(float4 &acc, float w, float4 p) {
   acc.w += w * p.w;
 }
 
-// this wave's item of a launch over n_direct + n_segs items, grid-stride
-__device__ __forceinline__ long long first_item() {
-  return ((long long)blockIdx.x * kGatThreads + threadIdx.x) / kWave;
-}
-__device__ __forceinline__ long long item_stride() { return (long long)gridDim.x * kGatWaves; }
-
-// the score maximum of slots [b, e) of row i's index list and the sum of exp(score - max)
-__device__ __forceinline__ void slot_stats(const int *__restrict__ idx, const float *__restrict__ v,
-                                           float ui, float slope, int b, int e, int lane, float *m,
-                                           float *s) {
-  float mx = -INFINITY;
-  for (int k = b + lane; k < e; k += kWave) mx = fmaxf(mx, leaky(ui + v[idx[k]], slope));
-  mx = wave_max(mx);
-  float sm = 0.0f;
-  for (int k = b + lane; k < e; k += kWave) sm += expf(leaky(ui + v[idx[k]], slope) - mx);
-  *m = mx;
-  *s = wave_sum(sm);
-}
-
-// sum over slots [b, e) of w_s P_j with w_s = exp(score_s - m) / s, every lane of group 0 (and
-// all others) ending with the wave's sum; alpha (or null) takes w_s
-template <int GL>
-__device__ __forceinline__ float4 slot_gather(const float *__restrict__ P, int ld_p, int d,
-                                              const int *__restrict__ idx,
-                                              const float *__restrict__ v, float ui, float slope,
-                                              int b, int e, float m, float s, float *alpha,
-                                              int lane) {
-  constexpr int NB = kWave / GL;
-  const int q = lane / GL, li = lane % GL, c0 = 4 * li;
-  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll 2
-  for (int k = b + q; k < e; k += NB) {
-    const int j = idx[k];
-    const float w = expf(leaky(ui + v[j], slope) - m) / s;
-    if (alpha && li == 0) alpha[k] = w;
-    axpy4(acc, w, row4(P + (long long)j * ld_p, c0, d, c0 < d));
-  }
-  return across_groups4<GL>(acc);
-}
-}  // namespace
-
-// u[i] = P_i . a_dst, v[i] = P_i . a_src: one row per group of GL lanes
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_scores(const float *__restrict__ P, int ld_p,
-                                                            int n, int d,
-                                                            const float *__restrict__ a_dst,
-                                                            const float *__restrict__ a_src,
-                                                            float *__restrict__ u,
-                                                            float *__restrict__ v) {
-  constexpr int RPB = kGatThreads / GL;
-  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
-  const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
-  for (long long base = (long long)blockIdx.x * RPB; base < n; base += (long long)gridDim.x * RPB) {
-    const long long r = base + grp;
-    const bool live = r < n;
-    const float4 p = row4(P + r * ld_p, c0, d, live && c0 < d);
-    const float su = group_sum<GL>(dot4(p, ad)), sv = group_sum<GL>(dot4(p, as));
-    if (live && li == 0) {
-      u[r] = su;
-      v[r] = sv;
-    }
-  }
-}
-
-// items [0, n): the rows of at most kGatSeg slots, whole; items [n, n + n_row_segs): the long
-// rows' segments, which leave {max, sum, unnormalised partial row} in row_ws
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_fwd(const GatPattern g,
-                                                         const float *__restrict__ P, int ld_p,
-                                                         const float *__restrict__ u,
-                                                         const float *__restrict__ v, float slope,
-                                                         float *__restrict__ Z, int ld_z, int d,
-                                                         float *__restrict__ alpha) {
-  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
-  const long long items = (long long)g.n + g.n_row_segs;
-  for (long long it = first_item(); it < items; it += item_stride()) {
-    if (it < g.n) {
-      const int i = (int)it, b = g.indptr[i], e = g.indptr[i + 1];
-      if (e - b > kGatSeg) continue;
-      float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (e > b) {
-        const float ui = u[i];
-        float m, s;
-        slot_stats(g.indices, v, ui, slope, b, e, lane, &m, &s);
-        z = slot_gather<GL>(P, ld_p, d, g.indices, v, ui, slope, b, e, m, s, alpha, lane);
-      }
-      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
-    } else {
-      const long long t = it - g.n;
-      const int4 sg = g.row_segs[t];
-      const float ui = u[sg.x];
-      float m, s;
-      slot_stats(g.indices, v, ui, slope, sg.y, sg.z, lane, &m, &s);
-      const float4 z =
-          slot_gather<GL>(P, ld_p, d, g.indices, v, ui, slope, sg.y, sg.z, m, 1.0f, nullptr, lane);
-      float *ws = g.row_ws + t * kGatWsStride;
-      if (lane == 0) {
-        ws[0] = m;
-        ws[1] = s;
-      }
-      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 4 + c0) = z;
-    }
-  }
-}
-
-// one wave per segment of a long row: the row's max and sum from its segments in order, the
-// segment's alpha, and (the row's first segment) Z
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_merge(const GatPattern g,
-                                                               const float *__restrict__ u,
-                                                               const float *__restrict__ v,
-                                                               float slope, float *__restrict__ Z,
-                                                               int ld_z, int d,
-                                                               float *__restrict__ alpha) {
-  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
-  for (long long t = first_item(); t < g.n_row_segs; t += item_stride()) {
-    const int4 sg = g.row_segs[t];
-    const int i = sg.x, first = sg.w;
-    const int nseg = (g.indptr[i + 1] - g.indptr[i] + kGatSeg - 1) / kGatSeg;
-    const float *ws = g.row_ws + (long long)first * kGatWsStride;
-    float m = -INFINITY;
-    for (int k = 0; k < nseg; k++) m = fmaxf(m, ws[(long long)k * kGatWsStride]);
-    float s = 0.0f;
-    for (int k = 0; k < nseg; k++)
-      s += ws[(long long)k * kGatWsStride + 1] * expf(ws[(long long)k * kGatWsStride] - m);
-    if (alpha) {
-      const float ui = u[i];
-      for (int k = sg.y + lane; k < sg.z; k += kWave)
-        alpha[k] = expf(leaky(ui + v[g.indices[k]], slope) - m) / s;
-    }
-    if (t == first && lane < GL && c0 < d) {
-      float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      for (int k = 0; k < nseg; k++) {
-        const float *w = ws + (long long)k * kGatWsStride;
-        axpy4(z, expf(w[0] - m), *reinterpret_cast<const float4 *>(w + 4 + c0));
-      }
-      z.x /= s;
-      z.y /= s;
-      z.z /= s;
-      z.w /= s;
-      *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
-    }
-  }
-}
-
-// backward row pass: dx_s = alpha_s (G_i . P_j - G_i . Z_i) leaky'(u_i + v_j) for every slot of
-// the item (items as in k_gat_fwd; a long row's segments need no merge)
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_rows(
-    const GatPattern g, const float *__restrict__ P, int ld_p, const float *__restrict__ u,
-    const float *__restrict__ v, float slope, const float *__restrict__ alpha,
-    const float *__restrict__ Z, int ld_z, const float *__restrict__ G, int ld_g, int d,
-    float *__restrict__ dx) {
-  constexpr int NB = kWave / GL;
-  const int lane = threadIdx.x % kWave, q = lane / GL, li = lane % GL, c0 = 4 * li;
-  const long long items = (long long)g.n + g.n_row_segs;
-  for (long long it = first_item(); it < items; it += item_stride()) {
-    int i, b, e;
-    if (it < g.n) {
-      i = (int)it;
-      b = g.indptr[i];
-      e = g.indptr[i + 1];
-      if (e - b > kGatSeg) continue;
-    } else {
-      const int4 sg = g.row_segs[it - g.n];
-      i = sg.x;
-      b = sg.y;
-      e = sg.z;
-    }
-    if (e <= b) continue;
-    const float4 gi = row4(G + (long long)i * ld_g, c0, d, c0 < d);
-    const float4 zi = row4(Z + (long long)i * ld_z, c0, d, c0 < d);
-    const float c = group_sum<GL>(dot4(gi, zi)), ui = u[i];
-    // (the same trip count for every group: the group sums run under uniform control flow)
-    for (int k0 = b; k0 < e; k0 += NB) {
-      const int k = k0 + q;
-      const bool on = k < e;
-      const int j = on ? g.indices[k] : i;
-      const float t = group_sum<GL>(dot4(gi, row4(P + (long long)j * ld_p, c0, d, on && c0 < d)));
-      if (on && li == 0) dx[k] = alpha[k] * (t - c) * (ui + v[j] > 0.0f ? 1.0f : slope);
-    }
-  }
-}
-
-// one item of the column pass: slots [b, e) of the transposed index; acc = sum alpha_s G_row,
-// dv = sum dx_s, both over the groups (every lane ends with the wave's sums)
-template <int GL>
-__device__ __forceinline__ float4 col_gather(const GatPattern &g, const float *__restrict__ alpha,
-                                             const float *__restrict__ dx,
-                                             const float *__restrict__ G, int ld_g, int d, int b,
-                                             int e, int lane, float *dv_out) {
-  constexpr int NB = kWave / GL;
-  const int q = lane / GL, c0 = 4 * (lane % GL);
-  float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  float dv = 0.0f;
-#pragma unroll 2
-  for (int o = b + q; o < e; o += NB) {
-    const int r = g.csc_row[o], k = g.csc_pos[o];
-    axpy4(acc, alpha[k], row4(G + (long long)r * ld_g, c0, d, c0 < d));
-    dv += dx[k];
-  }
-  *dv_out = across_groups<GL>(dv);
-  return across_groups4<GL>(acc);
-}
-
-// the final write of column j: du_j from row j's dx (one slot per lane, then the wave), then
-// dP_j = acc + du_j a_dst + dv_j a_src
-template <int GL>
-__device__ __forceinline__ void col_finish(const GatPattern &g, int j, float4 acc, float dv,
-                                           const float *__restrict__ dx,
-                                           const float *__restrict__ a_dst,
-                                           const float *__restrict__ a_src, int d,
-                                           float *__restrict__ dP, int ld_dp,
-                                           float *__restrict__ du_out, float *__restrict__ dv_out,
-                                           int lane) {
-  const int c0 = 4 * (lane % GL);
-  float du = 0.0f;
-  for (int k = g.indptr[j] + lane; k < g.indptr[j + 1]; k += kWave) du += dx[k];
-  du = wave_sum(du);
-  if (lane == 0) {
-    du_out[j] = du;
-    dv_out[j] = dv;
-  }
-  if (lane < GL && c0 < d) {
-    const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
-    float4 o;
-    o.x = (acc.x + du * ad.x) + dv * as.x;
-    o.y = (acc.y + du * ad.y) + dv * as.y;
-    o.z = (acc.z + du * ad.z) + dv * as.z;
-    o.w = (acc.w + du * ad.w) + dv * as.w;
-    *reinterpret_cast<float4 *>(dP + (long long)j * ld_dp + c0) = o;
-  }
-}
-
-// items [0, n): the columns of at most kGatSeg incoming slots, whole; items [n, n + n_col_segs):
-// the long columns' segments, which leave {dv, partial row} in col_ws
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_cols(
-    const GatPattern g, const float *__restrict__ alpha, const float *__restrict__ dx,
-    const float *__restrict__ G, int ld_g, const float *__restrict__ a_dst,
-    const float *__restrict__ a_src, int d, float *__restrict__ dP, int ld_dp,
-    float *__restrict__ du, float *__restrict__ dv, float *__restrict__ col_ws) {
-  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
-  const long long items = (long long)g.n + g.n_col_segs;
-  for (long long it = first_item(); it < items; it += item_stride()) {
-    if (it < g.n) {
-      const int j = (int)it, b = g.csc_ptr[j], e = g.csc_ptr[j + 1];
-      if (e - b > kGatSeg) continue;
-      float dvj;
-      const float4 acc = col_gather<GL>(g, alpha, dx, G, ld_g, d, b, e, lane, &dvj);
-      col_finish<GL>(g, j, acc, dvj, dx, a_dst, a_src, d, dP, ld_dp, du, dv, lane);
-    } else {
-      const long long t = it - g.n;
-      const int4 sg = g.col_segs[t];
-      float dvj;
-      const float4 acc = col_gather<GL>(g, alpha, dx, G, ld_g, d, sg.y, sg.z, lane, &dvj);
-      float *ws = col_ws + t * kGatWsStride;
-      if (lane == 0) ws[0] = dvj;
-      if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 4 + c0) = acc;
-    }
-  }
-}
-
-// one wave per long column: its segments' partials in segment order, then the final write
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_colmerge(
-    const GatPattern g, const float *__restrict__ dx, const float *__restrict__ a_dst,
-    const float *__restrict__ a_src, int d, float *__restrict__ dP, int ld_dp,
-    float *__restrict__ du, float *__restrict__ dv, const float *__restrict__ col_ws) {
-  const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
-  for (long long t = first_item(); t < g.n_long_cols; t += item_stride()) {
-    const int j = g.long_cols[t].x, first = g.long_cols[t].y;
-    const int nseg = (g.csc_ptr[j + 1] - g.csc_ptr[j] + kGatSeg - 1) / kGatSeg;
-    float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float dvj = 0.0f;
-    for (int k = 0; k < nseg; k++) {
-      const float *w = col_ws + (long long)(first + k) * kGatWsStride;
-      dvj += w[0];
-      if (c0 < d) {
-        const float4 p = *reinterpret_cast<const float4 *>(w + 4 + c0);
-        acc.x += p.x;
-        acc.y += p.y;
-        acc.z += p.z;
-        acc.w += p.w;
-      }
-    }
-    col_finish<GL>(g, j, acc, dvj, dx, a_dst, a_src, d, dP, ld_dp, du, dv, lane);
-  }
-}
-
-// this workgroup's rows of sum du_i P_i and sum dv_i P_i: per lane group in row order, then
-// the groups in group order (LDS), into partial [block][2][ldp]
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_da(const float *__restrict__ P, int ld_p,
-                                                        int n, int d, const float *__restrict__ du,
-                                                        const float *__restrict__ dv,
-                                                        float *__restrict__ partial, int ldp) {
-  constexpr int RPB = kGatThreads / GL;
-  constexpr int W = GL * 4;
-  __shared__ __align__(16) float sh[RPB * 2 * W];
-  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
-  float4 ad = make_float4(0.0f, 0.0f, 0.0f, 0.0f), as = ad;
-  for (long long r = (long long)blockIdx.x * RPB + grp; r < n; r += (long long)gridDim.x * RPB) {
-    const float4 p = row4(P + r * ld_p, c0, d, c0 < d);
-    axpy4(ad, du[r], p);
-    axpy4(as, dv[r], p);
-  }
-  *reinterpret_cast<float4 *>(&sh[(grp * 2 + 0) * W + c0]) = ad;
-  *reinterpret_cast<float4 *>(&sh[(grp * 2 + 1) * W + c0]) = as;
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * W; i += kGatThreads) {
-    const int c = i % W;
-    if (c >= ldp) continue;
-    float s = 0.0f;
-    for (int q = 0; q < RPB; q++) s += sh[q * 2 * W + i];
-    partial[((long long)blockIdx.x * 2 + i / W) * ldp + c] = s;
-  }
-}
-
-// da[k][c] = the nb partials [2][ldp] summed in block order
-__global__ __launch_bounds__(kGatThreads) void k_gat_da_reduce(const float *__restrict__ partial,
-                                                               int nb, int ldp, int d,
-                                                               float *__restrict__ da) {
-  const int i = blockIdx.x * kGatThreads + threadIdx.x;
-  if (i >= 2 * ldp) return;
-  const int c = i % ldp;
-  if (c >= d) return;
-  float s = 0.0f;
-#pragma unroll 8
-  for (int b = 0; b < nb; b++) s += partial[(long long)b * 2 * ldp + i];
-  da[(i / ldp) * d + c] = s;
-}
-
-static int gat_gl(int d) {
-  const int d4 = (d + 3) / 4;
-  return d4 <= 1 ? 1 : d4 <= 2 ? 2 : d4 <= 4 ? 4 : d4 <= 8 ? 8 : d4 <= 16 ? 16 : 32;
-}
-
-static dim3 gat_grid(long long items) {
-  return dim3((unsigned)std::max<long long>(1, std::min<long long>(ceil_div(items, kGatWaves),
-                                                                   kGatMaxBlocks)));
-}
-
-static int gat_da_blocks(int n, int d) {
-  return (int)std::max<long long>(
-      1, std::min<long long>(ceil_div(n, kGatThreads / gat_gl(d)), kGatDaBlocks));
-}
-
-#define GAT_DISPATCH(KERNEL, grid, s, ...)                                                  \
-  do {                                                                                      \
-    switch (gat_gl(d)) {                                                                    \
-      case 1: PGCN_LAUNCH((KERNEL<1>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 2: PGCN_LAUNCH((KERNEL<2>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 4: PGCN_LAUNCH((KERNEL<4>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 8: PGCN_LAUNCH((KERNEL<8>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 16: PGCN_LAUNCH((KERNEL<16>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
-      default: PGCN_LAUNCH((KERNEL<32>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
-    }                                                                                       \
-  } while (0)
-
-void launch_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
-                       const float *a_src, float *u, float *v, hipStream_t s) {
-  PGCN_CHECK(d >= 1 && d <= kGatMaxWidth && n >= 0, PGCN_E_INVALID, "gat_scores: 1 <= d <= 128");
-  if (n == 0) return;
-  const dim3 grid((unsigned)std::min<long long>(ceil_div(n, kGatThreads / gat_gl(d)),
-                                                kGatMaxBlocks));
-  GAT_DISPATCH(k_gat_scores, grid, s, P, ld_p, n, d, a_dst, a_src, u, v);
-}
-
-void launch_gat_fwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
-                    float slope, float *Z, int ld_z, int d, float *alpha, hipStream_t s) {
-  PGCN_CHECK(d >= 1 && d <= kGatMaxWidth && g.n >= 0, PGCN_E_INVALID, "gat_fwd: 1 <= d <= 128");
-  if (g.n == 0) return;
-  note_path(KP_GAT_FWD);
-  GAT_DISPATCH(k_gat_fwd, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v, slope, Z,
-               ld_z, d, alpha);
-  if (g.n_row_segs > 0)
-    GAT_DISPATCH(k_gat_fwd_merge, gat_grid(g.n_row_segs), s, g, u, v, slope, Z, ld_z, d, alpha);
-}
-
-namespace {
-struct GatBwdWs {
-  size_t dx, du, dv, col_ws, part, floats;
-};
-size_t up4(size_t x) { return (x + 3) / 4 * 4; }
-GatBwdWs gat_bwd_layout(const GatPattern &g, int d) {
-  GatBwdWs w;
-  w.dx = 0;
-  w.du = w.dx + up4((size_t)g.nnz);
-  w.dv = w.du + up4((size_t)g.n);
-  w.col_ws = w.dv + up4((size_t)g.n);
-  w.part = w.col_ws + (size_t)g.n_col_segs * kGatWsStride;
-  w.floats = w.part + (size_t)gat_da_blocks(g.n, d) * 2 * (size_t)((d + 3) / 4 * 4);
-  return w;
-}
-}  // namespace
-
-size_t gat_bwd_workspace(const GatPattern &g, int d) {
-  if (g.n <= 0 || d <= 0) return 0;
-  return gat_bwd_layout(g, d).floats * sizeof(float);
-}
-
-void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
-                    float slope, const float *alpha, const float *Z, int ld_z, const float *G,
-                    int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
-                    float *da, void *workspace, hipStream_t s) {
-  PGCN_CHECK(d >= 1 && d <= kGatMaxWidth && g.n >= 0, PGCN_E_INVALID, "gat_bwd: 1 <= d <= 128");
-  if (g.n == 0) return;
-  note_path(KP_GAT_BWD);
-  const GatBwdWs w = gat_bwd_layout(g, d);
-  float *ws = static_cast<float *>(workspace);
-  float *dx = ws + w.dx, *du = ws + w.du, *dv = ws + w.dv, *col_ws = ws + w.col_ws;
-  float *partial = ws + w.part;
-  GAT_DISPATCH(k_gat_bwd_rows, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v, slope,
-               alpha, Z, ld_z, G, ld_g, d, dx);
-  GAT_DISPATCH(k_gat_bwd_cols, gat_grid((long long)g.n + g.n_col_segs), s, g, alpha, dx, G, ld_g,
-               a_dst, a_src, d, dP, ld_dp, du, dv, col_ws);
-  if (g.n_long_cols > 0)
-    GAT_DISPATCH(k_gat_bwd_colmerge, gat_grid(g.n_long_cols), s, g, dx, a_dst, a_src, d, dP, ld_dp,
-                 du, dv, col_ws);
-  const int nb = gat_da_blocks(g.n, d), ldp = (d + 3) / 4 * 4;
-  GAT_DISPATCH(k_gat_da, dim3((unsigned)nb), s, P, ld_p, g.n, d, du, dv, partial, ldp);
-  PGCN_LAUNCH(k_gat_da_reduce, dim3((unsigned)ceil_div(2 * ldp, kGatThreads)), dim3(kGatThreads),
-              0, s, partial, nb, ldp, d, da);
-}
-
-// ---- several heads, dropout on the attention weights ------------------------------------------
-// Head h owns columns [h dh, (h + 1) dh) with dh = d / K in {4 .. 128}: the hl = dh / 4 lanes
-// [h hl, (h + 1) hl) of every GL-lane neighbour group, so a lane's float4 belongs to one head
-// and the dot products (u, v, t, c) are butterflies over the lane offsets below hl.  u, v are
-// [n][K], alpha, dx and the mask bits [nnz][K].  A row's per-head maximum and exponent sum are
-// taken in the gather layout (group q over slots q, q + 64 / GL, ..., then the offsets GL .. 32):
-// one pass over the row's index serves every head.  A segment's partial is {max[32], sum[32],
-// row[128]} (forward) / {dv[32], -, row[128]} (column pass).
-// ONE = a single head over any d in 1..128 (the output layer under attention dropout): the
-// single-head kernels' statements and summation orders with the mask factor put in, so an
-// all-ones mask of scale 1 gives their bits.
-namespace {
 struct GatDrop {
   const uint64_t *mask;  // bit base + s K + h: the weight of slot s, head h is kept; null: all
   long long base;
@@ -559,22 +117,6 @@ __device__ __forceinline__ float drop_factor(const GatDrop &dr, long long e) {
   if (!dr.mask) return 1.0f;
   const long long b = dr.base + e;
   return (dr.mask[b >> 6] >> (b & 63)) & 1ull ? dr.scale : 0.0f;
-}
-
-// sum over the hl lanes of a head (hl a power of two <= GL; ONE: the whole group, group_sum's
-// order)
-template <int GL, bool ONE>
-__device__ __forceinline__ float head_sum(float v, int hl) {
-  if constexpr (ONE) return group_sum<GL>(v);
-  for (int off = hl >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-template <int GL>
-__device__ __forceinline__ float across_groups_max(float v) {
-#pragma unroll
-  for (int off = GL; off < 64; off <<= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
 }
 
 // a lane's place: its head (clamped on the idle lanes past column d, which store nothing) and
@@ -595,13 +137,18 @@ struct HeadLane {
 // this lane's head over slots [b, e) of row i's index list: the score maximum and the sum of
 // exp(score - max); every lane of the wave takes part
 template <int GL, bool ONE>
-__device__ __forceinline__ void slot_stats_mh(const int *__restrict__ idx,
-                                              const float *__restrict__ v, int K, int hd, float ui,
-                                              float slope, int b, int e, int lane, float *m,
-                                              float *s) {
-  if constexpr (ONE) {
-    slot_stats(idx, v, ui, slope, b, e, lane, m, s);
-  } else {
+__device__ __forceinline__ void slot_stats(const int *__restrict__ idx, const float *__restrict__ v,
+                                           int K, int hd, float ui, float slope, int b, int e,
+                                           int lane, float *m, float *s) {
+  if constexpr (ONE) {  // one slot per lane, then the wave
+    float mx = -INFINITY;
+    for (int k = b + lane; k < e; k += kWave) mx = fmaxf(mx, leaky(ui + v[idx[k]], slope));
+    mx = wave_max(mx);
+    float sm = 0.0f;
+    for (int k = b + lane; k < e; k += kWave) sm += expf(leaky(ui + v[idx[k]], slope) - mx);
+    *m = mx;
+    *s = wave_sum(sm);
+  } else {  // one slot per group, then the groups
     constexpr int NB = kWave / GL;
     const int q = lane / GL;
     float mx = -INFINITY;
@@ -616,15 +163,17 @@ __device__ __forceinline__ void slot_stats_mh(const int *__restrict__ idx,
   }
 }
 
-// slot_gather with the head's own {ui, m, s} per lane and the mask factor on the summed weight;
-// alpha (or null) takes the weight before dropout
-template <int GL, bool ONE>
-__device__ __forceinline__ float4 slot_gather_mh(const float *__restrict__ P, int ld_p, int d,
-                                                 const int *__restrict__ idx,
-                                                 const float *__restrict__ v, int K,
-                                                 const HeadLane<GL, ONE> &hl, float ui, float slope,
-                                                 int b, int e, float m, float s, float *alpha,
-                                                 const GatDrop &dr) {
+// sum over slots [b, e) of m'_s w_s P_j with w_s = exp(score_s - m) / s of the lane's head,
+// every lane of group 0 (and all others) ending with the wave's sum; alpha (or null) takes w_s,
+// the weight before dropout
+// (MASK: 0 no mask, 1 a mask, -1 the pointer tested per slot)
+template <int GL, bool ONE, int MASK>
+__device__ __forceinline__ float4 slot_gather_loop(const float *__restrict__ P, int ld_p, int d,
+                                                   const int *__restrict__ idx,
+                                                   const float *__restrict__ v, int K,
+                                                   const HeadLane<GL, ONE> &hl, float ui,
+                                                   float slope, int b, int e, float m, float s,
+                                                   float *alpha, const GatDrop &dr) {
   constexpr int NB = kWave / GL;
   float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #pragma unroll 2
@@ -633,41 +182,66 @@ __device__ __forceinline__ float4 slot_gather_mh(const float *__restrict__ P, in
     const long long eh = (long long)k * K + hl.hd;
     const float w = expf(leaky(ui + v[(long long)j * K + hl.hd], slope) - m) / s;
     if (alpha && hl.lead) alpha[eh] = w;
-    axpy4(acc, dr.mask ? w * drop_factor(dr, eh) : w,
+    axpy4(acc, (MASK < 0 ? dr.mask != nullptr : MASK > 0) ? w * drop_factor(dr, eh) : w,
           row4(P + (long long)j * ld_p, hl.c0, d, hl.c0 < d));
   }
   return across_groups4<GL>(acc);
 }
+
+// (ONE: the null-mask test stands outside the slot loop -- inside it the d = 128 forward measured
+// 9 % slower than without the test; the many-head kernels keep one loop body, two of them cost
+// a wave of occupancy there)
+template <int GL, bool ONE>
+__device__ __forceinline__ float4 slot_gather(const float *__restrict__ P, int ld_p, int d,
+                                              const int *__restrict__ idx,
+                                              const float *__restrict__ v, int K,
+                                              const HeadLane<GL, ONE> &hl, float ui, float slope,
+                                              int b, int e, float m, float s, float *alpha,
+                                              const GatDrop &dr) {
+  if constexpr (!ONE)
+    return slot_gather_loop<GL, ONE, -1>(P, ld_p, d, idx, v, K, hl, ui, slope, b, e, m, s, alpha,
+                                         dr);
+  else
+    return dr.mask ? slot_gather_loop<GL, ONE, 1>(P, ld_p, d, idx, v, K, hl, ui, slope, b, e, m, s,
+                                                  alpha, dr)
+                   : slot_gather_loop<GL, ONE, 0>(P, ld_p, d, idx, v, K, hl, ui, slope, b, e, m, s,
+                                                  alpha, dr);
+}
 }  // namespace
 
-// u[i][h] = P_i[h] . a_dst[h], v[i][h] = P_i[h] . a_src[h]
-template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_scores_mh(
-    const float *__restrict__ P, int ld_p, int n, int d, int K, int hl,
+// u[i][h] = P_i[h] . a_dst[h], v[i][h] = P_i[h] . a_src[h]: one row per group of GL lanes
+template <int GL, bool ONE>
+__global__ __launch_bounds__(kItemThreads) void k_gat_scores(
+    const float *__restrict__ P, int ld_p, int n, int d, int K, int hlanes,
     const float *__restrict__ a_dst, const float *__restrict__ a_src, float *__restrict__ u,
     float *__restrict__ v) {
-  constexpr int RPB = kGatThreads / GL;
-  const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
+  constexpr int RPB = kItemThreads / GL;
+  if constexpr (ONE) K = 1;  // (the [..][K] indices fold to the one-head ones at compile time)
+  const HeadLane<GL, ONE> hl(threadIdx.x % kWave, d, K, hlanes);
+  const int grp = threadIdx.x / GL, c0 = hl.c0;
   const float4 ad = cols4(a_dst, c0, d), as = cols4(a_src, c0, d);
   for (long long base = (long long)blockIdx.x * RPB; base < n; base += (long long)gridDim.x * RPB) {
     const long long r = base + grp;
     const bool live = r < n;
     const float4 p = row4(P + r * ld_p, c0, d, live && c0 < d);
-    const float su = head_sum<GL, false>(dot4(p, ad), hl);
-    const float sv = head_sum<GL, false>(dot4(p, as), hl);
-    if (live && c0 < d && li % hl == 0) {
-      u[r * K + li / hl] = su;
-      v[r * K + li / hl] = sv;
+    const float su = head_sum<GL, ONE>(dot4(p, ad), hlanes);
+    const float sv = head_sum<GL, ONE>(dot4(p, as), hlanes);
+    if (live && hl.lead) {
+      u[r * K + hl.hd] = su;
+      v[r * K + hl.hd] = sv;
     }
   }
 }
 
+// items [0, n): the rows of at most kGatSeg slots, whole; items [n, n + n_row_segs): the long
+// rows' segments, which leave {max, sum, unnormalised partial row} in row_ws
 template <int GL, bool ONE>
-__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_mh(
+__global__ __launch_bounds__(kItemThreads) void k_gat_fwd(
     const GatPattern g, const float *__restrict__ P, int ld_p, const float *__restrict__ u,
     const float *__restrict__ v, float slope, float *__restrict__ Z, int ld_z, int d, int K,
     int hlanes, float *__restrict__ alpha, const GatDrop dr) {
   const int lane = threadIdx.x % kWave;
+  if constexpr (ONE) K = 1;  // (the [..][K] indices fold to the one-head ones at compile time)
   const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
   const int c0 = hl.c0;
   const long long items = (long long)g.n + g.n_row_segs;
@@ -679,9 +253,8 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_mh(
       if (e > b) {
         const float ui = u[(long long)i * K + hl.hd];
         float m, s;
-        slot_stats_mh<GL, ONE>(g.indices, v, K, hl.hd, ui, slope, b, e, lane, &m, &s);
-        z = slot_gather_mh<GL, ONE>(P, ld_p, d, g.indices, v, K, hl, ui, slope, b, e, m, s, alpha,
-                                    dr);
+        slot_stats<GL, ONE>(g.indices, v, K, hl.hd, ui, slope, b, e, lane, &m, &s);
+        z = slot_gather<GL, ONE>(P, ld_p, d, g.indices, v, K, hl, ui, slope, b, e, m, s, alpha, dr);
       }
       if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(Z + (long long)i * ld_z + c0) = z;
     } else {
@@ -689,10 +262,10 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_mh(
       const int4 sg = g.row_segs[t];
       const float ui = u[(long long)sg.x * K + hl.hd];
       float m, s;
-      slot_stats_mh<GL, ONE>(g.indices, v, K, hl.hd, ui, slope, sg.y, sg.z, lane, &m, &s);
-      const float4 z = slot_gather_mh<GL, ONE>(P, ld_p, d, g.indices, v, K, hl, ui, slope, sg.y,
-                                               sg.z, m, 1.0f, nullptr, dr);
-      float *ws = g.row_ws + t * kGatWsStrideMh;
+      slot_stats<GL, ONE>(g.indices, v, K, hl.hd, ui, slope, sg.y, sg.z, lane, &m, &s);
+      const float4 z = slot_gather<GL, ONE>(P, ld_p, d, g.indices, v, K, hl, ui, slope, sg.y, sg.z,
+                                            m, 1.0f, nullptr, dr);
+      float *ws = g.row_ws + t * kGatWsStride;
       if (lane < GL && hl.lead) {
         ws[hl.hd] = m;
         ws[kGatMaxHeads + hl.hd] = s;
@@ -702,25 +275,28 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_mh(
   }
 }
 
+// one wave per segment of a long row: the row's max and sum from its segments in order, the
+// segment's alpha, and (the row's first segment) Z
 template <int GL, bool ONE>
-__global__ __launch_bounds__(kGatThreads) void k_gat_fwd_merge_mh(
+__global__ __launch_bounds__(kItemThreads) void k_gat_fwd_merge(
     const GatPattern g, const float *__restrict__ u, const float *__restrict__ v, float slope,
     float *__restrict__ Z, int ld_z, int d, int K, int hlanes, float *__restrict__ alpha) {
   constexpr int NB = kWave / GL;
   const int lane = threadIdx.x % kWave;
+  if constexpr (ONE) K = 1;  // (the [..][K] indices fold to the one-head ones at compile time)
   const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
   const int c0 = hl.c0;
   for (long long t = first_item(); t < g.n_row_segs; t += item_stride()) {
     const int4 sg = g.row_segs[t];
     const int i = sg.x, first = sg.w;
     const int nseg = (g.indptr[i + 1] - g.indptr[i] + kGatSeg - 1) / kGatSeg;
-    const float *ws = g.row_ws + (long long)first * kGatWsStrideMh + hl.hd;
+    const float *ws = g.row_ws + (long long)first * kGatWsStride + hl.hd;
     float m = -INFINITY;
-    for (int k = 0; k < nseg; k++) m = fmaxf(m, ws[(long long)k * kGatWsStrideMh]);
+    for (int k = 0; k < nseg; k++) m = fmaxf(m, ws[(long long)k * kGatWsStride]);
     float s = 0.0f;
     for (int k = 0; k < nseg; k++)
-      s += ws[(long long)k * kGatWsStrideMh + kGatMaxHeads] *
-           expf(ws[(long long)k * kGatWsStrideMh] - m);
+      s += ws[(long long)k * kGatWsStride + kGatMaxHeads] *
+           expf(ws[(long long)k * kGatWsStride] - m);
     if (alpha) {
       const float ui = u[(long long)i * K + hl.hd];
       if constexpr (ONE) {
@@ -736,7 +312,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_merge_mh(
     if (t == first && lane < GL && c0 < d) {
       float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       for (int k = 0; k < nseg; k++) {
-        const float *w = ws + (long long)k * kGatWsStrideMh;
+        const float *w = ws + (long long)k * kGatWsStride;
         axpy4(z, expf(w[0] - m),
               *reinterpret_cast<const float4 *>(w - hl.hd + 2 * kGatMaxHeads + c0));
       }
@@ -749,15 +325,18 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_fwd_merge_mh(
   }
 }
 
-// dx_s^h = alpha_s^h (m'_s^h G_i[h] . P_j[h] - G_i[h] . Z_i[h]) leaky'(u_i^h + v_j^h)
+// backward row pass: dx_s^h = alpha_s^h (m'_s^h G_i[h] . P_j[h] - G_i[h] . Z_i[h])
+// leaky'(u_i^h + v_j^h) for every slot of the item (items as in k_gat_fwd; a long row's segments
+// need no merge)
 template <int GL, bool ONE>
-__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_rows_mh(
+__global__ __launch_bounds__(kItemThreads) void k_gat_bwd_rows(
     const GatPattern g, const float *__restrict__ P, int ld_p, const float *__restrict__ u,
     const float *__restrict__ v, float slope, const float *__restrict__ alpha,
     const float *__restrict__ Z, int ld_z, const float *__restrict__ G, int ld_g, int d, int K,
     int hlanes, const GatDrop dr, float *__restrict__ dx) {
   constexpr int NB = kWave / GL;
   const int lane = threadIdx.x % kWave;
+  if constexpr (ONE) K = 1;  // (the [..][K] indices fold to the one-head ones at compile time)
   const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
   const int c0 = hl.c0;
   const long long items = (long long)g.n + g.n_row_segs;
@@ -794,14 +373,15 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_rows_mh(
   }
 }
 
-// col_gather per head: acc = sum alpha_s^h m'_s^h G_row[h], dv^h = sum dx_s^h
+namespace {
+// one item of the column pass: slots [b, e) of the transposed index; acc = sum alpha_s^h m'_s^h
+// G_row[h], dv^h = sum dx_s^h, both over the groups (every lane ends with the wave's sums)
 template <int GL, bool ONE>
-__device__ __forceinline__ float4 col_gather_mh(const GatPattern &g,
-                                                const float *__restrict__ alpha,
-                                                const float *__restrict__ dx,
-                                                const float *__restrict__ G, int ld_g, int d, int K,
-                                                const HeadLane<GL, ONE> &hl, const GatDrop &dr,
-                                                int b, int e, float *dv_out) {
+__device__ __forceinline__ float4 col_gather(const GatPattern &g, const float *__restrict__ alpha,
+                                             const float *__restrict__ dx,
+                                             const float *__restrict__ G, int ld_g, int d, int K,
+                                             const HeadLane<GL, ONE> &hl, const GatDrop &dr, int b,
+                                             int e, float *dv_out) {
   constexpr int NB = kWave / GL;
   float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float dv = 0.0f;
@@ -817,16 +397,16 @@ __device__ __forceinline__ float4 col_gather_mh(const GatPattern &g,
   return across_groups4<GL>(acc);
 }
 
-// the final write of column j: du_j^h from row j's dx, then dP_j = acc + du a_dst + dv a_src
+// the final write of column j: du_j^h from row j's dx (ONE: one slot per lane, then the wave),
+// then dP_j = acc + du_j a_dst + dv_j a_src
 template <int GL, bool ONE>
-__device__ __forceinline__ void col_finish_mh(const GatPattern &g, int j, float4 acc, float dv,
-                                              const float *__restrict__ dx,
-                                              const float *__restrict__ a_dst,
-                                              const float *__restrict__ a_src, int d, int K,
-                                              const HeadLane<GL, ONE> &hl,
-                                              float *__restrict__ dP, int ld_dp,
-                                              float *__restrict__ du_out,
-                                              float *__restrict__ dv_out, int lane) {
+__device__ __forceinline__ void col_finish(const GatPattern &g, int j, float4 acc, float dv,
+                                           const float *__restrict__ dx,
+                                           const float *__restrict__ a_dst,
+                                           const float *__restrict__ a_src, int d, int K,
+                                           const HeadLane<GL, ONE> &hl, float *__restrict__ dP,
+                                           int ld_dp, float *__restrict__ du_out,
+                                           float *__restrict__ dv_out, int lane) {
   constexpr int NB = kWave / GL;
   const int c0 = hl.c0;
   float du = 0.0f;
@@ -851,15 +431,19 @@ __device__ __forceinline__ void col_finish_mh(const GatPattern &g, int j, float4
     *reinterpret_cast<float4 *>(dP + (long long)j * ld_dp + c0) = o;
   }
 }
+}  // namespace
 
+// items [0, n): the columns of at most kGatSeg incoming slots, whole; items [n, n + n_col_segs):
+// the long columns' segments, which leave {dv, partial row} in col_ws
 template <int GL, bool ONE>
-__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_cols_mh(
+__global__ __launch_bounds__(kItemThreads) void k_gat_bwd_cols(
     const GatPattern g, const float *__restrict__ alpha, const float *__restrict__ dx,
     const float *__restrict__ G, int ld_g, const float *__restrict__ a_dst,
     const float *__restrict__ a_src, int d, int K, int hlanes, const GatDrop dr,
     float *__restrict__ dP, int ld_dp, float *__restrict__ du, float *__restrict__ dv,
     float *__restrict__ col_ws) {
   const int lane = threadIdx.x % kWave;
+  if constexpr (ONE) K = 1;  // (the [..][K] indices fold to the one-head ones at compile time)
   const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
   const int c0 = hl.c0;
   const long long items = (long long)g.n + g.n_col_segs;
@@ -868,27 +452,29 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_cols_mh(
       const int j = (int)it, b = g.csc_ptr[j], e = g.csc_ptr[j + 1];
       if (e - b > kGatSeg) continue;
       float dvj;
-      const float4 acc = col_gather_mh<GL, ONE>(g, alpha, dx, G, ld_g, d, K, hl, dr, b, e, &dvj);
-      col_finish_mh<GL, ONE>(g, j, acc, dvj, dx, a_dst, a_src, d, K, hl, dP, ld_dp, du, dv, lane);
+      const float4 acc = col_gather<GL, ONE>(g, alpha, dx, G, ld_g, d, K, hl, dr, b, e, &dvj);
+      col_finish<GL, ONE>(g, j, acc, dvj, dx, a_dst, a_src, d, K, hl, dP, ld_dp, du, dv, lane);
     } else {
       const long long t = it - g.n;
       const int4 sg = g.col_segs[t];
       float dvj;
       const float4 acc =
-          col_gather_mh<GL, ONE>(g, alpha, dx, G, ld_g, d, K, hl, dr, sg.y, sg.z, &dvj);
-      float *ws = col_ws + t * kGatWsStrideMh;
+          col_gather<GL, ONE>(g, alpha, dx, G, ld_g, d, K, hl, dr, sg.y, sg.z, &dvj);
+      float *ws = col_ws + t * kGatWsStride;
       if (lane < GL && hl.lead) ws[hl.hd] = dvj;
       if (lane < GL && c0 < d) *reinterpret_cast<float4 *>(ws + 2 * kGatMaxHeads + c0) = acc;
     }
   }
 }
 
+// one wave per long column: its segments' partials in segment order, then the final write
 template <int GL, bool ONE>
-__global__ __launch_bounds__(kGatThreads) void k_gat_bwd_colmerge_mh(
+__global__ __launch_bounds__(kItemThreads) void k_gat_bwd_colmerge(
     const GatPattern g, const float *__restrict__ dx, const float *__restrict__ a_dst,
     const float *__restrict__ a_src, int d, int K, int hlanes, float *__restrict__ dP, int ld_dp,
     float *__restrict__ du, float *__restrict__ dv, const float *__restrict__ col_ws) {
   const int lane = threadIdx.x % kWave;
+  if constexpr (ONE) K = 1;  // (the [..][K] indices fold to the one-head ones at compile time)
   const HeadLane<GL, ONE> hl(lane, d, K, hlanes);
   const int c0 = hl.c0;
   for (long long t = first_item(); t < g.n_long_cols; t += item_stride()) {
@@ -897,7 +483,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_colmerge_mh(
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float dvj = 0.0f;
     for (int k = 0; k < nseg; k++) {
-      const float *w = col_ws + (long long)(first + k) * kGatWsStrideMh;
+      const float *w = col_ws + (long long)(first + k) * kGatWsStride;
       dvj += w[hl.hd];
       if (c0 < d) {
         const float4 p = *reinterpret_cast<const float4 *>(w + 2 * kGatMaxHeads + c0);
@@ -907,17 +493,19 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_bwd_colmerge_mh(
         acc.w += p.w;
       }
     }
-    col_finish_mh<GL, ONE>(g, j, acc, dvj, dx, a_dst, a_src, d, K, hl, dP, ld_dp, du, dv, lane);
+    col_finish<GL, ONE>(g, j, acc, dvj, dx, a_dst, a_src, d, K, hl, dP, ld_dp, du, dv, lane);
   }
 }
 
-// k_gat_da with a lane's own head of du, dv [n][K]
+// this workgroup's rows of sum du_i^h P_i[h] and sum dv_i^h P_i[h] (a lane's own head of du, dv
+// [n][K]): per lane group in row order, then the groups in group order (LDS), into partial
+// [block][2][ldp].  (No ONE form: at K = 1 the head index is 0 and nothing else depends on it.)
 template <int GL>
-__global__ __launch_bounds__(kGatThreads) void k_gat_da_mh(
+__global__ __launch_bounds__(kItemThreads) void k_gat_da(
     const float *__restrict__ P, int ld_p, int n, int d, int K, int hlanes,
     const float *__restrict__ du, const float *__restrict__ dv, float *__restrict__ partial,
     int ldp) {
-  constexpr int RPB = kGatThreads / GL;
+  constexpr int RPB = kItemThreads / GL;
   constexpr int W = GL * 4;
   __shared__ __align__(16) float sh[RPB * 2 * W];
   const int li = threadIdx.x % GL, grp = threadIdx.x / GL, c0 = 4 * li;
@@ -931,7 +519,7 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_da_mh(
   *reinterpret_cast<float4 *>(&sh[(grp * 2 + 0) * W + c0]) = ad;
   *reinterpret_cast<float4 *>(&sh[(grp * 2 + 1) * W + c0]) = as;
   __syncthreads();
-  for (int i = threadIdx.x; i < 2 * W; i += kGatThreads) {
+  for (int i = threadIdx.x; i < 2 * W; i += kItemThreads) {
     const int c = i % W;
     if (c >= ldp) continue;
     float s = 0.0f;
@@ -940,19 +528,38 @@ __global__ __launch_bounds__(kGatThreads) void k_gat_da_mh(
   }
 }
 
-// K > 1: the gather kernels' <GL, false>; one head under a mask: <GL, true>
-#define GAT_DISPATCH_ONE(KERNEL, ONE, grid, s, ...)                                              \
-  do {                                                                                           \
-    switch (gat_gl(d)) {                                                                         \
-      case 1: PGCN_LAUNCH((KERNEL<1, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 2: PGCN_LAUNCH((KERNEL<2, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 4: PGCN_LAUNCH((KERNEL<4, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 8: PGCN_LAUNCH((KERNEL<8, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break;   \
-      case 16: PGCN_LAUNCH((KERNEL<16, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
-      default: PGCN_LAUNCH((KERNEL<32, ONE>), grid, dim3(kGatThreads), 0, s, __VA_ARGS__); break; \
-    }                                                                                            \
+// da[k][c] = the nb partials [2][ldp] summed in block order
+__global__ __launch_bounds__(kItemThreads) void k_gat_da_reduce(const float *__restrict__ partial,
+                                                                int nb, int ldp, int d,
+                                                                float *__restrict__ da) {
+  const int i = blockIdx.x * kItemThreads + threadIdx.x;
+  if (i >= 2 * ldp) return;
+  const int c = i % ldp;
+  if (c >= d) return;
+  float s = 0.0f;
+#pragma unroll 8
+  for (int b = 0; b < nb; b++) s += partial[(long long)b * 2 * ldp + i];
+  da[(i / ldp) * d + c] = s;
+}
+
+static int gat_da_blocks(int n, int d) {
+  return (int)std::max<long long>(
+      1, std::min<long long>(ceil_div(n, kItemThreads / item_gl(d)), kGatDaBlocks));
+}
+
+// KERNEL<GL, ONE>: ONE where `heads` in scope is 1
+#define GAT_DISPATCH_ONE(KERNEL, ONE, grid, s, ...)                                               \
+  do {                                                                                            \
+    switch (item_gl(d)) {                                                                         \
+      case 1: PGCN_LAUNCH((KERNEL<1, ONE>), grid, dim3(kItemThreads), 0, s, __VA_ARGS__); break;   \
+      case 2: PGCN_LAUNCH((KERNEL<2, ONE>), grid, dim3(kItemThreads), 0, s, __VA_ARGS__); break;   \
+      case 4: PGCN_LAUNCH((KERNEL<4, ONE>), grid, dim3(kItemThreads), 0, s, __VA_ARGS__); break;   \
+      case 8: PGCN_LAUNCH((KERNEL<8, ONE>), grid, dim3(kItemThreads), 0, s, __VA_ARGS__); break;   \
+      case 16: PGCN_LAUNCH((KERNEL<16, ONE>), grid, dim3(kItemThreads), 0, s, __VA_ARGS__); break; \
+      default: PGCN_LAUNCH((KERNEL<32, ONE>), grid, dim3(kItemThreads), 0, s, __VA_ARGS__); break; \
+    }                                                                                             \
   } while (0)
-#define GAT_DISPATCH_MH(KERNEL, grid, s, ...)                 \
+#define GAT_DISPATCH(KERNEL, grid, s, ...)                    \
   do {                                                        \
     if (heads > 1)                                            \
       GAT_DISPATCH_ONE(KERNEL, false, grid, s, __VA_ARGS__);  \
@@ -969,91 +576,84 @@ bool gat_heads_ok(int d, int heads) {
 }
 
 // lanes per head: dh / 4 (one head: the whole group)
-static int gat_head_lanes(int d, int heads) { return heads > 1 ? d / heads / 4 : gat_gl(d); }
+static int gat_head_lanes(int d, int heads) { return heads > 1 ? d / heads / 4 : item_gl(d); }
 
-void launch_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
-                          const float *a_src, float *u, float *v, hipStream_t s) {
+void launch_gat_scores(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
+                       const float *a_src, float *u, float *v, hipStream_t s) {
   PGCN_CHECK(gat_heads_ok(d, heads) && n >= 0, PGCN_E_INVALID,
              "gat_scores: 1 <= d <= 128, heads dividing d into widths of 4 .. 128 (a power of two)");
-  if (heads == 1) return launch_gat_scores(P, ld_p, n, d, a_dst, a_src, u, v, s);
   if (n == 0) return;
-  const dim3 grid((unsigned)std::min<long long>(ceil_div(n, kGatThreads / gat_gl(d)),
-                                                kGatMaxBlocks));
-  GAT_DISPATCH(k_gat_scores_mh, grid, s, P, ld_p, n, d, heads, gat_head_lanes(d, heads), a_dst,
-               a_src, u, v);
+  const dim3 grid((unsigned)std::min<long long>(ceil_div(n, kItemThreads / item_gl(d)),
+                                                kItemMaxBlocks));
+  GAT_DISPATCH(k_gat_scores, grid, s, P, ld_p, n, d, heads, gat_head_lanes(d, heads), a_dst, a_src,
+               u, v);
 }
 
-void launch_gat_fwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
-                       const float *v, float slope, float *Z, int ld_z, int d, int heads,
-                       const uint64_t *drop_mask, long long drop_base, float drop_scale,
-                       float *alpha, hipStream_t s) {
+void launch_gat_fwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, float *Z, int ld_z, int d, int heads, const uint64_t *drop_mask,
+                    long long drop_base, float drop_scale, float *alpha, hipStream_t s) {
   PGCN_CHECK(gat_heads_ok(d, heads) && g.n >= 0, PGCN_E_INVALID,
              "gat_fwd: 1 <= d <= 128, heads dividing d into widths of 4 .. 128 (a power of two)");
-  if (heads == 1 && !drop_mask) return launch_gat_fwd(g, P, ld_p, u, v, slope, Z, ld_z, d, alpha, s);
   if (g.n == 0) return;
   note_path(KP_GAT_FWD);
   if (heads > 1) note_path(KP_GAT_HEADS);
   const int hl = gat_head_lanes(d, heads);
   const GatDrop dr{drop_mask, drop_base, drop_scale};
-  GAT_DISPATCH_MH(k_gat_fwd_mh, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v,
-                  slope, Z, ld_z, d, heads, hl, alpha, dr);
+  GAT_DISPATCH(k_gat_fwd, item_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v, slope, Z,
+               ld_z, d, heads, hl, alpha, dr);
   if (g.n_row_segs > 0)
-    GAT_DISPATCH_MH(k_gat_fwd_merge_mh, gat_grid(g.n_row_segs), s, g, u, v, slope, Z, ld_z, d,
-                    heads, hl, alpha);
+    GAT_DISPATCH(k_gat_fwd_merge, item_grid(g.n_row_segs), s, g, u, v, slope, Z, ld_z, d, heads, hl,
+                 alpha);
 }
 
 namespace {
-// the layout of the _mh entries: serves one head with and without a mask
-GatBwdWs gat_bwd_layout_mh(const GatPattern &g, int d, int heads) {
+struct GatBwdWs {
+  size_t dx, du, dv, col_ws, part, floats;
+};
+size_t up4(size_t x) { return (x + 3) / 4 * 4; }
+GatBwdWs gat_bwd_layout(const GatPattern &g, int d, int heads) {
   GatBwdWs w;
   w.dx = 0;
   w.du = w.dx + up4((size_t)g.nnz * heads);
   w.dv = w.du + up4((size_t)g.n * heads);
   w.col_ws = w.dv + up4((size_t)g.n * heads);
-  w.part = w.col_ws + (size_t)g.n_col_segs * kGatWsStrideMh;
+  w.part = w.col_ws + (size_t)g.n_col_segs * kGatWsStride;
   w.floats = w.part + (size_t)gat_da_blocks(g.n, d) * 2 * (size_t)((d + 3) / 4 * 4);
   return w;
 }
 }  // namespace
 
-size_t gat_bwd_workspace_mh(const GatPattern &g, int d, int heads) {
+size_t gat_bwd_workspace(const GatPattern &g, int d, int heads) {
   if (g.n <= 0 || !gat_heads_ok(d, heads)) return 0;
-  return gat_bwd_layout_mh(g, d, heads).floats * sizeof(float);
+  return gat_bwd_layout(g, d, heads).floats * sizeof(float);
 }
 
-void launch_gat_bwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
-                       const float *v, float slope, const float *alpha, const float *Z, int ld_z,
-                       const float *G, int ld_g, const float *a_dst, const float *a_src, float *dP,
-                       int ld_dp, int d, int heads, const uint64_t *drop_mask, long long drop_base,
-                       float drop_scale, float *da, void *workspace, hipStream_t s) {
+void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
+                    float slope, const float *alpha, const float *Z, int ld_z, const float *G,
+                    int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                    int heads, const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                    float *da, void *workspace, hipStream_t s) {
   PGCN_CHECK(gat_heads_ok(d, heads) && g.n >= 0, PGCN_E_INVALID,
              "gat_bwd: 1 <= d <= 128, heads dividing d into widths of 4 .. 128 (a power of two)");
-  if (heads == 1 && !drop_mask)
-    return launch_gat_bwd(g, P, ld_p, u, v, slope, alpha, Z, ld_z, G, ld_g, a_dst, a_src, dP,
-                          ld_dp, d, da, workspace, s);
   if (g.n == 0) return;
   note_path(KP_GAT_BWD);
   if (heads > 1) note_path(KP_GAT_HEADS);
-  const GatBwdWs w = gat_bwd_layout_mh(g, d, heads);
+  const GatBwdWs w = gat_bwd_layout(g, d, heads);
   float *ws = static_cast<float *>(workspace);
   float *dx = ws + w.dx, *du = ws + w.du, *dv = ws + w.dv, *col_ws = ws + w.col_ws;
   float *partial = ws + w.part;
   const int hl = gat_head_lanes(d, heads);
   const GatDrop dr{drop_mask, drop_base, drop_scale};
-  GAT_DISPATCH_MH(k_gat_bwd_rows_mh, gat_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v,
-                  slope, alpha, Z, ld_z, G, ld_g, d, heads, hl, dr, dx);
-  GAT_DISPATCH_MH(k_gat_bwd_cols_mh, gat_grid((long long)g.n + g.n_col_segs), s, g, alpha, dx, G,
-                  ld_g, a_dst, a_src, d, heads, hl, dr, dP, ld_dp, du, dv, col_ws);
+  GAT_DISPATCH(k_gat_bwd_rows, item_grid((long long)g.n + g.n_row_segs), s, g, P, ld_p, u, v, slope,
+               alpha, Z, ld_z, G, ld_g, d, heads, hl, dr, dx);
+  GAT_DISPATCH(k_gat_bwd_cols, item_grid((long long)g.n + g.n_col_segs), s, g, alpha, dx, G, ld_g,
+               a_dst, a_src, d, heads, hl, dr, dP, ld_dp, du, dv, col_ws);
   if (g.n_long_cols > 0)
-    GAT_DISPATCH_MH(k_gat_bwd_colmerge_mh, gat_grid(g.n_long_cols), s, g, dx, a_dst, a_src, d,
-                    heads, hl, dP, ld_dp, du, dv, col_ws);
+    GAT_DISPATCH(k_gat_bwd_colmerge, item_grid(g.n_long_cols), s, g, dx, a_dst, a_src, d, heads, hl,
+                 dP, ld_dp, du, dv, col_ws);
   const int nb = gat_da_blocks(g.n, d), ldp = (d + 3) / 4 * 4;
-  if (heads > 1)
-    GAT_DISPATCH(k_gat_da_mh, dim3((unsigned)nb), s, P, ld_p, g.n, d, heads, hl, du, dv, partial,
-                 ldp);
-  else
-    GAT_DISPATCH(k_gat_da, dim3((unsigned)nb), s, P, ld_p, g.n, d, du, dv, partial, ldp);
-  PGCN_LAUNCH(k_gat_da_reduce, dim3((unsigned)ceil_div(2 * ldp, kGatThreads)), dim3(kGatThreads),
+  ITEM_DISPATCH(k_gat_da, dim3((unsigned)nb), s, P, ld_p, g.n, d, heads, hl, du, dv, partial, ldp);
+  PGCN_LAUNCH(k_gat_da_reduce, dim3((unsigned)ceil_div(2 * ldp, kItemThreads)), dim3(kItemThreads),
               0, s, partial, nb, ldp, d, da);
 }
 

@@ -4,11 +4,9 @@
 // element to the one slot that won, without float atomics.  (The mean aggregator is a GraphSum
 // with values 1 / len_i: DevGraph on other scales, no kernel here.)
 //
-// Layout: k_gat.hip's.  One wave per work item -- a row (forward) or a column of the transposed
-// index (backward) -- cut into 64 / GL neighbour groups of GL lanes, lane li of a group holding
-// the float4 at column 4 * li of its neighbour's row:
-//   d <= 4: GL 1 | <= 8: 2 | <= 16: 4 | <= 32: 8 | <= 64: 16 | <= 128: 32
-// Group q takes slots q, q + 64 / GL, ... of the item in CSR order.
+// Layout: slot_items.hpp's, shared with k_gat.hip.  One wave per work item -- a row (forward) or
+// a column of the transposed index (backward) -- cut into 64 / GL neighbour groups of GL lanes;
+// group q takes slots q, q + 64 / GL, ... of the item in CSR order.
 //   forward: a lane keeps {value, slot} per component; a candidate replaces the incumbent only
 //   when strictly greater, so the lowest slot of equal values stays.  The groups meet in xor
 //   butterflies over the lane offsets GL .. 32 under "greater value, else lower slot", which is
@@ -26,34 +24,13 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "slot_items.hpp"
 
 #pragma clang fp contract(off)
 
 namespace pgcn {
 
 namespace {
-constexpr int kSageThreads = 256;  // 4 waves: 4 items per workgroup step
-constexpr int kSageWaves = kSageThreads / kWave;
-constexpr int kSageMaxBlocks = 32 * kCUs;
-
-// the float4 at columns c0 .. c0 + 3 of a row of logical width d: columns >= d read as zero
-// (the padding may hold anything)
-__device__ __forceinline__ float4 row4(const float *p, int c0, int d, bool on) {
-  float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if (on) {
-    v = *reinterpret_cast<const float4 *>(p + c0);
-    if (c0 + 1 >= d) v.y = 0.0f;
-    if (c0 + 2 >= d) v.z = 0.0f;
-    if (c0 + 3 >= d) v.w = 0.0f;
-  }
-  return v;
-}
-
-__device__ __forceinline__ long long first_item() {
-  return ((long long)blockIdx.x * kSageThreads + threadIdx.x) / kWave;
-}
-__device__ __forceinline__ long long item_stride() { return (long long)gridDim.x * kSageWaves; }
-
 // a lane's running maxima: empty = {-inf, INT_MAX}
 struct Best4 {
   float4 v;
@@ -147,7 +124,7 @@ __device__ __forceinline__ void row_finish(const Best4 &w, bool empty, int i, in
 // items [0, n): the rows of at most kGatSeg slots, whole; items [n, n + n_row_segs): the long
 // rows' segments, which leave their winners in ws.row_val / ws.row_arg
 template <int GL>
-__global__ __launch_bounds__(kSageThreads) void k_agg_max_fwd(
+__global__ __launch_bounds__(kItemThreads) void k_agg_max_fwd(
     const GatPattern g, const SageWs ws, const float *__restrict__ in, int ld_in, int d,
     const float *__restrict__ add, int ld_add, float *__restrict__ out, int ld_out,
     int *__restrict__ arg, int ld_arg) {
@@ -174,7 +151,7 @@ __global__ __launch_bounds__(kSageThreads) void k_agg_max_fwd(
 // one wave per long row (the wave of its first segment): its segments' winners in segment
 // order, then the final write
 template <int GL>
-__global__ __launch_bounds__(kSageThreads) void k_agg_max_fwd_merge(
+__global__ __launch_bounds__(kItemThreads) void k_agg_max_fwd_merge(
     const GatPattern g, const SageWs ws, int d, const float *__restrict__ add, int ld_add,
     float *__restrict__ out, int ld_out, int *__restrict__ arg, int ld_arg) {
   const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
@@ -197,13 +174,6 @@ __global__ __launch_bounds__(kSageThreads) void k_agg_max_fwd_merge(
 }
 
 namespace {
-template <int GL>
-__device__ __forceinline__ float across_groups(float v) {
-#pragma unroll
-  for (int off = GL; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // slots [b, e) of the transposed index: the sum of the G_i components whose arg is the slot,
 // over the groups (every lane ends with the wave's sums)
 template <int GL>
@@ -236,7 +206,7 @@ __device__ __forceinline__ float4 col_select(const GatPattern &g, const float *_
 // items [0, n): the columns of at most kGatSeg incoming slots, whole; items [n, n + n_col_segs):
 // the long columns' segments, which leave their partial rows in ws.col_ws
 template <int GL>
-__global__ __launch_bounds__(kSageThreads) void k_agg_max_bwd(
+__global__ __launch_bounds__(kItemThreads) void k_agg_max_bwd(
     const GatPattern g, const SageWs ws, const float *__restrict__ G, int ld_g,
     const int *__restrict__ arg, int ld_arg, int d, float *__restrict__ din, int ld_din) {
   const int lane = threadIdx.x % kWave, c0 = 4 * (lane % GL);
@@ -259,7 +229,7 @@ __global__ __launch_bounds__(kSageThreads) void k_agg_max_bwd(
 
 // one wave per long column: its segments' partials in segment order
 template <int GL>
-__global__ __launch_bounds__(kSageThreads) void k_agg_max_bwd_merge(const GatPattern g,
+__global__ __launch_bounds__(kItemThreads) void k_agg_max_bwd_merge(const GatPattern g,
                                                                     const SageWs ws, int d,
                                                                     float *__restrict__ din,
                                                                     int ld_din) {
@@ -282,11 +252,11 @@ __global__ __launch_bounds__(kSageThreads) void k_agg_max_bwd_merge(const GatPat
 }
 
 template <bool ADD>
-__global__ __launch_bounds__(kSageThreads) void k_copy_cols(const float *__restrict__ src,
+__global__ __launch_bounds__(kItemThreads) void k_copy_cols(const float *__restrict__ src,
                                                             int ld_src, float *__restrict__ dst,
                                                             int ld_dst, long long total, int cols) {
-  for (long long e = (long long)blockIdx.x * kSageThreads + threadIdx.x; e < total;
-       e += (long long)gridDim.x * kSageThreads) {
+  for (long long e = (long long)blockIdx.x * kItemThreads + threadIdx.x; e < total;
+       e += (long long)gridDim.x * kItemThreads) {
     const long long r = e / cols;
     const int c = (int)(e - r * cols);
     const float v = src[r * ld_src + c];
@@ -295,38 +265,16 @@ __global__ __launch_bounds__(kSageThreads) void k_copy_cols(const float *__restr
   }
 }
 
-static int sage_gl(int d) {
-  const int d4 = (d + 3) / 4;
-  return d4 <= 1 ? 1 : d4 <= 2 ? 2 : d4 <= 4 ? 4 : d4 <= 8 ? 8 : d4 <= 16 ? 16 : 32;
-}
-
-static dim3 sage_grid(long long items) {
-  return dim3((unsigned)std::max<long long>(
-      1, std::min<long long>(ceil_div(items, kSageWaves), kSageMaxBlocks)));
-}
-
-#define SAGE_DISPATCH(KERNEL, grid, s, ...)                                                   \
-  do {                                                                                        \
-    switch (sage_gl(d)) {                                                                     \
-      case 1: PGCN_LAUNCH((KERNEL<1>), grid, dim3(kSageThreads), 0, s, __VA_ARGS__); break;   \
-      case 2: PGCN_LAUNCH((KERNEL<2>), grid, dim3(kSageThreads), 0, s, __VA_ARGS__); break;   \
-      case 4: PGCN_LAUNCH((KERNEL<4>), grid, dim3(kSageThreads), 0, s, __VA_ARGS__); break;   \
-      case 8: PGCN_LAUNCH((KERNEL<8>), grid, dim3(kSageThreads), 0, s, __VA_ARGS__); break;   \
-      case 16: PGCN_LAUNCH((KERNEL<16>), grid, dim3(kSageThreads), 0, s, __VA_ARGS__); break; \
-      default: PGCN_LAUNCH((KERNEL<32>), grid, dim3(kSageThreads), 0, s, __VA_ARGS__); break; \
-    }                                                                                         \
-  } while (0)
-
 void launch_agg_max_fwd(const GatPattern &g, const SageWs &ws, const float *in, int ld_in, int d,
                         const float *add, int ld_add, float *out, int ld_out, int *arg,
                         int ld_arg, hipStream_t s) {
   PGCN_CHECK(d >= 1 && d <= kSageMaxWidth && g.n >= 0 && g.nnz <= INT_MAX, PGCN_E_INVALID,
              "agg_max_fwd: 1 <= d <= 128, nnz within an int");
   if (g.n == 0) return;
-  SAGE_DISPATCH(k_agg_max_fwd, sage_grid((long long)g.n + g.n_row_segs), s, g, ws, in, ld_in, d,
+  ITEM_DISPATCH(k_agg_max_fwd, item_grid((long long)g.n + g.n_row_segs), s, g, ws, in, ld_in, d,
                 add, ld_add, out, ld_out, arg, ld_arg);
   if (g.n_row_segs > 0)
-    SAGE_DISPATCH(k_agg_max_fwd_merge, sage_grid(g.n_row_segs), s, g, ws, d, add, ld_add, out,
+    ITEM_DISPATCH(k_agg_max_fwd_merge, item_grid(g.n_row_segs), s, g, ws, d, add, ld_add, out,
                   ld_out, arg, ld_arg);
 }
 
@@ -335,10 +283,10 @@ void launch_agg_max_bwd(const GatPattern &g, const SageWs &ws, const float *G, i
   PGCN_CHECK(d >= 1 && d <= kSageMaxWidth && g.n >= 0 && g.nnz <= INT_MAX, PGCN_E_INVALID,
              "agg_max_bwd: 1 <= d <= 128, nnz within an int");
   if (g.n == 0) return;
-  SAGE_DISPATCH(k_agg_max_bwd, sage_grid((long long)g.n + g.n_col_segs), s, g, ws, G, ld_g, arg,
+  ITEM_DISPATCH(k_agg_max_bwd, item_grid((long long)g.n + g.n_col_segs), s, g, ws, G, ld_g, arg,
                 ld_arg, d, din, ld_din);
   if (g.n_long_cols > 0)
-    SAGE_DISPATCH(k_agg_max_bwd_merge, sage_grid(g.n_long_cols), s, g, ws, d, din, ld_din);
+    ITEM_DISPATCH(k_agg_max_bwd_merge, item_grid(g.n_long_cols), s, g, ws, d, din, ld_din);
 }
 
 void launch_copy_cols(const float *src, int ld_src, float *dst, int ld_dst, int n, int cols,
@@ -347,12 +295,12 @@ void launch_copy_cols(const float *src, int ld_src, float *dst, int ld_dst, int 
              "copy_cols: strides");
   if (n == 0) return;
   const long long total = (long long)n * cols;
-  const dim3 grid((unsigned)std::min<long long>(ceil_div(total, kSageThreads), kSageMaxBlocks));
+  const dim3 grid((unsigned)std::min<long long>(ceil_div(total, kItemThreads), kItemMaxBlocks));
   if (add)
-    PGCN_LAUNCH(k_copy_cols<true>, grid, dim3(kSageThreads), 0, s, src, ld_src, dst, ld_dst, total,
+    PGCN_LAUNCH(k_copy_cols<true>, grid, dim3(kItemThreads), 0, s, src, ld_src, dst, ld_dst, total,
                 cols);
   else
-    PGCN_LAUNCH(k_copy_cols<false>, grid, dim3(kSageThreads), 0, s, src, ld_src, dst, ld_dst, total,
+    PGCN_LAUNCH(k_copy_cols<false>, grid, dim3(kItemThreads), 0, s, src, ld_src, dst, ld_dst, total,
                 cols);
 }
 

@@ -350,16 +350,23 @@ void launch_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_
                           const float *rstd, const float *gamma, int n, int d, float *dx, int ld_dx,
                           float *dgamma, float *dbeta, void *workspace, hipStream_t s);
 // ---- Graph attention over the CSR slots of a square pattern (k_gat.hip) ---------------------
-// Single head, additive (GAT): u_i = P_i . a_dst, v_j = P_j . a_src, e_s = leaky(u_i + v_j) per
+// Additive (GAT), per head: u_i = P_i . a_dst, v_j = P_j . a_src, e_s = leaky(u_i + v_j) per
 // slot s = (i, j), alpha = softmax of e over the row's slots, Z_i = sum alpha_s P_j.  1 <= d <=
 // kGatMaxWidth, every ld a multiple of 4 and >= d, rows 16-byte aligned; padding columns of the
 // inputs may hold anything, the float4s covering [0, round_up4(d)) of the outputs are written
 // (zero from column d on).  Rows (forward) and columns (backward) longer than kGatSeg slots are
 // cut into kGatSeg-slot segments summed by separate waves and merged in segment order; every
-// summation order depends on the pattern and d only (no float atomics).
+// summation order depends on the pattern, d and heads only (no float atomics).
+// Head h of `heads` owns columns [h dh, (h + 1) dh), dh = d / heads in {4, 8, .., 128}
+// (gat_heads_ok; one head: any d in 1..128), and runs the formulas on its slice: u, v
+// [n][heads], alpha [nnz][heads].  drop_mask (or null): bit drop_base + s heads + h keeps the
+// weight of slot s, head h, times drop_scale in Z and in the backward; alpha receives the
+// weights before dropout.  One launch serves every head.
 constexpr int kGatMaxWidth = 128;
 constexpr int kGatSeg = 512;
-constexpr int kGatWsStride = 4 + kGatMaxWidth;  // a segment's partial: {max, sum, -, -, row[128]}
+constexpr int kGatMaxHeads = kGatMaxWidth / 4;
+// a segment's partial: {max[32], sum[32], row[128]}; the column pass's {dv[32], -, row[128]}
+constexpr int kGatWsStride = 2 * kGatMaxHeads + kGatMaxWidth;
 // The pattern on the device (DevGraph::gat_pattern, built at its first use): the CSR, its
 // transposed index (column j's slots in CSR order: csc_row their rows, csc_pos their slots) and
 // the segment lists of the long rows / columns: segs {id, begin, end, the id's first segment}
@@ -371,46 +378,26 @@ struct GatPattern {
   int n_row_segs = 0, n_col_segs = 0, n_long_cols = 0;
   const int4 *row_segs = nullptr, *col_segs = nullptr;
   const int2 *long_cols = nullptr;  // {column, its first segment}
-  float *row_ws = nullptr;          // forward: [n_row_segs][kGatWsStrideMh] (one head: kGatWsStride)
+  float *row_ws = nullptr;          // forward: [n_row_segs][kGatWsStride]
 };
-void launch_gat_scores(const float *P, int ld_p, int n, int d, const float *a_dst,
+bool gat_heads_ok(int d, int heads);
+void launch_gat_scores(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
                        const float *a_src, float *u, float *v, hipStream_t s);
-// alpha [nnz] (training) or null
+// alpha [nnz][heads] (training) or null
 void launch_gat_fwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
-                    float slope, float *Z, int ld_z, int d, float *alpha, hipStream_t s);
-// workspace: dx [nnz], du [n], dv [n], the long columns' segment partials, the da partials
-size_t gat_bwd_workspace(const GatPattern &g, int d);
-// dP [n][ld_dp] = sum over column j's slots of alpha_s G_i + du_j a_dst + dv_j a_src with dx_s =
-// alpha_s (G_i . P_j - G_i . Z_i) leaky'(u_i + v_j), du_i / dv_j its row / column sums; da [2][d]
-// = {sum du_i P_i, sum dv_j P_j}
+                    float slope, float *Z, int ld_z, int d, int heads, const uint64_t *drop_mask,
+                    long long drop_base, float drop_scale, float *alpha, hipStream_t s);
+// workspace: dx [nnz][heads], du, dv [n][heads], the long columns' segment partials, the da
+// partials
+size_t gat_bwd_workspace(const GatPattern &g, int d, int heads);
+// dP [n][ld_dp] = sum over column j's slots of alpha_s m'_s G_i + du_j a_dst + dv_j a_src with
+// dx_s = alpha_s (m'_s G_i . P_j - G_i . Z_i) leaky'(u_i + v_j) (m'_s the slot's dropout factor),
+// du_i / dv_j its row / column sums, each per head; da [2][d] = {sum du_i P_i, sum dv_j P_j}
 void launch_gat_bwd(const GatPattern &g, const float *P, int ld_p, const float *u, const float *v,
                     float slope, const float *alpha, const float *Z, int ld_z, const float *G,
                     int ld_g, const float *a_dst, const float *a_src, float *dP, int ld_dp, int d,
+                    int heads, const uint64_t *drop_mask, long long drop_base, float drop_scale,
                     float *da, void *workspace, hipStream_t s);
-// Several heads and dropout on the attention weights: head h of `heads` owns columns [h dh,
-// (h + 1) dh), dh = d / heads in {4, 8, .., 128} (gat_heads_ok; one head: any d in 1..128), and
-// runs the formulas above on its slice: u, v [n][heads], alpha [nnz][heads].  drop_mask (or
-// null): bit drop_base + s heads + h keeps the weight of slot s, head h, times drop_scale in Z
-// and in the backward; alpha receives the weights before dropout.  One launch serves every
-// head; heads == 1 without a mask is the single-head launch above.
-constexpr int kGatMaxHeads = kGatMaxWidth / 4;
-// a segment's partial there: {max[32], sum[32], row[128]}; the column pass's {dv[32], -, row}
-constexpr int kGatWsStrideMh = 2 * kGatMaxHeads + kGatMaxWidth;
-bool gat_heads_ok(int d, int heads);
-void launch_gat_scores_mh(const float *P, int ld_p, int n, int d, int heads, const float *a_dst,
-                          const float *a_src, float *u, float *v, hipStream_t s);
-void launch_gat_fwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
-                       const float *v, float slope, float *Z, int ld_z, int d, int heads,
-                       const uint64_t *drop_mask, long long drop_base, float drop_scale,
-                       float *alpha, hipStream_t s);
-// dx [nnz][heads], du, dv [n][heads], the segment partials, the da partials (one head: enough
-// for a call with a mask and for one without)
-size_t gat_bwd_workspace_mh(const GatPattern &g, int d, int heads);
-void launch_gat_bwd_mh(const GatPattern &g, const float *P, int ld_p, const float *u,
-                       const float *v, float slope, const float *alpha, const float *Z, int ld_z,
-                       const float *G, int ld_g, const float *a_dst, const float *a_src, float *dP,
-                       int ld_dp, int d, int heads, const uint64_t *drop_mask, long long drop_base,
-                       float drop_scale, float *da, void *workspace, hipStream_t s);
 // ---- GraphSAGE's max aggregator over the same pattern (k_sage.hip) ----------------------------
 // out_i[c] = add_i[c] + max over row i's slots of in_j[c] (one add; `add` null: the maximum),
 // arg_i[c] (or null) the global CSR slot that won: a candidate replaces the incumbent only when

@@ -3,7 +3,9 @@ _bwd_mh) against the float64 reference of tests/gat_heads_ref.py (checked itself
 tests/test_cpu_gat_heads.py), on the graphs of tests/test_gpu_gat_kernels.py: the 300-node hub
 graph (a 4,100-slot row, segmented columns, an empty row, a one-slot row, rows of 63 / 64 / 65
 slots, a column without an incoming slot) and n = 1.  The bounds are that file's _close: rtol
-1e-4, atol 1e-6 max|ref| (da: x sqrt(n), as there).
+1e-4, atol 1e-6 max|ref| (da: x sqrt(n), as there).  There is one kernel family: the single-head
+entries are these kernels at heads = 1 with a null mask, so the tests that compare the two pin
+the two sets of ABI entries to each other.
 """
 import ctypes
 
@@ -32,7 +34,8 @@ def _grad(n, d, ld, seed):
 def run_mh(pgcn, graph, P, a_dst, a_src, d, ld, K, G=None, bits=None, base=0, scale=1.0,
            training=True, old=False):
     """scores + forward (+ backward when G is given) on guarded outputs, through the _mh entries
-    (old: the single-head entries); host copies with the guards."""
+    (old: the single-head entries pgcn_gat_scores / _fwd / _bwd, which reach the same kernels at
+    heads = 1 without a mask); host copies with the guards."""
     h, indptr, _ = graph
     n, nnz = len(indptr) - 1, int(indptr[-1])
     lib = pgcn.lib
@@ -167,10 +170,11 @@ def test_heads_of_different_scale(pgcn, graphs, d, ld, K):
 
 
 @pytest.mark.parametrize("name", sorted(GRAPHS))
-@pytest.mark.parametrize("d,ld", [(3, 4), (16, 16), (128, 128)])
+@pytest.mark.parametrize("d,ld", [(3, 4), (8, 8), (16, 16), (20, 20), (64, 64), (128, 128)])
 def test_one_head_without_mask_is_the_single_head_entry(pgcn, graphs, name, d, ld):
     """heads = 1 with a null mask through the _mh entries: the bits of pgcn_gat_scores / _fwd /
-    _bwd, forward and backward."""
+    _bwd, forward and backward, at one width inside every lane-group size (the single-head
+    entries are the same kernels behind their own argument checks)."""
     h, indptr, indices = graphs[name]
     n = len(indptr) - 1
     P, a_dst, a_src = _inputs(n, d, ld, 31 * d + n)
@@ -212,8 +216,9 @@ def test_mask_against_float64(pgcn, graphs, d, ld, K, base):
 @pytest.mark.parametrize("d,ld,K", [(8, 8, 2), (64, 64, 8), (128, 128, 32), (16, 16, 1),
                                     (3, 4, 1), (128, 128, 1)])
 def test_all_ones_mask_is_the_null_mask(pgcn, graphs, name, d, ld, K):
-    """An all-ones mask with scale 1 gives the null mask's bits; at one head those are the
-    single-head entries' bits."""
+    """An all-ones mask with scale 1 gives the null mask's bits; at one head the null-mask call
+    goes through the single-head entries (the same kernels at heads = 1 behind their own
+    argument checks)."""
     h, indptr, indices = graphs[name]
     n, nnz = len(indptr) - 1, int(indptr[-1])
     P, a_dst, a_src = _inputs(n, d, ld, 11 * d + K + n)

@@ -6,8 +6,9 @@
 
 Per graph -- cora (from tests/golden, or data/cora.* under --root) and bench.py's reddit shape
 (Dataset.synthetic: 232,965 nodes, 57,307,946 undirected edges, seed 1) -- the script times
-pgcn_gat_scores + pgcn_gat_fwd (training: alpha written), pgcn_gat_bwd and pgcn_graphsum through
-the kernel ABI (with --heads above 1: pgcn_gat_scores_mh / _fwd_mh / _bwd_mh, no mask) with HIP events around each call on the null stream: `warmup` calls, then `reps`
+pgcn_gat_scores_mh + pgcn_gat_fwd_mh (training: alpha written, no mask), pgcn_gat_bwd_mh and
+pgcn_graphsum through the kernel ABI (at one head these are the kernels behind pgcn_gat_scores /
+_fwd / _bwd) with HIP events around each call on the null stream: `warmup` calls, then `reps`
 timed ones, the three taken in turn; the median, minimum and maximum in microseconds.  Beside
 them the bytes each call has to move and the rate that implies:
     forward   indptr + idx + u, v (K per node and K per slot's column) + P rows gathered
@@ -69,7 +70,7 @@ def bench_graph(pg, torch, ds, reps, warmup, D=16, K=1):
     alpha = torch.zeros(max(nnz, 1) * K, device="cuda")
     da = torch.zeros(2 * D, device="cuda")
     # (builds the transposed index)
-    ws_bytes = lib.pgcn_gat_bwd_workspace(h, D) if K == 1 else lib.pgcn_gat_bwd_workspace_mh(h, D, K)
+    ws_bytes = lib.pgcn_gat_bwd_workspace_mh(h, D, K)
     assert ws_bytes > 0
     ws = torch.zeros(ws_bytes // 4 + 4, device="cuda")
 
@@ -77,22 +78,12 @@ def bench_graph(pg, torch, ds, reps, warmup, D=16, K=1):
         return ctypes.c_void_p(t.data_ptr())
 
     def fwd():
-        if K == 1:
-            pg.check(lib.pgcn_gat_scores(p(P), D, n, D, p(a_dst), p(a_src), p(u), p(v), None),
-                     "scores")
-            pg.check(lib.pgcn_gat_fwd(h, p(P), D, p(u), p(v), SLOPE, p(Z), D, D, p(alpha), None),
-                     "fwd")
-            return
         pg.check(lib.pgcn_gat_scores_mh(p(P), D, n, D, K, p(a_dst), p(a_src), p(u), p(v), None),
                  "scores_mh")
         pg.check(lib.pgcn_gat_fwd_mh(h, p(P), D, p(u), p(v), SLOPE, p(Z), D, D, K, None, 0, 1.0,
                                      p(alpha), None), "fwd_mh")
 
     def bwd():
-        if K == 1:
-            pg.check(lib.pgcn_gat_bwd(h, p(P), D, p(u), p(v), SLOPE, p(alpha), p(Z), D, p(G), D,
-                                      p(a_dst), p(a_src), p(dP), D, D, p(da), p(ws), None), "bwd")
-            return
         pg.check(lib.pgcn_gat_bwd_mh(h, p(P), D, p(u), p(v), SLOPE, p(alpha), p(Z), D, p(G), D,
                                      p(a_dst), p(a_src), p(dP), D, D, K, None, 0, 1.0, p(da),
                                      p(ws), None), "bwd_mh")
