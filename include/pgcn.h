@@ -880,6 +880,19 @@ int pgcn_debug_tn_reduce_blocks(float *partial, int n_blocks, int K, int N, int 
                                 int ldc, void *stream);
 int pgcn_debug_tn_reduce_one_pass(const float *partial, int n, int K, int N, int ldp, float *C,
                                   int ldc, void *stream);
+/* pgcn_gemm / pgcn_gemm_tn with A's dropout bits in the nibble layout as well (mask_nib, from
+ * pgcn_mask_nibbles of the same bitmap; NULL: none), as the engine hands them to a dense first
+ * layer of 33..128 columns: the wide kernels read the nibbles instead of the flat bitmap when
+ * a_mask is given and K <= 1024; every other shape ignores them.  Same argument checks and the
+ * same bits as the plain entries. */
+int pgcn_debug_gemm_nib(int M, int N, int K, const float *A, int lda, const float *B, int ldb,
+                        int trans_b, float *C, int ldc, const uint64_t *a_mask,
+                        long long mask_base, long long mask_ld, float a_scale,
+                        const uint64_t *mask_nib, void *stream);
+int pgcn_debug_gemm_tn_nib(int M, int N, int K, const float *A, int lda, const float *G, int ldg,
+                           float *C, int ldc, const uint64_t *a_mask, long long mask_base,
+                           long long mask_ld, float a_scale, const uint64_t *mask_nib,
+                           void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -227,6 +227,10 @@ _sig("pgcn_debug_tn_reduce_blocks", c_int, c_void_p, c_int, c_int, c_int, c_int,
      c_void_p)
 _sig("pgcn_debug_tn_reduce_one_pass", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
      c_int, c_void_p)
+_sig("pgcn_debug_gemm_nib", c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+     c_void_p, c_int, c_void_p, c_ll, c_ll, c_float, c_void_p, c_void_p)
+_sig("pgcn_debug_gemm_tn_nib", c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+     c_void_p, c_int, c_void_p, c_ll, c_ll, c_float, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_debug_lds_check", c_int, c_int, c_int, c_void_p, c_void_p, c_int, P(ctypes.c_double),
      P(c_ll))
 _sig("pgcn_debug_lds_counts", c_ll, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll,
@@ -835,6 +839,7 @@ EXPORTED = [
     "pgcn_debug_ring_slice_rows", "pgcn_debug_xent_fwd", "pgcn_debug_out_xent",
     "pgcn_debug_finalize_ring", "pgcn_debug_tn_reduce_blocks_workspace",
     "pgcn_debug_tn_reduce_blocks", "pgcn_debug_tn_reduce_one_pass",
+    "pgcn_debug_gemm_nib", "pgcn_debug_gemm_tn_nib",
     "pgcn_bce_fwd", "pgcn_predict_multilabel_rows", "pgcn_multilabel_counts",
     "pgcn_gcn_predict_multilabel", "pgcn_gcn_multilabel_counts", "pgcn_dataset_set_multilabel",
     "pgcn_dataset_load_labels",

@@ -1431,6 +1431,31 @@ int pgcn_debug_tn_reduce_one_pass(const float *partial, int n, int K, int N, int
   });
 }
 
+int pgcn_debug_gemm_nib(int M, int N, int K, const float *A, int lda, const float *B, int ldb,
+                        int trans_b, float *C, int ldc, const uint64_t *a_mask,
+                        long long mask_base, long long mask_ld, float a_scale,
+                        const uint64_t *mask_nib, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(A && B && C && M >= 0 && K > 0 && ldc >= N, PGCN_E_INVALID, "debug_gemm_nib args");
+    launch_gemm_nn(M, N, K, A, lda, B, ldb, trans_b, C, ldc, a_mask, mask_base, mask_ld, a_scale,
+                   as_stream(stream), mask_nib);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_gemm_tn_nib(int M, int N, int K, const float *A, int lda, const float *G, int ldg,
+                           float *C, int ldc, const uint64_t *a_mask, long long mask_base,
+                           long long mask_ld, float a_scale, const uint64_t *mask_nib,
+                           void *workspace, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(A && G && C && workspace && K > 0 && ldc >= N, PGCN_E_INVALID,
+               "debug_gemm_tn_nib args");
+    launch_gemm_tn(M, N, K, A, lda, G, ldg, C, ldc, a_mask, mask_base, mask_ld, a_scale,
+                   workspace, as_stream(stream), mask_nib);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 long long pgcn_debug_path_count(const char *name, int reset) {
   const bool thread = (reset & 2) != 0, zero = (reset & 1) != 0;
   if (reset & ~3) return PGCN_E_INVALID;

@@ -693,6 +693,8 @@ static void gemm_nn_slab(int M, int N, int K, const float *A, int lda, const flo
                         a_scale, s, nst, a_mask && K <= 1024 ? maskT : nullptr);
     return;
   }
+  // N <= 32 from here on (the wide kernels took 33..128): one or two 16-column tiles
+  PGCN_CHECK(N <= 32, PGCN_E_INVALID, "gemm: no kernel for N=" + std::to_string(N));
   note_path(KP_GEMM_NN);
   const int nt = (N + 15) / 16;
   const dim3 grid((unsigned)ceil_div(M, 64)), block(256);
@@ -702,7 +704,7 @@ static void gemm_nn_slab(int M, int N, int K, const float *A, int lda, const flo
                        ldc, a_mask, mask_base, mask_ld, a_scale, nst);                        \
     break;
   switch (nt) {
-    NN_CASE(1) NN_CASE(2) NN_CASE(3) NN_CASE(4) NN_CASE(5) NN_CASE(6) NN_CASE(7) NN_CASE(8)
+    NN_CASE(1) NN_CASE(2)
   }
 #undef NN_CASE
 }
@@ -718,6 +720,9 @@ static TnPlan tn_plan(int M, int N, int K) {
   p.nkc = (K + 63) / 64;
   p.wk = p.nkc >= 4 ? 4 : (p.nkc >= 2 ? 2 : 1);
   p.kcw = std::min(3, (p.nkc + p.wk - 1) / p.wk);
+  // one chunk per wave below 4 waves along K (the forms instantiated): three chunks run as two
+  // k-groups of two waves, the second group's last wave idle, not as (kcw 2, wk 2)
+  if (p.wk < 4) p.kcw = 1;
   if (p.nj > 4) p.kcw = 1;  // accumulators: 16 * kcw * nj registers (instantiated: kcw 1)
   p.kgroups = (p.nkc + p.wk * p.kcw - 1) / (p.wk * p.kcw);
   const int wr = 4 / p.wk;

@@ -70,6 +70,17 @@ constexpr int WNN_KC = 64;             // k per LDS chunk of B^T
 constexpr int WNN_S = WNN_KC + 4;      // B^T row stride in floats (== 4 mod 64: 2-way at most)
 constexpr int WNN_ROWS = 128;          // rows per workgroup (4 waves x 2 tiles x 16)
 
+// Bytes of the B operand from the launch's own B pointer to the end of its last element: the
+// range of the staging loads' buffer descriptor.  B may be a 128-column slab of a wider matrix
+// (B + j0, or B^T + j0 * ldb), so a bound of whole rows (K * ldb, N * ldb) would reach up to j0
+// elements past the allocation in the last row, where the staging lanes of the tile's unused
+// columns (loaded, then dropped) would read for real.
+template <bool TRANS_B>
+__device__ __forceinline__ int wnn_b_bytes(int N, int K, int ldb) {
+  const long long rows = TRANS_B ? N : K, cols = TRANS_B ? K : N;
+  return (int)(((rows - 1) * ldb + cols) * 4);
+}
+
 // Dropout bits of A (MK): 0 none, 1 the flat element-order bitmap (bit mask_base + row *
 // mask_ld + k), 2 the nibble layout of k_mask_nibbles (maskT[row][j] nibble c = bits of
 // k = 64c + 4j .. +3; K <= 1024).
@@ -114,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_w(int M, int N, int K,
   // buffer loads: one 32-bit voffset per thread, the q stride in the scalar offset, rows past
   // B's (K rows of B, N rows of B^T) read as 0 by the descriptor's range check
   const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(B), 0, (int)((long long)(TRANS_B ? N : K) * ldb * 4), 0x00020000);
+      const_cast<float *>(B), 0, wnn_b_bytes<TRANS_B>(N, K, ldb), 0x00020000);
   float stg[PER];
   auto load_chunk = [&](int c) {
     const int k = c * WNN_KC + skk;
@@ -288,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn_wp(int M, int N, int K,
     const int sj = TRANS_B ? tid / 64 : tid % NCP, skk = TRANS_B ? tid % WNN_KC : tid / NCP;
     constexpr int DJ = TRANS_B ? 4 : 0, DK = TRANS_B ? 0 : 256 / NCP;
     const __amdgpu_buffer_rsrc_t brs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(B), 0, (int)((long long)(TRANS_B ? N : K) * ldb * 4), 0x00020000);
+        const_cast<float *>(B), 0, wnn_b_bytes<TRANS_B>(N, K, ldb), 0x00020000);
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
       const int k = c * WNN_KC + skk;

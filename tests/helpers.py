@@ -267,6 +267,51 @@ def csr_reference(indptr, indices, vals, x, n_cols=None):
     return a @ x64, b @ np.abs(x64)
 
 
+# --------------------------------------------------------------------------- GEMM references
+def mask_bits(mask_words, n):
+    """the first n bits of a bitmap of uint64 words (bit i = word i / 64, bit i % 64)"""
+    b = np.unpackbits(mask_words.view(np.uint8), bitorder="little")
+    return b[:n].astype(bool)
+
+
+def mask_window(mask, base, M, K, mask_ld=None):
+    """bits base + m * mask_ld + k (mask_ld = K when not given) of a flat bitmap as an (M, K)
+    bool array"""
+    ld = K if mask_ld is None else mask_ld
+    if M == 0:
+        return np.zeros((0, K), bool)
+    bits = mask_bits(mask, base + (M - 1) * ld + K)[base:]
+    bits = np.concatenate([bits, np.zeros(M * ld - len(bits), bool)])
+    return bits.reshape(M, ld)[:, :K]
+
+
+def nibble_mask_ref(mask, base, M, K, mask_ld=None):
+    """maskT[m][j] nibble c = keep bits of (m, 64c + 4j .. +3), zero past K (numpy)"""
+    bits = np.zeros((M, 1024), np.uint64)
+    bits[:, :K] = mask_window(mask, base, M, K, mask_ld)
+    nib = bits.reshape(M, 16, 16, 4)  # [m][c][j][t]: k = 64c + 4j + t
+    vals = (nib << np.arange(4, dtype=np.uint64)).sum(-1)  # [m][c][j]
+    out = np.zeros((M, 16), np.uint64)
+    for c in range(16):
+        out |= vals[:, c, :] << np.uint64(4 * c)
+    return out
+
+
+def dropped64(A, K, keep=None, scale=1.0):
+    """drop(A)[:, :K] in float64: kept entries (keep, an (M, K) bool array; None: all) times
+    scale, the others zero"""
+    Ae = A[:, :K].astype(np.float64)
+    return Ae if keep is None else Ae * np.where(keep, scale, 0.0)
+
+
+def product_ref(Ae, B):
+    """(Ae B, |Ae| |B|) in float64: a product's reference and, per output element, the sum of
+    its terms' magnitudes -- the scale of an fp32 sum's reordering error (the GEMM tests bound
+    |got - ref| by 1e-5 of it)"""
+    B64 = B.astype(np.float64)
+    return Ae @ B64, np.abs(Ae) @ np.abs(B64)
+
+
 # --------------------------------------------------------------------------- engine knobs
 # pgcn_debug_set defaults of the engine (include/pgcn.h; parallel-gcn_amd/csrc/knobs.hpp, whose
 # table test_cpu_host.py compares with this one through pgcn_debug_knob)

@@ -475,6 +475,22 @@ def test_part2_configs_match_oracle(datasets, pgcn, name):
     g.close()
 
 
+def test_three_chunk_weight_grad_matches_oracle(loaded, pgcn):
+    """hidden_dims (160, 32): the second layer's weight gradient is a TN product of 32 output
+    columns over K = 160, three 64-wide chunks on the general TN kernel (tn_plan once paired
+    three chunks with a form the launcher does not list, and train_epoch failed with "gemm_tn:
+    no kernel for N=32 K=160").  Two epochs against the oracle."""
+    ds = loaded["cora"]
+    dims, drops = (160, 32), (0.5, 0.5, 0.5)
+    g = pgcn.GCN(pgcn.make_params(ds, hidden_dims=dims, dropouts=drops), ds)
+    ref = helpers.OracleGCN(helpers.ds_dict(ds), hidden_dims=dims, dropouts=drops)
+    cnt = _counts(ds)
+    for e in range(2):
+        helpers.assert_line_close(g.train_epoch() + g.eval(2), ref.train_epoch() + ref.eval(2),
+                                  cnt, what=f"epoch {e + 1}")
+    g.close()
+
+
 def _fused_run(pgcn, ds, fuse, epochs, reassoc_small=1, **make):
     with helpers.knobs(pgcn, fuse_epilogue=fuse, reassoc_small=reassoc_small):
         g = pgcn.GCN(pgcn.make_params(ds, **make), ds)

@@ -361,9 +361,7 @@ def test_graphsum_linearity_large(pgcn):
     pgcn.lib.pgcn_graph_destroy(g)
 
 
-def mask_bits(mask_words, n):
-    b = np.unpackbits(mask_words.view(np.uint8), bitorder="little")
-    return b[:n].astype(bool)
+mask_bits = helpers.mask_bits
 
 
 def test_dropout_masks_bit_exact(pgcn):
@@ -447,9 +445,7 @@ def test_relu_fwd_bwd(pgcn):
     np.testing.assert_array_equal(dg.cpu().numpy().view(np.uint32), want_g.view(np.uint32))
 
 
-def mask_window(mask, base, M, K):
-    """bits base .. base + M*K of a flat bitmap as an (M, K) bool array"""
-    return mask_bits(mask, base + M * K)[base:].reshape(M, K)
+mask_window = helpers.mask_window
 
 
 # every shape on the kernel the product dispatches it to: N <= 16 streaming (X-stream) kernels,
@@ -470,10 +466,8 @@ def test_gemm_nn(pgcn, M, N, K, drop, base):
     B = rng.standard_normal((K, N)).astype(np.float32)
     # exactly as many words as the bits need: the kernels must not read past the bitmap
     mask = rng.integers(0, 2**63, (base + M * K + 63) // 64, dtype=np.uint64)
-    Ae = A[:, :K].astype(np.float64)
-    if drop:
-        Ae = Ae * np.where(mask_window(mask, base, M, K), 2.0, 0.0)
-    ref = Ae @ B.astype(np.float64)
+    Ae = helpers.dropped64(A, K, mask_window(mask, base, M, K) if drop else None, 2.0)
+    ref, bound = helpers.product_ref(Ae, B)
     dA, dB = torch.from_numpy(A).to(DEV), torch.from_numpy(B).to(DEV)
     dm = torch.from_numpy(mask.view(np.int64)).to(DEV)
     ldc = (N + 3) // 4 * 4
@@ -486,7 +480,6 @@ def test_gemm_nn(pgcn, M, N, K, drop, base):
     pgcn.check(pgcn.lib.pgcn_gemm(M, N, K, vp(dA), lda, vp(dBt), K, 1, vp(C2), ldc,
                                   vp(dm) if drop else None, base, K, 2.0, stream()), "gemm_t")
     torch.cuda.synchronize()
-    bound = np.abs(Ae) @ np.abs(B.astype(np.float64))
     for out in (C, C2):
         o = out.cpu().numpy()
         assert (np.abs(o[:, :N] - ref) <= 1e-5 * bound + 1e-30).all()
@@ -508,10 +501,8 @@ def test_gemm_tn(pgcn, M, N, K, drop, base):
     A[:, K:] = np.nan
     Gm = rng.standard_normal((M, N)).astype(np.float32)
     mask = rng.integers(0, 2**63, (base + M * K + 63) // 64, dtype=np.uint64)
-    Ae = A[:, :K].astype(np.float64)
-    if drop:
-        Ae = Ae * np.where(mask_window(mask, base, M, K), 2.0, 0.0)
-    ref = Ae.T @ Gm.astype(np.float64)
+    Ae = helpers.dropped64(A, K, mask_window(mask, base, M, K) if drop else None, 2.0)
+    ref, bound = helpers.product_ref(Ae.T, Gm)
     ws = torch.empty(pgcn.lib.pgcn_gemm_tn_workspace(M, N, K) // 4 + 16, device=DEV)
     dA, dG = torch.from_numpy(A).to(DEV), torch.from_numpy(Gm).to(DEV)
     dm = torch.from_numpy(mask.view(np.int64)).to(DEV)
@@ -520,20 +511,10 @@ def test_gemm_tn(pgcn, M, N, K, drop, base):
                                      vp(dm) if drop else None, base, K, 2.0, vp(ws), stream()),
                "tn")
     torch.cuda.synchronize()
-    bound = np.abs(Ae).T @ np.abs(Gm.astype(np.float64))
     assert (np.abs(C.cpu().numpy() - ref) <= 1e-5 * bound + 1e-30).all()
 
 
-def nibble_mask_ref(mask, base, M, K):
-    """maskT[m][j] nibble c = keep bits of (m, 64c + 4j .. +3), zero past K (numpy)"""
-    bits = np.zeros((M, 1024), np.uint64)
-    bits[:, :K] = mask_window(mask, base, M, K)
-    nib = bits.reshape(M, 16, 16, 4)  # [m][c][j][t]: k = 64c + 4j + t
-    vals = (nib << np.arange(4, dtype=np.uint64)).sum(-1)  # [m][c][j]
-    out = np.zeros((M, 16), np.uint64)
-    for c in range(16):
-        out |= vals[:, c, :] << np.uint64(4 * c)
-    return out
+nibble_mask_ref = helpers.nibble_mask_ref
 
 
 @pytest.mark.parametrize("M,N,K,base", [(3001, 16, 602, 0), (40009, 16, 602, 9),
