@@ -800,7 +800,11 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * GraphSum), "gs_gather" (gather GraphSum), "out_xent" (output layer fused into the loss),
  * "gemm_nn" / "gemm_tn" (general MFMA GEMMs), "gat_fwd" / "gat_bwd" (graph attention forward /
  * backward calls, pgcn_gat_fwd / pgcn_gat_bwd and their _mh forms), "gat_heads" (those of them
- * with heads > 1), "launches" (every kernel launch of the library).
+ * with heads > 1), "spmm_csr" / "spmm_csr_dual" (sparse X: the CSR forward and its dual form,
+ * c = X b beside c2 = drop(X) b), "spmm_csc_256" / "spmm_csc_1024" (sparse X: the weight
+ * gradient's sequential-chain kernel, 256 threads per feature or 1024 on matrices of more than
+ * 512 entries per feature), "spmm_tree_256" / "spmm_tree_1024" (its fixed-tree form, csc_tree),
+ * "launches" (every kernel launch of the library).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank
@@ -893,6 +897,42 @@ int pgcn_debug_gemm_tn_nib(int M, int N, int K, const float *A, int lda, const f
                            float *C, int ldc, const uint64_t *a_mask, long long mask_base,
                            long long mask_ld, float a_scale, const uint64_t *mask_nib,
                            void *workspace, void *stream);
+/* The sparse first layer's products with every argument the engine varies (pgcn_spmm_csr and
+ * pgcn_spmm_csc_bwd fix ldc = ldg = p, mask_base = 0, nnz = 0, no order, the chain kernel).
+ * Bit `mask_base + position` of `mask` keeps value `position` of `a` (NULL: no dropout); b and
+ * bgrad are tight ([..][p]), c / c2 / cgrad have rows of ldc / ldg >= p floats whose padding is
+ * never written and never reaches a result.
+ * pgcn_debug_spmm_csr: c2 == NULL: c = drop(X) b; else the dual forward, c = X b and
+ * c2 = drop(X) b from one pass (mask required: PGCN_E_INVALID without it, nothing written).
+ * pgcn_debug_spmm_csc_bwd: bgrad = drop(X)^T cgrad over the transposed index of
+ * pgcn_csr_transpose; nnz (the entries of all nf columns, 0: unknown) above 512 nf selects the
+ * 1024-thread kernels; order (optional): the nf feature ids in workgroup launch order (any
+ * permutation gives the same bits); tree != 0: the fixed-tree kernel (csc_tree) instead of the
+ * sequential chain. */
+int pgcn_debug_spmm_csr(int m, int p, int ldc, const int *indptr, const int *indices,
+                        const float *a, const uint64_t *mask, long long mask_base, float scale,
+                        const float *b, float *c, float *c2, void *stream);
+int pgcn_debug_spmm_csc_bwd(int nf, int p, int ldg, const int *csc_ptr, const int *csc_row,
+                            const int *csc_pos, const float *a, const uint64_t *mask,
+                            long long mask_base, float scale, const float *cgrad, float *bgrad,
+                            long long nnz, const int *order, int tree, void *stream);
+/* pgcn_dropout_mask with the engine's other arguments: per = 1 | 2 mask words (64 draws each)
+ * per stored state (per = 2: state k sits at draw elem0 + 128 k and ceil(n_chunks / 2) states
+ * are read and advanced); max_blocks > 0 caps the grid (0: by size).  Words [0, n_chunks) of
+ * `mask` are written: bit j of word c is element elem0 + 64 c + j, zero from elem_end on.
+ * pgcn_debug_dropout_mask2 draws two such segments in one launch (one jump table: the same
+ * period); a segment with n_chunks = 0 is skipped. */
+int pgcn_debug_dropout_mask(uint64_t *states, long long n_chunks, long long elem0,
+                            long long elem_end, float p, uint64_t *mask, const void *table,
+                            int per, int max_blocks, void *stream);
+int pgcn_debug_dropout_mask2(uint64_t *states0, long long n_chunks0, long long elem0_0,
+                             long long elem_end0, float p0, uint64_t *mask0, int per0,
+                             uint64_t *states1, long long n_chunks1, long long elem0_1,
+                             long long elem_end1, float p1, uint64_t *mask1, int per1,
+                             const void *table, void *stream);
+/* pgcn_dropout_apply reading keep bit base + i for x[i] (x 16-byte aligned) */
+int pgcn_debug_dropout_apply(float *x, long long n, const uint64_t *mask, long long base,
+                             float scale, void *stream);
 
 #ifdef __cplusplus
 }

@@ -231,6 +231,15 @@ _sig("pgcn_debug_gemm_nib", c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_
      c_void_p, c_int, c_void_p, c_ll, c_ll, c_float, c_void_p, c_void_p)
 _sig("pgcn_debug_gemm_tn_nib", c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
      c_void_p, c_int, c_void_p, c_ll, c_ll, c_float, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_debug_spmm_csr", c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+     c_ll, c_float, c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_debug_spmm_csc_bwd", c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+     c_void_p, c_void_p, c_ll, c_float, c_void_p, c_void_p, c_ll, c_void_p, c_int, c_void_p)
+_sig("pgcn_debug_dropout_mask", c_int, c_void_p, c_ll, c_ll, c_ll, c_float, c_void_p, c_void_p,
+     c_int, c_int, c_void_p)
+_sig("pgcn_debug_dropout_mask2", c_int, c_void_p, c_ll, c_ll, c_ll, c_float, c_void_p, c_int,
+     c_void_p, c_ll, c_ll, c_ll, c_float, c_void_p, c_int, c_void_p, c_void_p)
+_sig("pgcn_debug_dropout_apply", c_int, c_void_p, c_ll, c_void_p, c_ll, c_float, c_void_p)
 _sig("pgcn_debug_lds_check", c_int, c_int, c_int, c_void_p, c_void_p, c_int, P(ctypes.c_double),
      P(c_ll))
 _sig("pgcn_debug_lds_counts", c_ll, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_ll,
@@ -260,7 +269,8 @@ def _ptr(a):
 
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
                 "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
-                "launches")
+                "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
+                "spmm_tree_1024", "launches")
 
 
 def path_counts(reset=False, thread=False):
@@ -840,6 +850,8 @@ EXPORTED = [
     "pgcn_debug_finalize_ring", "pgcn_debug_tn_reduce_blocks_workspace",
     "pgcn_debug_tn_reduce_blocks", "pgcn_debug_tn_reduce_one_pass",
     "pgcn_debug_gemm_nib", "pgcn_debug_gemm_tn_nib",
+    "pgcn_debug_spmm_csr", "pgcn_debug_spmm_csc_bwd", "pgcn_debug_dropout_mask",
+    "pgcn_debug_dropout_mask2", "pgcn_debug_dropout_apply",
     "pgcn_bce_fwd", "pgcn_predict_multilabel_rows", "pgcn_multilabel_counts",
     "pgcn_gcn_predict_multilabel", "pgcn_gcn_multilabel_counts", "pgcn_dataset_set_multilabel",
     "pgcn_dataset_load_labels",

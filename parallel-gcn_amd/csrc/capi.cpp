@@ -26,7 +26,9 @@ thread_local long long t_path_hits[KP_COUNT];  // the launching host thread's (l
 const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",   "xs_tn",
                                           "gs_ring",    "gs_gather",  "out_xent", "gemm_nn",
                                           "gemm_tn",    "gemm_nn_w",  "gemm_tn_w", "gat_fwd",
-                                          "gat_bwd",    "gat_heads",  "launches"};
+                                          "gat_bwd",    "gat_heads",  "spmm_csr",
+                                          "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024",
+                                          "spmm_tree_256", "spmm_tree_1024", "launches"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -1452,6 +1454,78 @@ int pgcn_debug_gemm_tn_nib(int M, int N, int K, const float *A, int lda, const f
                "debug_gemm_tn_nib args");
     launch_gemm_tn(M, N, K, A, lda, G, ldg, C, ldc, a_mask, mask_base, mask_ld, a_scale,
                    workspace, as_stream(stream), mask_nib);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_spmm_csr(int m, int p, int ldc, const int *indptr, const int *indices,
+                        const float *a, const uint64_t *mask, long long mask_base, float scale,
+                        const float *b, float *c, float *c2, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(m >= 0 && p >= 1 && ldc >= p && mask_base >= 0, PGCN_E_INVALID,
+               "debug_spmm_csr: m >= 0, 1 <= p <= ldc, mask_base >= 0");
+    PGCN_CHECK(m == 0 || (indptr && indices && a && b && c), PGCN_E_INVALID,
+               "debug_spmm_csr: null argument");
+    if (c2)
+      launch_spmm_csr_dual(m, p, ldc, indptr, indices, a, mask, mask_base, scale, b, c, c2,
+                           as_stream(stream));
+    else
+      launch_spmm_csr(m, p, ldc, indptr, indices, a, mask, mask_base, scale, b, c,
+                      as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_spmm_csc_bwd(int nf, int p, int ldg, const int *csc_ptr, const int *csc_row,
+                            const int *csc_pos, const float *a, const uint64_t *mask,
+                            long long mask_base, float scale, const float *cgrad, float *bgrad,
+                            long long nnz, const int *order, int tree, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(nf >= 0 && p >= 1 && ldg >= p && mask_base >= 0 && nnz >= 0, PGCN_E_INVALID,
+               "debug_spmm_csc_bwd: nf >= 0, 1 <= p <= ldg, mask_base >= 0, nnz >= 0");
+    PGCN_CHECK(nf == 0 || (csc_ptr && csc_row && csc_pos && a && cgrad && bgrad), PGCN_E_INVALID,
+               "debug_spmm_csc_bwd: null argument");
+    launch_spmm_csc_bwd(nf, p, ldg, csc_ptr, csc_row, csc_pos, a, mask, mask_base, scale, cgrad,
+                        bgrad, as_stream(stream), nnz, order, tree != 0);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_dropout_mask(uint64_t *states, long long n_chunks, long long elem0,
+                            long long elem_end, float p, uint64_t *mask, const void *table,
+                            int per, int max_blocks, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n_chunks >= 0 && max_blocks >= 0 && (n_chunks == 0 || (states && mask && table)),
+               PGCN_E_INVALID, "debug_dropout_mask args");
+    launch_dropout_mask(states, n_chunks, elem0, elem_end, p, mask, table, as_stream(stream),
+                        max_blocks, per);
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_dropout_mask2(uint64_t *states0, long long n_chunks0, long long elem0_0,
+                             long long elem_end0, float p0, uint64_t *mask0, int per0,
+                             uint64_t *states1, long long n_chunks1, long long elem0_1,
+                             long long elem_end1, float p1, uint64_t *mask1, int per1,
+                             const void *table, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n_chunks0 >= 0 && n_chunks1 >= 0 && (n_chunks0 == 0 || (states0 && mask0)) &&
+                   (n_chunks1 == 0 || (states1 && mask1)) &&
+                   (n_chunks0 + n_chunks1 == 0 || table),
+               PGCN_E_INVALID, "debug_dropout_mask2 args");
+    const MaskDraw d0{states0, n_chunks0, elem0_0, elem_end0, p0, mask0, per0};
+    const MaskDraw d1{states1, n_chunks1, elem0_1, elem_end1, p1, mask1, per1};
+    launch_dropout_mask2(d0, d1, table, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_dropout_apply(float *x, long long n, const uint64_t *mask, long long base,
+                             float scale, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && base >= 0 && (n == 0 || (x && mask)), PGCN_E_INVALID,
+               "debug_dropout_apply args");
+    launch_dropout_apply_based(x, n, mask, base, scale, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }

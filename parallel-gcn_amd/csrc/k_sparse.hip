@@ -318,6 +318,7 @@ void launch_spmm_csr(int m, int p, int ldc, const int *indptr, const int *indice
                      const float *b, float *c, hipStream_t s) {
   if (m <= 0) return;
   const long long threads = (long long)m * p;
+  note_path(KP_SPMM_CSR);
   PGCN_LAUNCH(k_spmm_csr<false>, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, s, m, p,
               ldc, indptr, indices, a, mask, mask_base, scale, b, c, nullptr);
 }
@@ -328,6 +329,7 @@ void launch_spmm_csr_dual(int m, int p, int ldc, const int *indptr, const int *i
   PGCN_CHECK(mask && c2, PGCN_E_INVALID, "spmm_csr_dual: needs the mask and the second output");
   if (m <= 0) return;
   const long long threads = (long long)m * p;
+  note_path(KP_SPMM_CSR_DUAL);
   PGCN_LAUNCH(k_spmm_csr<true>, dim3((unsigned)ceil_div(threads, 256)), dim3(256), 0, s, m, p,
               ldc, indptr, indices, a, mask, mask_base, scale, b, c, c2);
 }
@@ -339,20 +341,26 @@ void launch_spmm_csc_bwd(int nf, int p, int ldg, const int *csc_ptr, const int *
   if (nf <= 0 || p <= 0) return;
   const dim3 grid((unsigned)nf, (unsigned)ceil_div(p, 16));
   if (tree) {
-    if (nnz > 512LL * nf)
+    if (nnz > 512LL * nf) {
+      note_path(KP_SPMM_TREE_1024);
       PGCN_LAUNCH(k_spmm_csc_tree<1024>, grid, dim3(1024), 0, s, nf, p, ldg, csc_ptr, csc_row,
                   csc_pos, a, mask, mask_base, scale, cgrad, bgrad, order);
-    else
+    } else {
+      note_path(KP_SPMM_TREE_256);
       PGCN_LAUNCH(k_spmm_csc_tree<256>, grid, dim3(256), 0, s, nf, p, ldg, csc_ptr, csc_row,
                   csc_pos, a, mask, mask_base, scale, cgrad, bgrad, order);
+    }
     return;
   }
-  if (nnz > 512LL * nf)
+  if (nnz > 512LL * nf) {
+    note_path(KP_SPMM_CSC_1024);
     PGCN_LAUNCH(k_spmm_csc_bwd<1024>, grid, dim3(1024), 0, s, nf, p, ldg, csc_ptr, csc_row,
                 csc_pos, a, mask, mask_base, scale, cgrad, bgrad, order);
-  else
+  } else {
+    note_path(KP_SPMM_CSC_256);
     PGCN_LAUNCH(k_spmm_csc_bwd<256>, grid, dim3(256), 0, s, nf, p, ldg, csc_ptr, csc_row,
                 csc_pos, a, mask, mask_base, scale, cgrad, bgrad, order);
+  }
 }
 
 }  // namespace pgcn

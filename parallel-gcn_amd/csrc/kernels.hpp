@@ -14,7 +14,9 @@ namespace pgcn {
 // which kernels a configuration took
 enum KernelPath {
   KP_XS_NN_RING, KP_XS_TN_RING, KP_XS_NN, KP_XS_TN, KP_GS_RING, KP_GS_GATHER, KP_OUT_XENT,
-  KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS, KP_LAUNCHES, KP_COUNT
+  KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS,
+  KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
+  KP_SPMM_TREE_1024, KP_LAUNCHES, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
