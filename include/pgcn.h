@@ -304,6 +304,50 @@ int pgcn_agg_max_fwd(const pgcn_graph *g, const float *in, int ld_in, int d,
 int pgcn_agg_max_bwd(const pgcn_graph *g, const float *G, int ld_g, const int *arg, int ld_arg,
                      int d, float *din, int ld_din, void *stream);
 
+/* --- graph-level readout over contiguous row ranges (k_readout.hip; new: the reference has
+ *     no graph-level model) -------------------------------------------------------------------
+ * A batch of G graphs is one node variable whose rows [graph_ptr[g], graph_ptr[g + 1]) belong to
+ * graph g: graph_ptr [G + 1] (a DEVICE array), non-decreasing, graph_ptr[0] = 0, graph_ptr[G] = n;
+ * len_g is the range's length.  The adjacency pattern is not looked at.
+ *   pgcn_readout_fwd, mode PGCN_READOUT_SUM: out_g = sum of in_i over the range; _MEAN: that sum
+ *     times one 1.0f / (float)len_g (the mean aggregator's form); _MAX: the exact maximum per
+ *     column, arg_g[c] (arg may be NULL: an inference call) the row that holds it -- a candidate
+ *     replaces the incumbent only when strictly greater (pgcn_agg_max_fwd's rule), so among equal
+ *     values, -0.0 and +0.0 included, the LOWEST row wins.  An empty range: a zero row, arg -1.
+ *     arg is written by every mode that is given one (-1 for sum and mean).
+ *     max_len (a host value): the longest range's length, or any upper bound of it (n when
+ *     unknown).  Up to pgcn_readout_chunk_rows() = T the call is ONE kernel launch, a wave per
+ *     range, four ranges per workgroup step.  Above T the ranges longer than T take two more
+ *     launches: they are cut where the row index is a multiple of T, a 256-thread workgroup per
+ *     T-row block reduces the block's piece of the (at most two) long ranges that meet it into
+ *     `workspace` (pgcn_readout_workspace(n) bytes, 16-byte aligned; may be NULL when max_len <=
+ *     T), and a workgroup per long range reduces its pieces in order.  A max_len below the truth
+ *     costs time, never correctness: the one-launch form handles any length.
+ *   pgcn_readout_bwd: with G_out [G][ld_g] = dLoss/dout, node_graph [n] (device; the range of
+ *     every row) and the forward's arg: din_i = g_{graph(i)} (sum), g * (1.0f / (float)len) (mean),
+ *     g[c] where arg[graph(i)][c] == i and 0 elsewhere (max; arg is required then).  Every row of
+ *     din is written (a row whose node_graph is outside [0, G): zero).
+ * 1 <= d <= 128; every ld a multiple of 4 and >= d, rows 16-byte aligned.  The float4s / int4s
+ * covering [0, round_up4(d)) of out, arg and din are written -- 0 (arg: -1) from column d on --
+ * and columns beyond them are left alone; padding columns of in, G_out and arg may hold anything,
+ * NaN included, and never reach a result.  Inputs are taken as finite.  Anything else is
+ * PGCN_E_INVALID before anything touches the device.  The calls are asynchronous, allocate
+ * nothing and may be captured.  No float atomics: every summation order depends on graph_ptr and
+ * d only (and on whether max_len exceeds T), so two calls give the same bits. */
+#define PGCN_READOUT_NONE 0
+#define PGCN_READOUT_SUM 1
+#define PGCN_READOUT_MEAN 2
+#define PGCN_READOUT_MAX 3
+int pgcn_readout_chunk_rows(void);
+size_t pgcn_readout_workspace(int n);
+int pgcn_readout_fwd(const float *in, int ld_in, const int *graph_ptr, int G, int n, int d,
+                     int mode, int max_len, float *out, int ld_out,
+                     int *arg /* [G][ld_arg] or NULL */, int ld_arg, void *workspace,
+                     void *stream);
+int pgcn_readout_bwd(const float *G_out, int ld_g, const int *graph_ptr, const int *node_graph,
+                     const int *arg /* max only */, int ld_arg, int G, int n, int d, int mode,
+                     float *din, int ld_din, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -397,7 +441,22 @@ typedef struct {
    * attention; single GPU only (the edge-cut creators return PGCN_E_INVALID: the mean could be
    * partitioned, the max needs a max / arg exchange). */
   int aggregator, root_weight;
-  int epochs, early_stopping;
+  int epochs;
+  /* Graph classification.  0: node-level losses (the engine as it was, bit for bit); 1 = sum,
+   * 2 = mean, 3 = max: the nodes are a batch of pgcn_data.num_graphs graphs (contiguous row ranges
+   * pgcn_data.graph_ptr, required then), and behind the output layer's node logits out [N][C] a
+   * Readout (pgcn_readout_fwd) writes pooled [G][C]; the softmax cross-entropy runs on pooled
+   * with the truth of a split built from graph_label / graph_split and count = the split's
+   * labelled graphs.  Loss, accuracy, the results ring, early stopping, pgcn_gcn_predict (G rows)
+   * and pgcn_gcn_confusion are then per graph.  Every layer family runs unchanged on the batch
+   * (attention with heads, aggregator / root_weight, residual, layer_norm).  Every node row
+   * carries gradient, so whatever relies on only a split's labelled rows mattering is off: the
+   * fused output / loss kernel, the output-row restriction with its compact buffers, the
+   * column-subset backward and the reassociated output layer.  The readout draws nothing from the
+   * dropout stream.  Not with multilabel, single GPU only (the edge-cut creators return
+   * PGCN_E_INVALID). */
+  int readout;
+  int early_stopping;
   /* attention != 0 only (anything but 1 / 0 without it is PGCN_E_INVALID).  attention_heads = K
    * (0 counts as 1): every HIDDEN attention layer runs K heads concatenated inside its width d_l
    * -- head h owns columns [h dh, (h + 1) dh), dh = d_l / K, reads its own slice of a_dst / a_src
@@ -473,6 +532,12 @@ typedef struct {
    * ceil(output_dim / 32).  A node is labelled iff label[i] >= 0 (the value is not used). */
   const uint32_t *label_bits;
   int label_words;
+  /* read only when pgcn_params.readout != 0: the nodes are num_graphs >= 1 graphs, graph g owning
+   * rows [graph_ptr[g], graph_ptr[g + 1]) (graph_ptr [num_graphs + 1], non-decreasing, from 0 to
+   * num_nodes); graph_label [num_graphs] in [0, output_dim) or -1 (unlabelled), graph_split
+   * [num_graphs] in 0..3 as the node splits.  0 / NULL: none. */
+  int num_graphs;
+  const int *graph_ptr, *graph_label, *graph_split;
 } pgcn_data;
 
 typedef struct pgcn_gcn pgcn_gcn;
@@ -525,7 +590,8 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "residual_layers" (layers with a ResidualConnection, pgcn_params.residual) and
  * "fused_residuals" (how many of them the last training forward added inside a GraphSum's
  * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
- * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel) and
+ * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel), "readout" (the readout
+ * mode, pgcn_params.readout) and "num_graphs" (its graph count; 0 without a readout), and
  * "fused_norm_tails" (how many of them ran the ReLU / residual add /
  * Dropout behind them inside the LayerNorm kernel in the last training forward);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
@@ -644,6 +710,19 @@ int pgcn_checkpoint_attention(const char *path, int *heads, float *dropout);
  * otherwise.  pgcn_checkpoint_info and pgcn_checkpoint_flags accept version 6. */
 #define PGCN_CKPT_SAGE 16
 int pgcn_checkpoint_sage(const char *path, int *aggregator, int *root_weight);
+/* flags bit 5: saved by a graph-classification engine (pgcn_params.readout != 0).  Such an engine
+ * writes a version-7 file: the header with bit 5 set and bits 0-4 all known, then three 16-byte
+ * blocks under the checksum -- version 5's {u32 heads; f32 attention_dropout; u64 0} (1 and 0
+ * without attention), version 6's {u32 aggregator; u32 root_weight; u64 0} (0 and 0 without
+ * SAGE layers) and {u32 readout; u32 num_graphs; u64 0} -- then the payload as the flags say
+ * (the scale / shift tensor with bit 1, the attention tensor with bit 3, doubled layer weights
+ * with root_weight).  Every other engine keeps writing versions 1-6 byte for byte.
+ * pgcn_checkpoint_readout is host-only and validates as pgcn_checkpoint_info does: the readout
+ * mode and the graph count of the engine that saved the file; versions 1-6 give 0 and 0.  Any
+ * load (resume or weights only) refuses a file whose mode or graph count differs from the
+ * engine's.  pgcn_checkpoint_info, _flags, _attention and _sage accept version 7. */
+#define PGCN_CKPT_READOUT 32
+int pgcn_checkpoint_readout(const char *path, int *mode, int *num_graphs);
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
@@ -651,7 +730,9 @@ int pgcn_params_sizeof(void);
  * [rows][output_dim] dense.  Returns the row count (node_range's) or a status < 0.  Leaves
  * the training state exactly as it was: no results slot written, epoch count, Adam and
  * dropout position unchanged, and training continued after it is bit-identical to training
- * without it.  Edge-cut: a collective, every rank calls it. */
+ * without it.  Edge-cut: a collective, every rank calls it.  A readout engine (pgcn_params.readout):
+ * one row per graph -- num_graphs rows of pooled logits -- and pgcn_gcn_confusion counts the
+ * split's labelled graphs. */
 long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs);
 /* predict + pgcn_confusion against split's labels: counts[c*c], this rank's rows (the caller
  * adds the ranks' matrices, as it concatenates get_var's rows). */
@@ -710,7 +791,21 @@ int pgcn_dataset_set_multilabel(pgcn_dataset *ds, const uint32_t *bits, int word
  * min(num_classes or 128, 128)).  The .svmlight / .graph / .split parser and the .pgcnbin cache
  * are untouched: pgcn_dataset_save of a multi-label dataset returns PGCN_E_INVALID. */
 int pgcn_dataset_load_labels(pgcn_dataset *ds, const char *path, int num_classes);
-/* (label_bits / label_words of the view: NULL / 0 for single-label data) */
+/* Graph-level data: attaches G graphs as contiguous row ranges (graph_ptr [G + 1] from 0 to
+ * num_nodes, non-decreasing), their labels (in [0, classes) or -1: unlabelled) and splits (0..3),
+ * all copied; num_classes 0: max label + 1.  Sets output_dim = the class count, as
+ * pgcn_dataset_load_labels does.  PGCN_E_INVALID otherwise. */
+int pgcn_dataset_set_graphs(pgcn_dataset *ds, const int *graph_ptr, const int *label,
+                            const int *split, int G, int num_classes);
+/* The same from the sidecar text file `path` (by convention <root>/data/<name>.graphs): line g is
+ * `<rows> <label> <split>` -- graph g owns the next <rows> rows, the rows of all lines sum to
+ * num_nodes.  PGCN_E_IO for a missing file, a line that is not three integers, negative rows,
+ * rows that do not sum to num_nodes, a label below -1 or >= min(num_classes or 128, 128), a
+ * split outside 0..3.  The .pgcnbin cache does not carry graph arrays (pgcn_dataset_save writes
+ * the node-level arrays only): attach them after every load. */
+int pgcn_dataset_load_graphs(pgcn_dataset *ds, const char *path, int num_classes);
+/* (label_bits / label_words of the view: NULL / 0 for single-label data; num_graphs and the graph
+ * arrays: 0 / NULL without graphs) */
 int pgcn_dataset_view(const pgcn_dataset *ds, pgcn_data *view, int *input_dim, int *output_dim);
 int pgcn_dataset_free(pgcn_dataset *ds);
 

@@ -306,6 +306,26 @@ class BCEWithLogitsLoss : public Module {
   shared_ptr<Impl> impl_;
 };
 
+// Graph-level readout (new: the reference has no graph-level model): `in` [n][dim] holds one row
+// per node of a batch of graphs, graph g owning rows [graph_ptr[g], graph_ptr[g + 1]) (host
+// vector of G + 1 entries from 0 to n, non-decreasing); out [G][dim] = per graph the sum
+// (PGCN_READOUT_SUM), the mean (_MEAN) or the maximum (_MAX) of its rows (pgcn_readout_fwd).  Put
+// it between the module that produces the node logits and a CrossEntropyLoss on `out` whose
+// dev_truth has one entry per graph.  backward: in.grad = the gradient of every row's graph, as it
+// is, over the graph's length, or where the row held the maximum (pgcn_readout_bwd; the maximum's
+// rows are those of the last training forward).  Build it after the module producing `in`.
+class Readout : public Module {
+ public:
+  Readout(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
+          const std::vector<integer> &graph_ptr_, natural dim_, int mode_);
+  void forward(bool training, const smart_stream &stream) const override;
+  void backward(const smart_stream &stream) const override;
+  struct Impl;
+
+ private:
+  shared_ptr<Impl> impl_;
+};
+
 // include/optim.cuh:16-50
 struct AdamParams {
   real learning_rate{0.01f}, beta1{0.9f}, beta2{0.999f}, eps{1e-8f}, weight_decay{5e-4f};

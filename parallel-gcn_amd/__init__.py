@@ -42,7 +42,8 @@ class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("hidden_dims", c_int * MAX_LAYERS),
                 ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
-                ("root_weight", c_int), ("epochs", c_int), ("early_stopping", c_int),
+                ("root_weight", c_int), ("epochs", c_int), ("readout", c_int),
+                ("early_stopping", c_int),
                 ("attention_heads", c_int), ("attention_dropout", c_float),
                 ("learning_rate", c_float), ("weight_decay", c_float), ("beta1", c_float),
                 ("beta2", c_float), ("eps", c_float), ("attention", c_int),
@@ -54,7 +55,9 @@ class PgcnData(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("graph_indptr", P(c_int)), ("graph_indices", P(c_int)),
                 ("feat_indptr", P(c_int)), ("feat_indices", P(c_int)),
                 ("feat_values", P(c_float)), ("label", P(c_int)), ("split", P(c_int)),
-                ("label_bits", P(ctypes.c_uint32)), ("label_words", c_int)]
+                ("label_bits", P(ctypes.c_uint32)), ("label_words", c_int),
+                ("num_graphs", c_int), ("graph_ptr", P(c_int)), ("graph_label", P(c_int)),
+                ("graph_split", P(c_int))]
 
 
 class PgcnXentFinal(ctypes.Structure):
@@ -141,6 +144,12 @@ _sig("pgcn_agg_max_fwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_in
      c_void_p, c_int, c_void_p)
 _sig("pgcn_agg_max_bwd", c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
      c_void_p)
+_sig("pgcn_readout_chunk_rows", c_int)
+_sig("pgcn_readout_workspace", c_size_t, c_int)
+_sig("pgcn_readout_fwd", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+     c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p)
+_sig("pgcn_readout_bwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+     c_int, c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -181,6 +190,7 @@ _sig("pgcn_checkpoint_info", c_int, ctypes.c_char_p, P(c_ll))
 _sig("pgcn_checkpoint_flags", c_int, ctypes.c_char_p)
 _sig("pgcn_checkpoint_attention", c_int, ctypes.c_char_p, P(c_int), P(c_float))
 _sig("pgcn_checkpoint_sage", c_int, ctypes.c_char_p, P(c_int), P(c_int))
+_sig("pgcn_checkpoint_readout", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_gcn_predict", c_ll, c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -196,6 +206,8 @@ _sig("pgcn_gcn_predict_multilabel", c_ll, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_multilabel_counts", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_dataset_set_multilabel", c_int, c_void_p, c_void_p, c_int, c_int)
 _sig("pgcn_dataset_load_labels", c_int, c_void_p, ctypes.c_char_p, c_int)
+_sig("pgcn_dataset_set_graphs", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int)
+_sig("pgcn_dataset_load_graphs", c_int, c_void_p, ctypes.c_char_p, c_int)
 _sig("pgcn_gcn_profile", c_int, c_void_p, c_int)
 _sig("pgcn_gcn_profile_read", c_int, c_void_p, P(c_double), P(c_ll), P(c_double))
 _sig("pgcn_gcn_profile_read_mm", c_int, c_void_p, P(c_double), P(c_ll), P(c_double))
@@ -330,6 +342,35 @@ class Dataset:
             self.label_bits = np.ctypeslib.as_array(self.view.label_bits,
                                                     shape=(n, self.label_words))
 
+        # graph-level data: the row ranges, labels and splits of num_graphs graphs (None without)
+        self.num_graphs = self.view.num_graphs
+        self.graph_ptr = self.graph_label = self.graph_split = None
+        if self.num_graphs > 0 and self.view.graph_ptr:
+            g = self.num_graphs
+            self.graph_ptr = arr(self.view.graph_ptr, g + 1, np.int32)
+            self.graph_label = arr(self.view.graph_label, g, np.int32)
+            self.graph_split = arr(self.view.graph_split, g, np.int32)
+
+    def set_graphs(self, graph_ptr, labels, splits, num_classes=0):
+        """Attaches G graphs as contiguous row ranges: graph_ptr [G + 1] from 0 to num_nodes,
+        labels [G] in [0, classes) or -1 (unlabelled), splits [G] in 0..3; sets output_dim = the
+        class count (num_classes, or max label + 1 when 0)."""
+        gp = np.ascontiguousarray(graph_ptr, np.int32)
+        lb = np.ascontiguousarray(labels, np.int32)
+        sp = np.ascontiguousarray(splits, np.int32)
+        if gp.ndim != 1 or gp.size < 2 or lb.shape != (gp.size - 1,) or sp.shape != lb.shape:
+            raise ValueError("set_graphs: graph_ptr [G + 1], labels [G], splits [G]")
+        check(lib.pgcn_dataset_set_graphs(self._h, _ptr(gp), _ptr(lb), _ptr(sp), lb.size,
+                                          num_classes), "dataset_set_graphs")
+        self._refresh()
+
+    def load_graphs(self, path, num_classes=0):
+        """Reads the graph-level sidecar file (line g: `<rows> <label> <split>`; by convention
+        <root>/data/<name>.graphs); num_classes 0: max label + 1."""
+        check(lib.pgcn_dataset_load_graphs(self._h, os.fsencode(path), num_classes),
+              f"dataset_load_graphs {path}")
+        self._refresh()
+
     def set_multilabel(self, Y):
         """Attaches the label matrix Y (bool [num_nodes][C], 1 <= C <= 128) and sets output_dim =
         C; labelled nodes (label >= 0) stay labelled."""
@@ -425,15 +466,22 @@ def f1_scores(counts):
 
 
 AGGREGATORS = {None: 0, "mean": 1, "max": 2}
+READOUTS = {None: 0, "sum": 1, "mean": 2, "max": 3}
 
 
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
                 multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
-                aggregator=None, root_weight=False):
+                aggregator=None, root_weight=False, readout=None):
     """aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
-    own row through its own half of a [d_in][2 d_l] weight (with an aggregator only)."""
+    own row through its own half of a [d_in][2 d_l] weight (with an aggregator only).
+    readout: None (node classification), "sum", "mean" or "max": graph classification over the
+    graphs attached with Dataset.set_graphs / load_graphs (not with multilabel)."""
+    if readout not in READOUTS:
+        raise ValueError(f"readout must be one of {sorted(k for k in READOUTS if k)} or None")
+    if READOUTS[readout] and multilabel:
+        raise ValueError("readout cannot be combined with multilabel")
     if aggregator not in AGGREGATORS:
         raise ValueError(f"aggregator must be one of {sorted(k for k in AGGREGATORS if k)} or None")
     if root_weight and not AGGREGATORS[aggregator]:
@@ -447,6 +495,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     p.attention = 1 if attention else 0
     p.attention_heads, p.attention_dropout = attention_heads, attention_dropout
     p.multilabel = 1 if multilabel else 0
+    p.readout = READOUTS[readout]
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
@@ -555,9 +604,12 @@ class GCN:
 
     def predict(self, probs=False):
         """(classes int32 [rows], confidences float32 [rows]) of this rank's rows from an
-        eval-mode forward; with probs=True also the softmax rows [rows, output_dim]."""
+        eval-mode forward; with probs=True also the softmax rows [rows, output_dim].  A readout
+        engine: one row per graph."""
         a, b = self.node_range()
         n, c = b - a, self.params.output_dim
+        if self.params.readout:  # one row per graph
+            n = self.query("num_graphs")
         cls, conf = np.zeros(n, np.int32), np.zeros(n, np.float32)
         pr = np.zeros((n, c), np.float32) if probs else None
         got = lib.pgcn_gcn_predict(self._h, _ptr(cls), _ptr(conf), _ptr(pr) if probs else None)
@@ -719,6 +771,7 @@ CKPT_LAYERNORM = 2  # version-2 files: the scale / shift tensor behind the layer
 CKPT_MULTILABEL = 4  # saved by a multi-label engine (no payload change)
 CKPT_ATTENTION = 8  # version-4 files: the attention tensor last in the payloads
 CKPT_SAGE = 16  # version-6 files: a GraphSAGE engine's, with the {aggregator, root_weight} block
+CKPT_READOUT = 32  # version-7 files: a graph-classification engine's, with its three blocks
 
 
 def checkpoint_flags(path):
@@ -747,6 +800,15 @@ def checkpoint_sage(path):
     check(lib.pgcn_checkpoint_sage(os.fsencode(path), ctypes.byref(agg), ctypes.byref(root)),
           f"checkpoint_sage {path}")
     return agg.value, root.value
+
+
+def checkpoint_readout(path):
+    """Host-only: (readout mode, num_graphs) of the engine that saved the file -- a version-7
+    file's block; (0, 0) for versions 1-6.  PgcnError(PGCN_E_IO) for an invalid file."""
+    mode, g = c_int(), c_int()
+    check(lib.pgcn_checkpoint_readout(os.fsencode(path), ctypes.byref(mode), ctypes.byref(g)),
+          f"checkpoint_readout {path}")
+    return mode.value, g.value
 
 
 def comm_unique_id():
@@ -855,4 +917,6 @@ EXPORTED = [
     "pgcn_bce_fwd", "pgcn_predict_multilabel_rows", "pgcn_multilabel_counts",
     "pgcn_gcn_predict_multilabel", "pgcn_gcn_multilabel_counts", "pgcn_dataset_set_multilabel",
     "pgcn_dataset_load_labels",
+    "pgcn_readout_chunk_rows", "pgcn_readout_workspace", "pgcn_readout_fwd", "pgcn_readout_bwd",
+    "pgcn_dataset_set_graphs", "pgcn_dataset_load_graphs", "pgcn_checkpoint_readout",
 ]

@@ -64,6 +64,9 @@ void refuse_single_gpu_only(const pgcn_params *p) {
   // (the mean is linear and could be partitioned; the max needs a max / arg exchange)
   PGCN_CHECK(!p->aggregator && !p->root_weight, PGCN_E_INVALID,
              "aggregator: single GPU only (edge-cut SAGE layers are not supported)");
+  // (a graph's rows may lie on several ranks: its readout would need an exchange of its own)
+  PGCN_CHECK(!p->readout, PGCN_E_INVALID,
+             "readout: single GPU only (edge-cut graph classification is not supported)");
 }
 
 GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
@@ -88,6 +91,11 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
              "root_weight must be 0 or 1");
   q.aggregator = p->aggregator;
   q.root_weight = p->root_weight != 0;
+  PGCN_CHECK(p->readout >= kReadoutNone && p->readout <= kReadoutMax, PGCN_E_INVALID,
+             "readout must be 0 (none), 1 (sum), 2 (mean) or 3 (max)");
+  PGCN_CHECK(!p->readout || !p->multilabel, PGCN_E_INVALID,
+             "readout cannot be combined with multilabel");
+  q.readout = p->readout;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -121,6 +129,19 @@ GCNData to_data(const pgcn_data *d, const pgcn_params *p) {
                "multilabel: 1 <= output_dim <= 128 and label_words = ceil(output_dim / 32)");
     g.label_words = d->label_words;
     g.label_bits.assign(d->label_bits, d->label_bits + (size_t)n * d->label_words);
+  }
+  if (p->readout) {  // (the graph members are read only then)
+    PGCN_CHECK(d->num_graphs >= 1 && d->graph_ptr && d->graph_label && d->graph_split,
+               PGCN_E_INVALID, "readout: pgcn_data has no graphs attached");
+    PGCN_CHECK(graphs_valid(n, d->num_graphs, d->graph_ptr, d->graph_label, d->graph_split,
+                            p->output_dim),
+               PGCN_E_INVALID,
+               "readout: graph_ptr from 0 to num_nodes, labels in [-1, output_dim), splits 0..3");
+    const size_t G = (size_t)d->num_graphs;
+    g.num_graphs = d->num_graphs;
+    g.graph_ptr.assign(d->graph_ptr, d->graph_ptr + G + 1);
+    g.graph_label.assign(d->graph_label, d->graph_label + G);
+    g.graph_split.assign(d->graph_split, d->graph_split + G);
   }
   return g;
 }
@@ -676,6 +697,56 @@ int pgcn_agg_max_bwd(const pgcn_graph *g, const float *G, int ld_g, const int *a
   });
 }
 
+namespace {
+void check_readout_dims(int d, int mode, int G, int n, std::initializer_list<int> lds) {
+  PGCN_CHECK(d >= 1 && d <= kReadoutMaxWidth, PGCN_E_INVALID, "readout: 1 <= d <= 128");
+  PGCN_CHECK(mode >= kReadoutSum && mode <= kReadoutMax, PGCN_E_INVALID,
+             "readout: mode 1 (sum), 2 (mean) or 3 (max)");
+  PGCN_CHECK(G >= 0 && n >= 0, PGCN_E_INVALID, "readout: G >= 0, n >= 0");
+  for (int ld : lds) PGCN_CHECK(ln_ld_ok(ld, d), PGCN_E_INVALID, "readout: ld % 4 == 0, ld >= d");
+}
+}  // namespace
+
+int pgcn_readout_chunk_rows(void) { return kReadoutChunk; }
+
+size_t pgcn_readout_workspace(int n) { return readout_workspace(n); }
+
+int pgcn_readout_fwd(const float *in, int ld_in, const int *graph_ptr, int G, int n, int d,
+                     int mode, int max_len, float *out, int ld_out, int *arg, int ld_arg,
+                     void *workspace, void *stream) {
+  return guarded([&] {
+    check_readout_dims(d, mode, G, n, {ld_in, ld_out});
+    if (arg) check_readout_dims(d, mode, G, n, {ld_arg});
+    PGCN_CHECK(max_len >= 0, PGCN_E_INVALID, "readout_fwd: max_len >= 0");
+    PGCN_CHECK((in || n == 0) && graph_ptr && out && aligned16(in) && aligned16(out) &&
+                   aligned16(arg),
+               PGCN_E_INVALID, "readout_fwd: null or misaligned argument");
+    PGCN_CHECK(max_len <= kReadoutChunk || n <= kReadoutChunk ||
+                   (workspace && aligned16(workspace)),
+               PGCN_E_INVALID, "readout_fwd: ranges above the chunk length need the workspace");
+    check_device();
+    launch_readout_fwd(in, ld_in, graph_ptr, G, n, d, mode, max_len, out, ld_out, arg, ld_arg,
+                       workspace, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_readout_bwd(const float *G_out, int ld_g, const int *graph_ptr, const int *node_graph,
+                     const int *arg, int ld_arg, int G, int n, int d, int mode, float *din,
+                     int ld_din, void *stream) {
+  return guarded([&] {
+    check_readout_dims(d, mode, G, n, {ld_g, ld_din});
+    if (mode == kReadoutMax) check_readout_dims(d, mode, G, n, {ld_arg});
+    PGCN_CHECK(G_out && graph_ptr && node_graph && din && (mode != kReadoutMax || arg) &&
+                   aligned16(G_out) && aligned16(din) && aligned16(arg),
+               PGCN_E_INVALID, "readout_bwd: null or misaligned argument");
+    check_device();
+    launch_readout_bwd(G_out, ld_g, graph_ptr, node_graph, arg, ld_arg, G, n, d, mode, din, ld_din,
+                       as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -771,6 +842,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->aggregator = 0;
   p->root_weight = 0;
   p->epochs = 100;
+  p->readout = 0;
   p->early_stopping = 0;
   p->attention_heads = 1;
   p->attention_dropout = 0.0f;
@@ -928,6 +1000,8 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "aggregator")) return e.aggregator();
   if (!std::strcmp(key, "root_weight")) return e.root_weight() ? 1 : 0;
   if (!std::strcmp(key, "multilabel")) return e.get_params().multilabel ? 1 : 0;
+  if (!std::strcmp(key, "readout")) return e.get_params().readout;
+  if (!std::strcmp(key, "num_graphs")) return e.num_graphs();
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
@@ -1041,6 +1115,14 @@ int pgcn_checkpoint_sage(const char *path, int *aggregator, int *root_weight) {
     const Checkpoint ck = read_checkpoint(path);
     *aggregator = ck.aggregator;
     *root_weight = ck.root_weight;
+  });
+}
+int pgcn_checkpoint_readout(const char *path, int *mode, int *num_graphs) {
+  return guarded([&] {
+    PGCN_CHECK(path && mode && num_graphs, PGCN_E_INVALID, "checkpoint_readout args");
+    const Checkpoint ck = read_checkpoint(path);
+    *mode = ck.readout;
+    *num_graphs = ck.num_graphs;
   });
 }
 int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }
@@ -1157,6 +1239,11 @@ int pgcn_dataset_view(const pgcn_dataset *ds, pgcn_data *v, int *input_dim, int 
   v->split = ds->d.split.data();
   v->label_bits = ds->d.label_bits.empty() ? nullptr : ds->d.label_bits.data();
   v->label_words = ds->d.label_bits.empty() ? 0 : ds->d.label_words;
+  const bool graphs = ds->d.num_graphs > 0;
+  v->num_graphs = graphs ? ds->d.num_graphs : 0;
+  v->graph_ptr = graphs ? ds->d.graph_ptr.data() : nullptr;
+  v->graph_label = graphs ? ds->d.graph_label.data() : nullptr;
+  v->graph_split = graphs ? ds->d.graph_split.data() : nullptr;
   if (input_dim) *input_dim = ds->d.input_dim;
   if (output_dim) *output_dim = ds->d.output_dim;
   return PGCN_OK;
@@ -1192,6 +1279,44 @@ int pgcn_dataset_load_labels(pgcn_dataset *ds, const char *path, int num_classes
     ds->d.label_words = words;
     ds->d.output_dim = c;
     for (int &l : ds->d.label) l = std::max(l, 0);  // every line is a labelled node
+  });
+}
+
+int pgcn_dataset_set_graphs(pgcn_dataset *ds, const int *graph_ptr, const int *label,
+                            const int *split, int G, int num_classes) {
+  return guarded([&] {
+    PGCN_CHECK(ds && graph_ptr && label && split && G >= 1 && num_classes >= 0 &&
+                   num_classes <= 128,
+               PGCN_E_INVALID, "dataset_set_graphs: G >= 1, 0 <= num_classes <= 128");
+    int c = num_classes;
+    if (c == 0)
+      for (int g = 0; g < G; g++) c = std::max(c, label[g] + 1);
+    PGCN_CHECK(c >= 1 && c <= 128, PGCN_E_INVALID, "dataset_set_graphs: 1 <= classes <= 128");
+    PGCN_CHECK(graphs_valid(ds->d.num_nodes, G, graph_ptr, label, split, c), PGCN_E_INVALID,
+               "dataset_set_graphs: graph_ptr from 0 to num_nodes, non-decreasing; labels in "
+               "[-1, classes); splits 0..3");
+    ds->d.num_graphs = G;
+    ds->d.graph_ptr.assign(graph_ptr, graph_ptr + G + 1);
+    ds->d.graph_label.assign(label, label + G);
+    ds->d.graph_split.assign(split, split + G);
+    ds->d.output_dim = c;
+  });
+}
+
+int pgcn_dataset_load_graphs(pgcn_dataset *ds, const char *path, int num_classes) {
+  return guarded([&] {
+    PGCN_CHECK(ds && path && num_classes >= 0 && num_classes <= 128, PGCN_E_INVALID,
+               "dataset_load_graphs: 0 <= num_classes <= 128");
+    std::vector<int> ptr, label, split;
+    int c = 0;
+    std::string why;
+    if (!read_graphs_file(path, ds->d.num_nodes, num_classes, &ptr, &label, &split, &c, &why))
+      throw Error(PGCN_E_IO, why);
+    ds->d.num_graphs = (int)label.size();
+    ds->d.graph_ptr = std::move(ptr);
+    ds->d.graph_label = std::move(label);
+    ds->d.graph_split = std::move(split);
+    ds->d.output_dim = c;
   });
 }
 

@@ -650,6 +650,29 @@ void BCEWithLogitsLoss::forward(bool training, const smart_stream &stream) const
 void BCEWithLogitsLoss::backward(const smart_stream &) const {}  // the forward wrote the gradient
 real BCEWithLogitsLoss::accuracy() const { return impl_->res.get()[1]; }
 
+// ---------------------------------------------------------------------- Readout
+struct Readout::Impl {
+  std::unique_ptr<pgcn::Readout> mod;
+};
+Readout::Readout(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
+                 const std::vector<integer> &graph_ptr_, natural dim_, int mode_)
+    : impl_(std::make_shared<Impl>()) {
+  PGCN_CHECK(in_ && out_ && in_->impl() && graph_ptr_.size() >= 2, PGCN_E_INVALID,
+             "Readout: its input has no shape yet (build the module producing it first), or no "
+             "graph");
+  const std::vector<int> gp(graph_ptr_.begin(), graph_ptr_.end());
+  PGCN_CHECK(gp.front() == 0 && gp.back() == in_->impl()->rows, PGCN_E_INVALID,
+             "Readout: graph_ptr runs from 0 to the input's rows");
+  VariableAccess::bind(*out_, (int)gp.size() - 1, (int)dim_, true);
+  impl_->mod = std::make_unique<pgcn::Readout>(in_->impl(), out_->impl(), gp, (int)dim_, mode_);
+}
+void Readout::forward(bool training, const smart_stream &stream) const {
+  impl_->mod->forward(training, Stream::wrap(stream.get()));
+}
+void Readout::backward(const smart_stream &stream) const {
+  impl_->mod->backward(Stream::wrap(stream.get()));
+}
+
 // ---------------------------------------------------------------------- Adam
 Adam::Adam(const std::vector<shared_ptr<Variable>> &weights, const std::vector<bool> &decays,
            AdamParams const *params_)

@@ -48,8 +48,27 @@ CkSageExt sage_ext(const Checkpoint &ck) {
   return CkSageExt{(uint32_t)ck.aggregator, (uint32_t)ck.root_weight, 0};
 }
 
+// version 7: behind the other two blocks
+struct CkReadoutExt {
+  uint32_t readout, num_graphs;
+  uint64_t zero;
+};
+static_assert(sizeof(CkReadoutExt) == 16, "checkpoint extension layout");
+
+CkReadoutExt readout_ext(const Checkpoint &ck) {
+  return CkReadoutExt{(uint32_t)ck.readout, (uint32_t)ck.num_graphs, 0};
+}
+
 uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
   uint64_t x = fnv1a(kFnvBasis, &h, offsetof(CkHeader, checksum));
+  if (h.version == (uint32_t)kCheckpointVersionReadout) {
+    const CkHeadsExt e = heads_ext(ck);
+    const CkSageExt se = sage_ext(ck);
+    const CkReadoutExt re = readout_ext(ck);
+    x = fnv1a(x, &e, sizeof e);
+    x = fnv1a(x, &se, sizeof se);
+    x = fnv1a(x, &re, sizeof re);
+  }
   if (h.version == (uint32_t)kCheckpointVersionHeads) {
     const CkHeadsExt e = heads_ext(ck);
     x = fnv1a(x, &e, sizeof e);
@@ -106,6 +125,11 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
   if (version == (uint32_t)kCheckpointVersionSage)
     return (flags & kCheckpointSage) &&
            (flags & ~(kCheckpointKnownFlags | kCheckpointLayerNorm | kCheckpointSage)) == 0;
+  if (version == (uint32_t)kCheckpointVersionReadout)  // (the engine never has bits 2, or 3 with 4)
+    return (flags & kCheckpointReadout) && !(flags & kCheckpointMultilabel) &&
+           !((flags & kCheckpointAttention) && (flags & kCheckpointSage)) &&
+           (flags & ~(kCheckpointResidual | kCheckpointLayerNorm | kCheckpointAttention |
+                      kCheckpointSage | kCheckpointReadout)) == 0;
   return false;
 }
 
@@ -117,9 +141,11 @@ long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags,
 }
 
 // the extension's values against the file's version and hidden dims (the engine's own rules)
-bool heads_ok(uint32_t version, const int32_t *dims, int n_layers, long long heads, float p) {
-  if (version != (uint32_t)kCheckpointVersionHeads) return heads == 1 && p == 0.0f;
-  if (heads < 1 || heads > 32 || !(p >= 0.0f && p < 1.0f) || (heads == 1 && p == 0.0f))
+bool heads_ok(uint32_t version, uint32_t flags, const int32_t *dims, int n_layers,
+              long long heads, float p) {
+  const bool v7 = version == (uint32_t)kCheckpointVersionReadout && (flags & kCheckpointAttention);
+  if (version != (uint32_t)kCheckpointVersionHeads && !v7) return heads == 1 && p == 0.0f;
+  if (heads < 1 || heads > 32 || !(p >= 0.0f && p < 1.0f) || (!v7 && heads == 1 && p == 0.0f))
     return false;
   for (int l = 1; heads > 1 && l < n_layers; l++) {
     const long long dh = dims[l] / heads;
@@ -129,13 +155,21 @@ bool heads_ok(uint32_t version, const int32_t *dims, int n_layers, long long hea
 }
 
 // version 6's block against the file's version (the engine's own rules)
-bool sage_ok(uint32_t version, const int32_t *dims, int n_layers, long long aggregator,
-             long long root_weight) {
-  if (version != (uint32_t)kCheckpointVersionSage) return aggregator == 0 && root_weight == 0;
+bool sage_ok(uint32_t version, uint32_t flags, const int32_t *dims, int n_layers,
+             long long aggregator, long long root_weight) {
+  const bool v7 = version == (uint32_t)kCheckpointVersionReadout && (flags & kCheckpointSage);
+  if (version != (uint32_t)kCheckpointVersionSage && !v7)
+    return aggregator == 0 && root_weight == 0;
   if (aggregator < 1 || aggregator > 2 || root_weight < 0 || root_weight > 1) return false;
   for (int l = 1; l <= n_layers; l++)
     if (dims[l] > 128) return false;
   return true;
+}
+// version 7's own block against the file's version
+bool readout_ok(uint32_t version, long long readout, long long num_graphs, long long num_nodes) {
+  if (version != (uint32_t)kCheckpointVersionReadout) return readout == 0 && num_graphs == 0;
+  return readout >= 1 && readout <= 3 && num_graphs >= 1 && num_graphs < (1LL << 31) &&
+         num_nodes >= 0;
 }
 }  // namespace
 
@@ -163,16 +197,21 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   h.epochs = ck.epochs;
   h.n_results = (int64_t)(ck.results.size() / 4);
   h.n_weights = (int64_t)ck.w.size();
-  PGCN_CHECK(sage_ok(h.version, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
+  PGCN_CHECK(readout_ok(h.version, ck.readout, ck.num_graphs, ck.num_nodes), PGCN_E_INVALID,
+             "checkpoint: readout / graph count do not match the file's version");
+  PGCN_CHECK(sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: aggregator / root weight do not match the file's version");
   PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: weight count does not match the layer dims");
-  PGCN_CHECK(heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout), PGCN_E_INVALID,
+  PGCN_CHECK(heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout),
+             PGCN_E_INVALID,
              "checkpoint: heads / attention dropout do not match the file's version");
   const CkHeadsExt ext = heads_ext(ck);
-  const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads;
+  const bool v7 = h.version == (uint32_t)kCheckpointVersionReadout;
+  const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads || v7;
   const CkSageExt sext = sage_ext(ck);
-  const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage;
+  const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage || v7;
+  const CkReadoutExt rext = readout_ext(ck);
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
   std::FILE *f = std::fopen(tmp.c_str(), "wb");
@@ -180,6 +219,7 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1 &&
             (!with_ext || std::fwrite(&ext, sizeof(ext), 1, f) == 1) &&
             (!with_sage || std::fwrite(&sext, sizeof(sext), 1, f) == 1) &&
+            (!v7 || std::fwrite(&rext, sizeof(rext), 1, f) == 1) &&
             write_floats(f, ck.results) &&
             write_floats(f, ck.w) && write_floats(f, ck.m) && write_floats(f, ck.v);
   ok = (std::fclose(f) == 0) && ok;
@@ -203,21 +243,30 @@ Checkpoint read_checkpoint(const std::string &path) {
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
        h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
        h.n_weights < (1LL << 31);
-  if (ok && h.version == (uint32_t)kCheckpointVersionHeads) {
+  const bool v7 = ok && h.version == (uint32_t)kCheckpointVersionReadout;
+  if (ok && (h.version == (uint32_t)kCheckpointVersionHeads || v7)) {
     CkHeadsExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.heads <= 32;
     ck.heads = (int)e.heads;
     ck.attention_dropout = e.attention_dropout;
   }
-  if (ok && h.version == (uint32_t)kCheckpointVersionSage) {
+  if (ok && (h.version == (uint32_t)kCheckpointVersionSage || v7)) {
     CkSageExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.aggregator <= 2 &&
          e.root_weight <= 1;
     ck.aggregator = (int)e.aggregator;
     ck.root_weight = (int)e.root_weight;
   }
-  ok = ok && heads_ok(h.version, h.dims, L, ck.heads, ck.attention_dropout) &&
-       sage_ok(h.version, h.dims, L, ck.aggregator, ck.root_weight) &&
+  if (ok && v7) {
+    CkReadoutExt e{};
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.readout <= 3 &&
+         e.num_graphs < (1u << 31);
+    ck.readout = (int)e.readout;
+    ck.num_graphs = (int)e.num_graphs;
+  }
+  ok = ok && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
+       sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight) &&
+       readout_ok(h.version, ck.readout, ck.num_graphs, h.num_nodes) &&
        h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight);
   ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
        read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);

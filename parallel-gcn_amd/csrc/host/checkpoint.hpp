@@ -38,8 +38,15 @@
 // With root_weight 1 every layer weight is [d_in][2 d_l] (the root half first), so n_weights and
 // the w / m / v payloads count 2 * dims[l] * dims[l + 1] per layer; the scale / shift tensor
 // follows as in version 2.  Every other engine keeps writing versions 1-5 byte for byte.
+// Version 7 = saved by a graph-classification engine (pgcn_params.readout != 0): flags bit 5
+// always set, bits 0-4 all known, and three 16-byte blocks between the header and the payload:
+// version 5's (heads 1, dropout 0 without bit 3; with it any valid pair, the defaults included),
+// version 6's (0 and 0 without bit 4) and
+//   block  u32 readout (1 sum, 2 mean, 3 max); u32 num_graphs (>= 1); u64 0
+// The payload follows the flags as in versions 2, 4 and 6.  Every other engine keeps writing
+// versions 1-6 byte for byte.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (versions
-// 5 and 6) and the payload.
+// 5 and 6; version 7's three blocks) and the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
 // stored and the file does not depend on the world size.  Nothing newer than the reference:
@@ -62,6 +69,8 @@ constexpr int kCheckpointVersionAttention = 4;  // bits 0-3 known, bit 3 set
 constexpr int kCheckpointVersionHeads = 5;  // version 4 + the {heads, attention_dropout} extension
 constexpr unsigned kCheckpointSage = 16u;  // header flags, bit 4 (version 6 only)
 constexpr int kCheckpointVersionSage = 6;  // bits 0-2 and 4 known, bit 4 set, + its block
+constexpr unsigned kCheckpointReadout = 32u;  // header flags, bit 5 (version 7 only)
+constexpr int kCheckpointVersionReadout = 7;  // bits 0-5 known, bit 5 set, + three blocks
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -78,6 +87,8 @@ struct Checkpoint {
   float attention_dropout = 0.0f;
   // version 6's block; 0 and 0 in every other version
   int aggregator = 0, root_weight = 0;
+  // version 7's own block; 0 and 0 in every other version
+  int readout = 0, num_graphs = 0;
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

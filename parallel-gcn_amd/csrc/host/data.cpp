@@ -265,6 +265,73 @@ bool Parser::parse() {
   return ok;
 }
 
+bool graphs_valid(int num_nodes, int G, const int *ptr, const int *label, const int *split,
+                  int classes) {
+  if (G < 1 || !ptr || !label || !split || ptr[0] != 0 || ptr[G] != num_nodes) return false;
+  for (int g = 0; g < G; g++)
+    if (ptr[g + 1] < ptr[g] || label[g] < -1 || label[g] >= classes || split[g] < 0 ||
+        split[g] > 3)
+      return false;
+  return true;
+}
+
+bool read_graphs_file(const std::string &path, int num_nodes, int num_classes,
+                      std::vector<int> *ptr, std::vector<int> *label, std::vector<int> *split,
+                      int *classes, std::string *why) {
+  std::ifstream in(path);
+  if (!in) {
+    *why = "cannot open " + path;
+    return false;
+  }
+  const int limit = num_classes > 0 ? std::min(num_classes, 128) : 128;
+  ptr->assign(1, 0);
+  label->clear();
+  split->clear();
+  std::string line;
+  int max_label = -1;
+  long long total = 0;
+  while (std::getline(in, line)) {
+    const std::string at = path + ": line " + std::to_string(label->size() + 1);
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;  // (a blank line)
+    std::istringstream ls(line);
+    long long rows = 0, lab = 0, sp = 0;
+    std::string rest;
+    if (!(ls >> rows >> lab >> sp) || (ls >> rest)) {
+      *why = at + ": expected `<rows> <label> <split>`";
+      return false;
+    }
+    if (rows < 0 || total + rows > num_nodes) {
+      *why = at + ": the rows exceed the node count";
+      return false;
+    }
+    if (lab < -1 || lab >= limit) {
+      *why = at + ": label out of range";
+      return false;
+    }
+    if (sp < 0 || sp > 3) {
+      *why = at + ": split must be 0..3";
+      return false;
+    }
+    total += rows;
+    ptr->push_back((int)total);
+    label->push_back((int)lab);
+    split->push_back((int)sp);
+    max_label = std::max(max_label, (int)lab);
+  }
+  if (label->empty() || total != num_nodes) {
+    *why = path + ": the rows sum to " + std::to_string(total) + " for " +
+           std::to_string(num_nodes) + " nodes";
+    return false;
+  }
+  const int c = num_classes > 0 ? num_classes : max_label + 1;
+  if (c < 1 || c > 128) {
+    *why = path + ": 1 <= classes <= 128";
+    return false;
+  }
+  *classes = c;
+  return true;
+}
+
 bool read_labels_file(const std::string &path, int num_nodes, int num_classes,
                       std::vector<uint32_t> *bits, int *words, int *classes, std::string *why) {
   std::ifstream in(path);

@@ -28,6 +28,10 @@ struct GCNData {
   // word j / 32 = node i has class j; a node is labelled iff label[i] >= 0
   std::vector<uint32_t> label_bits;
   int label_words = 0;
+  // graph-level data (0 / empty: none): graph g owns rows [graph_ptr[g], graph_ptr[g + 1]);
+  // graph_label in [0, output_dim) or -1, graph_split 0..3 (GCNParams::readout)
+  int num_graphs = 0;
+  std::vector<int> graph_ptr, graph_label, graph_split;
 };
 
 class Parser {
@@ -76,6 +80,18 @@ bool load_dataset_cached(GCNData *d, const std::string &root, const std::string 
 // a number or an id outside [0, min(num_classes or 128, 128)).
 bool read_labels_file(const std::string &path, int num_nodes, int num_classes,
                       std::vector<uint32_t> *bits, int *words, int *classes, std::string *why);
+
+// Graph-level sidecar file: line g = `<rows> <label> <split>`.  Fills ptr [G + 1], label, split and
+// *classes (num_classes, or max label + 1 when 0); false (with *why) for a missing file, a line
+// that is not three integers, negative rows, rows that do not sum to num_nodes, a label below -1
+// or >= min(num_classes or 128, 128), a split outside 0..3.
+bool read_graphs_file(const std::string &path, int num_nodes, int num_classes,
+                      std::vector<int> *ptr, std::vector<int> *label, std::vector<int> *split,
+                      int *classes, std::string *why);
+// graph arrays as GCNData holds them: ptr [G + 1] from 0 to num_nodes, non-decreasing, labels in
+// [-1, classes), splits in 0..3
+bool graphs_valid(int num_nodes, int G, const int *ptr, const int *label, const int *split,
+                  int classes);
 
 // True when every row lists all features 0..F-1 in order (a dense matrix in CSR form).
 bool features_dense(const GCNData &d);

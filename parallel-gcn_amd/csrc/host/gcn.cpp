@@ -318,6 +318,24 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
     PGCN_CHECK(params.output_dim <= kSageMaxWidth, PGCN_E_INVALID,
                "aggregator != 0: output_dim up to 128");
   }
+  PGCN_CHECK(params.readout >= kReadoutNone && params.readout <= kReadoutMax, PGCN_E_INVALID,
+             "readout must be 0 (none), 1 (sum), 2 (mean) or 3 (max)");
+  if (params.readout) {
+    PGCN_CHECK(!params.multilabel, PGCN_E_INVALID, "readout cannot be combined with multilabel");
+    PGCN_CHECK(!dist, PGCN_E_INVALID,
+               "readout: single GPU only (edge-cut graph classification is not supported)");
+    PGCN_CHECK(params.output_dim <= kReadoutMaxWidth, PGCN_E_INVALID,
+               "readout: output_dim up to 128");
+    PGCN_CHECK(data.num_graphs >= 1 && (int)data.graph_ptr.size() == data.num_graphs + 1 &&
+                   (int)data.graph_label.size() == data.num_graphs &&
+                   (int)data.graph_split.size() == data.num_graphs &&
+                   graphs_valid(data.num_nodes, data.num_graphs, data.graph_ptr.data(),
+                                data.graph_label.data(), data.graph_split.data(),
+                                params.output_dim),
+               PGCN_E_INVALID, "readout: the data has no (valid) graphs attached");
+    num_graphs_ = data.num_graphs;
+    graph_ptr_host = data.graph_ptr;
+  }
   int lo_prio = 0, hi_prio = 0;
   PGCN_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
   stream = Stream::create(hi_prio);  // the reference uses High priority streams
@@ -542,7 +560,20 @@ void GCN::build(const GCNData &data) {
   }
   // truth per split for this rank's rows, padded with -1 (set_truth, src/gcn.cu:204-226)
   const int first = part.first(), rows = part.local_rows(), prow = part.maxrows;
-  for (int s = 1; s <= 3; s++) {
+  for (int s = 1; params.readout && s <= 3; s++) {  // per graph: the split's labelled graphs
+    std::vector<int> t((size_t)num_graphs_, -1);
+    int c = 0;
+    for (int g = 0; g < num_graphs_; g++)
+      if (data.graph_split[(size_t)g] == s && data.graph_label[(size_t)g] >= 0) {
+        t[(size_t)g] = data.graph_label[(size_t)g];
+        c++;
+      }
+    truth[s].allocate(t.size());
+    truth[s].upload(t);
+    truth_compact[s].allocate(1);
+    counts[s] = c;
+  }
+  for (int s = 1; !params.readout && s <= 3; s++) {
     std::vector<int> t((size_t)prow, -1);
     for (int i = 0; i < rows; i++)
       t[(size_t)i] = data.split[(size_t)first + i] == s ? data.label[(size_t)first + i] : -1;
@@ -646,7 +677,7 @@ void GCN::build(const GCNData &data) {
   init_dropout_rng(data, wtotal + atotal);
 
   // context buffers
-  xent_partials.allocate((size_t)xent_blocks(prow) * 2 + 2);
+  xent_partials.allocate((size_t)xent_blocks(std::max(prow, num_graphs_)) * 2 + 2);
   sums.allocate(4);
   results_ring.allocate((size_t)ring_cap * 4);
   results_ring.zero();
@@ -703,7 +734,7 @@ void GCN::build(const GCNData &data) {
       dropouts_[0] && dropouts_[1])
     const_cast<Dropout *>(dropouts_[0])->co_draw = dropouts_[1];
   // (multilabel: the output Matmul runs on its own, the `fuse_output 0` path)
-  if (knobs_.fuse_output && !params.multilabel) fuse_output_layer();
+  if (knobs_.fuse_output && !params.multilabel && !params.readout) fuse_output_layer();
   optimizer = Adam(weights, decays, adam_params);
   prepare_graphs();
   build_eval_ax();
@@ -998,7 +1029,7 @@ void GCN::insert_last_layer() {
   dropouts_.push_back(drop.get());
   modules.push_back(std::move(drop));
   const bool small = knobs_.reassoc_small && hl <= 16 && part.bounds.back() < kMmSideRows;
-  if (params.reassociate_last && !custom_aggregation() && (hl < C || small) && graph_symmetric) {
+  if (params.reassociate_last && !all_rows_matter() && (hl < C || small) && graph_symmetric) {
     // out = Â (H W) computed as (Â H) W: the same product (Â is symmetric, so the backward
     // Â dOut W^T = Â (dOut W^T) and W.grad = H^T Â dOut = (Â H)^T dOut also match), but the
     // GraphSum gathers rows of width hl instead of C.  Only the fp32 rounding order differs.
@@ -1035,9 +1066,15 @@ void GCN::insert_last_layer() {
   modules.push_back(std::make_unique<Matmul>(prev, weights.back(), var1, part.local_rows(), hl,
                                              wc, &ctx));
   auto out = std::make_shared<Variable>(prow, C, true, round_up4(C));
-  if (!custom_aggregation()) restricted_vars.push_back((int)variables.size());
+  if (!all_rows_matter()) restricted_vars.push_back((int)variables.size());
   variables.push_back(out);
   insert_aggregation(var1, out, C, L - 1, true);
+  if (params.readout) {  // node logits -> pooled [G][C] -> the loss over the graphs
+    pooled = std::make_shared<Variable>(num_graphs_, C, true, round_up4(C));
+    modules.push_back(std::make_unique<Readout>(out, pooled, graph_ptr_host, C, params.readout));
+    modules.push_back(std::make_unique<CrossEntropyLoss>(pooled, C, &ctx));
+    return;
+  }
   if (params.multilabel) modules.push_back(std::make_unique<BCEWithLogitsLoss>(out, C, &ctx));
   else modules.push_back(std::make_unique<CrossEntropyLoss>(out, C, &ctx));
 }
@@ -1052,7 +1089,7 @@ void GCN::set_split(int split) {
   ctx.split_graph = nullptr;
   ctx.split_rows = nullptr;
   ctx.split_colgraph = nullptr;
-  if (knobs_.split_rows && !comm && graph && !custom_aggregation()) {
+  if (knobs_.split_rows && !comm && graph && !all_rows_matter()) {
     if (!split_graphs[split]) {
       split_graphs[split] = graph->row_subset(split_rows_host[split]);
       split_rows_dev[split].allocate(std::max<size_t>(split_rows_host[split].size(), 1));
@@ -1098,7 +1135,7 @@ void GCN::set_split(int split) {
     }
     for (auto &cg : chunk_col_graphs) ctx.chunk_col_graphs.push_back(cg.get());
   }
-  if (knobs_.split_cols && !comm && graph && split == 1 && !custom_aggregation()) {  // (after training)
+  if (knobs_.split_cols && !comm && graph && split == 1 && !all_rows_matter()) {  // (after training)
     if (!split_colgraphs[split]) split_colgraphs[split] = graph->col_subset(split_rows_host[split]);
     ctx.split_colgraph = split_colgraphs[split].get();
   }
@@ -1112,7 +1149,7 @@ void GCN::set_split(int split) {
   } else {
     ctx.compact_n = 0;
     ctx.compact_truth = nullptr;
-    ctx.xent_blocks = xent_blocks(part.maxrows);
+    ctx.xent_blocks = xent_blocks(loss_prow());
   }
 }
 
@@ -1679,6 +1716,14 @@ void GCN::save(const std::string &path) {
     ck.aggregator = params.aggregator;
     ck.root_weight = params.root_weight ? 1 : 0;
   }
+  if (params.readout) {  // version 7: all three blocks, whatever the layer family
+    ck.flags |= kCheckpointReadout;
+    ck.version = kCheckpointVersionReadout;
+    ck.heads = params.attention_heads;
+    ck.attention_dropout = params.attention_dropout;
+    ck.readout = params.readout;
+    ck.num_graphs = num_graphs_;
+  }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1701,6 +1746,8 @@ void GCN::load(const std::string &path, int flags) {
   // (a weights-only load crosses the aggregator wherever the tensor shapes agree: the root weight
   // alone decides them)
   same = same && ck.root_weight == (params.root_weight ? 1 : 0);
+  // (the pooled loss is another model: neither kind of load crosses the mode or the graph count)
+  same = same && ck.readout == params.readout && ck.num_graphs == num_graphs_;
   if (same && resume) same = ck.aggregator == params.aggregator;
   if (same && resume) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
@@ -1750,7 +1797,7 @@ void GCN::load(const std::string &path, int flags) {
 // training forward would have made itself (the same stream positions, the same weights).
 void GCN::predict_forward() {
   if (!truth[0]) {
-    const std::vector<int> none((size_t)part.maxrows, -1);
+    const std::vector<int> none((size_t)loss_prow(), -1);
     truth[0].allocate(none.size());
     truth[0].upload(none);
   }
@@ -1765,7 +1812,7 @@ void GCN::predict_forward() {
   ctx.chunk_col_graphs.clear();
   ctx.compact_n = 0;
   ctx.compact_truth = nullptr;
-  ctx.xent_blocks = xent_blocks(part.maxrows);
+  ctx.xent_blocks = xent_blocks(loss_prow());
   out_restricted = false;
   ctx.fin = nullptr;
   ctx.fin_taken = false;
@@ -1779,12 +1826,12 @@ long long GCN::predict(int *cls, float *conf, float *probs) {
   const auto *ce = dynamic_cast<const CrossEntropyLoss *>(modules.back().get());
   PGCN_CHECK(ce, PGCN_E_INVALID, "predict: no output layer");
   const Variable &z = *ce->input();
-  const int n = part.local_rows(), C = params.output_dim, ldp = round_up4(C);
+  const int n = loss_rows(), C = params.output_dim, ldp = round_up4(C);
   if (!pred_cls) {
-    pred_cls.allocate((size_t)std::max(part.maxrows, 1));
-    pred_conf.allocate((size_t)std::max(part.maxrows, 1));
+    pred_cls.allocate((size_t)std::max(loss_prow(), 1));
+    pred_conf.allocate((size_t)std::max(loss_prow(), 1));
   }
-  if (probs && !pred_probs) pred_probs.allocate((size_t)std::max(part.maxrows, 1) * ldp);
+  if (probs && !pred_probs) pred_probs.allocate((size_t)std::max(loss_prow(), 1) * ldp);
   predict_forward();
   launch_predict_rows(z.dev_data.get(), z.ld, n, C, pred_cls.get(), pred_conf.get(),
                       probs ? pred_probs.get() : nullptr, ldp, stream.get());
@@ -1843,7 +1890,7 @@ void GCN::confusion(int split, long long *counts) {
   const int C = params.output_dim;
   predict(nullptr, nullptr, nullptr);
   if (!pred_counts) pred_counts.allocate((size_t)C * C);
-  launch_confusion(pred_cls.get(), truth[split].get(), part.local_rows(), C, pred_counts.get(),
+  launch_confusion(pred_cls.get(), truth[split].get(), loss_rows(), C, pred_counts.get(),
                    stream.get());
   sync();
   std::vector<unsigned> h((size_t)C * C);

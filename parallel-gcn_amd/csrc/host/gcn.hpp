@@ -60,6 +60,10 @@ struct GCNParams {
   // through the first d_l columns of H W_l.  Single GPU, widths <= 128
   int aggregator = 0;
   bool root_weight = false;
+  // graph classification: 1 sum, 2 mean, 3 max -- a Readout module (module.hpp) between the
+  // output layer's node logits and the loss, which then runs over GCNData::num_graphs rows with
+  // the graphs' labels and splits.  Single GPU, not with multilabel
+  int readout = 0;
 };
 
 struct AdamParams {
@@ -182,6 +186,7 @@ class GCN {
   int attention_heads() const { return attn_var ? params.attention_heads : 1; }
   int attention_dropout_layers() const { return (int)attn_rngs.size(); }
   int aggregator() const { return params.aggregator; }
+  int num_graphs() const { return num_graphs_; }
   bool root_weight() const { return params.root_weight; }
   // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
   int fused_norm_tails() const;
@@ -228,6 +233,17 @@ class GCN {
   // an engine whose aggregation is not a GraphSum module: no reassociated output layer, no Â X
   // precompute, no output-row restriction, the loss unfused
   bool custom_aggregation() const { return params.attention || params.aggregator != 0; }
+  // readout: every node row carries gradient, so nothing may rely on only a split's labelled rows
+  // mattering -- no reassociated output layer, no output-row restriction or compact buffers, no
+  // column-subset backward, the loss unfused
+  bool all_rows_matter() const { return custom_aggregation() || params.readout != 0; }
+  // readout: the graphs (0: none), their row ranges, and the pooled logits the loss reads
+  int num_graphs_ = 0;
+  std::vector<int> graph_ptr_host;
+  shared_ptr<Variable> pooled;
+  // the rows the loss, predict() and confusion() run over: the graphs, or this rank's nodes
+  int loss_rows() const { return params.readout ? num_graphs_ : part.local_rows(); }
+  int loss_prow() const { return params.readout ? num_graphs_ : part.maxrows; }
   // the layer's aggregation from var1 to var2: a GraphSum, a GraphAttention on attn_var or a
   // SageAggregate
   void insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,

@@ -813,6 +813,50 @@ void SageAggregate::backward(const Stream &s) const {
 }
 
 // ------------------------------------------------------------------------------------------
+// Readout (k_readout.hip)
+// ------------------------------------------------------------------------------------------
+Readout::Readout(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
+                 const std::vector<int> &graph_ptr_, int dim_, int mode_)
+    : in(std::move(in_)), out(std::move(out_)), n(graph_ptr_.empty() ? 0 : graph_ptr_.back()),
+      G((int)graph_ptr_.size() - 1), dim(dim_), mode(mode_), ld_s((dim_ + 3) / 4 * 4) {
+  PGCN_CHECK(in && out && G >= 1 && dim >= 1 && dim <= kReadoutMaxWidth && in->cols == dim &&
+                 out->cols == dim && in->rows >= n && out->rows >= G && in->ld % 4 == 0 &&
+                 out->ld % 4 == 0 && mode >= kReadoutSum && mode <= kReadoutMax &&
+                 graph_ptr_.front() == 0,
+             PGCN_E_INVALID, "readout: widths up to 128, mode 1..3, graph_ptr from 0");
+  std::vector<int> ng((size_t)std::max(n, 1), 0);
+  for (int g = 0; g < G; g++) {
+    PGCN_CHECK(graph_ptr_[(size_t)g + 1] >= graph_ptr_[(size_t)g], PGCN_E_INVALID,
+               "readout: graph_ptr must not decrease");
+    max_len = std::max(max_len, graph_ptr_[(size_t)g + 1] - graph_ptr_[(size_t)g]);
+    for (int i = graph_ptr_[(size_t)g]; i < graph_ptr_[(size_t)g + 1]; i++) ng[(size_t)i] = g;
+  }
+  graph_ptr.allocate(graph_ptr_.size());
+  graph_ptr.upload(graph_ptr_);
+  node_graph.allocate(ng.size());
+  node_graph.upload(ng);
+  if (mode == kReadoutMax) {
+    arg.allocate((size_t)G * ld_s);
+    arg.zero();
+  }
+  if (max_len > kReadoutChunk) ws.allocate(readout_workspace(n) / sizeof(float));
+}
+
+void Readout::forward(bool training, const Stream &s) const {
+  launch_readout_fwd(in->dev_data.get(), in->ld, graph_ptr.get(), G, n, dim, mode, max_len,
+                     out->dev_data.get(), out->ld,
+                     training && mode == kReadoutMax ? arg.get() : nullptr, ld_s,
+                     ws ? ws.get() : nullptr, s.get());
+}
+
+void Readout::backward(const Stream &s) const {
+  if (!in->dev_grad || !out->dev_grad) return;
+  launch_readout_bwd(out->dev_grad.get(), out->ld, graph_ptr.get(), node_graph.get(),
+                     mode == kReadoutMax ? arg.get() : nullptr, ld_s, G, n, dim, mode,
+                     in->dev_grad.get(), in->ld, s.get());
+}
+
+// ------------------------------------------------------------------------------------------
 // ReLU (src/module.cu:215-265)
 // ------------------------------------------------------------------------------------------
 ReLU::ReLU(shared_ptr<Variable> in_) : in(std::move(in_)) {

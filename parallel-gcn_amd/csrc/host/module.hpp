@@ -410,6 +410,30 @@ class SageAggregate : public Module {
   void backward(const Stream &s) const override;
 };
 
+// Graph-level readout behind the output layer (the reference has none): `in` [n][dim] holds the
+// node logits of a batch of G graphs, graph g owning rows [graph_ptr[g], graph_ptr[g + 1]); out
+// [G][dim] = their sum (mode 1), mean (2) or maximum (3) per graph (launch_readout_fwd: one launch
+// unless a range is longer than kReadoutChunk).  A training forward of the max keeps the winning
+// rows in `arg` (owned here).  The backward reads out->dev_grad -- the loss's gradient per graph --
+// and writes every row of in->dev_grad (launch_readout_bwd).  It draws nothing from the dropout
+// stream.  Single GPU only.
+class Readout : public Module {
+  shared_ptr<Variable> in, out;
+  int n, G, dim, mode, max_len = 0;
+  DeviceBuffer<int> graph_ptr, node_graph, arg;
+  DeviceBuffer<float> ws;
+  int ld_s;  // arg's stride: round_up4(dim)
+
+ public:
+  Readout(shared_ptr<Variable> in_, shared_ptr<Variable> out_, const std::vector<int> &graph_ptr_,
+          int dim_, int mode_);
+  const Variable *input() const { return in.get(); }
+  const Variable *output() const { return out.get(); }
+  int graphs() const { return G; }
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+};
+
 // include/module.cuh:90-99
 class ReLU : public Module {
   shared_ptr<Variable> in;

@@ -426,6 +426,27 @@ void launch_agg_max_bwd(const GatPattern &g, const SageWs &ws, const float *G, i
 // alignment: the root half of a SAGE layer in and out of its [n][2 d] variable
 void launch_copy_cols(const float *src, int ld_src, float *dst, int ld_dst, int n, int cols,
                       bool add, hipStream_t s);
+// ---- graph-level readout over contiguous row ranges (k_readout.hip) ---------------------------
+// out_g = the sum, the mean (the sum times one 1.0f / (float)len_g) or the exact maximum (arg_g[c]
+// the winning row, the lowest of equal values; arg may be null) of rows graph_ptr[g] ..
+// graph_ptr[g + 1] of `in`; an empty range: a zero row, arg -1.  graph_ptr is a device array.
+// max_len (host): the longest range's length or an upper bound of it -- above kReadoutChunk the
+// ranges longer than that go through two more launches and `workspace` (readout_workspace(n)
+// bytes, 16-byte aligned), else the call is one launch.  The widths, strides and padding rules
+// of the SAGE kernels.
+constexpr int kReadoutChunk = 512;
+constexpr int kReadoutMaxWidth = kSageMaxWidth;
+constexpr int kReadoutWsStride = kReadoutMaxWidth;
+enum { kReadoutNone = 0, kReadoutSum = 1, kReadoutMean = 2, kReadoutMax = 3 };
+size_t readout_workspace(int n);
+void launch_readout_fwd(const float *in, int ld_in, const int *graph_ptr, int G, int n, int d,
+                        int mode, int max_len, float *out, int ld_out, int *arg, int ld_arg,
+                        void *workspace, hipStream_t s);
+// din_i = G_out[graph(i)] (sum), times one 1 / len (mean), or its components whose arg is i (max):
+// every row of din written; node_graph [n] (device) is the range of every row
+void launch_readout_bwd(const float *Gout, int ld_g, const int *graph_ptr, const int *node_graph,
+                        const int *arg, int ld_arg, int G, int n, int d, int mode, float *din,
+                        int ld_din, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -24,6 +24,11 @@
 // aggregator=mean|max (or 1|2) [root_weight=1] (command line or parameter file): GraphSAGE layers
 // in the GraphSums' place, pgcn_params.aggregator / root_weight; `gcn-par cora aggregator=max
 // root_weight=1` trains the max-pooling variant with a self term.
+// readout=sum|mean|max (or 1|2|3; command line or parameter file): graph classification,
+// pgcn_params.readout -- the nodes are a batch of graphs read from the sidecar file
+// data/<name>.graphs (line g: `<rows> <label> <split>`), loss and accuracy are per graph, and
+// predict= writes one line `graph class confidence` per graph.
+#include <algorithm>
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -44,6 +49,17 @@ static int aggregator_id(const std::string &v) {
   if (v == "mean") return 1;
   if (v == "max") return 2;
   if (v == "gcn" || v == "none") return 0;
+  char *end = nullptr;
+  const long x = std::strtol(v.c_str(), &end, 10);
+  return (end && *end == '\0' && !v.empty()) ? (int)x : -1;
+}
+
+// readout=: sum / mean / max by name or 0 .. 3; anything else is left for the engine to refuse
+static int readout_id(const std::string &v) {
+  if (v == "sum") return 1;
+  if (v == "mean") return 2;
+  if (v == "max") return 3;
+  if (v == "none") return 0;
   char *end = nullptr;
   const long x = std::strtol(v.c_str(), &end, 10);
   return (end && *end == '\0' && !v.empty()) ? (int)x : -1;
@@ -90,6 +106,7 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "attn_dropout") p->attention_dropout = std::strtof(v.c_str(), nullptr);
     else if (k == "aggregator") p->aggregator = aggregator_id(v);
     else if (k == "root_weight") p->root_weight = std::atoi(v.c_str());
+    else if (k == "readout") p->readout = readout_id(v);
   }
   return true;
 }
@@ -107,7 +124,7 @@ int main(int argc, char **argv) {
   int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
   int root_weight = -1;
-  std::string aggregator;
+  std::string aggregator, readout;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -126,6 +143,7 @@ int main(int argc, char **argv) {
       attn_dropout = std::strtof(argv[i] + 13, nullptr);
     if (!std::strncmp(argv[i], "aggregator=", 11)) aggregator = argv[i] + 11;
     if (!std::strncmp(argv[i], "root_weight=", 12)) root_weight = std::atoi(argv[i] + 12);
+    if (!std::strncmp(argv[i], "readout=", 8)) readout = argv[i] + 8;
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -142,6 +160,7 @@ int main(int argc, char **argv) {
   if (attn_dropout >= 0.0f) p.attention_dropout = attn_dropout;
   if (!aggregator.empty()) p.aggregator = aggregator_id(aggregator);
   if (root_weight >= 0) p.root_weight = root_weight;
+  if (!readout.empty()) p.readout = readout_id(readout);
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
@@ -154,6 +173,13 @@ int main(int argc, char **argv) {
     const std::string labels = root + "/data/" + name + ".labels";
     if (pgcn_dataset_load_labels(ds, labels.c_str(), 0) != PGCN_OK) {
       fprintf(stderr, "Cannot read labels: %s\n", labels.c_str());
+      return EXIT_FAILURE;
+    }
+  }
+  if (p.readout) {
+    const std::string graphs = root + "/data/" + name + ".graphs";
+    if (pgcn_dataset_load_graphs(ds, graphs.c_str(), 0) != PGCN_OK) {
+      fprintf(stderr, "Cannot read graphs: %s\n", graphs.c_str());
       return EXIT_FAILURE;
     }
   }
@@ -191,8 +217,10 @@ int main(int argc, char **argv) {
       std::fclose(f);
     }
   } else if (st == PGCN_OK && !predict.empty()) {
-    std::vector<int> cls((size_t)view.num_nodes);
-    std::vector<float> conf((size_t)view.num_nodes);
+    // (one row per node, or per graph under readout)
+    const size_t rows = (size_t)std::max(view.num_nodes, view.num_graphs);
+    std::vector<int> cls(rows);
+    std::vector<float> conf(rows);
     const long long n = pgcn_gcn_predict(g, cls.data(), conf.data(), nullptr);
     FILE *f = n >= 0 ? std::fopen(predict.c_str(), "w") : nullptr;
     if (!f) {
