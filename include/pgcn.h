@@ -348,6 +348,49 @@ int pgcn_readout_bwd(const float *G_out, int ld_g, const int *graph_ptr, const i
                      const int *arg /* max only */, int ld_arg, int G, int n, int d, int mode,
                      float *din, int ld_din, void *stream);
 
+/* --- link prediction: pair scores over a node variable (k_link.hip; new: the reference has no
+ *     pair-level model) ------------------------------------------------------------------------
+ * pgcn_links is an opaque pair index, in the manner of pgcn_graph: n_pairs pairs (src_e, dst_e) of
+ * nodes in [0, n_nodes), all host arrays.  Every pair enters the forward; a pair enters the
+ * backward iff select == NULL or select[e] >= 0.  pgcn_links_create uploads src / dst and builds
+ * the INCIDENCE INDEX on the host: each node's list of (pair e, other endpoint) over the selected
+ * pairs that touch it, in ascending e, the entry of a pair's src role before that of its dst role
+ * -- a self pair (i, i) gives two consecutive entries in node i's list, a duplicated pair counts
+ * as often as it is listed.  Lists longer than pgcn_link_segment_slots() = T entries are cut into
+ * T-entry segments.  pgcn_links_slots: the incidence entries, 2 x the selected pairs.
+ * PGCN_E_INVALID: an endpoint outside [0, n_nodes), 2^30 or more selected pairs (the entries are
+ * indexed by int), n_pairs beyond an int.  The segment partials of the backward live in the
+ * handle: two backward calls on one handle must not overlap (the pgcn_agg_max_* contract).
+ *   pgcn_link_score_fwd, ONE launch: scores[e][0] = sum_c H[src_e][c] * H[dst_e][c] over c < d; the
+ *     float4 at scores[e][0..3] is written as {s, 0, 0, 0}, columns behind it are left alone.  GL
+ *     lanes take one pair (GL by width as for the attention kernels), each lane multiplies its
+ *     float4 of the two rows and the lanes of a group are summed by xor butterflies over the
+ *     offsets 1 .. GL / 2: a fixed order.
+ *   pgcn_link_score_bwd, one launch, two when any list exceeds T: with G[e][0] = dLoss/dscore_e,
+ *     dH_i[c] = sum over node i's incidence entries (e, o) of G[e][0] * H[o][c].  EVERY row of dH
+ *     is written: the float4s covering [0, round_up4(d)), zero from column d on and for a node
+ *     without entries; columns beyond are left alone.  G of an unselected pair is never read.
+ * 1 <= d <= 128; every ld a multiple of 4 and >= d (>= 1 for scores and G), rows 16-byte aligned;
+ * padding columns of H may hold anything, NaN included, and never reach a result.  Anything else
+ * is PGCN_E_INVALID before anything touches the device.  n_pairs == 0 launches nothing.  The
+ * calls are asynchronous, allocate nothing and may be captured.  No float atomics: every
+ * summation order depends on the pair list and d only, so two calls give the same bits. */
+typedef struct pgcn_links pgcn_links;
+int pgcn_links_create(int n_nodes, long long n_pairs, const int *src, const int *dst,
+                      const int *select /* [n_pairs] or NULL */, pgcn_links **out);
+int pgcn_links_destroy(pgcn_links *l);
+int pgcn_link_segment_slots(void);
+long long pgcn_links_slots(const pgcn_links *l);
+int pgcn_link_score_fwd(const pgcn_links *l, const float *H, int ld_h, int d, float *scores,
+                        int ld_s, void *stream);
+int pgcn_link_score_bwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *G,
+                        int ld_g /* dLoss/dscore = G[e][0] */, float *dH, int ld_dh,
+                        void *stream);
+/* host-only (no device): the incidence index pgcn_links_create would build -- ptr [n_nodes + 1],
+ * pair and other [ptr[n_nodes]] (either may be NULL: call once for ptr, then again) */
+int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, const int *dst,
+                               const int *select, int *ptr, int *pair, int *other);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -421,6 +464,23 @@ float pgcn_adam_step_size(float lr, float beta1, float beta2, int t);
 typedef struct {
   int num_nodes, input_dim, output_dim; /* filled by the loader */
   int n_layers;                          /* >= 2 */
+  /* Link prediction.  0: none (the engine as it was, bit for bit); 1: dot product.  The output
+   * layer's node variable out [N][D], D = output_dim <= 128, is an EMBEDDING; behind it a
+   * LinkDecoder (pgcn_link_score_fwd / _bwd) scores the pgcn_data.num_pairs pairs (required then)
+   * into scores [E][4], and the sigmoid binary cross-entropy (pgcn_bce_fwd with one class) runs on
+   * the scores with bit 0 = pair_label == 1, the truth of a split built from pair_label /
+   * pair_split and count = the split's labelled pairs.  Loss, accuracy ((score > 0) == label), the
+   * results ring and early stopping are then per pair.  The backward's pair index holds the
+   * TRAINING split's labelled pairs.  Every layer family runs unchanged (attention with heads,
+   * aggregator / root_weight, residual, layer_norm).  Every node row carries gradient, so the
+   * fused output / loss kernel, the output-row restriction with its compact buffers, the
+   * column-subset backward and the reassociated output layer are off.  The decoder draws nothing
+   * from the dropout stream and has no weights.  The message-passing adjacency is the dataset's
+   * graph as loaded: keeping validation and test positives out of it is the caller's job.  Not
+   * with multilabel or readout, single GPU only (the edge-cut creators return PGCN_E_INVALID); a
+   * split whose labelled pairs exceed 2^24 is refused (the sums travel as floats).  The engine has
+   * one more variable, the last (index pgcn_gcn_num_vars - 1): scores [E][1]. */
+  int link_decoder;
   int hidden_dims[PGCN_MAX_LAYERS];      /* n_layers - 1 */
   float dropouts[PGCN_MAX_LAYERS];       /* n_layers */
   /* GraphSAGE layers.  aggregator: 0 = GCN's Â (the engine as it was, bit for bit), 1 = mean,
@@ -527,6 +587,12 @@ typedef struct {
   const int *feat_indptr, *feat_indices;              /* n+1, nnz_x */
   const float *feat_values;                           /* nnz_x */
   const int *label, *split;                           /* n, n */
+  /* read only when pgcn_params.link_decoder != 0: num_pairs >= 1 node pairs (pair_src[e],
+   * pair_dst[e]) in [0, num_nodes), pair_label [num_pairs] 1 (a link), 0 (none) or -1
+   * (unlabelled), pair_split [num_pairs] in 0..3 as the node splits.  Self pairs and repeated
+   * pairs are allowed.  0 / NULL: none. */
+  int num_pairs;
+  const int *pair_src, *pair_dst, *pair_label, *pair_split;
   /* read only when pgcn_params.multilabel != 0: the label bit matrix [n][label_words], bit j % 32
    * of word j / 32 set iff node i has class j, bits from output_dim on zero; label_words =
    * ceil(output_dim / 32).  A node is labelled iff label[i] >= 0 (the value is not used). */
@@ -591,7 +657,8 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "fused_residuals" (how many of them the last training forward added inside a GraphSum's
  * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
  * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel), "readout" (the readout
- * mode, pgcn_params.readout) and "num_graphs" (its graph count; 0 without a readout), and
+ * mode, pgcn_params.readout) and "num_graphs" (its graph count; 0 without a readout),
+ * "link_decoder" (pgcn_params.link_decoder) and "num_pairs" (its pair count; 0 without), and
  * "fused_norm_tails" (how many of them ran the ReLU / residual add /
  * Dropout behind them inside the LayerNorm kernel in the last training forward);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
@@ -723,6 +790,19 @@ int pgcn_checkpoint_sage(const char *path, int *aggregator, int *root_weight);
  * engine's.  pgcn_checkpoint_info, _flags, _attention and _sage accept version 7. */
 #define PGCN_CKPT_READOUT 32
 int pgcn_checkpoint_readout(const char *path, int *mode, int *num_graphs);
+/* flags bit 6: saved by a link-prediction engine (pgcn_params.link_decoder != 0).  Such an engine
+ * writes a version-8 file: the header with bit 6 set, then version 7's three 16-byte blocks (the
+ * third all zero: a link engine has no readout) and a fourth {u32 link_decoder; u32 0; u64
+ * num_pairs}, all under the checksum, then the payload as the flags say -- unchanged: the decoder
+ * has no weights.  Every other engine keeps writing versions 1-7 byte for byte.
+ * pgcn_checkpoint_links is host-only and validates as pgcn_checkpoint_info does: the decoder and
+ * the pair count of the engine that saved the file; versions 1-7 give 0 and 0.  A resuming load
+ * (flags 0) refuses a file whose decoder or pair count differs from the engine's; a weights-only
+ * load crosses both -- the tensors are the same, so a node-classification model can warm-start a
+ * link model of equal dims, and the reverse.  pgcn_checkpoint_info, _flags, _attention, _sage and
+ * _readout accept version 8. */
+#define PGCN_CKPT_LINKS 64
+int pgcn_checkpoint_links(const char *path, int *decoder, long long *num_pairs);
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever
@@ -747,6 +827,19 @@ long long pgcn_gcn_predict_multilabel(pgcn_gcn *g, uint32_t *bits, float *probs)
  * class over this rank's rows (the caller adds the ranks' counts; micro / macro F1 follow from
  * the integer sums). */
 int pgcn_gcn_multilabel_counts(pgcn_gcn *g, int split, long long *counts);
+/* Link engines (pgcn_params.link_decoder; PGCN_E_INVALID otherwise, as pgcn_gcn_predict,
+ * pgcn_gcn_confusion and the multi-label services are on a link engine).
+ * pgcn_gcn_predict_links: pgcn_gcn_predict's eval-mode forward, with the same guarantees, then the
+ * scores of the engine's num_pairs pairs and their sigmoids (either may be NULL); returns the pair
+ * count or a status < 0.
+ * pgcn_gcn_link_counts: that forward + pgcn_multilabel_counts with one class against split's
+ * labelled pairs: counts[3] = tp, fp, fn (a pair is predicted a link iff its score > 0).
+ * pgcn_gcn_score_pairs: the same forward, then pgcn_link_score_fwd over m caller-given candidate
+ * pairs (host arrays, endpoints in [0, num_nodes)) through a temporary pair index; scores [m].
+ * The training state is untouched. */
+long long pgcn_gcn_predict_links(pgcn_gcn *g, float *scores, float *probs);
+int pgcn_gcn_link_counts(pgcn_gcn *g, int split, long long *counts);
+int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m, float *scores);
 /* per-call device timing of the GraphSum kernels (enable before the timed region) */
 int pgcn_gcn_profile(pgcn_gcn *g, int enable);
 int pgcn_gcn_profile_read(pgcn_gcn *g, double *graphsum_ms_total, long long *graphsum_calls,
@@ -804,8 +897,21 @@ int pgcn_dataset_set_graphs(pgcn_dataset *ds, const int *graph_ptr, const int *l
  * split outside 0..3.  The .pgcnbin cache does not carry graph arrays (pgcn_dataset_save writes
  * the node-level arrays only): attach them after every load. */
 int pgcn_dataset_load_graphs(pgcn_dataset *ds, const char *path, int num_classes);
+/* Pair-level data for link prediction: attaches E >= 1 node pairs (src, dst in [0, num_nodes)),
+ * their labels (1, 0 or -1: unlabelled) and splits (0..3), all copied, and sets output_dim =
+ * embed_dim in 1..128, the width of the node embedding the decoder reads.  PGCN_E_INVALID
+ * otherwise.  The adjacency is not changed: it stays the message-passing graph, so validation and
+ * test positives must be kept out of it by whoever builds the dataset. */
+int pgcn_dataset_set_links(pgcn_dataset *ds, const int *src, const int *dst, const int *label,
+                           const int *split, long long E, int embed_dim);
+/* The same from the sidecar text file `path` (by convention <root>/data/<name>.links): line e is
+ * `<src> <dst> <label> <split>`.  PGCN_E_IO for a missing file, a line that is not four integers,
+ * an endpoint out of range, a label outside {-1, 0, 1}, a split outside 0..3, no pair at all;
+ * PGCN_E_INVALID for embed_dim outside 1..128.  The .pgcnbin cache does not carry pair arrays
+ * (the .graphs rule): attach them after every load. */
+int pgcn_dataset_load_links(pgcn_dataset *ds, const char *path, int embed_dim);
 /* (label_bits / label_words of the view: NULL / 0 for single-label data; num_graphs and the graph
- * arrays: 0 / NULL without graphs) */
+ * arrays: 0 / NULL without graphs; num_pairs and the pair arrays: 0 / NULL without pairs) */
 int pgcn_dataset_view(const pgcn_dataset *ds, pgcn_data *view, int *input_dim, int *output_dim);
 int pgcn_dataset_free(pgcn_dataset *ds);
 
@@ -899,7 +1005,8 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * c = X b beside c2 = drop(X) b), "spmm_csc_256" / "spmm_csc_1024" (sparse X: the weight
  * gradient's sequential-chain kernel, 256 threads per feature or 1024 on matrices of more than
  * 512 entries per feature), "spmm_tree_256" / "spmm_tree_1024" (its fixed-tree form, csc_tree),
- * "launches" (every kernel launch of the library).
+ * "launches" (every kernel launch of the library), "link_fwd" / "link_bwd" (the pair-score
+ * forward and backward calls that launched).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

@@ -40,7 +40,8 @@ P = ctypes.POINTER
 
 class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
-                ("n_layers", c_int), ("hidden_dims", c_int * MAX_LAYERS),
+                ("n_layers", c_int), ("link_decoder", c_int),
+                ("hidden_dims", c_int * MAX_LAYERS),
                 ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
                 ("root_weight", c_int), ("epochs", c_int), ("readout", c_int),
                 ("early_stopping", c_int),
@@ -55,6 +56,8 @@ class PgcnData(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("graph_indptr", P(c_int)), ("graph_indices", P(c_int)),
                 ("feat_indptr", P(c_int)), ("feat_indices", P(c_int)),
                 ("feat_values", P(c_float)), ("label", P(c_int)), ("split", P(c_int)),
+                ("num_pairs", c_int), ("pair_src", P(c_int)), ("pair_dst", P(c_int)),
+                ("pair_label", P(c_int)), ("pair_split", P(c_int)),
                 ("label_bits", P(ctypes.c_uint32)), ("label_words", c_int),
                 ("num_graphs", c_int), ("graph_ptr", P(c_int)), ("graph_label", P(c_int)),
                 ("graph_split", P(c_int))]
@@ -150,6 +153,15 @@ _sig("pgcn_readout_fwd", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, 
      c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p)
 _sig("pgcn_readout_bwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
      c_int, c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_links_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, P(c_void_p))
+_sig("pgcn_links_destroy", c_int, c_void_p)
+_sig("pgcn_link_segment_slots", c_int)
+_sig("pgcn_links_slots", c_ll, c_void_p)
+_sig("pgcn_link_score_fwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_link_score_bwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+     c_int, c_void_p)
+_sig("pgcn_debug_links_incidence", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
+     c_void_p, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -191,6 +203,12 @@ _sig("pgcn_checkpoint_flags", c_int, ctypes.c_char_p)
 _sig("pgcn_checkpoint_attention", c_int, ctypes.c_char_p, P(c_int), P(c_float))
 _sig("pgcn_checkpoint_sage", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_checkpoint_readout", c_int, ctypes.c_char_p, P(c_int), P(c_int))
+_sig("pgcn_checkpoint_links", c_int, ctypes.c_char_p, P(c_int), P(c_ll))
+_sig("pgcn_gcn_predict_links", c_ll, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_gcn_link_counts", c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_gcn_score_pairs", c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p)
+_sig("pgcn_dataset_set_links", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int)
+_sig("pgcn_dataset_load_links", c_int, c_void_p, ctypes.c_char_p, c_int)
 _sig("pgcn_gcn_predict", c_ll, c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_confusion", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_predict_rows", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
@@ -282,7 +300,7 @@ def _ptr(a):
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
                 "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
-                "spmm_tree_1024", "launches")
+                "spmm_tree_1024", "launches", "link_fwd", "link_bwd")
 
 
 def path_counts(reset=False, thread=False):
@@ -350,6 +368,35 @@ class Dataset:
             self.graph_ptr = arr(self.view.graph_ptr, g + 1, np.int32)
             self.graph_label = arr(self.view.graph_label, g, np.int32)
             self.graph_split = arr(self.view.graph_split, g, np.int32)
+
+        # pair-level data for link prediction (None without)
+        self.num_pairs = self.view.num_pairs
+        self.pair_src = self.pair_dst = self.pair_label = self.pair_split = None
+        if self.num_pairs > 0 and self.view.pair_src:
+            e = self.num_pairs
+            self.pair_src = arr(self.view.pair_src, e, np.int32)
+            self.pair_dst = arr(self.view.pair_dst, e, np.int32)
+            self.pair_label = arr(self.view.pair_label, e, np.int32)
+            self.pair_split = arr(self.view.pair_split, e, np.int32)
+
+    def set_links(self, src, dst, labels, splits, embed_dim):
+        """Attaches E node pairs for link prediction: src, dst [E] in [0, num_nodes), labels [E]
+        1 (a link), 0 (none) or -1 (unlabelled), splits [E] in 0..3; sets output_dim = embed_dim
+        (1..128), the width of the node embedding the decoder reads.  The adjacency stays as it
+        is: keep validation and test positives out of it."""
+        a = [np.ascontiguousarray(x, np.int32) for x in (src, dst, labels, splits)]
+        if a[0].ndim != 1 or any(x.shape != a[0].shape for x in a):
+            raise ValueError("set_links: src, dst, labels, splits [E]")
+        check(lib.pgcn_dataset_set_links(self._h, *(_ptr(x) for x in a), a[0].size, embed_dim),
+              "dataset_set_links")
+        self._refresh()
+
+    def load_links(self, path, embed_dim):
+        """Reads the pair sidecar file (line e: `<src> <dst> <label> <split>`; by convention
+        <root>/data/<name>.links) and sets output_dim = embed_dim."""
+        check(lib.pgcn_dataset_load_links(self._h, os.fsencode(path), embed_dim),
+              f"dataset_load_links {path}")
+        self._refresh()
 
     def set_graphs(self, graph_ptr, labels, splits, num_classes=0):
         """Attaches G graphs as contiguous row ranges: graph_ptr [G + 1] from 0 to num_nodes,
@@ -465,19 +512,119 @@ def f1_scores(counts):
     return (float(2 * tp.sum() / tot) if tot > 0 else 0.0), float(per.mean())
 
 
+class Links:
+    """A pair index on the device (pgcn_links): n_pairs pairs (src, dst) over n_nodes nodes; the
+    pairs with select >= 0 (all when None) enter the backward's incidence index."""
+
+    def __init__(self, n_nodes, src, dst, select=None):
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        if src.ndim != 1 or dst.shape != src.shape:
+            raise ValueError("Links: src [E], dst [E]")
+        sel = None if select is None else np.ascontiguousarray(select, np.int32)
+        if sel is not None and sel.shape != src.shape:
+            raise ValueError("Links: select [E]")
+        h = c_void_p()
+        check(lib.pgcn_links_create(n_nodes, src.size, _ptr(src), _ptr(dst),
+                                    _ptr(sel) if sel is not None else None, ctypes.byref(h)),
+              "links_create")
+        self._h, self.n_nodes, self.n_pairs = h, n_nodes, int(src.size)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def slots(self):
+        return int(lib.pgcn_links_slots(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and lib is not None:
+            lib.pgcn_links_destroy(self._h)
+            self._h = c_void_p()
+
+    __del__ = close
+
+
+def links_incidence(n_nodes, src, dst, select=None):
+    """Host-only: (ptr [n_nodes + 1], pair, other) -- the incidence index pgcn_links_create
+    builds (pgcn_debug_links_incidence)."""
+    src = np.ascontiguousarray(src, np.int32)
+    dst = np.ascontiguousarray(dst, np.int32)
+    sel = None if select is None else np.ascontiguousarray(select, np.int32)
+    ps = _ptr(sel) if sel is not None else None
+    ptr = np.zeros(n_nodes + 1, np.int32)
+    check(lib.pgcn_debug_links_incidence(n_nodes, src.size, _ptr(src), _ptr(dst), ps, _ptr(ptr),
+                                         None, None), "debug_links_incidence")
+    pair, other = np.zeros(ptr[-1], np.int32), np.zeros(ptr[-1], np.int32)
+    check(lib.pgcn_debug_links_incidence(n_nodes, src.size, _ptr(src), _ptr(dst), ps, _ptr(ptr),
+                                         _ptr(pair), _ptr(other)), "debug_links_incidence")
+    return ptr, pair, other
+
+
+def link_auc(scores, labels):
+    """Area under the ROC curve of `scores` against labels in {0, 1} (-1: unlabelled, skipped):
+    rank-based (Mann-Whitney), tied scores sharing their average rank.  nan when a class is
+    empty."""
+    s = np.asarray(scores, np.float64).ravel()
+    y = np.asarray(labels).ravel()
+    keep = y >= 0
+    s, y = s[keep], y[keep]
+    pos, neg = int((y == 1).sum()), int((y == 0).sum())
+    if pos == 0 or neg == 0:
+        return float("nan")
+    order = np.argsort(s, kind="stable")
+    ss = s[order]
+    start = np.flatnonzero(np.r_[True, ss[1:] != ss[:-1]])  # the first of every run of equals
+    end = np.r_[start[1:], ss.size]
+    avg = (start + end + 1) / 2.0  # ranks from 1: the mean of start + 1 .. end
+    rank = np.empty(s.size, np.float64)
+    rank[order] = np.repeat(avg, end - start)
+    return float((rank[y == 1].sum() - pos * (pos + 1) / 2.0) / (pos * neg))
+
+
+def sample_negative_pairs(ds, src, ratio=1, seed=0):
+    """Negative pairs for link prediction, on the host: for every entry of `src`, `ratio` pairs
+    (src, dst) with dst drawn uniformly from the nodes, redrawn while it is src itself or a
+    neighbour of src in ds's adjacency (either direction).  Deterministic in `seed`.  Returns
+    (src int32 [len(src) * ratio], dst int32 [the same])."""
+    n = ds.num_nodes
+    indptr, indices = np.asarray(ds.graph_indptr), np.asarray(ds.graph_indices)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+    cols = indices.astype(np.int64)
+    edges = np.unique(np.concatenate([rows * n + cols, cols * n + rows]))
+    s = np.repeat(np.asarray(src, np.int64).ravel(), int(ratio))
+    if s.size and (s.min() < 0 or s.max() >= n):
+        raise ValueError("sample_negative_pairs: src out of range")
+    rng = np.random.default_rng(seed)
+    d = rng.integers(0, n, s.size)
+    for _ in range(1000):
+        bad = np.flatnonzero((d == s) | np.isin(s * n + d, edges))
+        if bad.size == 0:
+            return s.astype(np.int32), d.astype(np.int32)
+        d[bad] = rng.integers(0, n, bad.size)
+    raise ValueError("sample_negative_pairs: a source node is adjacent to every other node")
+
+
 AGGREGATORS = {None: 0, "mean": 1, "max": 2}
 READOUTS = {None: 0, "sum": 1, "mean": 2, "max": 3}
+LINK_DECODERS = {None: 0, "dot": 1}
 
 
 def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_stopping=0,
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
                 multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
-                aggregator=None, root_weight=False, readout=None):
+                aggregator=None, root_weight=False, readout=None, link_decoder=None):
     """aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
     own row through its own half of a [d_in][2 d_l] weight (with an aggregator only).
     readout: None (node classification), "sum", "mean" or "max": graph classification over the
-    graphs attached with Dataset.set_graphs / load_graphs (not with multilabel)."""
+    graphs attached with Dataset.set_graphs / load_graphs (not with multilabel).
+    link_decoder: None or "dot": link prediction over the pairs attached with Dataset.set_links /
+    load_links, output_dim being the embedding width (not with multilabel or readout)."""
+    if link_decoder not in LINK_DECODERS:
+        raise ValueError("link_decoder must be 'dot' or None")
+    if LINK_DECODERS[link_decoder] and (multilabel or READOUTS.get(readout)):
+        raise ValueError("link_decoder cannot be combined with multilabel or readout")
     if readout not in READOUTS:
         raise ValueError(f"readout must be one of {sorted(k for k in READOUTS if k)} or None")
     if READOUTS[readout] and multilabel:
@@ -496,6 +643,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     p.attention_heads, p.attention_dropout = attention_heads, attention_dropout
     p.multilabel = 1 if multilabel else 0
     p.readout = READOUTS[readout]
+    p.link_decoder = LINK_DECODERS[link_decoder]
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
@@ -646,6 +794,36 @@ class GCN:
         check(lib.pgcn_gcn_multilabel_counts(self._h, split, _ptr(out)), "multilabel_counts")
         return out
 
+    def predict_links(self, probs=False):
+        """float32 [num_pairs]: the scores of a link engine's pairs from an eval-mode forward; with
+        probs=True also their sigmoids."""
+        n = self.query("num_pairs")
+        sc = np.zeros(n, np.float32)
+        pr = np.zeros(n, np.float32) if probs else None
+        got = lib.pgcn_gcn_predict_links(self._h, _ptr(sc), _ptr(pr) if probs else None)
+        if got < 0:
+            raise PgcnError(int(got), "predict_links")
+        assert got == n
+        return (sc, pr) if probs else sc
+
+    def link_counts(self, split):
+        """int64 [3]: tp, fp, fn over `split`'s labelled pairs (predicted a link iff score > 0)."""
+        out = np.zeros(3, np.int64)
+        check(lib.pgcn_gcn_link_counts(self._h, split, _ptr(out)), "link_counts")
+        return out
+
+    def score_pairs(self, src, dst):
+        """float32 [m]: the decoder's scores of caller-given candidate pairs from the same
+        eval-mode forward; the training state is untouched."""
+        src = np.ascontiguousarray(src, np.int32)
+        dst = np.ascontiguousarray(dst, np.int32)
+        if src.ndim != 1 or dst.shape != src.shape:
+            raise ValueError("score_pairs: src [m], dst [m]")
+        out = np.zeros(src.size, np.float32)
+        check(lib.pgcn_gcn_score_pairs(self._h, _ptr(src), _ptr(dst), src.size, _ptr(out)),
+              "score_pairs")
+        return out
+
     def profile(self, on):
         check(lib.pgcn_gcn_profile(self._h, 1 if on else 0), "profile")
 
@@ -772,6 +950,7 @@ CKPT_MULTILABEL = 4  # saved by a multi-label engine (no payload change)
 CKPT_ATTENTION = 8  # version-4 files: the attention tensor last in the payloads
 CKPT_SAGE = 16  # version-6 files: a GraphSAGE engine's, with the {aggregator, root_weight} block
 CKPT_READOUT = 32  # version-7 files: a graph-classification engine's, with its three blocks
+CKPT_LINKS = 64  # version-8 files: a link-prediction engine's, with its four blocks
 
 
 def checkpoint_flags(path):
@@ -800,6 +979,15 @@ def checkpoint_sage(path):
     check(lib.pgcn_checkpoint_sage(os.fsencode(path), ctypes.byref(agg), ctypes.byref(root)),
           f"checkpoint_sage {path}")
     return agg.value, root.value
+
+
+def checkpoint_links(path):
+    """Host-only: (link decoder, num_pairs) of the engine that saved the file -- a version-8
+    file's block; (0, 0) for versions 1-7.  PgcnError(PGCN_E_IO) for an invalid file."""
+    dec, e = c_int(), c_ll()
+    check(lib.pgcn_checkpoint_links(os.fsencode(path), ctypes.byref(dec), ctypes.byref(e)),
+          f"checkpoint_links {path}")
+    return dec.value, e.value
 
 
 def checkpoint_readout(path):
@@ -919,4 +1107,8 @@ EXPORTED = [
     "pgcn_dataset_load_labels",
     "pgcn_readout_chunk_rows", "pgcn_readout_workspace", "pgcn_readout_fwd", "pgcn_readout_bwd",
     "pgcn_dataset_set_graphs", "pgcn_dataset_load_graphs", "pgcn_checkpoint_readout",
+    "pgcn_links_create", "pgcn_links_destroy", "pgcn_link_segment_slots", "pgcn_links_slots",
+    "pgcn_link_score_fwd", "pgcn_link_score_bwd", "pgcn_debug_links_incidence",
+    "pgcn_checkpoint_links", "pgcn_gcn_predict_links", "pgcn_gcn_link_counts",
+    "pgcn_gcn_score_pairs", "pgcn_dataset_set_links", "pgcn_dataset_load_links",
 ]

@@ -28,7 +28,8 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "gemm_tn",    "gemm_nn_w",  "gemm_tn_w", "gat_fwd",
                                           "gat_bwd",    "gat_heads",  "spmm_csr",
                                           "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024",
-                                          "spmm_tree_256", "spmm_tree_1024", "launches"};
+                                          "spmm_tree_256", "spmm_tree_1024", "launches",
+                                          "link_fwd",   "link_bwd"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -38,6 +39,9 @@ void note_path(KernelPath p) {
 
 struct pgcn_graph {
   std::unique_ptr<DevGraph> g;
+};
+struct pgcn_links {
+  std::unique_ptr<LinkIndexDev> l;
 };
 struct pgcn_gcn {
   std::unique_ptr<GCN> g;
@@ -67,6 +71,9 @@ void refuse_single_gpu_only(const pgcn_params *p) {
   // (a graph's rows may lie on several ranks: its readout would need an exchange of its own)
   PGCN_CHECK(!p->readout, PGCN_E_INVALID,
              "readout: single GPU only (edge-cut graph classification is not supported)");
+  // (a pair's endpoints may lie on two ranks: its score would need an exchange of its own)
+  PGCN_CHECK(!p->link_decoder, PGCN_E_INVALID,
+             "link_decoder: single GPU only (edge-cut link prediction is not supported)");
 }
 
 GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
@@ -96,6 +103,11 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   PGCN_CHECK(!p->readout || !p->multilabel, PGCN_E_INVALID,
              "readout cannot be combined with multilabel");
   q.readout = p->readout;
+  PGCN_CHECK(p->link_decoder == 0 || p->link_decoder == 1, PGCN_E_INVALID,
+             "link_decoder must be 0 (none) or 1 (dot product)");
+  PGCN_CHECK(!p->link_decoder || (!p->multilabel && !p->readout), PGCN_E_INVALID,
+             "link_decoder cannot be combined with multilabel or readout");
+  q.link_decoder = p->link_decoder;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -142,6 +154,19 @@ GCNData to_data(const pgcn_data *d, const pgcn_params *p) {
     g.graph_ptr.assign(d->graph_ptr, d->graph_ptr + G + 1);
     g.graph_label.assign(d->graph_label, d->graph_label + G);
     g.graph_split.assign(d->graph_split, d->graph_split + G);
+  }
+  if (p->link_decoder) {  // (the pair members are read only then)
+    PGCN_CHECK(d->num_pairs >= 1 && d->pair_src && d->pair_dst && d->pair_label && d->pair_split,
+               PGCN_E_INVALID, "link_decoder: pgcn_data has no pairs attached");
+    PGCN_CHECK(links_valid(n, d->num_pairs, d->pair_src, d->pair_dst, d->pair_label,
+                           d->pair_split),
+               PGCN_E_INVALID,
+               "link_decoder: endpoints in [0, num_nodes), labels -1 / 0 / 1, splits 0..3");
+    const size_t E = (size_t)d->num_pairs;
+    g.pair_src.assign(d->pair_src, d->pair_src + E);
+    g.pair_dst.assign(d->pair_dst, d->pair_dst + E);
+    g.pair_label.assign(d->pair_label, d->pair_label + E);
+    g.pair_split.assign(d->pair_split, d->pair_split + E);
   }
   return g;
 }
@@ -747,6 +772,75 @@ int pgcn_readout_bwd(const float *G_out, int ld_g, const int *graph_ptr, const i
   });
 }
 
+namespace {
+// widths and strides of the pair-score entries: `wide` strides span d columns, `one` strides one
+void check_link_dims(int d, std::initializer_list<int> wide, std::initializer_list<int> one) {
+  PGCN_CHECK(d >= 1 && d <= kLinkMaxWidth, PGCN_E_INVALID, "link_score: 1 <= d <= 128");
+  for (int ld : wide) PGCN_CHECK(ln_ld_ok(ld, d), PGCN_E_INVALID, "link_score: ld % 4 == 0, ld >= d");
+  for (int ld : one) PGCN_CHECK(ln_ld_ok(ld, 1), PGCN_E_INVALID, "link_score: ld % 4 == 0, ld >= 1");
+}
+}  // namespace
+
+int pgcn_links_create(int n_nodes, long long n_pairs, const int *src, const int *dst,
+                      const int *select, pgcn_links **out) {
+  return guarded([&] {
+    PGCN_CHECK(out, PGCN_E_INVALID, "links_create args");
+    validate_pairs(n_nodes, n_pairs, src, dst);
+    check_device();
+    auto h = std::make_unique<pgcn_links>();
+    h->l = std::make_unique<LinkIndexDev>(n_nodes, n_pairs, src, dst, select);
+    *out = h.release();
+  });
+}
+
+int pgcn_links_destroy(pgcn_links *l) {
+  delete l;
+  return PGCN_OK;
+}
+
+int pgcn_link_segment_slots(void) { return kGatSeg; }
+
+long long pgcn_links_slots(const pgcn_links *l) {
+  return l && l->l ? l->l->slots() : (long long)PGCN_E_INVALID;
+}
+
+int pgcn_link_score_fwd(const pgcn_links *l, const float *H, int ld_h, int d, float *scores,
+                        int ld_s, void *stream) {
+  return guarded([&] {
+    check_link_dims(d, {ld_h}, {ld_s});
+    PGCN_CHECK(l && l->l && H && scores && aligned16(H) && aligned16(scores), PGCN_E_INVALID,
+               "link_score_fwd: null or misaligned argument");
+    check_device();
+    launch_link_score_fwd(l->l->index(), H, ld_h, d, scores, ld_s, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_link_score_bwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *G,
+                        int ld_g, float *dH, int ld_dh, void *stream) {
+  return guarded([&] {
+    check_link_dims(d, {ld_h, ld_dh}, {ld_g});
+    PGCN_CHECK(l && l->l && H && G && dH && aligned16(H) && aligned16(G) && aligned16(dH),
+               PGCN_E_INVALID, "link_score_bwd: null or misaligned argument");
+    check_device();
+    launch_link_score_bwd(l->l->index(), H, ld_h, d, G, ld_g, dH, ld_dh, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, const int *dst,
+                               const int *select, int *ptr, int *pair, int *other) {
+  return guarded([&] {
+    PGCN_CHECK(ptr, PGCN_E_INVALID, "debug_links_incidence: ptr [n_nodes + 1] is required");
+    std::vector<int> p, e, o;
+    validate_pairs(n_nodes, n_pairs, src, dst);
+    build_incidence(n_nodes, n_pairs, src, dst, select, &p, &e, &o);
+    std::memcpy(ptr, p.data(), p.size() * sizeof(int));
+    if (pair && !e.empty()) std::memcpy(pair, e.data(), e.size() * sizeof(int));
+    if (other && !o.empty()) std::memcpy(other, o.data(), o.size() * sizeof(int));
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -843,6 +937,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->root_weight = 0;
   p->epochs = 100;
   p->readout = 0;
+  p->link_decoder = 0;
   p->early_stopping = 0;
   p->attention_heads = 1;
   p->attention_dropout = 0.0f;
@@ -1002,6 +1097,8 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "multilabel")) return e.get_params().multilabel ? 1 : 0;
   if (!std::strcmp(key, "readout")) return e.get_params().readout;
   if (!std::strcmp(key, "num_graphs")) return e.num_graphs();
+  if (!std::strcmp(key, "link_decoder")) return e.get_params().link_decoder;
+  if (!std::strcmp(key, "num_pairs")) return e.num_pairs();
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
@@ -1125,6 +1222,14 @@ int pgcn_checkpoint_readout(const char *path, int *mode, int *num_graphs) {
     *num_graphs = ck.num_graphs;
   });
 }
+int pgcn_checkpoint_links(const char *path, int *decoder, long long *num_pairs) {
+  return guarded([&] {
+    PGCN_CHECK(path && decoder && num_pairs, PGCN_E_INVALID, "checkpoint_links args");
+    const Checkpoint ck = read_checkpoint(path);
+    *decoder = ck.link_decoder;
+    *num_pairs = ck.num_pairs;
+  });
+}
 int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }
 long long pgcn_gcn_predict(pgcn_gcn *g, int *cls, float *conf, float *probs) {
   long long n = -1;
@@ -1152,6 +1257,27 @@ int pgcn_gcn_multilabel_counts(pgcn_gcn *g, int split, long long *counts) {
   return guarded([&] {
     PGCN_CHECK(g && counts, PGCN_E_INVALID, "gcn_multilabel_counts args");
     g->g->multilabel_counts(split, counts);
+  });
+}
+long long pgcn_gcn_predict_links(pgcn_gcn *g, float *scores, float *probs) {
+  long long n = -1;
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_predict_links: null engine");
+    n = g->g->predict_links(scores, probs);
+  });
+  return st == PGCN_OK ? n : st;
+}
+int pgcn_gcn_link_counts(pgcn_gcn *g, int split, long long *counts) {
+  return guarded([&] {
+    PGCN_CHECK(g && counts, PGCN_E_INVALID, "gcn_link_counts args");
+    g->g->link_counts(split, counts);
+  });
+}
+int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m,
+                         float *scores) {
+  return guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_score_pairs: null engine");
+    g->g->score_pairs(src, dst, m, scores);
   });
 }
 int pgcn_gcn_profile(pgcn_gcn *g, int enable) {
@@ -1244,6 +1370,12 @@ int pgcn_dataset_view(const pgcn_dataset *ds, pgcn_data *v, int *input_dim, int 
   v->graph_ptr = graphs ? ds->d.graph_ptr.data() : nullptr;
   v->graph_label = graphs ? ds->d.graph_label.data() : nullptr;
   v->graph_split = graphs ? ds->d.graph_split.data() : nullptr;
+  const bool pairs = !ds->d.pair_src.empty();
+  v->num_pairs = (int)ds->d.pair_src.size();
+  v->pair_src = pairs ? ds->d.pair_src.data() : nullptr;
+  v->pair_dst = pairs ? ds->d.pair_dst.data() : nullptr;
+  v->pair_label = pairs ? ds->d.pair_label.data() : nullptr;
+  v->pair_split = pairs ? ds->d.pair_split.data() : nullptr;
   if (input_dim) *input_dim = ds->d.input_dim;
   if (output_dim) *output_dim = ds->d.output_dim;
   return PGCN_OK;
@@ -1317,6 +1449,38 @@ int pgcn_dataset_load_graphs(pgcn_dataset *ds, const char *path, int num_classes
     ds->d.graph_label = std::move(label);
     ds->d.graph_split = std::move(split);
     ds->d.output_dim = c;
+  });
+}
+
+int pgcn_dataset_set_links(pgcn_dataset *ds, const int *src, const int *dst, const int *label,
+                           const int *split, long long E, int embed_dim) {
+  return guarded([&] {
+    PGCN_CHECK(ds && embed_dim >= 1 && embed_dim <= kLinkMaxWidth, PGCN_E_INVALID,
+               "dataset_set_links: 1 <= embed_dim <= 128");
+    PGCN_CHECK(links_valid(ds->d.num_nodes, E, src, dst, label, split), PGCN_E_INVALID,
+               "dataset_set_links: E >= 1 pairs, endpoints in [0, num_nodes), labels -1 / 0 / 1, "
+               "splits 0..3");
+    ds->d.pair_src.assign(src, src + E);
+    ds->d.pair_dst.assign(dst, dst + E);
+    ds->d.pair_label.assign(label, label + E);
+    ds->d.pair_split.assign(split, split + E);
+    ds->d.output_dim = embed_dim;
+  });
+}
+
+int pgcn_dataset_load_links(pgcn_dataset *ds, const char *path, int embed_dim) {
+  return guarded([&] {
+    PGCN_CHECK(ds && path && embed_dim >= 1 && embed_dim <= kLinkMaxWidth, PGCN_E_INVALID,
+               "dataset_load_links: 1 <= embed_dim <= 128");
+    std::vector<int> src, dst, label, split;
+    std::string why;
+    if (!read_links_file(path, ds->d.num_nodes, &src, &dst, &label, &split, &why))
+      throw Error(PGCN_E_IO, why);
+    ds->d.pair_src = std::move(src);
+    ds->d.pair_dst = std::move(dst);
+    ds->d.pair_label = std::move(label);
+    ds->d.pair_split = std::move(split);
+    ds->d.output_dim = embed_dim;
   });
 }
 

@@ -59,15 +59,36 @@ CkReadoutExt readout_ext(const Checkpoint &ck) {
   return CkReadoutExt{(uint32_t)ck.readout, (uint32_t)ck.num_graphs, 0};
 }
 
+// version 8: behind version 7's three blocks
+struct CkLinksExt {
+  uint32_t link_decoder, zero;
+  uint64_t num_pairs;
+};
+static_assert(sizeof(CkLinksExt) == 16, "checkpoint extension layout");
+
+CkLinksExt links_ext(const Checkpoint &ck) {
+  return CkLinksExt{(uint32_t)ck.link_decoder, 0, (uint64_t)ck.num_pairs};
+}
+
+// versions 7 and 8 carry the heads, SAGE and readout blocks whatever the layer family
+bool three_blocks(uint32_t version) {
+  return version == (uint32_t)kCheckpointVersionReadout ||
+         version == (uint32_t)kCheckpointVersionLinks;
+}
+
 uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
   uint64_t x = fnv1a(kFnvBasis, &h, offsetof(CkHeader, checksum));
-  if (h.version == (uint32_t)kCheckpointVersionReadout) {
+  if (three_blocks(h.version)) {
     const CkHeadsExt e = heads_ext(ck);
     const CkSageExt se = sage_ext(ck);
     const CkReadoutExt re = readout_ext(ck);
     x = fnv1a(x, &e, sizeof e);
     x = fnv1a(x, &se, sizeof se);
     x = fnv1a(x, &re, sizeof re);
+  }
+  if (h.version == (uint32_t)kCheckpointVersionLinks) {
+    const CkLinksExt le = links_ext(ck);
+    x = fnv1a(x, &le, sizeof le);
   }
   if (h.version == (uint32_t)kCheckpointVersionHeads) {
     const CkHeadsExt e = heads_ext(ck);
@@ -130,6 +151,11 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
            !((flags & kCheckpointAttention) && (flags & kCheckpointSage)) &&
            (flags & ~(kCheckpointResidual | kCheckpointLayerNorm | kCheckpointAttention |
                       kCheckpointSage | kCheckpointReadout)) == 0;
+  if (version == (uint32_t)kCheckpointVersionLinks)  // (never bits 2 or 5, or 3 with 4)
+    return (flags & kCheckpointLinks) &&
+           !((flags & kCheckpointAttention) && (flags & kCheckpointSage)) &&
+           (flags & ~(kCheckpointResidual | kCheckpointLayerNorm | kCheckpointAttention |
+                      kCheckpointSage | kCheckpointLinks)) == 0;
   return false;
 }
 
@@ -143,7 +169,7 @@ long long expected_weights(const int32_t *dims, int n_layers, uint32_t flags,
 // the extension's values against the file's version and hidden dims (the engine's own rules)
 bool heads_ok(uint32_t version, uint32_t flags, const int32_t *dims, int n_layers,
               long long heads, float p) {
-  const bool v7 = version == (uint32_t)kCheckpointVersionReadout && (flags & kCheckpointAttention);
+  const bool v7 = three_blocks(version) && (flags & kCheckpointAttention);
   if (version != (uint32_t)kCheckpointVersionHeads && !v7) return heads == 1 && p == 0.0f;
   if (heads < 1 || heads > 32 || !(p >= 0.0f && p < 1.0f) || (!v7 && heads == 1 && p == 0.0f))
     return false;
@@ -157,7 +183,7 @@ bool heads_ok(uint32_t version, uint32_t flags, const int32_t *dims, int n_layer
 // version 6's block against the file's version (the engine's own rules)
 bool sage_ok(uint32_t version, uint32_t flags, const int32_t *dims, int n_layers,
              long long aggregator, long long root_weight) {
-  const bool v7 = version == (uint32_t)kCheckpointVersionReadout && (flags & kCheckpointSage);
+  const bool v7 = three_blocks(version) && (flags & kCheckpointSage);
   if (version != (uint32_t)kCheckpointVersionSage && !v7)
     return aggregator == 0 && root_weight == 0;
   if (aggregator < 1 || aggregator > 2 || root_weight < 0 || root_weight > 1) return false;
@@ -170,6 +196,11 @@ bool readout_ok(uint32_t version, long long readout, long long num_graphs, long 
   if (version != (uint32_t)kCheckpointVersionReadout) return readout == 0 && num_graphs == 0;
   return readout >= 1 && readout <= 3 && num_graphs >= 1 && num_graphs < (1LL << 31) &&
          num_nodes >= 0;
+}
+// version 8's own block against the file's version
+bool links_ok(uint32_t version, long long decoder, long long num_pairs) {
+  if (version != (uint32_t)kCheckpointVersionLinks) return decoder == 0 && num_pairs == 0;
+  return decoder == 1 && num_pairs >= 1 && num_pairs < (1LL << 31);
 }
 }  // namespace
 
@@ -199,6 +230,8 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   h.n_weights = (int64_t)ck.w.size();
   PGCN_CHECK(readout_ok(h.version, ck.readout, ck.num_graphs, ck.num_nodes), PGCN_E_INVALID,
              "checkpoint: readout / graph count do not match the file's version");
+  PGCN_CHECK(links_ok(h.version, ck.link_decoder, ck.num_pairs), PGCN_E_INVALID,
+             "checkpoint: link decoder / pair count do not match the file's version");
   PGCN_CHECK(sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: aggregator / root weight do not match the file's version");
   PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight), PGCN_E_INVALID,
@@ -207,11 +240,13 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
              PGCN_E_INVALID,
              "checkpoint: heads / attention dropout do not match the file's version");
   const CkHeadsExt ext = heads_ext(ck);
-  const bool v7 = h.version == (uint32_t)kCheckpointVersionReadout;
+  const bool v7 = three_blocks(h.version);
+  const bool v8 = h.version == (uint32_t)kCheckpointVersionLinks;
   const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads || v7;
   const CkSageExt sext = sage_ext(ck);
   const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage || v7;
   const CkReadoutExt rext = readout_ext(ck);
+  const CkLinksExt lext = links_ext(ck);
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
   std::FILE *f = std::fopen(tmp.c_str(), "wb");
@@ -220,6 +255,7 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
             (!with_ext || std::fwrite(&ext, sizeof(ext), 1, f) == 1) &&
             (!with_sage || std::fwrite(&sext, sizeof(sext), 1, f) == 1) &&
             (!v7 || std::fwrite(&rext, sizeof(rext), 1, f) == 1) &&
+            (!v8 || std::fwrite(&lext, sizeof(lext), 1, f) == 1) &&
             write_floats(f, ck.results) &&
             write_floats(f, ck.w) && write_floats(f, ck.m) && write_floats(f, ck.v);
   ok = (std::fclose(f) == 0) && ok;
@@ -243,7 +279,7 @@ Checkpoint read_checkpoint(const std::string &path) {
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
        h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
        h.n_weights < (1LL << 31);
-  const bool v7 = ok && h.version == (uint32_t)kCheckpointVersionReadout;
+  const bool v7 = ok && three_blocks(h.version);
   if (ok && (h.version == (uint32_t)kCheckpointVersionHeads || v7)) {
     CkHeadsExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.heads <= 32;
@@ -264,7 +300,14 @@ Checkpoint read_checkpoint(const std::string &path) {
     ck.readout = (int)e.readout;
     ck.num_graphs = (int)e.num_graphs;
   }
-  ok = ok && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
+  if (ok && h.version == (uint32_t)kCheckpointVersionLinks) {
+    CkLinksExt e{};
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.link_decoder <= 1 &&
+         e.num_pairs < (1ull << 31);
+    ck.link_decoder = (int)e.link_decoder;
+    ck.num_pairs = (long long)e.num_pairs;
+  }
+  ok = ok && links_ok(h.version, ck.link_decoder, ck.num_pairs) && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
        sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight) &&
        readout_ok(h.version, ck.readout, ck.num_graphs, h.num_nodes) &&
        h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight);

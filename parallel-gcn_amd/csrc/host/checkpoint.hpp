@@ -45,8 +45,14 @@
 //   block  u32 readout (1 sum, 2 mean, 3 max); u32 num_graphs (>= 1); u64 0
 // The payload follows the flags as in versions 2, 4 and 6.  Every other engine keeps writing
 // versions 1-6 byte for byte.
+// Version 8 = saved by a link-prediction engine (pgcn_params.link_decoder != 0): flags bit 6
+// always set, bits 2 and 5 never, and four 16-byte blocks between the header and the payload:
+// version 7's three (the third all zero) and
+//   block  u32 link_decoder (1 dot product); u32 0; u64 num_pairs (>= 1)
+// The payload follows the flags as before (the decoder has no weights).  Every other engine keeps
+// writing versions 1-7 byte for byte.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (versions
-// 5 and 6; version 7's three blocks) and the payload.
+// 5 and 6; the blocks of versions 7 and 8) and the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
 // stored and the file does not depend on the world size.  Nothing newer than the reference:
@@ -71,6 +77,8 @@ constexpr unsigned kCheckpointSage = 16u;  // header flags, bit 4 (version 6 onl
 constexpr int kCheckpointVersionSage = 6;  // bits 0-2 and 4 known, bit 4 set, + its block
 constexpr unsigned kCheckpointReadout = 32u;  // header flags, bit 5 (version 7 only)
 constexpr int kCheckpointVersionReadout = 7;  // bits 0-5 known, bit 5 set, + three blocks
+constexpr unsigned kCheckpointLinks = 64u;  // header flags, bit 6 (version 8 only)
+constexpr int kCheckpointVersionLinks = 8;  // bit 6 set, + four blocks
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -89,6 +97,9 @@ struct Checkpoint {
   int aggregator = 0, root_weight = 0;
   // version 7's own block; 0 and 0 in every other version
   int readout = 0, num_graphs = 0;
+  // version 8's own block; 0 and 0 in every other version
+  int link_decoder = 0;
+  long long num_pairs = 0;
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

@@ -332,6 +332,63 @@ bool read_graphs_file(const std::string &path, int num_nodes, int num_classes,
   return true;
 }
 
+bool links_valid(int num_nodes, long long E, const int *src, const int *dst, const int *label,
+                 const int *split) {
+  if (E < 1 || E >= (1LL << 31) || !src || !dst || !label || !split) return false;
+  for (long long e = 0; e < E; e++)
+    if (src[e] < 0 || src[e] >= num_nodes || dst[e] < 0 || dst[e] >= num_nodes || label[e] < -1 ||
+        label[e] > 1 || split[e] < 0 || split[e] > 3)
+      return false;
+  return true;
+}
+
+bool read_links_file(const std::string &path, int num_nodes, std::vector<int> *src,
+                     std::vector<int> *dst, std::vector<int> *label, std::vector<int> *split,
+                     std::string *why) {
+  std::ifstream in(path);
+  if (!in) {
+    *why = "cannot open " + path;
+    return false;
+  }
+  src->clear();
+  dst->clear();
+  label->clear();
+  split->clear();
+  std::string line;
+  while (std::getline(in, line)) {
+    const std::string at = path + ": line " + std::to_string(src->size() + 1);
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;  // (a blank line)
+    std::istringstream ls(line);
+    long long s = 0, d = 0, lab = 0, sp = 0;
+    std::string rest;
+    if (!(ls >> s >> d >> lab >> sp) || (ls >> rest)) {
+      *why = at + ": expected `<src> <dst> <label> <split>`";
+      return false;
+    }
+    if (s < 0 || s >= num_nodes || d < 0 || d >= num_nodes) {
+      *why = at + ": endpoint out of range";
+      return false;
+    }
+    if (lab < -1 || lab > 1) {
+      *why = at + ": label must be -1, 0 or 1";
+      return false;
+    }
+    if (sp < 0 || sp > 3) {
+      *why = at + ": split must be 0..3";
+      return false;
+    }
+    src->push_back((int)s);
+    dst->push_back((int)d);
+    label->push_back((int)lab);
+    split->push_back((int)sp);
+  }
+  if (src->empty()) {
+    *why = path + ": no pair";
+    return false;
+  }
+  return true;
+}
+
 bool read_labels_file(const std::string &path, int num_nodes, int num_classes,
                       std::vector<uint32_t> *bits, int *words, int *classes, std::string *why) {
   std::ifstream in(path);

@@ -32,6 +32,9 @@ struct GCNData {
   // graph_label in [0, output_dim) or -1, graph_split 0..3 (GCNParams::readout)
   int num_graphs = 0;
   std::vector<int> graph_ptr, graph_label, graph_split;
+  // pair-level data for link prediction (empty: none): pair e = (pair_src[e], pair_dst[e]),
+  // pair_label 1 / 0 / -1 (unlabelled), pair_split 0..3 (GCNParams::link_decoder)
+  std::vector<int> pair_src, pair_dst, pair_label, pair_split;
 };
 
 class Parser {
@@ -92,6 +95,17 @@ bool read_graphs_file(const std::string &path, int num_nodes, int num_classes,
 // [-1, classes), splits in 0..3
 bool graphs_valid(int num_nodes, int G, const int *ptr, const int *label, const int *split,
                   int classes);
+
+// Link-prediction sidecar file: line e = `<src> <dst> <label> <split>`.  Fills the four arrays;
+// false (with *why) for a missing file, a line that is not four integers, an endpoint outside
+// [0, num_nodes), a label outside {-1, 0, 1}, a split outside 0..3, no pair at all.
+bool read_links_file(const std::string &path, int num_nodes, std::vector<int> *src,
+                     std::vector<int> *dst, std::vector<int> *label, std::vector<int> *split,
+                     std::string *why);
+// pair arrays as GCNData holds them: E >= 1 pairs within an int, endpoints in [0, num_nodes),
+// labels in {-1, 0, 1}, splits in 0..3
+bool links_valid(int num_nodes, long long E, const int *src, const int *dst, const int *label,
+                 const int *split);
 
 // True when every row lists all features 0..F-1 in order (a dense matrix in CSR form).
 bool features_dense(const GCNData &d);

@@ -336,6 +336,32 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
     num_graphs_ = data.num_graphs;
     graph_ptr_host = data.graph_ptr;
   }
+  PGCN_CHECK(params.link_decoder == 0 || params.link_decoder == 1, PGCN_E_INVALID,
+             "link_decoder must be 0 (none) or 1 (dot product)");
+  if (params.link_decoder) {
+    PGCN_CHECK(!params.multilabel, PGCN_E_INVALID,
+               "link_decoder cannot be combined with multilabel");
+    PGCN_CHECK(!params.readout, PGCN_E_INVALID, "link_decoder cannot be combined with readout");
+    PGCN_CHECK(!dist, PGCN_E_INVALID,
+               "link_decoder: single GPU only (edge-cut link prediction is not supported)");
+    PGCN_CHECK(params.output_dim >= 1 && params.output_dim <= kLinkMaxWidth, PGCN_E_INVALID,
+               "link_decoder: output_dim (the embedding width) up to 128");
+    const size_t E = data.pair_src.size();
+    PGCN_CHECK(data.pair_dst.size() == E && data.pair_label.size() == E &&
+                   data.pair_split.size() == E &&
+                   links_valid(data.num_nodes, (long long)E, data.pair_src.data(),
+                               data.pair_dst.data(), data.pair_label.data(),
+                               data.pair_split.data()),
+               PGCN_E_INVALID, "link_decoder: the data has no (valid) pairs attached");
+    // the float pipeline behind the loss is exact up to 2^24 (the multilabel rule)
+    long long labelled[4] = {0, 0, 0, 0};
+    for (size_t e = 0; e < E; e++)
+      if (data.pair_label[e] >= 0) labelled[data.pair_split[e]]++;
+    for (int s = 1; s <= 3; s++)
+      PGCN_CHECK(labelled[s] <= (1LL << 24), PGCN_E_INVALID,
+                 "link_decoder: the labelled pairs of a split must not exceed 2^24");
+    num_pairs_ = (int)E;
+  }
   int lo_prio = 0, hi_prio = 0;
   PGCN_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
   stream = Stream::create(hi_prio);  // the reference uses High priority streams
@@ -573,7 +599,32 @@ void GCN::build(const GCNData &data) {
     truth_compact[s].allocate(1);
     counts[s] = c;
   }
-  for (int s = 1; !params.readout && s <= 3; s++) {
+  for (int s = 1; params.link_decoder && s <= 3; s++) {  // per pair: the split's labelled pairs
+    std::vector<int> t((size_t)num_pairs_, -1);
+    int c = 0;
+    for (int e = 0; e < num_pairs_; e++)
+      if (data.pair_split[(size_t)e] == s && data.pair_label[(size_t)e] >= 0) {
+        t[(size_t)e] = data.pair_label[(size_t)e];
+        c++;
+      }
+    truth[s].allocate(t.size());
+    truth[s].upload(t);
+    truth_compact[s].allocate(1);
+    counts[s] = c;
+    if (s == 1)  // (the only split that runs a backward; host work, outside any capture)
+      links_ = std::make_unique<LinkIndexDev>(N, num_pairs_, data.pair_src.data(),
+                                              data.pair_dst.data(), t.data());
+  }
+  if (params.link_decoder) {  // the one-class bit matrix [E][1]: bit 0 = the pair is a link
+    std::vector<uint32_t> b((size_t)num_pairs_, 0u);
+    for (int e = 0; e < num_pairs_; e++) b[(size_t)e] = data.pair_label[(size_t)e] == 1 ? 1u : 0u;
+    label_bits.allocate(b.size());
+    label_bits.upload(b);
+    label_words = 1;
+    ctx.label_bits = label_bits.get();
+    ctx.label_words = 1;
+  }
+  for (int s = 1; !head_rows() && s <= 3; s++) {
     std::vector<int> t((size_t)prow, -1);
     for (int i = 0; i < rows; i++)
       t[(size_t)i] = data.split[(size_t)first + i] == s ? data.label[(size_t)first + i] : -1;
@@ -677,7 +728,7 @@ void GCN::build(const GCNData &data) {
   init_dropout_rng(data, wtotal + atotal);
 
   // context buffers
-  xent_partials.allocate((size_t)xent_blocks(std::max(prow, num_graphs_)) * 2 + 2);
+  xent_partials.allocate((size_t)xent_blocks(std::max(prow, head_rows())) * 2 + 2);
   sums.allocate(4);
   results_ring.allocate((size_t)ring_cap * 4);
   results_ring.zero();
@@ -727,6 +778,7 @@ void GCN::build(const GCNData &data) {
     weights.push_back(attn_var);
     decays.push_back(false);
   }
+  if (link_scores) variables.push_back(link_scores);  // (a link engine's last variable)
   // (edge-cut: the tails run in k_gs_finish on the rank's rows after the reduce-scatter)
   if (knobs_.fuse_epilogue & kFuseTails) fuse_epilogues();
   if (knobs_.fuse_epilogue & kFuseMatmulTails) fuse_matmul_tails();
@@ -734,7 +786,7 @@ void GCN::build(const GCNData &data) {
       dropouts_[0] && dropouts_[1])
     const_cast<Dropout *>(dropouts_[0])->co_draw = dropouts_[1];
   // (multilabel: the output Matmul runs on its own, the `fuse_output 0` path)
-  if (knobs_.fuse_output && !params.multilabel && !params.readout) fuse_output_layer();
+  if (knobs_.fuse_output && !params.multilabel && !head_rows()) fuse_output_layer();
   optimizer = Adam(weights, decays, adam_params);
   prepare_graphs();
   build_eval_ax();
@@ -1073,6 +1125,13 @@ void GCN::insert_last_layer() {
     pooled = std::make_shared<Variable>(num_graphs_, C, true, round_up4(C));
     modules.push_back(std::make_unique<Readout>(out, pooled, graph_ptr_host, C, params.readout));
     modules.push_back(std::make_unique<CrossEntropyLoss>(pooled, C, &ctx));
+    return;
+  }
+  if (params.link_decoder) {  // node embedding -> scores [E][4] -> the one-class loss over the pairs
+    link_embed = out;
+    link_scores = std::make_shared<Variable>(num_pairs_, 1, true, 4);
+    modules.push_back(std::make_unique<LinkDecoder>(out, link_scores, links_.get(), C));
+    modules.push_back(std::make_unique<BCEWithLogitsLoss>(link_scores, 1, &ctx));
     return;
   }
   if (params.multilabel) modules.push_back(std::make_unique<BCEWithLogitsLoss>(out, C, &ctx));
@@ -1724,6 +1783,14 @@ void GCN::save(const std::string &path) {
     ck.readout = params.readout;
     ck.num_graphs = num_graphs_;
   }
+  if (params.link_decoder) {  // version 8: version 7's blocks (no readout) and its own
+    ck.flags |= kCheckpointLinks;
+    ck.version = kCheckpointVersionLinks;
+    ck.heads = params.attention_heads;
+    ck.attention_dropout = params.attention_dropout;
+    ck.link_decoder = params.link_decoder;
+    ck.num_pairs = num_pairs_;
+  }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1749,6 +1816,8 @@ void GCN::load(const std::string &path, int flags) {
   // (the pooled loss is another model: neither kind of load crosses the mode or the graph count)
   same = same && ck.readout == params.readout && ck.num_graphs == num_graphs_;
   if (same && resume) same = ck.aggregator == params.aggregator;
+  // (a weights-only load crosses the link decoder: it has no weights, the tensors are the same)
+  if (same && resume) same = ck.link_decoder == params.link_decoder && ck.num_pairs == num_pairs_;
   if (same && resume) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
     // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)
@@ -1823,6 +1892,8 @@ void GCN::predict_forward() {
 }
 
 long long GCN::predict(int *cls, float *conf, float *probs) {
+  PGCN_CHECK(!params.link_decoder, PGCN_E_INVALID,
+             "predict: a link engine has per-pair scores (predict_links)");
   const auto *ce = dynamic_cast<const CrossEntropyLoss *>(modules.back().get());
   PGCN_CHECK(ce, PGCN_E_INVALID, "predict: no output layer");
   const Variable &z = *ce->input();
@@ -1850,7 +1921,8 @@ long long GCN::predict(int *cls, float *conf, float *probs) {
 
 long long GCN::predict_multilabel(uint32_t *bits, float *probs) {
   const auto *bl = dynamic_cast<const BCEWithLogitsLoss *>(modules.back().get());
-  PGCN_CHECK(bl, PGCN_E_INVALID, "predict_multilabel: not a multi-label engine");
+  PGCN_CHECK(bl && params.multilabel, PGCN_E_INVALID,
+             "predict_multilabel: not a multi-label engine");
   const Variable &z = *bl->input();
   const int n = part.local_rows(), C = params.output_dim, ldp = round_up4(C), W = label_words;
   if (!pred_bits) pred_bits.allocate((size_t)std::max(part.maxrows, 1) * W);
@@ -1883,10 +1955,68 @@ void GCN::multilabel_counts(int split, long long *counts) {
   for (size_t i = 0; i < h.size(); i++) counts[i] = (long long)h[i];
 }
 
+long long GCN::predict_links(float *scores, float *probs) {
+  PGCN_CHECK(params.link_decoder && link_scores, PGCN_E_INVALID,
+             "predict_links: not a link engine");
+  const Variable &z = *link_scores;
+  const int n = num_pairs_, ldp = 4;
+  if (!pred_bits) pred_bits.allocate((size_t)n);
+  if (probs && !pred_probs) pred_probs.allocate((size_t)n * ldp);
+  predict_forward();
+  launch_predict_multilabel(z.dev_data.get(), z.ld, n, 1, pred_bits.get(), 1,
+                            probs ? pred_probs.get() : nullptr, ldp, stream.get());
+  sync();
+  std::vector<float> raw;
+  if (scores) {
+    raw.resize((size_t)n * z.ld);
+    z.dev_data.download(raw.data(), raw.size());
+    for (int e = 0; e < n; e++) scores[e] = raw[(size_t)e * z.ld];
+  }
+  if (probs) {
+    raw.resize((size_t)n * ldp);
+    pred_probs.download(raw.data(), raw.size());
+    for (int e = 0; e < n; e++) probs[e] = raw[(size_t)e * ldp];
+  }
+  return n;
+}
+
+void GCN::link_counts(int split, long long *counts) {
+  PGCN_CHECK(split >= 1 && split <= 3 && counts, PGCN_E_INVALID, "link_counts: split 1, 2 or 3");
+  predict_links(nullptr, nullptr);
+  if (!pred_counts) pred_counts.allocate(3);
+  launch_multilabel_counts(pred_bits.get(), label_bits.get(), truth[split].get(), num_pairs_, 1, 1,
+                           pred_counts.get(), stream.get());
+  sync();
+  unsigned h[3];
+  pred_counts.download(h, 3);
+  for (int i = 0; i < 3; i++) counts[i] = (long long)h[i];
+}
+
+void GCN::score_pairs(const int *src, const int *dst, long long m, float *scores) {
+  PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "score_pairs: not a link engine");
+  PGCN_CHECK(m >= 0 && (m == 0 || (src && dst && scores)), PGCN_E_INVALID, "score_pairs args");
+  if (m == 0) return;
+  validate_pairs(params.num_nodes, m, src, dst);
+  // (a temporary index with no backward entries, built before anything is enqueued)
+  std::vector<int> none((size_t)m, -1);
+  const LinkIndexDev tmp(params.num_nodes, m, src, dst, none.data());
+  DeviceBuffer<float> out((size_t)m * 4);
+  predict_forward();
+  const Variable &h = *link_embed;
+  launch_link_score_fwd(tmp.index(), h.dev_data.get(), h.ld, params.output_dim, out.get(), 4,
+                        stream.get());
+  sync();
+  std::vector<float> raw((size_t)m * 4);
+  out.download(raw.data(), raw.size());
+  for (long long e = 0; e < m; e++) scores[e] = raw[(size_t)e * 4];
+}
+
 void GCN::confusion(int split, long long *counts) {
   PGCN_CHECK(split >= 1 && split <= 3 && counts, PGCN_E_INVALID, "confusion: split 1, 2 or 3");
   PGCN_CHECK(!params.multilabel, PGCN_E_INVALID,
              "confusion: a multi-label engine has per-class counts (multilabel_counts)");
+  PGCN_CHECK(!params.link_decoder, PGCN_E_INVALID,
+             "confusion: a link engine has per-pair counts (link_counts)");
   const int C = params.output_dim;
   predict(nullptr, nullptr, nullptr);
   if (!pred_counts) pred_counts.allocate((size_t)C * C);

@@ -64,6 +64,10 @@ struct GCNParams {
   // output layer's node logits and the loss, which then runs over GCNData::num_graphs rows with
   // the graphs' labels and splits.  Single GPU, not with multilabel
   int readout = 0;
+  // link prediction: 1 dot product -- a LinkDecoder module (module.hpp) between the output
+  // layer's node embedding and a one-class BCEWithLogitsLoss over GCNData's pairs with their
+  // labels and splits.  Single GPU, not with multilabel or readout
+  int link_decoder = 0;
 };
 
 struct AdamParams {
@@ -159,6 +163,12 @@ class GCN {
   // labels: counts [3][C] = tp, fp, fn of this rank's rows
   long long predict_multilabel(uint32_t *bits, float *probs);
   void multilabel_counts(int split, long long *counts);
+  // link engines: predict()'s forward, then the pairs' scores and sigmoids (either may be null);
+  // k_multilabel_counts with one class against `split`'s labelled pairs: counts[3] = tp, fp, fn;
+  // and the same forward followed by launch_link_score_fwd over m caller-given pairs
+  long long predict_links(float *scores, float *probs);
+  void link_counts(int split, long long *counts);
+  void score_pairs(const int *src, const int *dst, long long m, float *scores);
   long long adam_steps() const { return optimizer.steps(); }
   void set_profile(bool on);
   void profile_read_mm(double *ms, long long *calls, double *flops);  // XW contractions
@@ -187,6 +197,7 @@ class GCN {
   int attention_dropout_layers() const { return (int)attn_rngs.size(); }
   int aggregator() const { return params.aggregator; }
   int num_graphs() const { return num_graphs_; }
+  long long num_pairs() const { return num_pairs_; }
   bool root_weight() const { return params.root_weight; }
   // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
   int fused_norm_tails() const;
@@ -233,17 +244,25 @@ class GCN {
   // an engine whose aggregation is not a GraphSum module: no reassociated output layer, no Â X
   // precompute, no output-row restriction, the loss unfused
   bool custom_aggregation() const { return params.attention || params.aggregator != 0; }
-  // readout: every node row carries gradient, so nothing may rely on only a split's labelled rows
+  // readout, link_decoder: every node row carries gradient, so nothing may rely on only a split's labelled rows
   // mattering -- no reassociated output layer, no output-row restriction or compact buffers, no
   // column-subset backward, the loss unfused
-  bool all_rows_matter() const { return custom_aggregation() || params.readout != 0; }
+  bool all_rows_matter() const {
+    return custom_aggregation() || params.readout != 0 || params.link_decoder != 0;
+  }
   // readout: the graphs (0: none), their row ranges, and the pooled logits the loss reads
   int num_graphs_ = 0;
   std::vector<int> graph_ptr_host;
   shared_ptr<Variable> pooled;
   // the rows the loss, predict() and confusion() run over: the graphs, or this rank's nodes
-  int loss_rows() const { return params.readout ? num_graphs_ : part.local_rows(); }
-  int loss_prow() const { return params.readout ? num_graphs_ : part.maxrows; }
+  int loss_rows() const { return head_rows() ? head_rows() : part.local_rows(); }
+  int loss_prow() const { return head_rows() ? head_rows() : part.maxrows; }
+  int head_rows() const { return params.readout ? num_graphs_ : num_pairs_; }
+  // link_decoder: the pairs (0: none), their index on the device (its backward entries: the
+  // training split's labelled pairs), the node embedding the decoder reads and its scores [E][4]
+  int num_pairs_ = 0;
+  std::unique_ptr<LinkIndexDev> links_;
+  shared_ptr<Variable> link_embed, link_scores;
   // the layer's aggregation from var1 to var2: a GraphSum, a GraphAttention on attn_var or a
   // SageAggregate
   void insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,

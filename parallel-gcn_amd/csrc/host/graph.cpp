@@ -4,6 +4,7 @@
 #include <atomic>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <functional>
 #include <numeric>
@@ -750,6 +751,77 @@ const SageWs &DevGraph::sage_ws() {
   s->w.col_ws = s->col_ws.get();
   sage_ = std::move(s);
   return sage_->w;
+}
+
+void validate_pairs(int n, long long n_pairs, const int *src, const int *dst) {
+  PGCN_CHECK(n >= 0 && n_pairs >= 0 && n_pairs <= INT_MAX && (n_pairs == 0 || (src && dst)),
+             PGCN_E_INVALID, "links: n >= 0, 0 <= n_pairs within an int, src and dst");
+  for (long long e = 0; e < n_pairs; e++)
+    PGCN_CHECK(src[e] >= 0 && src[e] < n && dst[e] >= 0 && dst[e] < n, PGCN_E_INVALID,
+               "links: endpoint out of range");
+}
+
+void build_incidence(int n, long long n_pairs, const int *src, const int *dst, const int *select,
+                     std::vector<int> *ptr, std::vector<int> *pair, std::vector<int> *other) {
+  long long selected = 0;
+  for (long long e = 0; e < n_pairs; e++)
+    if (!select || select[e] >= 0) selected++;
+  PGCN_CHECK(selected < (1LL << 30), PGCN_E_INVALID,
+             "links: the incidence entries (2 per selected pair) must fit an int");
+  ptr->assign((size_t)n + 1, 0);
+  for (long long e = 0; e < n_pairs; e++)
+    if (!select || select[e] >= 0) {
+      (*ptr)[(size_t)src[e] + 1]++;
+      (*ptr)[(size_t)dst[e] + 1]++;
+    }
+  for (int i = 0; i < n; i++) (*ptr)[(size_t)i + 1] += (*ptr)[(size_t)i];
+  pair->assign((size_t)(2 * selected), 0);
+  other->assign((size_t)(2 * selected), 0);
+  std::vector<int> fill(ptr->begin(), ptr->end() - 1);
+  for (long long e = 0; e < n_pairs; e++)
+    if (!select || select[e] >= 0) {
+      int o = fill[(size_t)src[e]]++;  // the src role first: a self pair's two entries in a row
+      (*pair)[(size_t)o] = (int)e;
+      (*other)[(size_t)o] = dst[e];
+      o = fill[(size_t)dst[e]]++;
+      (*pair)[(size_t)o] = (int)e;
+      (*other)[(size_t)o] = src[e];
+    }
+}
+
+LinkIndexDev::LinkIndexDev(int n, long long n_pairs, const int *src, const int *dst,
+                           const int *select) {
+  std::vector<int> ptr, pair, other;
+  build_incidence(n, n_pairs, src, dst, select, &ptr, &pair, &other);
+  std::vector<int4> segs;
+  std::vector<int2> longs;
+  gat_segments(n, ptr, &segs, &longs);
+  auto up = [](auto &buf, const auto *host, size_t count) {
+    buf.allocate(std::max<size_t>(count, 1));
+    if (count) buf.upload(host, count);
+  };
+  up(src_, src, (size_t)n_pairs);
+  up(dst_, dst, (size_t)n_pairs);
+  up(ptr_, ptr.data(), ptr.size());
+  up(pair_, pair.data(), pair.size());
+  up(other_, other.data(), other.size());
+  up(segs_, segs.data(), segs.size());
+  up(longs_, longs.data(), longs.size());
+  ws_.allocate(std::max<size_t>(segs.size() * kLinkWsStride, 4));
+  ws_.zero();
+  slots_ = (long long)pair.size();
+  l_.n = n;
+  l_.n_pairs = n_pairs;
+  l_.src = src_.get();
+  l_.dst = dst_.get();
+  l_.inc_ptr = ptr_.get();
+  l_.inc_pair = pair_.get();
+  l_.inc_other = other_.get();
+  l_.n_segs = (int)segs.size();
+  l_.n_long = (int)longs.size();
+  l_.segs = segs_.get();
+  l_.longs = longs_.get();
+  l_.ws = ws_.get();
 }
 
 double DevGraph::algorithmic_bytes(int dim) const {

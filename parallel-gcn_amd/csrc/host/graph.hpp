@@ -222,4 +222,37 @@ class DevGraph {
   std::map<int, std::unique_ptr<Sched>> scheds_;
 };
 
+// A pair list as the link kernels take it: PGCN_E_INVALID for an endpoint outside [0, n), a pair
+// count beyond an int or null arrays.  Host only.
+void validate_pairs(int n, long long n_pairs, const int *src, const int *dst);
+
+// Link prediction's incidence index on the host (no device), of a list validate_pairs accepted:
+// over the pairs e with select null or select[e] >= 0, node i's entries ptr[i] .. ptr[i + 1] are
+// {pair, other endpoint} in ascending pair order, a pair's src role before its dst role -- a self
+// pair gives two consecutive entries, a duplicated pair counts as often as it is listed.
+// PGCN_E_INVALID for entries beyond an int.
+void build_incidence(int n, long long n_pairs, const int *src, const int *dst, const int *select,
+                     std::vector<int> *ptr, std::vector<int> *pair, std::vector<int> *other);
+
+// A pair list on the device for k_link.hip: the endpoints of every pair, the incidence index of
+// the selected ones and the segment records of the nodes above kGatSeg entries (the records
+// DevGraph::gat_pattern builds for its long columns).  The backward's segment partials live here,
+// so two backward calls on one index must not overlap.  Construction is host work and blocking
+// copies: not inside a stream capture.  The list is one validate_pairs accepted (the caller's
+// check, made once: the C entry, the engine's build, score_pairs).
+class LinkIndexDev {
+ public:
+  LinkIndexDev(int n, long long n_pairs, const int *src, const int *dst, const int *select);
+  const LinkIndex &index() const { return l_; }
+  long long slots() const { return slots_; }
+
+ private:
+  LinkIndex l_;
+  long long slots_ = 0;
+  DeviceBuffer<int> src_, dst_, ptr_, pair_, other_;
+  DeviceBuffer<int4> segs_;
+  DeviceBuffer<int2> longs_;
+  DeviceBuffer<float> ws_;
+};
+
 }  // namespace pgcn

@@ -857,6 +857,29 @@ void Readout::backward(const Stream &s) const {
 }
 
 // ------------------------------------------------------------------------------------------
+// LinkDecoder (k_link.hip)
+// ------------------------------------------------------------------------------------------
+LinkDecoder::LinkDecoder(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
+                         const LinkIndexDev *links_, int dim_)
+    : in(std::move(in_)), out(std::move(out_)), links(links_), dim(dim_) {
+  PGCN_CHECK(in && out && links && dim >= 1 && dim <= kLinkMaxWidth && in->cols == dim &&
+                 in->rows >= links->index().n && in->ld % 4 == 0 && out->cols == 1 &&
+                 out->ld % 4 == 0 && out->ld >= 4 && out->rows >= links->index().n_pairs,
+             PGCN_E_INVALID, "link decoder: embedding width up to 128, scores [pairs][4]");
+}
+
+void LinkDecoder::forward(bool, const Stream &s) const {
+  launch_link_score_fwd(links->index(), in->dev_data.get(), in->ld, dim, out->dev_data.get(),
+                        out->ld, s.get());
+}
+
+void LinkDecoder::backward(const Stream &s) const {
+  if (!in->dev_grad || !out->dev_grad) return;
+  launch_link_score_bwd(links->index(), in->dev_data.get(), in->ld, dim, out->dev_grad.get(),
+                        out->ld, in->dev_grad.get(), in->ld, s.get());
+}
+
+// ------------------------------------------------------------------------------------------
 // ReLU (src/module.cu:215-265)
 // ------------------------------------------------------------------------------------------
 ReLU::ReLU(shared_ptr<Variable> in_) : in(std::move(in_)) {

@@ -434,6 +434,25 @@ class Readout : public Module {
   void backward(const Stream &s) const override;
 };
 
+// Link prediction's decoder behind the output layer (the reference has none): `in` [n][dim] is
+// the node embedding, out [E][4] = {H[src_e] . H[dst_e], 0, 0, 0} per pair of `links`
+// (launch_link_score_fwd, one launch).  The backward reads out->dev_grad -- the loss's gradient per
+// pair in column 0 -- and writes every row of in->dev_grad (launch_link_score_bwd) over the pairs
+// `links` selected for it.  No weights, nothing drawn from the dropout stream.  Single GPU only.
+class LinkDecoder : public Module {
+  shared_ptr<Variable> in, out;
+  const LinkIndexDev *links;  // owned by the engine
+  int dim;
+
+ public:
+  LinkDecoder(shared_ptr<Variable> in_, shared_ptr<Variable> out_, const LinkIndexDev *links_,
+              int dim_);
+  const Variable *input() const { return in.get(); }
+  const Variable *output() const { return out.get(); }
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+};
+
 // include/module.cuh:90-99
 class ReLU : public Module {
   shared_ptr<Variable> in;

@@ -16,7 +16,7 @@ enum KernelPath {
   KP_XS_NN_RING, KP_XS_TN_RING, KP_XS_NN, KP_XS_TN, KP_GS_RING, KP_GS_GATHER, KP_OUT_XENT,
   KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS,
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
-  KP_SPMM_TREE_1024, KP_LAUNCHES, KP_COUNT
+  KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -447,6 +447,33 @@ void launch_readout_fwd(const float *in, int ld_in, const int *graph_ptr, int G,
 void launch_readout_bwd(const float *Gout, int ld_g, const int *graph_ptr, const int *node_graph,
                         const int *arg, int ld_arg, int G, int n, int d, int mode, float *din,
                         int ld_din, hipStream_t s);
+// ---- link prediction: pair scores over a node variable (k_link.hip) ---------------------------
+// The pair index on the device (LinkIndexDev, host/graph.hpp): the endpoints of every pair and the
+// incidence index of the selected ones -- node i's entries inc_ptr[i] .. inc_ptr[i + 1], each
+// {inc_pair: the pair, inc_other: its other endpoint}, in ascending pair order, a pair's src role
+// before its dst role -- with the segment lists of the nodes whose entries exceed kGatSeg: segs
+// {node, begin, end, the node's first segment}, longs {node, its first segment}.
+constexpr int kLinkMaxWidth = kSageMaxWidth;
+constexpr int kLinkWsStride = kLinkMaxWidth;
+struct LinkIndex {
+  int n = 0;
+  long long n_pairs = 0;
+  const int *src = nullptr, *dst = nullptr;
+  const int *inc_ptr = nullptr, *inc_pair = nullptr, *inc_other = nullptr;
+  int n_segs = 0, n_long = 0;
+  const int4 *segs = nullptr;
+  const int2 *longs = nullptr;
+  float *ws = nullptr;  // backward: [n_segs][kLinkWsStride] the segments' partial rows
+};
+// scores[e][0..3] = {H[src_e] . H[dst_e] over d columns, 0, 0, 0}: GL lanes per pair, the lanes'
+// float4 products summed by xor butterflies over the offsets 1 .. GL / 2 (a fixed order)
+void launch_link_score_fwd(const LinkIndex &l, const float *H, int ld_h, int d, float *scores,
+                           int ld_s, hipStream_t s);
+// dH_i = sum over node i's entries (e, o) of G[e][0] * H[o], every row written (zero without
+// entries, zero in [d, round_up4(d))); a wave per node, the nodes above kGatSeg entries through
+// their segments' partials in l.ws and a second launch that adds them in segment order
+void launch_link_score_bwd(const LinkIndex &l, const float *H, int ld_h, int d, const float *G,
+                           int ld_g, float *dH, int ld_dh, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D>] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -28,6 +28,11 @@
 // pgcn_params.readout -- the nodes are a batch of graphs read from the sidecar file
 // data/<name>.graphs (line g: `<rows> <label> <split>`), loss and accuracy are per graph, and
 // predict= writes one line `graph class confidence` per graph.
+// link=dot (or 1) [embed=<D>, default 32] (command line or parameter file): link prediction,
+// pgcn_params.link_decoder -- the pairs come from the sidecar file data/<name>.links (line e:
+// `<src> <dst> <label> <split>`), the output layer is a D-wide node embedding, loss and accuracy
+// are per pair, and predict= writes one line `src dst score probability` per pair.  The adjacency
+// is used as loaded: keep validation and test positives out of it.
 #include <algorithm>
 #include <vector>
 #include <cstdio>
@@ -65,7 +70,16 @@ static int readout_id(const std::string &v) {
   return (end && *end == '\0' && !v.empty()) ? (int)x : -1;
 }
 
-static bool load_params(const char *path, pgcn_params *p) {
+// link=: dot by name or 0 / 1; anything else is left for the engine to refuse
+static int link_id(const std::string &v) {
+  if (v == "dot") return 1;
+  if (v == "none") return 0;
+  char *end = nullptr;
+  const long x = std::strtol(v.c_str(), &end, 10);
+  return (end && *end == '\0' && !v.empty()) ? (int)x : -1;
+}
+
+static bool load_params(const char *path, pgcn_params *p, int *embed) {
   std::ifstream f(path);
   if (!f.is_open()) return false;
   std::string line;
@@ -107,6 +121,8 @@ static bool load_params(const char *path, pgcn_params *p) {
     else if (k == "aggregator") p->aggregator = aggregator_id(v);
     else if (k == "root_weight") p->root_weight = std::atoi(v.c_str());
     else if (k == "readout") p->readout = readout_id(v);
+    else if (k == "link") p->link_decoder = link_id(v);
+    else if (k == "embed") *embed = std::atoi(v.c_str());
   }
   return true;
 }
@@ -124,7 +140,8 @@ int main(int argc, char **argv) {
   int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
   int root_weight = -1;
-  std::string aggregator, readout;
+  std::string aggregator, readout, link;
+  int embed = 32, embed_arg = -1;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -144,10 +161,12 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "aggregator=", 11)) aggregator = argv[i] + 11;
     if (!std::strncmp(argv[i], "root_weight=", 12)) root_weight = std::atoi(argv[i] + 12);
     if (!std::strncmp(argv[i], "readout=", 8)) readout = argv[i] + 8;
+    if (!std::strncmp(argv[i], "link=", 5)) link = argv[i] + 5;
+    if (!std::strncmp(argv[i], "embed=", 6)) embed_arg = std::atoi(argv[i] + 6);
   }
   pgcn_params p;
   pgcn_params_default(&p);
-  if (!file.empty() && !load_params(file.c_str(), &p)) {
+  if (!file.empty() && !load_params(file.c_str(), &p, &embed)) {
     fprintf(stderr, "cannot read parameter file %s\n", file.c_str());
     return EXIT_FAILURE;
   }
@@ -161,6 +180,8 @@ int main(int argc, char **argv) {
   if (!aggregator.empty()) p.aggregator = aggregator_id(aggregator);
   if (root_weight >= 0) p.root_weight = root_weight;
   if (!readout.empty()) p.readout = readout_id(readout);
+  if (!link.empty()) p.link_decoder = link_id(link);
+  if (embed_arg >= 0) embed = embed_arg;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
                         : pgcn_dataset_load(root.c_str(), name, &ds);
@@ -180,6 +201,13 @@ int main(int argc, char **argv) {
     const std::string graphs = root + "/data/" + name + ".graphs";
     if (pgcn_dataset_load_graphs(ds, graphs.c_str(), 0) != PGCN_OK) {
       fprintf(stderr, "Cannot read graphs: %s\n", graphs.c_str());
+      return EXIT_FAILURE;
+    }
+  }
+  if (p.link_decoder) {
+    const std::string links = root + "/data/" + name + ".links";
+    if (pgcn_dataset_load_links(ds, links.c_str(), embed) != PGCN_OK) {
+      fprintf(stderr, "Cannot read links: %s (embed=%d)\n", links.c_str(), embed);
       return EXIT_FAILURE;
     }
   }
@@ -214,6 +242,19 @@ int main(int argc, char **argv) {
           if ((bits[(size_t)i * words + j / 32] >> (j % 32)) & 1u) fprintf(f, " %d", j);
         fprintf(f, "\n");
       }
+      std::fclose(f);
+    }
+  } else if (st == PGCN_OK && !predict.empty() && p.link_decoder) {
+    std::vector<float> score((size_t)view.num_pairs), prob((size_t)view.num_pairs);
+    const long long n = pgcn_gcn_predict_links(g, score.data(), prob.data());
+    FILE *f = n >= 0 ? std::fopen(predict.c_str(), "w") : nullptr;
+    if (!f) {
+      fprintf(stderr, "cannot write predictions to %s\n", predict.c_str());
+      st = n < 0 ? (int)n : PGCN_E_IO;
+    } else {
+      for (long long e = 0; e < n; e++)
+        fprintf(f, "%d %d %.6f %.6f\n", view.pair_src[e], view.pair_dst[e], score[(size_t)e],
+                prob[(size_t)e]);
       std::fclose(f);
     }
   } else if (st == PGCN_OK && !predict.empty()) {
