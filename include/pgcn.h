@@ -391,6 +391,57 @@ int pgcn_link_score_bwd(const pgcn_links *l, const float *H, int ld_h, int d, co
 int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, const int *dst,
                                const int *select, int *ptr, int *pair, int *other);
 
+/* --- link prediction: 1-vs-all ranking counts (k_rank.hip; new: the reference has no pair-level
+ * model).  For a held-out link (anchor a, target t) ranking metrics ask where t stands among all
+ * candidates v for a.  The rank score over an embedding H [n][ld_h] of logical width d is the
+ * k-ordered fp32 fused chain
+ *     r(a, v) = s_d,  s_0 = 0,  s_{c+1} = fmaf(H[a][c], H[v][c], s_c)  for c = 0 .. d - 1
+ * -- deliberately NOT pgcn_link_score_fwd's order (float4 partials met in xor butterflies): a chain
+ * is what the f32 MFMA computes bit for bit, so every kernel below produces the same bits for the
+ * same (a, v) and scores are compared with > and == exactly.  Columns >= d are never read into a
+ * result (the padding may hold NaN); inputs are taken as finite.
+ *
+ * pgcn_rank_queries is an opaque query set built from host arrays: anchors, targets and optionally
+ * per query e a list F_e = filter_idx[filter_ptr[e] .. filter_ptr[e + 1]) of candidates to leave
+ * out.  Creation validates on the host, before a device is looked for -- PGCN_E_INVALID for an
+ * endpoint outside [0, n_nodes), a list that is not strictly ascending (so deduplicated) or has
+ * an entry out of range, a list holding its query's target, n_queries beyond an int.  The handle
+ * owns the thresholds r(a_e, t_e) a call writes: pgcn_link_rank allocates nothing (it can be
+ * captured), and two calls on one handle must not overlap.
+ *
+ * pgcn_link_rank_scores: scores[e] = r(src_e, dst_e) of m explicit pairs (src, dst: device
+ * arrays), a lane per pair with an fmaf loop: the definition itself.
+ * pgcn_link_rank: for every query e (greater, equal: device, [n_queries])
+ *     greater[e] = #{ v in [0, n) : v != t_e, v not in F_e, r(a_e, v) >  r(a_e, t_e) }
+ *     equal[e]   = #{ v in [0, n) : v != t_e, v not in F_e, r(a_e, v) == r(a_e, t_e) }
+ * so the optimistic rank is greater + 1 and the pessimistic one greater + equal + 1.  At most
+ * three launches: the thresholds (which also zero the counts), the sweep -- workgroups of
+ * pgcn_link_rank_tile's queries_per_block queries over candidates_per_tile-candidate tiles of H on
+ * the f32 MFMA, a grid of query blocks x candidate splits, the splits a function of (n_queries, n)
+ * only, counts added with unsigned integer atomics -- and with lists the filter correction (a wave
+ * per query).  Asynchronous, no float atomics; integer sums do not depend on their order, so two
+ * calls give the same bits.  1 <= d <= 128, ld_h a multiple of 4 and >= d, H 16-byte aligned:
+ * anything else is PGCN_E_INVALID before the device is touched; n_queries == 0 launches nothing.
+ * pgcn_debug_rank_filter: host-only, the query set pgcn_gcn_link_ranks builds (see there) from a
+ * CSR pattern and a pair list: returns the query count (or a status < 0), *n_filter = the filter
+ * entries; anchor, target [queries], ptr [queries + 1], idx [*n_filter] are optional: call once for
+ * the sizes, then again for the data. */
+typedef struct pgcn_rank_queries pgcn_rank_queries;
+int pgcn_rank_queries_create(int n_nodes, long long n_queries, const int *anchor, const int *target,
+                             const long long *filter_ptr /* [n_queries + 1] or NULL */,
+                             const int *filter_idx, pgcn_rank_queries **out);
+int pgcn_rank_queries_destroy(pgcn_rank_queries *q);
+void pgcn_link_rank_tile(int *queries_per_block, int *candidates_per_tile);
+int pgcn_link_rank_scores(const int *src, const int *dst, long long m, const float *H, int ld_h,
+                          int d, float *scores /* [m] */, void *stream);
+int pgcn_link_rank(const pgcn_rank_queries *q, const float *H, int ld_h, int d,
+                   unsigned int *greater, unsigned int *equal, void *stream);
+long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indices,
+                                 long long n_pairs, const int *pair_src, const int *pair_dst,
+                                 const int *pair_label, const int *pair_split, int split, int side,
+                                 int filtered, long long *n_filter, int *anchor, int *target,
+                                 long long *ptr, int *idx);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -836,9 +887,22 @@ int pgcn_gcn_multilabel_counts(pgcn_gcn *g, int split, long long *counts);
  * labelled pairs: counts[3] = tp, fp, fn (a pair is predicted a link iff its score > 0).
  * pgcn_gcn_score_pairs: the same forward, then pgcn_link_score_fwd over m caller-given candidate
  * pairs (host arrays, endpoints in [0, num_nodes)) through a temporary pair index; scores [m].
+ * pgcn_gcn_link_ranks: the same forward, then pgcn_link_rank over the output embedding for split's
+ * (1..3) positive pairs (pair_label == 1) in pair order; returns their number, or a status < 0.
+ * greater / equal: host arrays of at least that many entries; both NULL returns the number only.
+ * side 0: the anchor is src_e, the target dst_e (the destination is corrupted); side 1: the
+ * anchor is dst_e, the target src_e.  filtered 0: every node but the target competes.  filtered 1:
+ * F_e is the ascending, deduplicated union, minus the target, of the anchor itself, the anchor's
+ * neighbours in the message-passing pattern (side 0: the j of row a's slots; side 1: the i of the
+ * slots into column a) and the other endpoints of every pair with pair_label == 1, of any split,
+ * that has the anchor in the anchor's role (side 0: dst_p where src_p == a; side 1: src_p where
+ * dst_p == a).  The query set of a (split, side, filtered) is built on the host at its first call
+ * and kept until the engine is destroyed.
  * The training state is untouched. */
 long long pgcn_gcn_predict_links(pgcn_gcn *g, float *scores, float *probs);
 int pgcn_gcn_link_counts(pgcn_gcn *g, int split, long long *counts);
+long long pgcn_gcn_link_ranks(pgcn_gcn *g, int split, int side, int filtered, long long *greater,
+                              long long *equal);
 int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m, float *scores);
 /* per-call device timing of the GraphSum kernels (enable before the timed region) */
 int pgcn_gcn_profile(pgcn_gcn *g, int enable);
@@ -1006,7 +1070,8 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * gradient's sequential-chain kernel, 256 threads per feature or 1024 on matrices of more than
  * 512 entries per feature), "spmm_tree_256" / "spmm_tree_1024" (its fixed-tree form, csc_tree),
  * "launches" (every kernel launch of the library), "link_fwd" / "link_bwd" (the pair-score
- * forward and backward calls that launched).
+ * forward and backward calls that launched), "rank_sweep" / "rank_filter" (pgcn_link_rank's
+ * sweep and filter-correction launches).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

@@ -162,6 +162,16 @@ _sig("pgcn_link_score_bwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c
      c_int, c_void_p)
 _sig("pgcn_debug_links_incidence", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
      c_void_p, c_void_p)
+_sig("pgcn_rank_queries_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
+     P(c_void_p))
+_sig("pgcn_rank_queries_destroy", c_int, c_void_p)
+_sig("pgcn_link_rank_tile", None, P(c_int), P(c_int))
+_sig("pgcn_link_rank_scores", c_int, c_void_p, c_void_p, c_ll, c_void_p, c_int, c_int, c_void_p,
+     c_void_p)
+_sig("pgcn_link_rank", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_debug_rank_filter", c_ll, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
+     c_void_p, c_int, c_int, c_int, P(c_ll), c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_gcn_link_ranks", c_ll, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -300,7 +310,7 @@ def _ptr(a):
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
                 "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
-                "spmm_tree_1024", "launches", "link_fwd", "link_bwd")
+                "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter")
 
 
 def path_counts(reset=False, thread=False):
@@ -561,6 +571,103 @@ def links_incidence(n_nodes, src, dst, select=None):
     return ptr, pair, other
 
 
+class RankQueries:
+    """A ranking query set on the device (pgcn_rank_queries): per query an anchor and a target
+    over n_nodes nodes and, with filter_ptr [Q + 1] / filter_idx, a strictly ascending list of
+    candidates to leave out (never the target)."""
+
+    def __init__(self, n_nodes, anchor, target, filter_ptr=None, filter_idx=None):
+        anchor = np.ascontiguousarray(anchor, np.int32)
+        target = np.ascontiguousarray(target, np.int32)
+        if anchor.ndim != 1 or target.shape != anchor.shape:
+            raise ValueError("RankQueries: anchor [Q], target [Q]")
+        fp = fi = None
+        if filter_ptr is not None:
+            fp = np.ascontiguousarray(filter_ptr, np.int64)
+            fi = np.ascontiguousarray(filter_idx if filter_idx is not None else [], np.int32)
+            if fp.shape != (anchor.size + 1,) or fi.ndim != 1 or (fp.size and fp[-1] != fi.size):
+                raise ValueError("RankQueries: filter_ptr [Q + 1], filter_idx [filter_ptr[Q]]")
+        h = c_void_p()
+        check(lib.pgcn_rank_queries_create(n_nodes, anchor.size, _ptr(anchor), _ptr(target),
+                                           _ptr(fp) if fp is not None else None,
+                                           _ptr(fi) if fi is not None else None, ctypes.byref(h)),
+              "rank_queries_create")
+        self._h, self.n_nodes, self.n_queries = h, n_nodes, int(anchor.size)
+        self.filtered = fp is not None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and lib is not None:
+            lib.pgcn_rank_queries_destroy(self._h)
+            self._h = c_void_p()
+
+    __del__ = close
+
+
+def link_rank_tile():
+    """(queries per workgroup, candidates per tile) of the ranking sweep (pgcn_link_rank_tile)."""
+    tq, tc = c_int(), c_int()
+    lib.pgcn_link_rank_tile(ctypes.byref(tq), ctypes.byref(tc))
+    return tq.value, tc.value
+
+
+def rank_filter(n_nodes, indptr, indices, pair_src, pair_dst, pair_label, pair_split, split,
+                side="dst", filtered=True):
+    """Host-only: (anchor, target, ptr int64 [Q + 1], idx) -- the query set GCN.link_ranks builds
+    for `split` (pgcn_debug_rank_filter): the split's positive pairs in pair order and, filtered,
+    per query the ascending union of the anchor, its neighbours in the pattern and its known links
+    of every split, minus the target."""
+    indptr = np.ascontiguousarray(indptr, np.int32)
+    indices = np.ascontiguousarray(indices, np.int32)
+    a = [np.ascontiguousarray(x, np.int32) for x in (pair_src, pair_dst, pair_label, pair_split)]
+    if any(x.ndim != 1 or x.shape != a[0].shape for x in a):
+        raise ValueError("rank_filter: pair_src, pair_dst, pair_label, pair_split [E]")
+    args = (n_nodes, _ptr(indptr), _ptr(indices), a[0].size, *(_ptr(x) for x in a), split,
+            RANK_SIDES[side], 1 if filtered else 0)
+    nf = c_ll()
+    q = lib.pgcn_debug_rank_filter(*args, ctypes.byref(nf), None, None, None, None)
+    if q < 0:
+        raise PgcnError(int(q), "debug_rank_filter")
+    anchor, target = np.zeros(q, np.int32), np.zeros(q, np.int32)
+    ptr, idx = np.zeros(q + 1, np.int64), np.zeros(nf.value, np.int32)
+    got = lib.pgcn_debug_rank_filter(*args, ctypes.byref(nf), _ptr(anchor), _ptr(target),
+                                     _ptr(ptr), _ptr(idx))
+    if got < 0:
+        raise PgcnError(int(got), "debug_rank_filter")
+    return anchor, target, ptr, idx
+
+
+RANK_SIDES = {"dst": 0, "src": 1, 0: 0, 1: 1}
+
+
+def rank_from_counts(greater, equal, ties="mean"):
+    """float64 ranks from link_ranks' counts: 'optimistic' greater + 1, 'pessimistic'
+    greater + equal + 1, 'mean' greater + equal / 2 + 1."""
+    g, e = np.asarray(greater, np.float64), np.asarray(equal, np.float64)
+    if ties == "optimistic":
+        return g + 1.0
+    if ties == "pessimistic":
+        return g + e + 1.0
+    if ties == "mean":
+        return g + e / 2.0 + 1.0
+    raise ValueError("ties must be 'mean', 'optimistic' or 'pessimistic'")
+
+
+def mrr(ranks):
+    """Mean reciprocal rank (nan without queries)."""
+    r = np.asarray(ranks, np.float64).ravel()
+    return float((1.0 / r).mean()) if r.size else float("nan")
+
+
+def hits_at(ranks, k):
+    """The share of queries ranked at or above position k (nan without queries)."""
+    r = np.asarray(ranks, np.float64).ravel()
+    return float((r <= k).mean()) if r.size else float("nan")
+
+
 def link_auc(scores, labels):
     """Area under the ROC curve of `scores` against labels in {0, 1} (-1: unlabelled, skipped):
     rank-based (Mann-Whitney), tied scores sharing their average rank.  nan when a class is
@@ -811,6 +918,24 @@ class GCN:
         out = np.zeros(3, np.int64)
         check(lib.pgcn_gcn_link_counts(self._h, split, _ptr(out)), "link_counts")
         return out
+
+    def link_ranks(self, split, side="dst", filtered=True):
+        """(greater, equal) int64 [Q]: for `split`'s Q positive pairs in pair order, the candidates
+        scoring above / exactly the true endpoint from an eval-mode forward (side 'dst': the
+        destination is ranked among all nodes, 'src': the source; filtered: the anchor, its
+        neighbours and its known links do not compete).  See rank_from_counts, mrr, hits_at."""
+        if side not in RANK_SIDES:
+            raise ValueError("side must be 'dst' or 'src'")
+        args = (self._h, split, RANK_SIDES[side], 1 if filtered else 0)
+        q = lib.pgcn_gcn_link_ranks(*args, None, None)
+        if q < 0:
+            raise PgcnError(int(q), "link_ranks")
+        greater, equal = np.zeros(q, np.int64), np.zeros(q, np.int64)
+        got = lib.pgcn_gcn_link_ranks(*args, _ptr(greater), _ptr(equal))
+        if got < 0:
+            raise PgcnError(int(got), "link_ranks")
+        assert got == q
+        return greater, equal
 
     def score_pairs(self, src, dst):
         """float32 [m]: the decoder's scores of caller-given candidate pairs from the same
@@ -1111,4 +1236,6 @@ EXPORTED = [
     "pgcn_link_score_fwd", "pgcn_link_score_bwd", "pgcn_debug_links_incidence",
     "pgcn_checkpoint_links", "pgcn_gcn_predict_links", "pgcn_gcn_link_counts",
     "pgcn_gcn_score_pairs", "pgcn_dataset_set_links", "pgcn_dataset_load_links",
+    "pgcn_rank_queries_create", "pgcn_rank_queries_destroy", "pgcn_link_rank_tile",
+    "pgcn_link_rank_scores", "pgcn_link_rank", "pgcn_debug_rank_filter", "pgcn_gcn_link_ranks",
 ]

@@ -29,7 +29,8 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "gat_bwd",    "gat_heads",  "spmm_csr",
                                           "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024",
                                           "spmm_tree_256", "spmm_tree_1024", "launches",
-                                          "link_fwd",   "link_bwd"};
+                                          "link_fwd",   "link_bwd",   "rank_sweep",
+                                          "rank_filter"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -42,6 +43,9 @@ struct pgcn_graph {
 };
 struct pgcn_links {
   std::unique_ptr<LinkIndexDev> l;
+};
+struct pgcn_rank_queries {
+  std::unique_ptr<RankQueriesDev> q;
 };
 struct pgcn_gcn {
   std::unique_ptr<GCN> g;
@@ -841,6 +845,76 @@ int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, c
   });
 }
 
+int pgcn_rank_queries_create(int n_nodes, long long n_queries, const int *anchor, const int *target,
+                             const long long *filter_ptr, const int *filter_idx,
+                             pgcn_rank_queries **out) {
+  return guarded([&] {
+    PGCN_CHECK(out, PGCN_E_INVALID, "rank_queries_create args");
+    validate_rank_queries(n_nodes, n_queries, anchor, target, filter_ptr, filter_idx);
+    check_device();
+    auto h = std::make_unique<pgcn_rank_queries>();
+    h->q = std::make_unique<RankQueriesDev>(n_nodes, n_queries, anchor, target, filter_ptr,
+                                            filter_idx);
+    *out = h.release();
+  });
+}
+
+int pgcn_rank_queries_destroy(pgcn_rank_queries *q) {
+  delete q;
+  return PGCN_OK;
+}
+
+void pgcn_link_rank_tile(int *queries_per_block, int *candidates_per_tile) {
+  if (queries_per_block) *queries_per_block = kRankTQ;
+  if (candidates_per_tile) *candidates_per_tile = kRankTC;
+}
+
+int pgcn_link_rank_scores(const int *src, const int *dst, long long m, const float *H, int ld_h,
+                          int d, float *scores, void *stream) {
+  return guarded([&] {
+    check_link_dims(d, {ld_h}, {});
+    PGCN_CHECK(m >= 0 && H && aligned16(H) && (m == 0 || (src && dst && scores)), PGCN_E_INVALID,
+               "link_rank_scores: null or misaligned argument");
+    check_device();
+    launch_rank_scores(src, dst, m, H, ld_h, d, scores, nullptr, nullptr, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_link_rank(const pgcn_rank_queries *q, const float *H, int ld_h, int d,
+                   unsigned int *greater, unsigned int *equal, void *stream) {
+  return guarded([&] {
+    check_link_dims(d, {ld_h}, {});
+    PGCN_CHECK(q && q->q && H && aligned16(H), PGCN_E_INVALID,
+               "link_rank: null or misaligned argument");
+    PGCN_CHECK(q->q->queries().n_queries == 0 || (greater && equal), PGCN_E_INVALID,
+               "link_rank: greater and equal [n_queries]");
+    check_device();
+    launch_link_rank(q->q->queries(), H, ld_h, d, greater, equal, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indices,
+                                 long long n_pairs, const int *pair_src, const int *pair_dst,
+                                 const int *pair_label, const int *pair_split, int split, int side,
+                                 int filtered, long long *n_filter, int *anchor, int *target,
+                                 long long *ptr, int *idx) {
+  long long n = -1;
+  const int st = guarded([&] {
+    const RankFilterHost f = build_rank_filter(n_nodes, indptr, indices, n_pairs, pair_src,
+                                               pair_dst, pair_label, pair_split, split, side,
+                                               filtered);
+    n = (long long)f.anchor.size();
+    if (n_filter) *n_filter = (long long)f.idx.size();
+    if (anchor && n) std::memcpy(anchor, f.anchor.data(), f.anchor.size() * sizeof(int));
+    if (target && n) std::memcpy(target, f.target.data(), f.target.size() * sizeof(int));
+    if (ptr) std::memcpy(ptr, f.ptr.data(), f.ptr.size() * sizeof(long long));
+    if (idx && !f.idx.empty()) std::memcpy(idx, f.idx.data(), f.idx.size() * sizeof(int));
+  });
+  return st == PGCN_OK ? n : st;
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -1272,6 +1346,15 @@ int pgcn_gcn_link_counts(pgcn_gcn *g, int split, long long *counts) {
     PGCN_CHECK(g && counts, PGCN_E_INVALID, "gcn_link_counts args");
     g->g->link_counts(split, counts);
   });
+}
+long long pgcn_gcn_link_ranks(pgcn_gcn *g, int split, int side, int filtered, long long *greater,
+                              long long *equal) {
+  long long n = -1;
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_link_ranks: null engine");
+    n = g->g->link_ranks(split, side, filtered, greater, equal);
+  });
+  return st == PGCN_OK ? n : st;
 }
 int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m,
                          float *scores) {

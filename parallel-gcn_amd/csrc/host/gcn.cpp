@@ -361,6 +361,12 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
       PGCN_CHECK(labelled[s] <= (1LL << 24), PGCN_E_INVALID,
                  "link_decoder: the labelled pairs of a split must not exceed 2^24");
     num_pairs_ = (int)E;
+    // link_ranks builds its query sets from the pattern and the pairs (host copies)
+    rank_graph_ = data.graph;
+    rank_pairs_[0] = data.pair_src;
+    rank_pairs_[1] = data.pair_dst;
+    rank_pairs_[2] = data.pair_label;
+    rank_pairs_[3] = data.pair_split;
   }
   int lo_prio = 0, hi_prio = 0;
   PGCN_HIP(hipDeviceGetStreamPriorityRange(&lo_prio, &hi_prio));
@@ -2009,6 +2015,45 @@ void GCN::score_pairs(const int *src, const int *dst, long long m, float *scores
   std::vector<float> raw((size_t)m * 4);
   out.download(raw.data(), raw.size());
   for (long long e = 0; e < m; e++) scores[e] = raw[(size_t)e * 4];
+}
+
+long long GCN::link_ranks(int split, int side, int filtered, long long *greater, long long *equal) {
+  PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "link_ranks: not a link engine");
+  PGCN_CHECK(split >= 1 && split <= 3 && (side == 0 || side == 1) &&
+                 (filtered == 0 || filtered == 1) && !greater == !equal,
+             PGCN_E_INVALID,
+             "link_ranks: split 1..3, side 0 / 1, filtered 0 / 1, both outputs or neither");
+  if (!greater) {
+    long long c = 0;
+    for (int e = 0; e < num_pairs_; e++)
+      c += rank_pairs_[2][(size_t)e] == 1 && rank_pairs_[3][(size_t)e] == split;
+    return c;
+  }
+  // (host work, allocations and blocking copies: before anything is enqueued)
+  RankSet &rs = rank_sets_[(split * 2 + side) * 2 + filtered];
+  if (!rs.q) {
+    const RankFilterHost f = build_rank_filter(
+        params.num_nodes, rank_graph_.indptr.data(), rank_graph_.indices.data(), num_pairs_,
+        rank_pairs_[0].data(), rank_pairs_[1].data(), rank_pairs_[2].data(),
+        rank_pairs_[3].data(), split, side, filtered);
+    const long long Q = (long long)f.anchor.size();
+    rs.q = std::make_unique<RankQueriesDev>(params.num_nodes, Q, f.anchor.data(), f.target.data(),
+                                            filtered ? f.ptr.data() : nullptr, f.idx.data());
+    rs.counts.allocate(std::max<size_t>((size_t)(2 * Q), 1));
+  }
+  const int Q = rs.q->queries().n_queries;
+  predict_forward();
+  const Variable &h = *link_embed;
+  launch_link_rank(rs.q->queries(), h.dev_data.get(), h.ld, params.output_dim, rs.counts.get(),
+                   rs.counts.get() + Q, stream.get());
+  sync();
+  std::vector<unsigned> raw((size_t)(2 * Q));
+  rs.counts.download(raw.data(), raw.size());
+  for (int e = 0; e < Q; e++) {
+    greater[e] = (long long)raw[(size_t)e];
+    equal[e] = (long long)raw[(size_t)(Q + e)];
+  }
+  return Q;
 }
 
 void GCN::confusion(int split, long long *counts) {

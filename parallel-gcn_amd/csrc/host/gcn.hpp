@@ -169,6 +169,11 @@ class GCN {
   long long predict_links(float *scores, float *probs);
   void link_counts(int split, long long *counts);
   void score_pairs(const int *src, const int *dst, long long m, float *scores);
+  // the same forward, then launch_link_rank over `split`'s positive pairs in pair order (side 0:
+  // the destination is ranked among all nodes, side 1: the source; filtered: build_rank_filter's
+  // lists): their number, and with outputs their greater / equal counts.  Both outputs null: the
+  // number only, nothing runs.  The query set of a (split, side, filtered) is built once
+  long long link_ranks(int split, int side, int filtered, long long *greater, long long *equal);
   long long adam_steps() const { return optimizer.steps(); }
   void set_profile(bool on);
   void profile_read_mm(double *ms, long long *calls, double *flops);  // XW contractions
@@ -263,6 +268,15 @@ class GCN {
   int num_pairs_ = 0;
   std::unique_ptr<LinkIndexDev> links_;
   shared_ptr<Variable> link_embed, link_scores;
+  // link_ranks: the pattern and the pairs on the host (src, dst, label, split), and per
+  // (split, side, filtered) the query set on the device with its counts [2][queries]
+  SparseIndex rank_graph_;
+  std::vector<int> rank_pairs_[4];
+  struct RankSet {
+    std::unique_ptr<RankQueriesDev> q;
+    DeviceBuffer<unsigned> counts;
+  };
+  std::map<int, RankSet> rank_sets_;
   // the layer's aggregation from var1 to var2: a GraphSum, a GraphAttention on attn_var or a
   // SageAggregate
   void insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,

@@ -824,6 +824,124 @@ LinkIndexDev::LinkIndexDev(int n, long long n_pairs, const int *src, const int *
   l_.ws = ws_.get();
 }
 
+void validate_rank_queries(int n, long long n_queries, const int *anchor, const int *target,
+                           const long long *filter_ptr, const int *filter_idx) {
+  PGCN_CHECK(n >= 1 && n_queries >= 0 && n_queries <= INT_MAX &&
+                 (n_queries == 0 || (anchor && target)),
+             PGCN_E_INVALID, "rank_queries: n >= 1, 0 <= n_queries within an int, anchor and target");
+  for (long long e = 0; e < n_queries; e++)
+    PGCN_CHECK(anchor[e] >= 0 && anchor[e] < n && target[e] >= 0 && target[e] < n, PGCN_E_INVALID,
+               "rank_queries: endpoint out of range");
+  if (!filter_ptr) return;
+  PGCN_CHECK(filter_ptr[0] == 0, PGCN_E_INVALID, "rank_queries: filter_ptr[0] must be 0");
+  for (long long e = 0; e < n_queries; e++) {
+    const long long b = filter_ptr[e], en = filter_ptr[e + 1];
+    PGCN_CHECK(en >= b && en - b <= n && (en == b || filter_idx), PGCN_E_INVALID,
+               "rank_queries: filter_ptr must ascend, a list holds at most n entries");
+    for (long long k = b; k < en; k++) {
+      const int f = filter_idx[k];
+      PGCN_CHECK(f >= 0 && f < n, PGCN_E_INVALID, "rank_queries: filter entry out of range");
+      PGCN_CHECK(k == b || filter_idx[k - 1] < f, PGCN_E_INVALID,
+                 "rank_queries: a filter list must be strictly ascending");
+      PGCN_CHECK(f != target[e], PGCN_E_INVALID,
+                 "rank_queries: a filter list must not hold its query's target");
+    }
+  }
+}
+
+RankFilterHost build_rank_filter(int n, const int *indptr, const int *indices, long long n_pairs,
+                                 const int *pair_src, const int *pair_dst, const int *pair_label,
+                                 const int *pair_split, int split, int side, int filtered) {
+  PGCN_CHECK(n >= 1 && indptr && n_pairs >= 0 && n_pairs <= INT_MAX &&
+                 (n_pairs == 0 || (pair_src && pair_dst && pair_label && pair_split)),
+             PGCN_E_INVALID, "rank_filter: n >= 1, a CSR and the four pair arrays");
+  PGCN_CHECK(split >= 1 && split <= 3 && (side == 0 || side == 1) &&
+                 (filtered == 0 || filtered == 1),
+             PGCN_E_INVALID, "rank_filter: split 1..3, side 0 / 1, filtered 0 / 1");
+  PGCN_CHECK(indptr[0] == 0, PGCN_E_INVALID, "rank_filter: indptr[0] must be 0");
+  for (int i = 0; i < n; i++)
+    PGCN_CHECK(indptr[i + 1] >= indptr[i], PGCN_E_INVALID, "rank_filter: indptr must ascend");
+  const int nnz = indptr[n];
+  PGCN_CHECK(nnz == 0 || indices, PGCN_E_INVALID, "rank_filter: indices");
+  for (int k = 0; k < nnz; k++)
+    PGCN_CHECK(indices[k] >= 0 && indices[k] < n, PGCN_E_INVALID,
+               "rank_filter: column out of range");
+  validate_pairs(n, n_pairs, pair_src, pair_dst);
+  const int *anc = side == 0 ? pair_src : pair_dst, *oth = side == 0 ? pair_dst : pair_src;
+
+  RankFilterHost out;
+  for (long long e = 0; e < n_pairs; e++)
+    if (pair_label[e] == 1 && pair_split[e] == split) {
+      out.anchor.push_back(anc[e]);
+      out.target.push_back(oth[e]);
+    }
+  out.ptr.assign(out.anchor.size() + 1, 0);
+  if (!filtered) return out;
+
+  // the neighbours by anchor: the CSR as given (side 0) or its transpose (side 1)
+  std::vector<int> tptr, tidx;
+  const int *nptr = indptr, *nidx = indices;
+  if (side == 1) {
+    tptr.assign((size_t)n + 1, 0);
+    for (int k = 0; k < nnz; k++) tptr[(size_t)indices[k] + 1]++;
+    for (int i = 0; i < n; i++) tptr[(size_t)i + 1] += tptr[(size_t)i];
+    tidx.resize((size_t)nnz);
+    std::vector<int> fill(tptr.begin(), tptr.end() - 1);
+    for (int i = 0; i < n; i++)
+      for (int k = indptr[i]; k < indptr[i + 1]; k++) tidx[(size_t)fill[(size_t)indices[k]]++] = i;
+    nptr = tptr.data();
+    nidx = tidx.data();
+  }
+  // the known links by anchor: every positive pair of any split
+  std::vector<long long> pptr((size_t)n + 1, 0);
+  for (long long e = 0; e < n_pairs; e++)
+    if (pair_label[e] == 1) pptr[(size_t)anc[e] + 1]++;
+  for (int i = 0; i < n; i++) pptr[(size_t)i + 1] += pptr[(size_t)i];
+  std::vector<int> pidx((size_t)pptr[(size_t)n]);
+  {
+    std::vector<long long> fill(pptr.begin(), pptr.end() - 1);
+    for (long long e = 0; e < n_pairs; e++)
+      if (pair_label[e] == 1) pidx[(size_t)fill[(size_t)anc[e]]++] = oth[e];
+  }
+  std::vector<int> list;
+  for (size_t q = 0; q < out.anchor.size(); q++) {
+    const int a = out.anchor[q], t = out.target[q];
+    list.clear();
+    list.push_back(a);
+    list.insert(list.end(), nidx + nptr[a], nidx + nptr[a + 1]);
+    list.insert(list.end(), pidx.begin() + pptr[(size_t)a], pidx.begin() + pptr[(size_t)a + 1]);
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    for (int v : list)
+      if (v != t) out.idx.push_back(v);
+    out.ptr[q + 1] = (long long)out.idx.size();
+  }
+  return out;
+}
+
+RankQueriesDev::RankQueriesDev(int n, long long n_queries, const int *anchor, const int *target,
+                               const long long *filter_ptr, const int *filter_idx) {
+  auto up = [](auto &buf, const auto *host, size_t count) {
+    buf.allocate(std::max<size_t>(count, 1));
+    if (count) buf.upload(host, count);
+  };
+  up(anchor_, anchor, (size_t)n_queries);
+  up(target_, target, (size_t)n_queries);
+  thr_.allocate(std::max<size_t>((size_t)n_queries, 1));
+  thr_.zero();
+  q_.n = n;
+  q_.n_queries = (int)n_queries;
+  q_.anchor = anchor_.get();
+  q_.target = target_.get();
+  q_.thr = thr_.get();
+  if (filter_ptr) {
+    up(fptr_, filter_ptr, (size_t)n_queries + 1);
+    up(fidx_, filter_idx, (size_t)filter_ptr[n_queries]);
+    q_.filter_ptr = fptr_.get();
+    q_.filter_idx = fidx_.get();
+  }
+}
+
 double DevGraph::algorithmic_bytes(int dim) const {
   // 4(N+1) indptr + 8 nnz (index + value) + 4 N_in d (read) + 4 N d (write)
   return 4.0 * (n_rows_ + 1) + 8.0 * (double)nnz_ + 4.0 * (double)n_cols_ * dim +

@@ -255,4 +255,42 @@ class LinkIndexDev {
   DeviceBuffer<float> ws_;
 };
 
+// A ranking query set as k_rank.hip takes it: PGCN_E_INVALID for an endpoint outside [0, n), a
+// query count beyond an int, a filter list that is not strictly ascending (so deduplicated), has
+// an entry outside [0, n) or holds its query's target.  filter_ptr null: no lists.  Host only.
+void validate_rank_queries(int n, long long n_queries, const int *anchor, const int *target,
+                           const long long *filter_ptr, const int *filter_idx);
+
+// The ranking queries of a link data set's split, on the host (no device): the pairs with
+// label == 1 and pair_split == split, in pair order; side 0: anchor src_e, target dst_e; side 1:
+// anchor dst_e, target src_e.  filtered: per query the ascending, deduplicated union of the anchor
+// itself, its neighbours in the CSR (side 0: the columns of row a; side 1: the rows with a slot in
+// column a) and the other endpoints of every pair with label == 1, of any split, that has the
+// anchor in the anchor's role -- minus the target.  Without: ptr all zero, idx empty.
+// PGCN_E_INVALID for a CSR or a pair list out of range.
+struct RankFilterHost {
+  std::vector<int> anchor, target;
+  std::vector<long long> ptr;  // [queries + 1]
+  std::vector<int> idx;
+};
+RankFilterHost build_rank_filter(int n, const int *indptr, const int *indices, long long n_pairs,
+                                 const int *pair_src, const int *pair_dst, const int *pair_label,
+                                 const int *pair_split, int split, int side, int filtered);
+
+// A query set on the device for k_rank.hip, of arrays validate_rank_queries accepted.  It owns the
+// thresholds a rank call writes, so two calls on one set must not overlap.  Construction is host
+// work and blocking copies: not inside a stream capture.
+class RankQueriesDev {
+ public:
+  RankQueriesDev(int n, long long n_queries, const int *anchor, const int *target,
+                 const long long *filter_ptr, const int *filter_idx);
+  const RankQueries &queries() const { return q_; }
+
+ private:
+  RankQueries q_;
+  DeviceBuffer<int> anchor_, target_, fidx_;
+  DeviceBuffer<long long> fptr_;
+  DeviceBuffer<float> thr_;
+};
+
 }  // namespace pgcn

@@ -16,7 +16,8 @@ enum KernelPath {
   KP_XS_NN_RING, KP_XS_TN_RING, KP_XS_NN, KP_XS_TN, KP_GS_RING, KP_GS_GATHER, KP_OUT_XENT,
   KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS,
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
-  KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_COUNT
+  KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_RANK_SWEEP, KP_RANK_FILTER,
+  KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -474,6 +475,32 @@ void launch_link_score_fwd(const LinkIndex &l, const float *H, int ld_h, int d, 
 // their segments' partials in l.ws and a second launch that adds them in segment order
 void launch_link_score_bwd(const LinkIndex &l, const float *H, int ld_h, int d, const float *G,
                            int ld_g, float *dH, int ld_dh, hipStream_t s);
+// ---- link prediction: 1-vs-all ranking counts (k_rank.hip) -------------------------------------
+// The rank score r(a, v) is the k-ordered fp32 fmaf chain over the d columns of rows a and v -- not
+// launch_link_score_fwd's order -- which is what the sweep's f32 MFMA tiles compute bit for bit.
+// A query set on the device (RankQueriesDev, host/graph.hpp): anchors, targets, the thresholds
+// r(a_e, t_e) a call leaves in thr, and optionally per query an ascending list of candidates to
+// leave out (never the target).
+constexpr int kRankTQ = 128;  // queries per workgroup of the sweep
+constexpr int kRankTC = 64;   // candidates per tile
+struct RankQueries {
+  int n = 0, n_queries = 0;
+  const int *anchor = nullptr, *target = nullptr;
+  float *thr = nullptr;                   // [n_queries]
+  const long long *filter_ptr = nullptr;  // [n_queries + 1], null: no lists
+  const int *filter_idx = nullptr;
+};
+// candidate splits of the sweep's grid: a function of (Q, n) only
+int rank_splits(int Q, int n);
+// scores[e] = r(src_e, dst_e), a lane per pair (src, dst on the device); zero0 / zero1 (both or
+// neither): [m] words zeroed in the same pass
+void launch_rank_scores(const int *src, const int *dst, long long m, const float *H, int ld_h,
+                        int d, float *scores, unsigned *zero0, unsigned *zero1, hipStream_t s);
+// greater[e] / equal[e] = the candidates v in [0, n), v != t_e, v not in F_e, with r(a_e, v) > / ==
+// r(a_e, t_e).  Three launches at most: thresholds (which zero the counts), the sweep (query
+// blocks x rank_splits; integer atomics), the filter correction (a wave per query; with lists)
+void launch_link_rank(const RankQueries &q, const float *H, int ld_h, int d, unsigned *greater,
+                      unsigned *equal, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D>] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [rank=1|<file>]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -33,6 +33,10 @@
 // `<src> <dst> <label> <split>`), the output layer is a D-wide node embedding, loss and accuracy
 // are per pair, and predict= writes one line `src dst score probability` per pair.  The adjacency
 // is used as loaded: keep validation and test positives out of it.
+// rank=1 (with link=): after the run, one line with the filtered ranking metrics of the test split
+// (pgcn_gcn_link_ranks; mean ties) for both sides: `rank side=dst queries=.. mrr=.. hits@10=..
+// hits@50=.. hits@100=.. side=src ...`; rank=<file> also writes `src dst greater equal` per test
+// positive pair for the dst side.
 #include <algorithm>
 #include <vector>
 #include <cstdio>
@@ -136,7 +140,7 @@ int main(int argc, char **argv) {
   std::string root = ".", file;
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
-  std::string load, save, predict;
+  std::string load, save, predict, rank;
   int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
   int root_weight = -1;
@@ -163,6 +167,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "readout=", 8)) readout = argv[i] + 8;
     if (!std::strncmp(argv[i], "link=", 5)) link = argv[i] + 5;
     if (!std::strncmp(argv[i], "embed=", 6)) embed_arg = std::atoi(argv[i] + 6);
+    if (!std::strncmp(argv[i], "rank=", 5)) rank = argv[i] + 5;
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -272,6 +277,47 @@ int main(int argc, char **argv) {
         fprintf(f, "%lld %d %.6f\n", i, cls[(size_t)i], conf[(size_t)i]);
       std::fclose(f);
     }
+  }
+  if (st == PGCN_OK && !rank.empty() && rank != "0" && p.link_decoder) {
+    printf("rank");
+    for (int side = 0; side < 2 && st == PGCN_OK; side++) {
+      const long long q = pgcn_gcn_link_ranks(g, 3, side, 1, nullptr, nullptr);
+      std::vector<long long> greater((size_t)std::max(q, 0LL)), equal(greater.size());
+      const long long got = q < 0 ? q : pgcn_gcn_link_ranks(g, 3, side, 1, greater.data(), equal.data());
+      if (got < 0) {
+        st = (int)got;
+        break;
+      }
+      double rr = 0.0;
+      long long hits[3] = {0, 0, 0};
+      const double at[3] = {10.0, 50.0, 100.0};
+      for (long long e = 0; e < q; e++) {
+        const double r = (double)greater[(size_t)e] + (double)equal[(size_t)e] / 2.0 + 1.0;
+        rr += 1.0 / r;
+        for (int k = 0; k < 3; k++) hits[k] += r <= at[k];
+      }
+      const double den = q > 0 ? (double)q : 1.0;
+      printf(" side=%s queries=%lld mrr=%.6f hits@10=%.6f hits@50=%.6f hits@100=%.6f",
+             side == 0 ? "dst" : "src", q, rr / den, hits[0] / den, hits[1] / den, hits[2] / den);
+      if (side == 0 && rank != "1") {
+        FILE *f = std::fopen(rank.c_str(), "w");
+        if (!f) {
+          fprintf(stderr, "cannot write ranks to %s\n", rank.c_str());
+          st = PGCN_E_IO;
+        } else {
+          long long k = 0;
+          for (long long e = 0; e < view.num_pairs; e++)
+            if (view.pair_label[e] == 1 && view.pair_split[e] == 3) {
+              fprintf(f, "%d %d %lld %lld\n", view.pair_src[e], view.pair_dst[e], greater[(size_t)k],
+                      equal[(size_t)k]);
+              k++;
+            }
+          std::fclose(f);
+        }
+      }
+    }
+    printf("\n");
+    if (st != PGCN_OK) fprintf(stderr, "ranking failed: %s\n", pgcn_status_string(st));
   }
   pgcn_gcn_destroy(g);
   pgcn_dataset_free(ds);
