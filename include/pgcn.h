@@ -442,6 +442,67 @@ long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indi
                                  int filtered, long long *n_filter, int *anchor, int *target,
                                  long long *ptr, int *idx);
 
+/* --- link prediction: 1-vs-all top-K retrieval (k_topk.hip; new: the reference has no pair-level
+ * model).  "For this node, which nodes should it be linked to?": per query the k best candidates
+ * by the rank score, never forming the [n_queries][n] score matrix.
+ *
+ * Score.  r(a, v) is the rank score above, unchanged: the fused chain over columns 0 .. d - 1,
+ * columns >= d never read from memory.
+ * Candidates of query e with anchor a_e: every v in [0, n) that is not in the query's exclude list
+ * X_e = exclude_idx[exclude_ptr[e] .. exclude_ptr[e + 1]).  There is no target.
+ * Order.  Candidate v precedes candidate w when r(a, v) > r(a, w), or when r(a, v) == r(a, w) and
+ * v < w, by float comparison, so -0.0 == +0.0 (a chain may end in a zero of either sign; it is
+ * canonicalised before any selection key is formed).  This is a total order on candidates, so the
+ * answer is unique:
+ *     idx[e][j], score[e][j], j < k: the j-th candidate in that order and its score;
+ *     the positions from min(k, candidates) on hold idx = -1 and score = -inf.
+ * Limits: 1 <= k <= 128 (pgcn_link_topk_tile's k_max, which covers Hits@100), 1 <= d <= 128, ld_h a
+ * multiple of 4 and >= d, H 16-byte aligned, inputs finite.
+ *
+ * pgcn_topk_queries is an opaque query set built from host arrays.  Creation validates on the host,
+ * before a device is looked for -- PGCN_E_INVALID for an anchor or a list entry outside
+ * [0, n_nodes), a list that is not strictly ascending, k outside [1, 128], n_queries beyond an int.
+ * A list may hold the anchor; nothing else about the lists is assumed.  The handle owns every byte
+ * of workspace a call needs, pgcn_topk_queries_workspace =
+ *     n_queries * pgcn_link_topk_splits(n_queries, n_nodes) * cap(k) * 8 bytes,
+ *     cap(k) = 128 for k <= 64 and 256 above
+ * (per query and candidate split an append buffer of cap 64-bit keys), so pgcn_link_topk allocates
+ * nothing and can be captured; two calls on one handle must not overlap.
+ *
+ * pgcn_link_topk (idx, score: device, [n_queries][k]): exactly TWO launches whatever (n_queries, n,
+ * k) and the data are, none when n_queries == 0 --
+ *   the sweep: k_rank.hip's workgroups (pgcn_link_topk_tile's queries_per_block queries over
+ *     candidates_per_tile-candidate tiles on the f32 MFMA), a grid of query blocks x
+ *     pgcn_link_topk_splits -- a function of (n_queries, n_nodes) only, and the function the
+ *     launcher uses -- whose epilogue selects: per query a threshold that only rises, an append
+ *     buffer pruned to its k best whenever it could overflow; it leaves k keys per (query, split);
+ *   the merge: a wave per query takes the k best of its splits' keys and writes idx and score
+ *     with the padding.
+ * No atomics and no data-dependent order: two calls on equal inputs give the same bits.  Argument
+ * errors are PGCN_E_INVALID before the device is touched.
+ * pgcn_link_topk_chunk: the queries pgcn_gcn_top_links hands to one pgcn_link_topk call.
+ * pgcn_debug_topk_filter: host-only, the exclude lists pgcn_gcn_top_links builds for m anchor
+ * nodes (see there) from a CSR pattern and a pair list: returns m (or a status < 0), *n_exclude =
+ * the entries; ptr [m + 1] and idx [*n_exclude] are optional: call once for the sizes, then again
+ * for the data. */
+typedef struct pgcn_topk_queries pgcn_topk_queries;
+int pgcn_topk_queries_create(int n_nodes, long long n_queries, const int *anchor,
+                             const long long *exclude_ptr /* [n_queries + 1] or NULL */,
+                             const int *exclude_idx, int k, pgcn_topk_queries **out);
+int pgcn_topk_queries_destroy(pgcn_topk_queries *q);
+long long pgcn_topk_queries_workspace(const pgcn_topk_queries *q); /* device bytes it owns */
+void pgcn_link_topk_tile(int *queries_per_block, int *candidates_per_tile, int *k_max);
+int pgcn_link_topk_splits(long long n_queries, int n_nodes); /* host only, pure */
+int pgcn_link_topk_chunk(void);
+int pgcn_link_topk(const pgcn_topk_queries *q, const float *H, int ld_h, int d,
+                   int *idx /* dev [n_queries][k] */, float *score /* dev [n_queries][k] */,
+                   void *stream);
+long long pgcn_debug_topk_filter(int n_nodes, const int *indptr, const int *indices,
+                                 long long n_pairs, const int *pair_src, const int *pair_dst,
+                                 const int *pair_label, const int *pair_split, long long m,
+                                 const int *nodes, int side, int filtered, long long *n_exclude,
+                                 long long *ptr, int *idx);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -898,11 +959,19 @@ int pgcn_gcn_multilabel_counts(pgcn_gcn *g, int split, long long *counts);
  * that has the anchor in the anchor's role (side 0: dst_p where src_p == a; side 1: src_p where
  * dst_p == a).  The query set of a (split, side, filtered) is built on the host at its first call
  * and kept until the engine is destroyed.
+ * pgcn_gcn_top_links: the same forward, then pgcn_link_topk over the output embedding for m anchor
+ * nodes (host array, in [0, num_nodes), duplicates allowed); idx / score: host, [m][k]; returns m or
+ * a status < 0.  side 0: the candidates are destinations for src = node; side 1: sources for dst =
+ * node.  filtered 1: X_e is pgcn_gcn_link_ranks' list without its "minus the target".  The nodes
+ * are processed pgcn_link_topk_chunk() = 16,384 at a time; the query set and the device outputs
+ * of a chunk are freed after it, so the device memory in use is bounded whatever m is.
  * The training state is untouched. */
 long long pgcn_gcn_predict_links(pgcn_gcn *g, float *scores, float *probs);
 int pgcn_gcn_link_counts(pgcn_gcn *g, int split, long long *counts);
 long long pgcn_gcn_link_ranks(pgcn_gcn *g, int split, int side, int filtered, long long *greater,
                               long long *equal);
+long long pgcn_gcn_top_links(pgcn_gcn *g, const int *nodes, long long m, int k, int side,
+                             int filtered, int *idx, float *score);
 int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m, float *scores);
 /* per-call device timing of the GraphSum kernels (enable before the timed region) */
 int pgcn_gcn_profile(pgcn_gcn *g, int enable);
@@ -1071,7 +1140,7 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * 512 entries per feature), "spmm_tree_256" / "spmm_tree_1024" (its fixed-tree form, csc_tree),
  * "launches" (every kernel launch of the library), "link_fwd" / "link_bwd" (the pair-score
  * forward and backward calls that launched), "rank_sweep" / "rank_filter" (pgcn_link_rank's
- * sweep and filter-correction launches).
+ * sweep and filter-correction launches), "topk_sweep" / "topk_merge" (pgcn_link_topk's two).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

@@ -172,6 +172,17 @@ _sig("pgcn_link_rank", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void
 _sig("pgcn_debug_rank_filter", c_ll, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
      c_void_p, c_int, c_int, c_int, P(c_ll), c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_link_ranks", c_ll, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)
+_sig("pgcn_topk_queries_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_int,
+     P(c_void_p))
+_sig("pgcn_topk_queries_destroy", c_int, c_void_p)
+_sig("pgcn_topk_queries_workspace", c_ll, c_void_p)
+_sig("pgcn_link_topk_tile", None, P(c_int), P(c_int), P(c_int))
+_sig("pgcn_link_topk_splits", c_int, c_ll, c_int)
+_sig("pgcn_link_topk_chunk", c_int)
+_sig("pgcn_link_topk", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_debug_topk_filter", c_ll, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
+     c_void_p, c_ll, c_void_p, c_int, c_int, P(c_ll), c_void_p, c_void_p)
+_sig("pgcn_gcn_top_links", c_ll, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p)
 _sig("pgcn_params_sizeof", c_int)
 _sig("pgcn_xent_blocks", c_int, c_int)
 _sig("pgcn_xent_fwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
@@ -310,7 +321,8 @@ def _ptr(a):
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
                 "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
-                "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter")
+                "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter",
+                "topk_sweep", "topk_merge")
 
 
 def path_counts(reset=False, thread=False):
@@ -643,6 +655,90 @@ def rank_filter(n_nodes, indptr, indices, pair_src, pair_dst, pair_label, pair_s
 RANK_SIDES = {"dst": 0, "src": 1, 0: 0, 1: 1}
 
 
+class TopKQueries:
+    """A top-K query set on the device (pgcn_topk_queries): per query an anchor over n_nodes nodes
+    and, with exclude_ptr [Q + 1] / exclude_idx, a strictly ascending list of candidates to leave
+    out (it may hold the anchor); k results per query.  It owns the workspace of pgcn_link_topk."""
+
+    def __init__(self, n_nodes, anchor, exclude_ptr=None, exclude_idx=None, k=10):
+        anchor = np.ascontiguousarray(anchor, np.int32)
+        if anchor.ndim != 1:
+            raise ValueError("TopKQueries: anchor [Q]")
+        xp = xi = None
+        if exclude_ptr is not None:
+            xp = np.ascontiguousarray(exclude_ptr, np.int64)
+            xi = np.ascontiguousarray(exclude_idx if exclude_idx is not None else [], np.int32)
+            if xp.shape != (anchor.size + 1,) or xi.ndim != 1 or (xp.size and xp[-1] != xi.size):
+                raise ValueError("TopKQueries: exclude_ptr [Q + 1], exclude_idx [exclude_ptr[Q]]")
+        h = c_void_p()
+        check(lib.pgcn_topk_queries_create(n_nodes, anchor.size, _ptr(anchor),
+                                           _ptr(xp) if xp is not None else None,
+                                           _ptr(xi) if xi is not None else None, int(k),
+                                           ctypes.byref(h)), "topk_queries_create")
+        self._h, self.n_nodes, self.n_queries, self.k = h, n_nodes, int(anchor.size), int(k)
+        self.filtered = xp is not None
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def workspace(self):
+        """Device bytes of workspace the handle owns."""
+        return int(lib.pgcn_topk_queries_workspace(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and lib is not None:
+            lib.pgcn_topk_queries_destroy(self._h)
+            self._h = c_void_p()
+
+    __del__ = close
+
+
+def link_topk_tile():
+    """(queries per workgroup, candidates per tile, largest k) of the top-K sweep
+    (pgcn_link_topk_tile)."""
+    tq, tc, km = c_int(), c_int(), c_int()
+    lib.pgcn_link_topk_tile(ctypes.byref(tq), ctypes.byref(tc), ctypes.byref(km))
+    return tq.value, tc.value, km.value
+
+
+def link_topk_splits(n_queries, n_nodes):
+    """Candidate splits of the top-K sweep's grid for (n_queries, n_nodes): host only."""
+    return int(lib.pgcn_link_topk_splits(int(n_queries), int(n_nodes)))
+
+
+def link_topk_chunk():
+    """Queries GCN.top_links hands to one top-K call (pgcn_link_topk_chunk)."""
+    return int(lib.pgcn_link_topk_chunk())
+
+
+def topk_filter(n_nodes, indptr, indices, pair_src, pair_dst, pair_label, pair_split, nodes,
+                side="dst", filtered=True):
+    """Host-only: (ptr int64 [m + 1], idx) -- the exclude lists GCN.top_links builds for `nodes`
+    (pgcn_debug_topk_filter): filtered, per node the ascending union of the node, its neighbours in
+    the pattern and its known links of every split (rank_filter's list with the target left in)."""
+    indptr = np.ascontiguousarray(indptr, np.int32)
+    indices = np.ascontiguousarray(indices, np.int32)
+    a = [np.ascontiguousarray(x, np.int32) for x in (pair_src, pair_dst, pair_label, pair_split)]
+    if any(x.ndim != 1 or x.shape != a[0].shape for x in a):
+        raise ValueError("topk_filter: pair_src, pair_dst, pair_label, pair_split [E]")
+    nodes = np.ascontiguousarray(nodes, np.int32)
+    if nodes.ndim != 1:
+        raise ValueError("topk_filter: nodes [m]")
+    args = (n_nodes, _ptr(indptr), _ptr(indices), a[0].size, *(_ptr(x) for x in a), nodes.size,
+            _ptr(nodes), RANK_SIDES[side], 1 if filtered else 0)
+    nx = c_ll()
+    m = lib.pgcn_debug_topk_filter(*args, ctypes.byref(nx), None, None)
+    if m < 0:
+        raise PgcnError(int(m), "debug_topk_filter")
+    ptr, idx = np.zeros(nodes.size + 1, np.int64), np.zeros(nx.value, np.int32)
+    got = lib.pgcn_debug_topk_filter(*args, ctypes.byref(nx), _ptr(ptr), _ptr(idx))
+    if got < 0:
+        raise PgcnError(int(got), "debug_topk_filter")
+    return ptr, idx
+
+
 def rank_from_counts(greater, equal, ties="mean"):
     """float64 ranks from link_ranks' counts: 'optimistic' greater + 1, 'pessimistic'
     greater + equal + 1, 'mean' greater + equal / 2 + 1."""
@@ -936,6 +1032,26 @@ class GCN:
             raise PgcnError(int(got), "link_ranks")
         assert got == q
         return greater, equal
+
+    def top_links(self, nodes, k=10, side="dst", filtered=True):
+        """(idx int32 [m][k], scores float32 [m][k]): per node of `nodes` the k nodes with the
+        highest rank score against it from an eval-mode forward, ties to the lower index (side
+        'dst': destinations for the node as a source, 'src': sources for it as a destination;
+        filtered: the node, its neighbours and its known links are left out).  Rows with fewer than
+        k candidates end in idx -1, score -inf.  The training state is untouched."""
+        if side not in RANK_SIDES:
+            raise ValueError("side must be 'dst' or 'src'")
+        nodes = np.ascontiguousarray(nodes, np.int32)
+        if nodes.ndim != 1:
+            raise ValueError("top_links: nodes [m]")
+        k = int(k)
+        idx = np.zeros((nodes.size, max(k, 0)), np.int32)
+        sc = np.zeros((nodes.size, max(k, 0)), np.float32)
+        got = lib.pgcn_gcn_top_links(self._h, _ptr(nodes), nodes.size, k, RANK_SIDES[side],
+                                     1 if filtered else 0, _ptr(idx), _ptr(sc))
+        if got < 0:
+            raise PgcnError(int(got), "top_links")
+        return idx, sc
 
     def score_pairs(self, src, dst):
         """float32 [m]: the decoder's scores of caller-given candidate pairs from the same
@@ -1238,4 +1354,7 @@ EXPORTED = [
     "pgcn_gcn_score_pairs", "pgcn_dataset_set_links", "pgcn_dataset_load_links",
     "pgcn_rank_queries_create", "pgcn_rank_queries_destroy", "pgcn_link_rank_tile",
     "pgcn_link_rank_scores", "pgcn_link_rank", "pgcn_debug_rank_filter", "pgcn_gcn_link_ranks",
+    "pgcn_topk_queries_create", "pgcn_topk_queries_destroy", "pgcn_topk_queries_workspace",
+    "pgcn_link_topk_tile", "pgcn_link_topk_splits", "pgcn_link_topk_chunk", "pgcn_link_topk",
+    "pgcn_debug_topk_filter", "pgcn_gcn_top_links",
 ]

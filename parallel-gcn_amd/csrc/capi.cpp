@@ -30,7 +30,7 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024",
                                           "spmm_tree_256", "spmm_tree_1024", "launches",
                                           "link_fwd",   "link_bwd",   "rank_sweep",
-                                          "rank_filter"};
+                                          "rank_filter", "topk_sweep", "topk_merge"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -46,6 +46,9 @@ struct pgcn_links {
 };
 struct pgcn_rank_queries {
   std::unique_ptr<RankQueriesDev> q;
+};
+struct pgcn_topk_queries {
+  std::unique_ptr<TopKQueriesDev> q;
 };
 struct pgcn_gcn {
   std::unique_ptr<GCN> g;
@@ -915,6 +918,70 @@ long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indi
   return st == PGCN_OK ? n : st;
 }
 
+int pgcn_topk_queries_create(int n_nodes, long long n_queries, const int *anchor,
+                             const long long *exclude_ptr, const int *exclude_idx, int k,
+                             pgcn_topk_queries **out) {
+  return guarded([&] {
+    PGCN_CHECK(out, PGCN_E_INVALID, "topk_queries_create args");
+    validate_topk_queries(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k);
+    check_device();
+    auto h = std::make_unique<pgcn_topk_queries>();
+    h->q = std::make_unique<TopKQueriesDev>(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k);
+    *out = h.release();
+  });
+}
+
+int pgcn_topk_queries_destroy(pgcn_topk_queries *q) {
+  delete q;
+  return PGCN_OK;
+}
+
+long long pgcn_topk_queries_workspace(const pgcn_topk_queries *q) {
+  return q && q->q ? q->q->workspace() : (long long)PGCN_E_INVALID;
+}
+
+void pgcn_link_topk_tile(int *queries_per_block, int *candidates_per_tile, int *k_max) {
+  if (queries_per_block) *queries_per_block = kRankTQ;
+  if (candidates_per_tile) *candidates_per_tile = kRankTC;
+  if (k_max) *k_max = kTopKMax;
+}
+
+int pgcn_link_topk_splits(long long n_queries, int n_nodes) {
+  return topk_splits(n_queries, n_nodes);
+}
+
+int pgcn_link_topk_chunk(void) { return kTopKChunk; }
+
+int pgcn_link_topk(const pgcn_topk_queries *q, const float *H, int ld_h, int d, int *idx,
+                   float *score, void *stream) {
+  return guarded([&] {
+    check_link_dims(d, {ld_h}, {});
+    PGCN_CHECK(q && q->q && H && aligned16(H), PGCN_E_INVALID,
+               "link_topk: null or misaligned argument");
+    PGCN_CHECK(q->q->queries().n_queries == 0 || (idx && score), PGCN_E_INVALID,
+               "link_topk: idx and score [n_queries][k]");
+    check_device();
+    launch_link_topk(q->q->queries(), H, ld_h, d, idx, score, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+long long pgcn_debug_topk_filter(int n_nodes, const int *indptr, const int *indices,
+                                 long long n_pairs, const int *pair_src, const int *pair_dst,
+                                 const int *pair_label, const int *pair_split, long long m,
+                                 const int *nodes, int side, int filtered, long long *n_exclude,
+                                 long long *ptr, int *idx) {
+  const int st = guarded([&] {
+    const TopKFilterHost f = build_topk_filter(n_nodes, indptr, indices, n_pairs, pair_src,
+                                               pair_dst, pair_label, pair_split, m, nodes, side,
+                                               filtered);
+    if (n_exclude) *n_exclude = (long long)f.idx.size();
+    if (ptr) std::memcpy(ptr, f.ptr.data(), f.ptr.size() * sizeof(long long));
+    if (idx && !f.idx.empty()) std::memcpy(idx, f.idx.data(), f.idx.size() * sizeof(int));
+  });
+  return st == PGCN_OK ? m : st;
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -1355,6 +1422,14 @@ long long pgcn_gcn_link_ranks(pgcn_gcn *g, int split, int side, int filtered, lo
     n = g->g->link_ranks(split, side, filtered, greater, equal);
   });
   return st == PGCN_OK ? n : st;
+}
+long long pgcn_gcn_top_links(pgcn_gcn *g, const int *nodes, long long m, int k, int side,
+                             int filtered, int *idx, float *score) {
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_top_links: null engine");
+    g->g->top_links(nodes, m, k, side, filtered, idx, score);
+  });
+  return st == PGCN_OK ? m : st;
 }
 int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m,
                          float *scores) {

@@ -2056,6 +2056,37 @@ long long GCN::link_ranks(int split, int side, int filtered, long long *greater,
   return Q;
 }
 
+void GCN::top_links(const int *nodes, long long m, int k, int side, int filtered, int *idx,
+                    float *score) {
+  PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "top_links: not a link engine");
+  PGCN_CHECK(m >= 0 && (m == 0 || (nodes && idx && score)) && k >= 1 && k <= kTopKMax &&
+                 (side == 0 || side == 1) && (filtered == 0 || filtered == 1),
+             PGCN_E_INVALID, "top_links: nodes, idx, score; 1 <= k <= 128, side 0 / 1, filtered 0 / 1");
+  for (long long i = 0; i < m; i++)
+    PGCN_CHECK(nodes[i] >= 0 && nodes[i] < params.num_nodes, PGCN_E_INVALID,
+               "top_links: node out of range");
+  if (m == 0) return;
+  predict_forward();
+  const Variable &h = *link_embed;
+  for (long long b = 0; b < m; b += kTopKChunk) {
+    const long long c = std::min<long long>(kTopKChunk, m - b);
+    // (host work, allocations and blocking copies; the forward's output stays where it is)
+    const TopKFilterHost f = build_topk_filter(
+        params.num_nodes, rank_graph_.indptr.data(), rank_graph_.indices.data(), num_pairs_,
+        rank_pairs_[0].data(), rank_pairs_[1].data(), rank_pairs_[2].data(),
+        rank_pairs_[3].data(), c, nodes + b, side, filtered);
+    const TopKQueriesDev q(params.num_nodes, c, nodes + b, filtered ? f.ptr.data() : nullptr,
+                           f.idx.data(), k);
+    DeviceBuffer<int> di((size_t)c * k);
+    DeviceBuffer<float> ds((size_t)c * k);
+    launch_link_topk(q.queries(), h.dev_data.get(), h.ld, params.output_dim, di.get(), ds.get(),
+                     stream.get());
+    sync();
+    di.download(idx + b * k, (size_t)c * k);
+    ds.download(score + b * k, (size_t)c * k);
+  }
+}
+
 void GCN::confusion(int split, long long *counts) {
   PGCN_CHECK(split >= 1 && split <= 3 && counts, PGCN_E_INVALID, "confusion: split 1, 2 or 3");
   PGCN_CHECK(!params.multilabel, PGCN_E_INVALID,

@@ -174,6 +174,11 @@ class GCN {
   // lists): their number, and with outputs their greater / equal counts.  Both outputs null: the
   // number only, nothing runs.  The query set of a (split, side, filtered) is built once
   long long link_ranks(int split, int side, int filtered, long long *greater, long long *equal);
+  // the same forward, then launch_link_topk over the output embedding for m anchor nodes: idx /
+  // score [m][k] on the host (side, filtered: build_topk_filter's lists).  kTopKChunk queries at a
+  // time, the query set and the device outputs of a chunk freed after it
+  void top_links(const int *nodes, long long m, int k, int side, int filtered, int *idx,
+                 float *score);
   long long adam_steps() const { return optimizer.steps(); }
   void set_profile(bool on);
   void profile_read_mm(double *ms, long long *calls, double *flops);  // XW contractions

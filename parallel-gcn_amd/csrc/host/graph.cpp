@@ -849,74 +849,166 @@ void validate_rank_queries(int n, long long n_queries, const int *anchor, const 
   }
 }
 
+namespace {
+// The per-anchor lists of the ranking filter and of top-K's exclude lists: the anchor, its
+// neighbours by side and its known links, ascending and deduplicated.  The constructor validates
+// the CSR and the pair list.
+class AnchorLists {
+ public:
+  AnchorLists(int n, const int *indptr, const int *indices, long long n_pairs, const int *pair_src,
+              const int *pair_dst, const int *pair_label, const int *pair_split, int side,
+              int filtered, const char *what) {
+    PGCN_CHECK(n >= 1 && indptr && n_pairs >= 0 && n_pairs <= INT_MAX &&
+                   (n_pairs == 0 || (pair_src && pair_dst && pair_label && pair_split)),
+               PGCN_E_INVALID, std::string(what) + ": n >= 1, a CSR and the four pair arrays");
+    PGCN_CHECK((side == 0 || side == 1) && (filtered == 0 || filtered == 1), PGCN_E_INVALID,
+               std::string(what) + ": side 0 / 1, filtered 0 / 1");
+    PGCN_CHECK(indptr[0] == 0, PGCN_E_INVALID, std::string(what) + ": indptr[0] must be 0");
+    for (int i = 0; i < n; i++)
+      PGCN_CHECK(indptr[i + 1] >= indptr[i], PGCN_E_INVALID,
+                 std::string(what) + ": indptr must ascend");
+    const int nnz = indptr[n];
+    PGCN_CHECK(nnz == 0 || indices, PGCN_E_INVALID, std::string(what) + ": indices");
+    for (int k = 0; k < nnz; k++)
+      PGCN_CHECK(indices[k] >= 0 && indices[k] < n, PGCN_E_INVALID,
+                 std::string(what) + ": column out of range");
+    validate_pairs(n, n_pairs, pair_src, pair_dst);
+    anc = side == 0 ? pair_src : pair_dst;
+    oth = side == 0 ? pair_dst : pair_src;
+    if (!filtered) return;
+
+    // the neighbours by anchor: the CSR as given (side 0) or its transpose (side 1)
+    nptr_ = indptr;
+    nidx_ = indices;
+    if (side == 1) {
+      tptr_.assign((size_t)n + 1, 0);
+      for (int k = 0; k < nnz; k++) tptr_[(size_t)indices[k] + 1]++;
+      for (int i = 0; i < n; i++) tptr_[(size_t)i + 1] += tptr_[(size_t)i];
+      tidx_.resize((size_t)nnz);
+      std::vector<int> fill(tptr_.begin(), tptr_.end() - 1);
+      for (int i = 0; i < n; i++)
+        for (int k = indptr[i]; k < indptr[i + 1]; k++)
+          tidx_[(size_t)fill[(size_t)indices[k]]++] = i;
+      nptr_ = tptr_.data();
+      nidx_ = tidx_.data();
+    }
+    // the known links by anchor: every positive pair of any split
+    pptr_.assign((size_t)n + 1, 0);
+    for (long long e = 0; e < n_pairs; e++)
+      if (pair_label[e] == 1) pptr_[(size_t)anc[e] + 1]++;
+    for (int i = 0; i < n; i++) pptr_[(size_t)i + 1] += pptr_[(size_t)i];
+    pidx_.resize((size_t)pptr_[(size_t)n]);
+    std::vector<long long> fill(pptr_.begin(), pptr_.end() - 1);
+    for (long long e = 0; e < n_pairs; e++)
+      if (pair_label[e] == 1) pidx_[(size_t)fill[(size_t)anc[e]]++] = oth[e];
+  }
+  // anchor a's list (a filtered set only)
+  const std::vector<int> &of(int a) {
+    list_.clear();
+    list_.push_back(a);
+    list_.insert(list_.end(), nidx_ + nptr_[a], nidx_ + nptr_[a + 1]);
+    list_.insert(list_.end(), pidx_.begin() + pptr_[(size_t)a], pidx_.begin() + pptr_[(size_t)a + 1]);
+    std::sort(list_.begin(), list_.end());
+    list_.erase(std::unique(list_.begin(), list_.end()), list_.end());
+    return list_;
+  }
+  const int *anc = nullptr, *oth = nullptr;  // the pairs' endpoints in the anchor's / other role
+
+ private:
+  std::vector<int> tptr_, tidx_, pidx_, list_;
+  std::vector<long long> pptr_;
+  const int *nptr_ = nullptr, *nidx_ = nullptr;
+};
+}  // namespace
+
 RankFilterHost build_rank_filter(int n, const int *indptr, const int *indices, long long n_pairs,
                                  const int *pair_src, const int *pair_dst, const int *pair_label,
                                  const int *pair_split, int split, int side, int filtered) {
-  PGCN_CHECK(n >= 1 && indptr && n_pairs >= 0 && n_pairs <= INT_MAX &&
-                 (n_pairs == 0 || (pair_src && pair_dst && pair_label && pair_split)),
-             PGCN_E_INVALID, "rank_filter: n >= 1, a CSR and the four pair arrays");
-  PGCN_CHECK(split >= 1 && split <= 3 && (side == 0 || side == 1) &&
-                 (filtered == 0 || filtered == 1),
-             PGCN_E_INVALID, "rank_filter: split 1..3, side 0 / 1, filtered 0 / 1");
-  PGCN_CHECK(indptr[0] == 0, PGCN_E_INVALID, "rank_filter: indptr[0] must be 0");
-  for (int i = 0; i < n; i++)
-    PGCN_CHECK(indptr[i + 1] >= indptr[i], PGCN_E_INVALID, "rank_filter: indptr must ascend");
-  const int nnz = indptr[n];
-  PGCN_CHECK(nnz == 0 || indices, PGCN_E_INVALID, "rank_filter: indices");
-  for (int k = 0; k < nnz; k++)
-    PGCN_CHECK(indices[k] >= 0 && indices[k] < n, PGCN_E_INVALID,
-               "rank_filter: column out of range");
-  validate_pairs(n, n_pairs, pair_src, pair_dst);
-  const int *anc = side == 0 ? pair_src : pair_dst, *oth = side == 0 ? pair_dst : pair_src;
-
+  PGCN_CHECK(split >= 1 && split <= 3, PGCN_E_INVALID, "rank_filter: split 1..3");
+  AnchorLists lists(n, indptr, indices, n_pairs, pair_src, pair_dst, pair_label, pair_split, side,
+                    filtered, "rank_filter");
   RankFilterHost out;
   for (long long e = 0; e < n_pairs; e++)
     if (pair_label[e] == 1 && pair_split[e] == split) {
-      out.anchor.push_back(anc[e]);
-      out.target.push_back(oth[e]);
+      out.anchor.push_back(lists.anc[e]);
+      out.target.push_back(lists.oth[e]);
     }
   out.ptr.assign(out.anchor.size() + 1, 0);
   if (!filtered) return out;
-
-  // the neighbours by anchor: the CSR as given (side 0) or its transpose (side 1)
-  std::vector<int> tptr, tidx;
-  const int *nptr = indptr, *nidx = indices;
-  if (side == 1) {
-    tptr.assign((size_t)n + 1, 0);
-    for (int k = 0; k < nnz; k++) tptr[(size_t)indices[k] + 1]++;
-    for (int i = 0; i < n; i++) tptr[(size_t)i + 1] += tptr[(size_t)i];
-    tidx.resize((size_t)nnz);
-    std::vector<int> fill(tptr.begin(), tptr.end() - 1);
-    for (int i = 0; i < n; i++)
-      for (int k = indptr[i]; k < indptr[i + 1]; k++) tidx[(size_t)fill[(size_t)indices[k]]++] = i;
-    nptr = tptr.data();
-    nidx = tidx.data();
-  }
-  // the known links by anchor: every positive pair of any split
-  std::vector<long long> pptr((size_t)n + 1, 0);
-  for (long long e = 0; e < n_pairs; e++)
-    if (pair_label[e] == 1) pptr[(size_t)anc[e] + 1]++;
-  for (int i = 0; i < n; i++) pptr[(size_t)i + 1] += pptr[(size_t)i];
-  std::vector<int> pidx((size_t)pptr[(size_t)n]);
-  {
-    std::vector<long long> fill(pptr.begin(), pptr.end() - 1);
-    for (long long e = 0; e < n_pairs; e++)
-      if (pair_label[e] == 1) pidx[(size_t)fill[(size_t)anc[e]]++] = oth[e];
-  }
-  std::vector<int> list;
   for (size_t q = 0; q < out.anchor.size(); q++) {
-    const int a = out.anchor[q], t = out.target[q];
-    list.clear();
-    list.push_back(a);
-    list.insert(list.end(), nidx + nptr[a], nidx + nptr[a + 1]);
-    list.insert(list.end(), pidx.begin() + pptr[(size_t)a], pidx.begin() + pptr[(size_t)a + 1]);
-    std::sort(list.begin(), list.end());
-    list.erase(std::unique(list.begin(), list.end()), list.end());
-    for (int v : list)
+    const int t = out.target[q];
+    for (int v : lists.of(out.anchor[q]))
       if (v != t) out.idx.push_back(v);
     out.ptr[q + 1] = (long long)out.idx.size();
   }
   return out;
+}
+
+TopKFilterHost build_topk_filter(int n, const int *indptr, const int *indices, long long n_pairs,
+                                 const int *pair_src, const int *pair_dst, const int *pair_label,
+                                 const int *pair_split, long long m, const int *nodes, int side,
+                                 int filtered) {
+  PGCN_CHECK(m >= 0 && m <= INT_MAX && (m == 0 || nodes), PGCN_E_INVALID,
+             "topk_filter: 0 <= m within an int, nodes");
+  AnchorLists lists(n, indptr, indices, n_pairs, pair_src, pair_dst, pair_label, pair_split, side,
+                    filtered, "topk_filter");
+  for (long long q = 0; q < m; q++)
+    PGCN_CHECK(nodes[q] >= 0 && nodes[q] < n, PGCN_E_INVALID, "topk_filter: node out of range");
+  TopKFilterHost out;
+  out.ptr.assign((size_t)m + 1, 0);
+  if (!filtered) return out;
+  for (long long q = 0; q < m; q++) {
+    const std::vector<int> &l = lists.of(nodes[q]);
+    out.idx.insert(out.idx.end(), l.begin(), l.end());
+    out.ptr[(size_t)q + 1] = (long long)out.idx.size();
+  }
+  return out;
+}
+
+void validate_topk_queries(int n, long long n_queries, const int *anchor,
+                           const long long *exclude_ptr, const int *exclude_idx, int k) {
+  PGCN_CHECK(n >= 1 && n_queries >= 0 && n_queries <= INT_MAX && (n_queries == 0 || anchor),
+             PGCN_E_INVALID, "topk_queries: n >= 1, 0 <= n_queries within an int, anchor");
+  PGCN_CHECK(k >= 1 && k <= kTopKMax, PGCN_E_INVALID, "topk_queries: 1 <= k <= 128");
+  for (long long e = 0; e < n_queries; e++)
+    PGCN_CHECK(anchor[e] >= 0 && anchor[e] < n, PGCN_E_INVALID,
+               "topk_queries: anchor out of range");
+  if (!exclude_ptr) return;
+  PGCN_CHECK(exclude_ptr[0] == 0, PGCN_E_INVALID, "topk_queries: exclude_ptr[0] must be 0");
+  for (long long e = 0; e < n_queries; e++) {
+    const long long b = exclude_ptr[e], en = exclude_ptr[e + 1];
+    PGCN_CHECK(en >= b && en - b <= n && (en == b || exclude_idx), PGCN_E_INVALID,
+               "topk_queries: exclude_ptr must ascend, a list holds at most n entries");
+    for (long long i = b; i < en; i++) {
+      const int f = exclude_idx[i];
+      PGCN_CHECK(f >= 0 && f < n, PGCN_E_INVALID, "topk_queries: exclude entry out of range");
+      PGCN_CHECK(i == b || exclude_idx[i - 1] < f, PGCN_E_INVALID,
+                 "topk_queries: an exclude list must be strictly ascending");
+    }
+  }
+}
+
+TopKQueriesDev::TopKQueriesDev(int n, long long n_queries, const int *anchor,
+                               const long long *exclude_ptr, const int *exclude_idx, int k) {
+  auto up = [](auto &buf, const auto *host, size_t count) {
+    buf.allocate(std::max<size_t>(count, 1));
+    if (count) buf.upload(host, count);
+  };
+  up(anchor_, anchor, (size_t)n_queries);
+  ws_bytes_ = topk_workspace_bytes(n_queries, n, k);
+  ws_.allocate(std::max<size_t>((size_t)ws_bytes_ / sizeof(unsigned long long), 1));
+  q_.n = n;
+  q_.n_queries = (int)n_queries;
+  q_.k = k;
+  q_.splits = topk_splits(n_queries, n);
+  q_.anchor = anchor_.get();
+  q_.ws = ws_.get();
+  if (exclude_ptr) {
+    up(xptr_, exclude_ptr, (size_t)n_queries + 1);
+    up(xidx_, exclude_idx, (size_t)exclude_ptr[n_queries]);
+    q_.exclude_ptr = xptr_.get();
+    q_.exclude_idx = xidx_.get();
+  }
 }
 
 RankQueriesDev::RankQueriesDev(int n, long long n_queries, const int *anchor, const int *target,

@@ -277,6 +277,20 @@ RankFilterHost build_rank_filter(int n, const int *indptr, const int *indices, l
                                  const int *pair_src, const int *pair_dst, const int *pair_label,
                                  const int *pair_split, int split, int side, int filtered);
 
+// build_rank_filter's list without its "minus the target", for m anchor nodes (link top-K's
+// exclude lists): per node the ascending, deduplicated union of the node, its neighbours in the CSR
+// (by side, as above) and the other endpoints of every label == 1 pair of any split that has the
+// node in the anchor's role.  Without `filtered`: ptr all zero, idx empty.  PGCN_E_INVALID for a
+// CSR or a pair list out of range or a node outside [0, n).
+struct TopKFilterHost {
+  std::vector<long long> ptr;  // [m + 1]
+  std::vector<int> idx;
+};
+TopKFilterHost build_topk_filter(int n, const int *indptr, const int *indices, long long n_pairs,
+                                 const int *pair_src, const int *pair_dst, const int *pair_label,
+                                 const int *pair_split, long long m, const int *nodes, int side,
+                                 int filtered);
+
 // A query set on the device for k_rank.hip, of arrays validate_rank_queries accepted.  It owns the
 // thresholds a rank call writes, so two calls on one set must not overlap.  Construction is host
 // work and blocking copies: not inside a stream capture.
@@ -291,6 +305,30 @@ class RankQueriesDev {
   DeviceBuffer<int> anchor_, target_, fidx_;
   DeviceBuffer<long long> fptr_;
   DeviceBuffer<float> thr_;
+};
+
+// A top-K query set as k_topk.hip takes it: PGCN_E_INVALID for an anchor outside [0, n), a query
+// count beyond an int, k outside [1, kTopKMax], an exclude list that is not strictly ascending or
+// has an entry outside [0, n) (it may hold the anchor).  exclude_ptr null: no lists.  Host only.
+void validate_topk_queries(int n, long long n_queries, const int *anchor,
+                           const long long *exclude_ptr, const int *exclude_idx, int k);
+
+// A top-K query set on the device, of arrays validate_topk_queries accepted.  It owns every byte a
+// call needs (topk_workspace_bytes), so two calls on one set must not overlap.  Construction is
+// host work and blocking copies: not inside a stream capture.
+class TopKQueriesDev {
+ public:
+  TopKQueriesDev(int n, long long n_queries, const int *anchor, const long long *exclude_ptr,
+                 const int *exclude_idx, int k);
+  const TopKQueries &queries() const { return q_; }
+  long long workspace() const { return ws_bytes_; }
+
+ private:
+  TopKQueries q_;
+  long long ws_bytes_ = 0;
+  DeviceBuffer<int> anchor_, xidx_;
+  DeviceBuffer<long long> xptr_;
+  DeviceBuffer<unsigned long long> ws_;
 };
 
 }  // namespace pgcn

@@ -27,42 +27,16 @@
 //   k_rank_filter: a wave per query walks the filter list F_e, each lane the chain of one entry,
 //       and takes what the sweep counted for it out of the two counts.
 // Every count is an integer sum: two calls give the same bits.
+// The chain, the staging and the MFMA loop live in rank_sweep.hpp, shared with k_topk.hip.
 #include <algorithm>
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "rank_sweep.hpp"
 
 #pragma clang fp contract(off)
 
 namespace pgcn {
-
-namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kRankThreads = 256;
-
-// r(a, v) over d columns of two rows (16-byte aligned, readable up to round_up4(d))
-__device__ __forceinline__ float chain_score(const float *__restrict__ a,
-                                             const float *__restrict__ b, int d) {
-  float s = 0.0f;
-  int c = 0;
-  for (; c + 4 <= d; c += 4) {
-    const float4 x = *reinterpret_cast<const float4 *>(a + c);
-    const float4 y = *reinterpret_cast<const float4 *>(b + c);
-    s = __fmaf_rn(x.x, y.x, s);
-    s = __fmaf_rn(x.y, y.y, s);
-    s = __fmaf_rn(x.z, y.z, s);
-    s = __fmaf_rn(x.w, y.w, s);
-  }
-  if (c < d) {
-    const float4 x = *reinterpret_cast<const float4 *>(a + c);
-    const float4 y = *reinterpret_cast<const float4 *>(b + c);
-    s = __fmaf_rn(x.x, y.x, s);
-    if (c + 1 < d) s = __fmaf_rn(x.y, y.y, s);
-    if (c + 2 < d) s = __fmaf_rn(x.z, y.z, s);
-  }
-  return s;
-}
-}  // namespace
 
 __global__ __launch_bounds__(kRankThreads) void k_rank_scores(
     const int *__restrict__ src, const int *__restrict__ dst, long long m,
@@ -78,39 +52,15 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_scores(
   }
 }
 
-namespace {
-// the float4 at columns 4 ch .. 4 ch + 3 into a split row: even columns at [0, HD), odd at [HD, 2 HD)
-template <int HD>
-__device__ __forceinline__ void put_split(float *row, int ch, float4 v) {
-  *reinterpret_cast<float2 *>(row + 2 * ch) = make_float2(v.x, v.z);
-  *reinterpret_cast<float2 *>(row + HD + 2 * ch) = make_float2(v.y, v.w);
-}
-
-// the float4 at chunk ch of row `node` of H (always loaded, from a clamped address), zero where
-// the row or the column does not exist
-__device__ __forceinline__ float4 load_chunk(const float *__restrict__ H, int ld_h, int d, int n,
-                                             int node, int ch) {
-  const int c0 = 4 * ch, last = ((d + 3) / 4 - 1) * 4;
-  const float4 r = *reinterpret_cast<const float4 *>(H + (long long)min(node, n - 1) * ld_h +
-                                                     min(c0, last));
-  const bool row_on = node < n;
-  float4 v;
-  v.x = row_on && c0 < d ? r.x : 0.0f;
-  v.y = row_on && c0 + 1 < d ? r.y : 0.0f;
-  v.z = row_on && c0 + 2 < d ? r.z : 0.0f;
-  v.w = row_on && c0 + 3 < d ? r.w : 0.0f;
-  return v;
-}
-}  // namespace
-
 // NV: float4s a thread stages per candidate tile; LDS rows hold W = 16 NV >= round_up8(d) columns
 template <int NV>
 __global__ __launch_bounds__(kRankThreads) void k_rank_sweep(
     const int *__restrict__ anchor, const int *__restrict__ target, const float *__restrict__ thr,
     int Q, int n, const float *__restrict__ H, int ld_h, int d, int tiles, int tiles_per_split,
     unsigned *__restrict__ greater, unsigned *__restrict__ equal) {
-  constexpr int W = 16 * NV, S = W + 4, HD = W / 2, CPR = 4 * NV;
-  __shared__ float lds[(kRankTQ + 2 * kRankTC) * S];
+  using L = SweepLds<NV>;
+  constexpr int S = L::S, HD = L::HD;
+  __shared__ float lds[L::kFloats];
   float *As = lds, *Bs = lds + kRankTQ * S;
 
   const int tid = threadIdx.x, lane = tid % kWave, wave = tid / kWave;
@@ -121,24 +71,10 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_sweep(
   if (t_begin >= t_end) return;
 
   // the anchors' rows, once
-#pragma unroll
-  for (int i = 0; i < 2 * NV; i++) {
-    const int idx = i * kRankThreads + tid, row = idx / CPR, ch = idx % CPR, q = q0 + row;
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (q < Q) v = load_chunk(H, ld_h, d, n, anchor[q], ch);
-    put_split<HD>(As + row * S, ch, v);
-  }
+  sweep_gather_anchors<NV>(As, anchor, q0, Q, H, ld_h, d, n, tid);
   float4 stage[NV];
-#pragma unroll
-  for (int i = 0; i < NV; i++) {
-    const int idx = i * kRankThreads + tid;
-    stage[i] = load_chunk(H, ld_h, d, n, t_begin * kRankTC + idx / CPR, idx % CPR);
-  }
-#pragma unroll
-  for (int i = 0; i < NV; i++) {
-    const int idx = i * kRankThreads + tid;
-    put_split<HD>(Bs + (idx / CPR) * S, idx % CPR, stage[i]);
-  }
+  sweep_load_tile<NV>(stage, H, ld_h, d, n, t_begin, tid);
+  sweep_store_tile<NV>(Bs, stage, tid);
 
   // accumulator register r of this lane is query row (r & 3) + 8 (r >> 2) + 4 half of the wave's 32
   float th[16];
@@ -162,30 +98,10 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_sweep(
   for (int t = t_begin; t < t_end; t++) {
     const int cur = (t - t_begin) & 1;
     const bool more = t + 1 < t_end;
-    if (more) {
-#pragma unroll
-      for (int i = 0; i < NV; i++) {
-        const int idx = i * kRankThreads + tid;
-        stage[i] = load_chunk(H, ld_h, d, n, (t + 1) * kRankTC + idx / CPR, idx % CPR);
-      }
-    }
+    if (more) sweep_load_tile<NV>(stage, H, ld_h, d, n, t + 1, tid);
     const float *b_row = Bs + cur * (kRankTC * S) + col * S + half * HD;
     f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; r++) acc0[r] = acc1[r] = 0.0f;
-    for (int j = 0; j < groups; j++) {
-      const float4 a = *reinterpret_cast<const float4 *>(a_row + 4 * j);
-      const float4 b0 = *reinterpret_cast<const float4 *>(b_row + 4 * j);
-      const float4 b1 = *reinterpret_cast<const float4 *>(b_row + 32 * S + 4 * j);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0.x, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b0.y, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b0.z, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc1, 0, 0, 0);
-    }
+    sweep_mfma<S>(a_row, b_row, groups, acc0, acc1);
     const int v0 = t * kRankTC + col, v1 = v0 + 32;
     const bool masked = (t + 1) * kRankTC > n ||
                         __ballot((unsigned)(my_t - t * kRankTC) < (unsigned)kRankTC) != 0ull;
@@ -204,14 +120,7 @@ __global__ __launch_bounds__(kRankThreads) void k_rank_sweep(
         ce[r] += (ok0 && acc0[r] == th[r] ? 1u : 0u) + (ok1 && acc1[r] == th[r] ? 1u : 0u);
       }
     }
-    if (more) {
-      float *nxt = Bs + (cur ^ 1) * (kRankTC * S);
-#pragma unroll
-      for (int i = 0; i < NV; i++) {
-        const int idx = i * kRankThreads + tid;
-        put_split<HD>(nxt + (idx / CPR) * S, idx % CPR, stage[i]);
-      }
-    }
+    if (more) sweep_store_tile<NV>(Bs + (cur ^ 1) * (kRankTC * S), stage, tid);
     __syncthreads();
   }
 
@@ -298,10 +207,7 @@ void launch_link_rank(const RankQueries &q, const float *H, int ld_h, int d, uns
 #define RANK_SWEEP(NV)                                                                        \
   PGCN_LAUNCH((k_rank_sweep<NV>), grid, dim3(kRankThreads), 0, s, q.anchor, q.target, q.thr, Q, \
               q.n, H, ld_h, d, tiles, tps, greater, equal)
-  if (d <= 16) RANK_SWEEP(1);
-  else if (d <= 32) RANK_SWEEP(2);
-  else if (d <= 64) RANK_SWEEP(4);
-  else RANK_SWEEP(8);
+  PGCN_SWEEP_BY_WIDTH(d, RANK_SWEEP);
 #undef RANK_SWEEP
   if (q.filter_ptr) {
     note_path(KP_RANK_FILTER);

@@ -17,7 +17,7 @@ enum KernelPath {
   KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS,
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
   KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_RANK_SWEEP, KP_RANK_FILTER,
-  KP_COUNT
+  KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -501,6 +501,31 @@ void launch_rank_scores(const int *src, const int *dst, long long m, const float
 // blocks x rank_splits; integer atomics), the filter correction (a wave per query; with lists)
 void launch_link_rank(const RankQueries &q, const float *H, int ld_h, int d, unsigned *greater,
                       unsigned *equal, hipStream_t s);
+// ---- link prediction: 1-vs-all top-K retrieval (k_topk.hip) ------------------------------------
+// Per query (anchor a_e, ascending exclude list X_e) the k candidates v in [0, n) \ X_e first in
+// the order "higher r(a_e, v), then lower v"; the positions from the candidate count on hold idx -1,
+// score -inf.  A query set on the device (TopKQueriesDev, host/graph.hpp) owns the workspace: per
+// (query, split) an append buffer of topk_cap(k) 64-bit keys.
+constexpr int kTopKMax = 128;
+constexpr int kTopKChunk = 16384;  // queries per call of the engine's top_links
+struct TopKQueries {
+  int n = 0, n_queries = 0, k = 0, splits = 0;
+  const int *anchor = nullptr;
+  const long long *exclude_ptr = nullptr;  // [n_queries + 1], null: no lists
+  const int *exclude_idx = nullptr;
+  void *ws = nullptr;  // topk_workspace_bytes(n_queries, n, k)
+};
+// candidate splits of the sweep's grid (rank_splits' ranges, the ones that hold a tile): a function
+// of (Q, n) only
+int topk_splits(long long Q, int n);
+// keys per append buffer: 128 for k <= 64, 256 above (>= k + kRankTC)
+int topk_cap(int k);
+// Q * topk_splits(Q, n) * topk_cap(k) * 8
+long long topk_workspace_bytes(long long Q, int n, int k);
+// idx / score [n_queries][k].  Two launches whatever the data: the sweep (query blocks x
+// topk_splits), the merge (a wave per query)
+void launch_link_topk(const TopKQueries &q, const float *H, int ld_h, int d, int *idx, float *score,
+                      hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [rank=1|<file>]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -37,6 +37,11 @@
 // (pgcn_gcn_link_ranks; mean ties) for both sides: `rank side=dst queries=.. mrr=.. hits@10=..
 // hits@50=.. hits@100=.. side=src ...`; rank=<file> also writes `src dst greater equal` per test
 // positive pair for the dst side.
+// recommend=<file> [topk=<K>, default 10, at most 128] (with link=): after the run, one line per
+// node `node v1 s1 v2 s2 ...` with the K best destinations for the node as a source
+// (pgcn_gcn_top_links: dst side, filtered -- the node, its neighbours and its known links are left
+// out -- best first, ties to the lower index; a node with fewer than K candidates gets a shorter
+// line).
 #include <algorithm>
 #include <vector>
 #include <cstdio>
@@ -140,7 +145,8 @@ int main(int argc, char **argv) {
   std::string root = ".", file;
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
-  std::string load, save, predict, rank;
+  std::string load, save, predict, rank, recommend;
+  int topk = 10;
   int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
   int root_weight = -1;
@@ -168,6 +174,8 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "link=", 5)) link = argv[i] + 5;
     if (!std::strncmp(argv[i], "embed=", 6)) embed_arg = std::atoi(argv[i] + 6);
     if (!std::strncmp(argv[i], "rank=", 5)) rank = argv[i] + 5;
+    if (!std::strncmp(argv[i], "recommend=", 10)) recommend = argv[i] + 10;
+    if (!std::strncmp(argv[i], "topk=", 5)) topk = std::atoi(argv[i] + 5);
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -318,6 +326,27 @@ int main(int argc, char **argv) {
     }
     printf("\n");
     if (st != PGCN_OK) fprintf(stderr, "ranking failed: %s\n", pgcn_status_string(st));
+  }
+  if (st == PGCN_OK && !recommend.empty() && p.link_decoder) {
+    const long long m = view.num_nodes;
+    std::vector<int> nodes((size_t)m), idx((size_t)m * (size_t)std::max(topk, 0));
+    std::vector<float> score(idx.size());
+    for (long long i = 0; i < m; i++) nodes[(size_t)i] = (int)i;
+    const long long got = pgcn_gcn_top_links(g, nodes.data(), m, topk, 0, 1, idx.data(), score.data());
+    FILE *f = got >= 0 ? std::fopen(recommend.c_str(), "w") : nullptr;
+    if (!f) {
+      fprintf(stderr, "cannot write recommendations to %s%s%s\n", recommend.c_str(),
+              got < 0 ? ": " : "", got < 0 ? pgcn_status_string((int)got) : "");
+      st = got < 0 ? (int)got : PGCN_E_IO;
+    } else {
+      for (long long i = 0; i < m; i++) {
+        fprintf(f, "%lld", i);
+        for (int j = 0; j < topk && idx[(size_t)(i * topk + j)] >= 0; j++)
+          fprintf(f, " %d %.6f", idx[(size_t)(i * topk + j)], score[(size_t)(i * topk + j)]);
+        fprintf(f, "\n");
+      }
+      std::fclose(f);
+    }
   }
   pgcn_gcn_destroy(g);
   pgcn_dataset_free(ds);
