@@ -386,6 +386,33 @@ int pgcn_link_score_fwd(const pgcn_links *l, const float *H, int ld_h, int d, fl
 int pgcn_link_score_bwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *G,
                         int ld_g /* dLoss/dscore = G[e][0] */, float *dH, int ld_dh,
                         void *stream);
+/* The Hadamard-MLP pair decoder over the same handle (k_link_mlp.hip).  With z_e = H[src_e] o
+ * H[dst_e] over d columns and ONE packed parameter tensor P [d + 3][ld_p] -- rows 0 .. d - 1: W1
+ * [d][h]; row d: b1; row d + 1: w2; row d + 2: {b2, 0, ...} --
+ *     pre_e[u] = b1[u] + sum_i z_e[i] W1[i][u],   score_e = b2 + sum_u w2[u] max(pre_e[u], 0).
+ *   pgcn_link_mlp_fwd, ONE launch: scores[e][0..3] = {score_e, 0, 0, 0}.  Persistent workgroups
+ *     keep W1 in LDS and walk pgcn_link_mlp_tile()-pair tiles with f32 MFMA; neither z nor the
+ *     hidden layer is written to memory.
+ *   pgcn_link_mlp_bwd, three launches, four when any list exceeds T: with G[e][0] =
+ *     dLoss/dscore_e, READ FOR EVERY PAIR (zero where a pair takes no part), every row of dH is
+ *     written as pgcn_link_score_bwd writes it (the incidence index decides which pairs reach dH)
+ *     and every element of dP [d + 3][ld_dp], zero where P holds padding.  ws: at least
+ *     pgcn_link_mlp_workspace(l, d, h) bytes of device memory, 16-byte aligned (host-only query:
+ *     the [E][round_up4(d)] pair gradients, one P-shaped partial block per workgroup, the segment
+ *     rows); two calls on one workspace must not overlap.
+ * 1 <= d, h <= 128; ld_h, ld_dh >= d, ld_p, ld_dp >= h, ld_s, ld_g >= 1, all multiples of 4; rows
+ * 16-byte aligned; padding columns of H and P may hold anything.  Anything else, a workspace that
+ * is too small included, is PGCN_E_INVALID before anything touches the device.  n_pairs == 0 (or
+ * n_nodes == 0) launches nothing, as pgcn_link_score_bwd: dH and dP are then left as they are (an
+ * engine never has such a list: pgcn_params.link_decoder needs at least one pair).  No float atomics:
+ * every summation order depends on (pair list, d, h) only, so two calls give the same bits. */
+void pgcn_link_mlp_tile(int *pairs_per_tile);
+long long pgcn_link_mlp_workspace(const pgcn_links *l, int d, int h); /* bytes, host only */
+int pgcn_link_mlp_fwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *P,
+                      int ld_p, int h, float *scores, int ld_s, void *stream);
+int pgcn_link_mlp_bwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *P,
+                      int ld_p, int h, const float *G, int ld_g, float *dH, int ld_dh, float *dP,
+                      int ld_dp, void *ws, long long ws_bytes, void *stream);
 /* host-only (no device): the incidence index pgcn_links_create would build -- ptr [n_nodes + 1],
  * pair and other [ptr[n_nodes]] (either may be NULL: call once for ptr, then again) */
 int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, const int *dst,
@@ -594,6 +621,19 @@ typedef struct {
    * one more variable, the last (index pgcn_gcn_num_vars - 1): scores [E][1]. */
   int link_decoder;
   int hidden_dims[PGCN_MAX_LAYERS];      /* n_layers - 1 */
+  /* The link decoder's hidden width (here, behind hidden_dims: the members around link_decoder
+   * keep their offsets).  0: the dot product above (the engine as it was, bit for
+   * bit).  1..128 with link_decoder == 1: the Hadamard-MLP decoder of pgcn_link_mlp_fwd with that
+   * many hidden units (one ReLU layer, no dropout: it draws nothing from the mask stream).  Its
+   * packed tensor P [output_dim + 3][round_up4(link_hidden)] is one more trainable variable and
+   * optimizer entry (decayed), directly before the scores (index pgcn_gcn_num_vars - 2); W1 and w2
+   * are Glorot-uniform, b1 = b2 = 0, drawn after every other variable, so a seed's encoder weights
+   * are the dot engine's.  pgcn_gcn_predict_links / _link_counts / _score_pairs run the MLP;
+   * pgcn_gcn_link_ranks and pgcn_gcn_top_links return PGCN_E_INVALID on such an engine (a 1-vs-all
+   * sweep over an MLP score is not the dot-product sweep: evaluate with pgcn_gcn_score_pairs over
+   * fixed candidate lists).  Anything else, link_hidden != 0 without a decoder included, is
+   * PGCN_E_INVALID. */
+  int link_hidden;
   float dropouts[PGCN_MAX_LAYERS];       /* n_layers */
   /* GraphSAGE layers.  aggregator: 0 = GCN's Â (the engine as it was, bit for bit), 1 = mean,
    * 2 = max; root_weight: 0 / 1, 1 only with aggregator != 0.  With H the layer's input as it
@@ -770,7 +810,7 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
  * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel), "readout" (the readout
  * mode, pgcn_params.readout) and "num_graphs" (its graph count; 0 without a readout),
- * "link_decoder" (pgcn_params.link_decoder) and "num_pairs" (its pair count; 0 without), and
+ * "link_decoder" (pgcn_params.link_decoder), "link_hidden" (pgcn_params.link_hidden) and "num_pairs" (its pair count; 0 without), and
  * "fused_norm_tails" (how many of them ran the ReLU / residual add /
  * Dropout behind them inside the LayerNorm kernel in the last training forward);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
@@ -915,6 +955,10 @@ int pgcn_checkpoint_readout(const char *path, int *mode, int *num_graphs);
  * _readout accept version 8. */
 #define PGCN_CKPT_LINKS 64
 int pgcn_checkpoint_links(const char *path, int *decoder, long long *num_pairs);
+/* Version 9 = version 8 with link_hidden (1..128) in the link block's second u32, which version 8
+ * requires to be 0; the payload gains the decoder tensor [output_dim + 3][round_up4(link_hidden)]
+ * and its two Adam moments behind the attention tensor's.  Host-only: 0 for versions 1-8. */
+int pgcn_checkpoint_link_hidden(const char *path, int *link_hidden);
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever

@@ -41,7 +41,7 @@ P = ctypes.POINTER
 class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("link_decoder", c_int),
-                ("hidden_dims", c_int * MAX_LAYERS),
+                ("hidden_dims", c_int * MAX_LAYERS), ("link_hidden", c_int),
                 ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
                 ("root_weight", c_int), ("epochs", c_int), ("readout", c_int),
                 ("early_stopping", c_int),
@@ -160,6 +160,12 @@ _sig("pgcn_links_slots", c_ll, c_void_p)
 _sig("pgcn_link_score_fwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_link_score_bwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
      c_int, c_void_p)
+_sig("pgcn_link_mlp_tile", None, P(c_int))
+_sig("pgcn_link_mlp_workspace", c_ll, c_void_p, c_int, c_int)
+_sig("pgcn_link_mlp_fwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+     c_int, c_void_p)
+_sig("pgcn_link_mlp_bwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+     c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p)
 _sig("pgcn_debug_links_incidence", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
      c_void_p, c_void_p)
 _sig("pgcn_rank_queries_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -225,6 +231,7 @@ _sig("pgcn_checkpoint_attention", c_int, ctypes.c_char_p, P(c_int), P(c_float))
 _sig("pgcn_checkpoint_sage", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_checkpoint_readout", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_checkpoint_links", c_int, ctypes.c_char_p, P(c_int), P(c_ll))
+_sig("pgcn_checkpoint_link_hidden", c_int, ctypes.c_char_p, P(c_int))
 _sig("pgcn_gcn_predict_links", c_ll, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_link_counts", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_gcn_score_pairs", c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p)
@@ -318,11 +325,19 @@ def _ptr(a):
     return a.ctypes.data_as(c_void_p)
 
 
+def _dptr(t):
+    """A device address: None, an int, or anything with data_ptr() (a torch tensor)."""
+    if t is None:
+        return None
+    return c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else int(t))
+
+
+
 KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gather", "out_xent",
                 "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
                 "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter",
-                "topk_sweep", "topk_merge")
+                "topk_sweep", "topk_merge", "link_mlp_fwd", "link_mlp_bwd")
 
 
 def path_counts(reset=False, thread=False):
@@ -558,6 +573,27 @@ class Links:
 
     def slots(self):
         return int(lib.pgcn_links_slots(self._h))
+
+    def mlp_workspace(self, d, h):
+        """Bytes of device workspace mlp_bwd needs at widths (d, h) (pgcn_link_mlp_workspace)."""
+        n = int(lib.pgcn_link_mlp_workspace(self._h, d, h))
+        if n < 0:
+            raise PgcnError(n, "link_mlp_workspace")
+        return n
+
+    def mlp_fwd(self, H, ld_h, d, P, ld_p, h, scores, ld_s, stream=None):
+        """The Hadamard-MLP decoder's scores (pgcn_link_mlp_fwd): H, P, scores are device
+        addresses (or objects with data_ptr()); scores[e][0..3] = {score_e, 0, 0, 0}."""
+        check(lib.pgcn_link_mlp_fwd(self._h, _dptr(H), ld_h, d, _dptr(P), ld_p, h, _dptr(scores),
+                                    ld_s, stream), "link_mlp_fwd")
+
+    def mlp_bwd(self, H, ld_h, d, P, ld_p, h, G, ld_g, dH, ld_dh, dP, ld_dp, ws, ws_bytes,
+                stream=None):
+        """Its backward (pgcn_link_mlp_bwd): G[e][0] = dLoss/dscore_e, read for every pair; every
+        row of dH and every element of dP is written; ws: mlp_workspace(d, h) device bytes."""
+        check(lib.pgcn_link_mlp_bwd(self._h, _dptr(H), ld_h, d, _dptr(P), ld_p, h, _dptr(G), ld_g,
+                                    _dptr(dH), ld_dh, _dptr(dP), ld_dp, _dptr(ws), ws_bytes,
+                                    stream), "link_mlp_bwd")
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value and lib is not None:
@@ -817,17 +853,23 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
                 learning_rate=0.01, weight_decay=5e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
                 multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
-                aggregator=None, root_weight=False, readout=None, link_decoder=None):
+                aggregator=None, root_weight=False, readout=None, link_decoder=None,
+                link_hidden=0):
     """aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
     own row through its own half of a [d_in][2 d_l] weight (with an aggregator only).
     readout: None (node classification), "sum", "mean" or "max": graph classification over the
     graphs attached with Dataset.set_graphs / load_graphs (not with multilabel).
+    link_hidden: 0 (the dot product) or 1..128 with link_decoder="dot": the Hadamard-MLP decoder
+    of that hidden width, one more trainable variable directly before the scores.
     link_decoder: None or "dot": link prediction over the pairs attached with Dataset.set_links /
     load_links, output_dim being the embedding width (not with multilabel or readout)."""
     if link_decoder not in LINK_DECODERS:
         raise ValueError("link_decoder must be 'dot' or None")
     if LINK_DECODERS[link_decoder] and (multilabel or READOUTS.get(readout)):
         raise ValueError("link_decoder cannot be combined with multilabel or readout")
+    if int(link_hidden) != link_hidden or not 0 <= link_hidden <= 128 or \
+            (link_hidden and not LINK_DECODERS[link_decoder]):
+        raise ValueError("link_hidden: 0, or 1..128 with link_decoder='dot' (the MLP decoder)")
     if readout not in READOUTS:
         raise ValueError(f"readout must be one of {sorted(k for k in READOUTS if k)} or None")
     if READOUTS[readout] and multilabel:
@@ -847,6 +889,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     p.multilabel = 1 if multilabel else 0
     p.readout = READOUTS[readout]
     p.link_decoder = LINK_DECODERS[link_decoder]
+    p.link_hidden = int(link_hidden)
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
@@ -1231,6 +1274,15 @@ def checkpoint_links(path):
     return dec.value, e.value
 
 
+def checkpoint_link_hidden(path):
+    """Host-only: the link decoder's hidden width of the engine that saved the file -- a version-9
+    file's; 0 for versions 1-8.  PgcnError(PGCN_E_IO) for an invalid file."""
+    h = c_int()
+    check(lib.pgcn_checkpoint_link_hidden(os.fsencode(path), ctypes.byref(h)),
+          f"checkpoint_link_hidden {path}")
+    return h.value
+
+
 def checkpoint_readout(path):
     """Host-only: (readout mode, num_graphs) of the engine that saved the file -- a version-7
     file's block; (0, 0) for versions 1-6.  PgcnError(PGCN_E_IO) for an invalid file."""
@@ -1350,7 +1402,8 @@ EXPORTED = [
     "pgcn_dataset_set_graphs", "pgcn_dataset_load_graphs", "pgcn_checkpoint_readout",
     "pgcn_links_create", "pgcn_links_destroy", "pgcn_link_segment_slots", "pgcn_links_slots",
     "pgcn_link_score_fwd", "pgcn_link_score_bwd", "pgcn_debug_links_incidence",
-    "pgcn_checkpoint_links", "pgcn_gcn_predict_links", "pgcn_gcn_link_counts",
+    "pgcn_link_mlp_tile", "pgcn_link_mlp_workspace", "pgcn_link_mlp_fwd", "pgcn_link_mlp_bwd",
+    "pgcn_checkpoint_links", "pgcn_checkpoint_link_hidden", "pgcn_gcn_predict_links", "pgcn_gcn_link_counts",
     "pgcn_gcn_score_pairs", "pgcn_dataset_set_links", "pgcn_dataset_load_links",
     "pgcn_rank_queries_create", "pgcn_rank_queries_destroy", "pgcn_link_rank_tile",
     "pgcn_link_rank_scores", "pgcn_link_rank", "pgcn_debug_rank_filter", "pgcn_gcn_link_ranks",

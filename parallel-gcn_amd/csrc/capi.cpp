@@ -30,7 +30,8 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024",
                                           "spmm_tree_256", "spmm_tree_1024", "launches",
                                           "link_fwd",   "link_bwd",   "rank_sweep",
-                                          "rank_filter", "topk_sweep", "topk_merge"};
+                                          "rank_filter", "topk_sweep", "topk_merge",
+                                          "link_mlp_fwd", "link_mlp_bwd"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -115,6 +116,10 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   PGCN_CHECK(!p->link_decoder || (!p->multilabel && !p->readout), PGCN_E_INVALID,
              "link_decoder cannot be combined with multilabel or readout");
   q.link_decoder = p->link_decoder;
+  PGCN_CHECK(p->link_hidden >= 0 && p->link_hidden <= kLinkMlpMaxHidden &&
+                 (p->link_hidden == 0 || p->link_decoder == 1),
+             PGCN_E_INVALID, "link_hidden: 0, or 1..128 with link_decoder 1");
+  q.link_hidden = p->link_hidden;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -835,6 +840,54 @@ int pgcn_link_score_bwd(const pgcn_links *l, const float *H, int ld_h, int d, co
   });
 }
 
+void pgcn_link_mlp_tile(int *pairs_per_tile) {
+  if (pairs_per_tile) *pairs_per_tile = kLinkMlpTile;
+}
+
+namespace {
+void check_link_mlp_dims(int d, int h, std::initializer_list<int> wide,
+                         std::initializer_list<int> hidden, std::initializer_list<int> one) {
+  check_link_dims(d, wide, one);
+  PGCN_CHECK(h >= 1 && h <= kLinkMlpMaxHidden, PGCN_E_INVALID, "link_mlp: 1 <= h <= 128");
+  for (int ld : hidden) PGCN_CHECK(ln_ld_ok(ld, h), PGCN_E_INVALID, "link_mlp: ld % 4 == 0, ld >= h");
+}
+}  // namespace
+
+long long pgcn_link_mlp_workspace(const pgcn_links *l, int d, int h) {
+  if (!l || !l->l || d < 1 || d > kLinkMaxWidth || h < 1 || h > kLinkMlpMaxHidden)
+    return (long long)PGCN_E_INVALID;
+  return link_mlp_workspace_bytes(l->l->index(), d, h);
+}
+
+int pgcn_link_mlp_fwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *P,
+                      int ld_p, int h, float *scores, int ld_s, void *stream) {
+  return guarded([&] {
+    check_link_mlp_dims(d, h, {ld_h}, {ld_p}, {ld_s});
+    PGCN_CHECK(l && l->l && H && P && scores && aligned16(H) && aligned16(P) && aligned16(scores),
+               PGCN_E_INVALID, "link_mlp_fwd: null or misaligned argument");
+    check_device();
+    launch_link_mlp_fwd(l->l->index(), H, ld_h, d, P, ld_p, h, scores, ld_s, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_link_mlp_bwd(const pgcn_links *l, const float *H, int ld_h, int d, const float *P,
+                      int ld_p, int h, const float *G, int ld_g, float *dH, int ld_dh, float *dP,
+                      int ld_dp, void *ws, long long ws_bytes, void *stream) {
+  return guarded([&] {
+    check_link_mlp_dims(d, h, {ld_h, ld_dh}, {ld_p, ld_dp}, {ld_g});
+    PGCN_CHECK(l && l->l && H && P && G && dH && dP && ws && aligned16(H) && aligned16(P) &&
+                   aligned16(G) && aligned16(dH) && aligned16(dP) && aligned16(ws),
+               PGCN_E_INVALID, "link_mlp_bwd: null or misaligned argument");
+    PGCN_CHECK(ws_bytes >= link_mlp_workspace_bytes(l->l->index(), d, h), PGCN_E_INVALID,
+               "link_mlp_bwd: the workspace is smaller than pgcn_link_mlp_workspace");
+    check_device();
+    launch_link_mlp_bwd(l->l->index(), H, ld_h, d, P, ld_p, h, G, ld_g, dH, ld_dh, dP, ld_dp, ws,
+                        ws_bytes, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, const int *dst,
                                const int *select, int *ptr, int *pair, int *other) {
   return guarded([&] {
@@ -1079,6 +1132,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->epochs = 100;
   p->readout = 0;
   p->link_decoder = 0;
+  p->link_hidden = 0;
   p->early_stopping = 0;
   p->attention_heads = 1;
   p->attention_dropout = 0.0f;
@@ -1239,6 +1293,7 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "readout")) return e.get_params().readout;
   if (!std::strcmp(key, "num_graphs")) return e.num_graphs();
   if (!std::strcmp(key, "link_decoder")) return e.get_params().link_decoder;
+  if (!std::strcmp(key, "link_hidden")) return e.get_params().link_hidden;
   if (!std::strcmp(key, "num_pairs")) return e.num_pairs();
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
@@ -1369,6 +1424,12 @@ int pgcn_checkpoint_links(const char *path, int *decoder, long long *num_pairs) 
     const Checkpoint ck = read_checkpoint(path);
     *decoder = ck.link_decoder;
     *num_pairs = ck.num_pairs;
+  });
+}
+int pgcn_checkpoint_link_hidden(const char *path, int *link_hidden) {
+  return guarded([&] {
+    PGCN_CHECK(path && link_hidden, PGCN_E_INVALID, "checkpoint_link_hidden args");
+    *link_hidden = read_checkpoint(path).link_hidden;
   });
 }
 int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }

@@ -61,19 +61,22 @@ CkReadoutExt readout_ext(const Checkpoint &ck) {
 
 // version 8: behind version 7's three blocks
 struct CkLinksExt {
-  uint32_t link_decoder, zero;
+  uint32_t link_decoder, link_hidden;  // (link_hidden: 0 in version 8)
   uint64_t num_pairs;
 };
 static_assert(sizeof(CkLinksExt) == 16, "checkpoint extension layout");
 
 CkLinksExt links_ext(const Checkpoint &ck) {
-  return CkLinksExt{(uint32_t)ck.link_decoder, 0, (uint64_t)ck.num_pairs};
+  return CkLinksExt{(uint32_t)ck.link_decoder, (uint32_t)ck.link_hidden, (uint64_t)ck.num_pairs};
 }
 
 // versions 7 and 8 carry the heads, SAGE and readout blocks whatever the layer family
+bool link_blocks(uint32_t version) {  // ... and the link block behind them
+  return version == (uint32_t)kCheckpointVersionLinks ||
+         version == (uint32_t)kCheckpointVersionLinkMlp;
+}
 bool three_blocks(uint32_t version) {
-  return version == (uint32_t)kCheckpointVersionReadout ||
-         version == (uint32_t)kCheckpointVersionLinks;
+  return version == (uint32_t)kCheckpointVersionReadout || link_blocks(version);
 }
 
 uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
@@ -86,7 +89,7 @@ uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
     x = fnv1a(x, &se, sizeof se);
     x = fnv1a(x, &re, sizeof re);
   }
-  if (h.version == (uint32_t)kCheckpointVersionLinks) {
+  if (link_blocks(h.version)) {
     const CkLinksExt le = links_ext(ck);
     x = fnv1a(x, &le, sizeof le);
   }
@@ -151,7 +154,7 @@ bool version_flags_ok(uint32_t version, uint32_t flags) {
            !((flags & kCheckpointAttention) && (flags & kCheckpointSage)) &&
            (flags & ~(kCheckpointResidual | kCheckpointLayerNorm | kCheckpointAttention |
                       kCheckpointSage | kCheckpointReadout)) == 0;
-  if (version == (uint32_t)kCheckpointVersionLinks)  // (never bits 2 or 5, or 3 with 4)
+  if (link_blocks(version))  // (never bits 2 or 5, or 3 with 4)
     return (flags & kCheckpointLinks) &&
            !((flags & kCheckpointAttention) && (flags & kCheckpointSage)) &&
            (flags & ~(kCheckpointResidual | kCheckpointLayerNorm | kCheckpointAttention |
@@ -198,9 +201,16 @@ bool readout_ok(uint32_t version, long long readout, long long num_graphs, long 
          num_nodes >= 0;
 }
 // version 8's own block against the file's version
-bool links_ok(uint32_t version, long long decoder, long long num_pairs) {
-  if (version != (uint32_t)kCheckpointVersionLinks) return decoder == 0 && num_pairs == 0;
-  return decoder == 1 && num_pairs >= 1 && num_pairs < (1LL << 31);
+bool links_ok(uint32_t version, long long decoder, long long num_pairs, long long hidden,
+              long long embed) {
+  if (!link_blocks(version)) return decoder == 0 && num_pairs == 0 && hidden == 0;
+  const bool mlp = version == (uint32_t)kCheckpointVersionLinkMlp;
+  return decoder == 1 && num_pairs >= 1 && num_pairs < (1LL << 31) &&
+         (mlp ? hidden >= 1 && hidden <= 128 && embed <= 128 : hidden == 0);
+}
+// version 9's decoder tensor [embed + 3][round_up4(hidden)]
+long long link_mlp_count(long long hidden, long long embed) {
+  return hidden ? (embed + 3) * ((hidden + 3) / 4 * 4) : 0;
 }
 }  // namespace
 
@@ -230,18 +240,21 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   h.n_weights = (int64_t)ck.w.size();
   PGCN_CHECK(readout_ok(h.version, ck.readout, ck.num_graphs, ck.num_nodes), PGCN_E_INVALID,
              "checkpoint: readout / graph count do not match the file's version");
-  PGCN_CHECK(links_ok(h.version, ck.link_decoder, ck.num_pairs), PGCN_E_INVALID,
+  PGCN_CHECK(links_ok(h.version, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]),
+             PGCN_E_INVALID,
              "checkpoint: link decoder / pair count do not match the file's version");
   PGCN_CHECK(sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: aggregator / root weight do not match the file's version");
-  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight), PGCN_E_INVALID,
+  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight) +
+                                link_mlp_count(ck.link_hidden, h.dims[L]),
+             PGCN_E_INVALID,
              "checkpoint: weight count does not match the layer dims");
   PGCN_CHECK(heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout),
              PGCN_E_INVALID,
              "checkpoint: heads / attention dropout do not match the file's version");
   const CkHeadsExt ext = heads_ext(ck);
   const bool v7 = three_blocks(h.version);
-  const bool v8 = h.version == (uint32_t)kCheckpointVersionLinks;
+  const bool v8 = link_blocks(h.version);
   const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads || v7;
   const CkSageExt sext = sage_ext(ck);
   const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage || v7;
@@ -300,17 +313,19 @@ Checkpoint read_checkpoint(const std::string &path) {
     ck.readout = (int)e.readout;
     ck.num_graphs = (int)e.num_graphs;
   }
-  if (ok && h.version == (uint32_t)kCheckpointVersionLinks) {
+  if (ok && link_blocks(h.version)) {
     CkLinksExt e{};
-    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.link_decoder <= 1 &&
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.link_hidden <= 128 && e.link_decoder <= 1 &&
          e.num_pairs < (1ull << 31);
+    ck.link_hidden = (int)e.link_hidden;
     ck.link_decoder = (int)e.link_decoder;
     ck.num_pairs = (long long)e.num_pairs;
   }
-  ok = ok && links_ok(h.version, ck.link_decoder, ck.num_pairs) && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
+  ok = ok && links_ok(h.version, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]) && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
        sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight) &&
        readout_ok(h.version, ck.readout, ck.num_graphs, h.num_nodes) &&
-       h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight);
+       h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight) +
+                          link_mlp_count(ck.link_hidden, h.dims[L]);
   ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
        read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);
   ok = ok && std::fgetc(f) == EOF;  // nothing trailing

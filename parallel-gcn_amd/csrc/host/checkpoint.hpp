@@ -51,6 +51,9 @@
 //   block  u32 link_decoder (1 dot product); u32 0; u64 num_pairs (>= 1)
 // The payload follows the flags as before (the decoder has no weights).  Every other engine keeps
 // writing versions 1-7 byte for byte.
+// Version 9 = version 8 saved with pgcn_params.link_hidden > 0: the link block's second u32 holds
+// link_hidden (1..128; version 8 requires 0 there), and the payload gains the decoder tensor
+// [dims[L] + 3][round_up4(link_hidden)] -- and its two Adam moments -- behind the attention tensor.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (versions
 // 5 and 6; the blocks of versions 7 and 8) and the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
@@ -79,6 +82,7 @@ constexpr unsigned kCheckpointReadout = 32u;  // header flags, bit 5 (version 7 
 constexpr int kCheckpointVersionReadout = 7;  // bits 0-5 known, bit 5 set, + three blocks
 constexpr unsigned kCheckpointLinks = 64u;  // header flags, bit 6 (version 8 only)
 constexpr int kCheckpointVersionLinks = 8;  // bit 6 set, + four blocks
+constexpr int kCheckpointVersionLinkMlp = 9;  // version 8 + link_hidden and the decoder tensor
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -100,6 +104,7 @@ struct Checkpoint {
   // version 8's own block; 0 and 0 in every other version
   int link_decoder = 0;
   long long num_pairs = 0;
+  int link_hidden = 0;  // version 9 only
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

@@ -338,6 +338,9 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
   }
   PGCN_CHECK(params.link_decoder == 0 || params.link_decoder == 1, PGCN_E_INVALID,
              "link_decoder must be 0 (none) or 1 (dot product)");
+  PGCN_CHECK(params.link_hidden >= 0 && params.link_hidden <= kLinkMlpMaxHidden &&
+                 (params.link_hidden == 0 || params.link_decoder == 1),
+             PGCN_E_INVALID, "link_hidden: 0, or 1..128 with link_decoder 1");
   if (params.link_decoder) {
     PGCN_CHECK(!params.multilabel, PGCN_E_INVALID,
                "link_decoder cannot be combined with multilabel");
@@ -689,7 +692,10 @@ void GCN::build(const GCNData &data) {
   long long atotal = 0;  // attention: a_dst and a_src of every layer, behind everything else
   if (params.attention)
     for (int l = 0; l < L; l++) atotal += 2LL * dims[(size_t)l + 1];
-  grad_arena.allocate((size_t)(wtotal + ntotal + atotal));
+  // link_hidden: the decoder's packed tensor [C + 3][round_up4(h)], behind everything else
+  const int link_ld = round_up4(params.link_hidden);
+  const long long ptotal = params.link_hidden ? (long long)(params.output_dim + 3) * link_ld : 0;
+  grad_arena.allocate((size_t)(wtotal + ntotal + atotal + ptotal));
   grad_arena.zero();
   uint64_t rs[2];
   if (params.seed) pgcn_rng_seed_glibc(params.seed, rs);
@@ -730,8 +736,25 @@ void GCN::build(const GCNData &data) {
     attn_var->dev_data.upload(h);
     attn_var->dev_grad = grad_arena.slice((size_t)(woff + ntotal), (size_t)atotal);
   }
-  // (the dropout streams start after the attention draws: one draw per element, as the weights)
-  init_dropout_rng(data, wtotal + atotal);
+  long long pdraws = 0;
+  if (ptotal > 0) {  // W1 [C][h] and w2 [h][1] glorot, b1 = b2 = 0: drawn after everything above
+    const int C = params.output_dim, hh = params.link_hidden;
+    link_var = std::make_shared<Variable>(C + 3, link_ld, false);
+    std::vector<float> h((size_t)ptotal, 0.0f), w1((size_t)C * hh), w2((size_t)hh);
+    glorot_host(w1, C, hh, rs);
+    glorot_host(w2, hh, 1, rs);
+    for (int i = 0; i < C; i++)
+      std::copy(w1.begin() + (size_t)i * hh, w1.begin() + (size_t)(i + 1) * hh,
+                h.begin() + (size_t)i * link_ld);
+    std::copy(w2.begin(), w2.end(), h.begin() + (size_t)(C + 1) * link_ld);
+    link_var->dev_data.upload(h);
+    link_var->dev_grad = grad_arena.slice((size_t)(woff + ntotal + atotal), (size_t)ptotal);
+    pdraws = (long long)w1.size() + (long long)w2.size();
+    link_mlp_ws.allocate(
+        (size_t)(link_mlp_workspace_bytes(links_->index(), C, hh) / (long long)sizeof(float)) + 4);
+  }
+  // (the dropout streams start after the last glorot draw: one draw per element, as the weights)
+  init_dropout_rng(data, wtotal + atotal + pdraws);
 
   // context buffers
   xent_partials.allocate((size_t)xent_blocks(std::max(prow, head_rows())) * 2 + 2);
@@ -783,6 +806,11 @@ void GCN::build(const GCNData &data) {
     variables.push_back(attn_var);
     weights.push_back(attn_var);
     decays.push_back(false);
+  }
+  if (link_var) {  // the decoder tensor directly before the scores, decayed like a layer weight
+    variables.push_back(link_var);
+    weights.push_back(link_var);
+    decays.push_back(true);
   }
   if (link_scores) variables.push_back(link_scores);  // (a link engine's last variable)
   // (edge-cut: the tails run in k_gs_finish on the rank's rows after the reduce-scatter)
@@ -1136,7 +1164,12 @@ void GCN::insert_last_layer() {
   if (params.link_decoder) {  // node embedding -> scores [E][4] -> the one-class loss over the pairs
     link_embed = out;
     link_scores = std::make_shared<Variable>(num_pairs_, 1, true, 4);
-    modules.push_back(std::make_unique<LinkDecoder>(out, link_scores, links_.get(), C));
+    if (link_var)
+      modules.push_back(std::make_unique<LinkMlpDecoder>(
+          out, link_var, link_scores, links_.get(), C, params.link_hidden, link_mlp_ws.get(),
+          (long long)(link_mlp_ws.size() * sizeof(float))));
+    else
+      modules.push_back(std::make_unique<LinkDecoder>(out, link_scores, links_.get(), C));
     modules.push_back(std::make_unique<BCEWithLogitsLoss>(link_scores, 1, &ctx));
     return;
   }
@@ -1796,6 +1829,10 @@ void GCN::save(const std::string &path) {
     ck.attention_dropout = params.attention_dropout;
     ck.link_decoder = params.link_decoder;
     ck.num_pairs = num_pairs_;
+    if (link_var) {  // version 9: the hidden width in the block, the decoder tensor last
+      ck.version = kCheckpointVersionLinkMlp;
+      ck.link_hidden = params.link_hidden;
+    }
   }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
@@ -1824,6 +1861,10 @@ void GCN::load(const std::string &path, int flags) {
   if (same && resume) same = ck.aggregator == params.aggregator;
   // (a weights-only load crosses the link decoder: it has no weights, the tensors are the same)
   if (same && resume) same = ck.link_decoder == params.link_decoder && ck.num_pairs == num_pairs_;
+  // (the decoder tensor's shape: a file that has one must match; one without leaves it as it is,
+  // weights only)
+  same = same && (resume ? ck.link_hidden == params.link_hidden
+                         : ck.link_hidden == 0 || ck.link_hidden == params.link_hidden);
   if (same && resume) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
     // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)
@@ -1846,6 +1887,7 @@ void GCN::load(const std::string &path, int flags) {
     // it into a plain engine: the tensor behind the layer weights is not read)
     if (w == norm_var && !(ck.flags & kCheckpointLayerNorm)) continue;
     if (w == attn_var && !(ck.flags & kCheckpointAttention)) continue;  // (the same for attn)
+    if (w == link_var && !ck.link_hidden) continue;  // (... and the decoder tensor keeps its init)
     // (a file's norm tensor sits before its attention tensor: skipped by an engine without one)
     if (w == attn_var && (ck.flags & kCheckpointLayerNorm) && !norm_var)
       for (int h : params.hidden_dims) at += 2 * (size_t)h;
@@ -2009,8 +2051,13 @@ void GCN::score_pairs(const int *src, const int *dst, long long m, float *scores
   DeviceBuffer<float> out((size_t)m * 4);
   predict_forward();
   const Variable &h = *link_embed;
-  launch_link_score_fwd(tmp.index(), h.dev_data.get(), h.ld, params.output_dim, out.get(), 4,
+  if (link_var)
+    launch_link_mlp_fwd(tmp.index(), h.dev_data.get(), h.ld, params.output_dim,
+                        link_var->dev_data.get(), link_var->ld, params.link_hidden, out.get(), 4,
                         stream.get());
+  else
+    launch_link_score_fwd(tmp.index(), h.dev_data.get(), h.ld, params.output_dim, out.get(), 4,
+                          stream.get());
   sync();
   std::vector<float> raw((size_t)m * 4);
   out.download(raw.data(), raw.size());
@@ -2019,6 +2066,9 @@ void GCN::score_pairs(const int *src, const int *dst, long long m, float *scores
 
 long long GCN::link_ranks(int split, int side, int filtered, long long *greater, long long *equal) {
   PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "link_ranks: not a link engine");
+  PGCN_CHECK(!link_var, PGCN_E_INVALID,
+             "link_ranks: the 1-vs-all sweep ranks the dot product only; with link_hidden > 0 "
+             "evaluate with score_pairs over fixed candidate lists");
   PGCN_CHECK(split >= 1 && split <= 3 && (side == 0 || side == 1) &&
                  (filtered == 0 || filtered == 1) && !greater == !equal,
              PGCN_E_INVALID,
@@ -2059,6 +2109,9 @@ long long GCN::link_ranks(int split, int side, int filtered, long long *greater,
 void GCN::top_links(const int *nodes, long long m, int k, int side, int filtered, int *idx,
                     float *score) {
   PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "top_links: not a link engine");
+  PGCN_CHECK(!link_var, PGCN_E_INVALID,
+             "top_links: the 1-vs-all sweep ranks the dot product only; with link_hidden > 0 "
+             "evaluate with score_pairs over fixed candidate lists");
   PGCN_CHECK(m >= 0 && (m == 0 || (nodes && idx && score)) && k >= 1 && k <= kTopKMax &&
                  (side == 0 || side == 1) && (filtered == 0 || filtered == 1),
              PGCN_E_INVALID, "top_links: nodes, idx, score; 1 <= k <= 128, side 0 / 1, filtered 0 / 1");

@@ -68,6 +68,9 @@ struct GCNParams {
   // layer's node embedding and a one-class BCEWithLogitsLoss over GCNData's pairs with their
   // labels and splits.  Single GPU, not with multilabel or readout
   int link_decoder = 0;
+  // 0: the dot product; 1..128 (with link_decoder 1): a LinkMlpDecoder of that hidden width on
+  // the packed tensor link_var, one more weight and optimizer entry
+  int link_hidden = 0;
 };
 
 struct AdamParams {
@@ -273,6 +276,8 @@ class GCN {
   int num_pairs_ = 0;
   std::unique_ptr<LinkIndexDev> links_;
   shared_ptr<Variable> link_embed, link_scores;
+  shared_ptr<Variable> link_var;  // link_hidden > 0: P [output_dim + 3][round_up4(link_hidden)]
+  DeviceBuffer<float> link_mlp_ws;  // ... and the decoder backward's workspace
   // link_ranks: the pattern and the pairs on the host (src, dst, label, split), and per
   // (split, side, filtered) the query set on the device with its counts [2][queries]
   SparseIndex rank_graph_;

@@ -880,6 +880,35 @@ void LinkDecoder::backward(const Stream &s) const {
 }
 
 // ------------------------------------------------------------------------------------------
+// LinkMlpDecoder (k_link_mlp.hip)
+// ------------------------------------------------------------------------------------------
+LinkMlpDecoder::LinkMlpDecoder(shared_ptr<Variable> in_, shared_ptr<Variable> p_,
+                               shared_ptr<Variable> out_, const LinkIndexDev *links_, int dim_,
+                               int hidden_, float *ws_, long long ws_bytes_)
+    : in(std::move(in_)), p(std::move(p_)), out(std::move(out_)), links(links_), dim(dim_),
+      hidden(hidden_), ws(ws_), ws_bytes(ws_bytes_) {
+  PGCN_CHECK(in && p && out && links && dim >= 1 && dim <= kLinkMaxWidth && hidden >= 1 &&
+                 hidden <= kLinkMlpMaxHidden && in->cols == dim &&
+                 in->rows >= links->index().n && in->ld % 4 == 0 && p->rows == dim + 3 &&
+                 p->ld % 4 == 0 && p->ld >= hidden && out->cols == 1 && out->ld % 4 == 0 &&
+                 out->ld >= 4 && out->rows >= links->index().n_pairs && ws &&
+                 ws_bytes >= link_mlp_workspace_bytes(links->index(), dim, hidden),
+             PGCN_E_INVALID, "link MLP decoder: widths up to 128, P [dim + 3][ld], scores [pairs][4]");
+}
+
+void LinkMlpDecoder::forward(bool, const Stream &s) const {
+  launch_link_mlp_fwd(links->index(), in->dev_data.get(), in->ld, dim, p->dev_data.get(), p->ld,
+                      hidden, out->dev_data.get(), out->ld, s.get());
+}
+
+void LinkMlpDecoder::backward(const Stream &s) const {
+  if (!in->dev_grad || !out->dev_grad || !p->dev_grad) return;
+  launch_link_mlp_bwd(links->index(), in->dev_data.get(), in->ld, dim, p->dev_data.get(), p->ld,
+                      hidden, out->dev_grad.get(), out->ld, in->dev_grad.get(), in->ld,
+                      p->dev_grad.get(), p->ld, ws, ws_bytes, s.get());
+}
+
+// ------------------------------------------------------------------------------------------
 // ReLU (src/module.cu:215-265)
 // ------------------------------------------------------------------------------------------
 ReLU::ReLU(shared_ptr<Variable> in_) : in(std::move(in_)) {

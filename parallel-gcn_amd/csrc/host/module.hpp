@@ -453,6 +453,25 @@ class LinkDecoder : public Module {
   void backward(const Stream &s) const override;
 };
 
+// The Hadamard-MLP decoder in LinkDecoder's place (k_link_mlp.hip): out [E][4] = {score_e, 0, 0, 0}
+// from `in` [n][dim] and the packed tensor `p` [dim + 3][round_up4(hidden)] (launch_link_mlp_fwd,
+// one launch).  The backward reads out->dev_grad for every pair (the loss leaves zero outside the
+// split) and writes every row of in->dev_grad and every element of p->dev_grad
+// (launch_link_mlp_bwd) through the engine's workspace `ws`.  Nothing drawn from the dropout stream.
+class LinkMlpDecoder : public Module {
+  shared_ptr<Variable> in, p, out;
+  const LinkIndexDev *links;  // owned by the engine
+  int dim, hidden;
+  float *ws;
+  long long ws_bytes;
+
+ public:
+  LinkMlpDecoder(shared_ptr<Variable> in_, shared_ptr<Variable> p_, shared_ptr<Variable> out_,
+                 const LinkIndexDev *links_, int dim_, int hidden_, float *ws_, long long ws_bytes_);
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+};
+
 // include/module.cuh:90-99
 class ReLU : public Module {
   shared_ptr<Variable> in;

@@ -81,14 +81,6 @@ __device__ __forceinline__ float4 entries_sum(const LinkIndex &l, const float *_
   acc.w = across_groups<GL>(acc.w);
   return acc;
 }
-
-// the float4 at column c0 of a row of width d: zero from column d on, whatever the sums hold there
-__device__ __forceinline__ void store_row4(float *p, int c0, int d, float4 v) {
-  if (c0 + 1 >= d) v.y = 0.0f;
-  if (c0 + 2 >= d) v.z = 0.0f;
-  if (c0 + 3 >= d) v.w = 0.0f;
-  *reinterpret_cast<float4 *>(p + c0) = v;
-}
 }  // namespace
 
 // items [0, n): the nodes of at most kGatSeg entries, whole (none: a zero row); items [n, n +
@@ -157,6 +149,10 @@ void launch_link_score_bwd(const LinkIndex &l, const float *H, int ld_h, int d, 
   note_path(KP_LINK_BWD);
   ITEM_DISPATCH(k_link_score_bwd, item_grid((long long)l.n + l.n_segs), s, l, H, ld_h, d, G, ld_g,
                 dH, ld_dh);
+  launch_link_bwd_merge(l, d, dH, ld_dh, s);
+}
+
+void launch_link_bwd_merge(const LinkIndex &l, int d, float *dH, int ld_dh, hipStream_t s) {
   if (l.n_long > 0) ITEM_DISPATCH(k_link_score_bwd_merge, item_grid(l.n_long), s, l, d, dH, ld_dh);
 }
 

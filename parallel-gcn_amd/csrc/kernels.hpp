@@ -17,7 +17,7 @@ enum KernelPath {
   KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS,
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
   KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_RANK_SWEEP, KP_RANK_FILTER,
-  KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_COUNT
+  KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_LINK_MLP_FWD, KP_LINK_MLP_BWD, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -475,6 +475,28 @@ void launch_link_score_fwd(const LinkIndex &l, const float *H, int ld_h, int d, 
 // their segments' partials in l.ws and a second launch that adds them in segment order
 void launch_link_score_bwd(const LinkIndex &l, const float *H, int ld_h, int d, const float *G,
                            int ld_g, float *dH, int ld_dh, hipStream_t s);
+// the long nodes' rows of a pair backward: their segments' partials in l.ws added in segment order
+// (nothing without long nodes); shared with k_link_mlp.hip
+void launch_link_bwd_merge(const LinkIndex &l, int d, float *dH, int ld_dh, hipStream_t s);
+// ---- link prediction: the Hadamard-MLP decoder (k_link_mlp.hip) --------------------------------
+// z_e = H[src_e] o H[dst_e]; P [d + 3][ld_p] packs W1 [d][h] (rows 0 .. d - 1), b1 (row d), w2
+// (row d + 1) and {b2, 0, ...} (row d + 2): score_e = b2 + sum_u w2[u] max(b1[u] + (z_e W1)[u], 0).
+constexpr int kLinkMlpMaxHidden = 128;
+constexpr int kLinkMlpTile = 64;  // pairs per tile of the two pair kernels
+// bytes of launch_link_mlp_bwd's workspace: dz [E][round_up4(d)], one [d + 3][round_up4(h)] block
+// per workgroup of the pair kernel, the segments' partial rows.  Host only.
+long long link_mlp_workspace_bytes(const LinkIndex &l, int d, int h);
+// scores[e][0..3] = {score_e, 0, 0, 0}: ONE launch of persistent workgroups with W1 in LDS, f32
+// MFMA over 64-pair tiles; neither z nor the hidden layer reaches memory
+void launch_link_mlp_fwd(const LinkIndex &l, const float *H, int ld_h, int d, const float *P,
+                         int ld_p, int h, float *scores, int ld_s, hipStream_t s);
+// with G[e][0] = dLoss/dscore_e (read for every pair): every row of dH (zero without entries, zero
+// in [d, round_up4(d))) and every element of dP [d + 3][ld_dp] (zero in the padding).  Three
+// launches -- pairs, reduce, nodes -- and the merge when a list exceeds kGatSeg; no float atomics,
+// every order a function of (pair list, d, h)
+void launch_link_mlp_bwd(const LinkIndex &l, const float *H, int ld_h, int d, const float *P,
+                         int ld_p, int h, const float *G, int ld_g, float *dH, int ld_dh,
+                         float *dP, int ld_dp, void *ws, long long ws_bytes, hipStream_t s);
 // ---- link prediction: 1-vs-all ranking counts (k_rank.hip) -------------------------------------
 // The rank score r(a, v) is the k-ordered fp32 fmaf chain over the d columns of rows a and v -- not
 // launch_link_score_fwd's order -- which is what the sweep's f32 MFMA tiles compute bit for bit.

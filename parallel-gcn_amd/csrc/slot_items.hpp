@@ -33,6 +33,14 @@ __device__ __forceinline__ float4 row4(const float *p, int c0, int d, bool on) {
   return v;
 }
 
+// the float4 at column c0 of a row of width d: zero from column d on, whatever the sums hold there
+__device__ __forceinline__ void store_row4(float *p, int c0, int d, float4 v) {
+  if (c0 + 1 >= d) v.y = 0.0f;
+  if (c0 + 2 >= d) v.z = 0.0f;
+  if (c0 + 3 >= d) v.w = 0.0f;
+  *reinterpret_cast<float4 *>(p + c0) = v;
+}
+
 // this wave's item of a launch over the direct items and the segments, grid-stride
 __device__ __forceinline__ long long first_item() {
   return ((long long)blockIdx.x * kItemThreads + threadIdx.x) / kWave;
