@@ -418,6 +418,63 @@ int pgcn_link_mlp_bwd(const pgcn_links *l, const float *H, int ld_h, int d, cons
 int pgcn_debug_links_incidence(int n_nodes, long long n_pairs, const int *src, const int *dst,
                                const int *select, int *ptr, int *pair, int *other);
 
+/* --- link prediction: negative sampling and a rebuildable pair index (k_neg.hip; new: the
+ *     reference has no pair-level model) ---------------------------------------------------------
+ * Fresh negatives each epoch without leaving the device: draw new dst endpoints, write them into a
+ * pgcn_links handle, rebuild its incidence index.  Integer work throughout; every result is a
+ * function of the arguments alone.
+ * pgcn_links_create_dynamic: a pgcn_links of FIXED CAPACITY (n_pairs and the selection) whose
+ *   index is built on the device -- this first time too, complete on return -- and can be rebuilt.
+ *   It serves every pgcn_link_* call as a pgcn_links_create handle of the same arrays does, bit for
+ *   bit.  It reserves the worst case once: with N2 = pgcn_links_slots(l) at most N2 / (T + 1) lists
+ *   exceed T = pgcn_link_segment_slots() entries, in at most ceil(N2 / T) + N2 / (T + 1) segments
+ *   (+ 1 row of padding), and the backward calls always launch over that capacity -- two launches
+ *   whenever N2 > T, one otherwise -- since a rebuild never reports to the host what it found.
+ * pgcn_links_set_dst_range: dst[first .. first + count) = dev_dst[0 .. count) (DEVICE memory), an
+ *   asynchronous device copy; the index is stale until the next rebuild.  The values must lie in
+ *   [0, n_nodes): the host cannot check them; the rebuild reads a value outside as the nearest node.
+ * pgcn_links_rebuild: the incidence index of the pair arrays as they are at this point of the
+ *   stream, equal to pgcn_debug_links_incidence's, by a stable LSD radix sort of the 2 x selected
+ *   role entries by node (8-bit digits, ceil(bits(n_nodes - 1) / 8) passes, at least one, over
+ *   pgcn_links_sort_tile()-entry tiles; 3 launches a pass), two launches for ptr / pair / other and,
+ *   when N2 > T, three for the segment records.  Allocates nothing, never syncs, may be captured.
+ *   It must not overlap a call that reads the handle.
+ * pgcn_links_incidence_copy: a debug read-back (syncs the device): ptr [n_nodes + 1], pair and other
+ *   [pgcn_links_slots(l)] to host memory; pair / other may be NULL.  Any handle.
+ * PGCN_E_INVALID, before anything touches the device: set_dst_range / rebuild on a handle of
+ *   pgcn_links_create, a range outside the pairs, a null handle.
+ *
+ * pgcn_neg_sampler holds an EXCLUSION CSR over the nodes (host arrays, uploaded once): row i =
+ * excl_idx[excl_ptr[i] .. excl_ptr[i + 1]) is strictly ascending within [0, n_nodes) and contains i
+ * itself.  PGCN_E_INVALID otherwise, and for a row that excludes every node (nothing to draw).
+ * pgcn_neg_sample, ONE launch, a lane per draw: for e < m, with s = dev_src[e], L the length of row
+ *   s and free = n_nodes - L, dev_dst[e] = the r-th node (ascending, from 0) not in row s, where
+ *     mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *             z ^ (z >> 31)                                  (64-bit, wrapping)
+ *     k = mix(seed + 0x9E3779B97F4A7C15 * (round + 1)),  h = mix(k + 0x9E3779B97F4A7C15 * (e + 1)),
+ *     r = ((h >> 32) * free) >> 32.
+ *   Exact -- no rejection loop: a binary search for the r-th missing value of the row -- and
+ *   stateless: the same (seed, round, e, row) gives the same node on any launch.  dev_src and
+ *   dev_dst are device arrays; an anchor outside [0, n_nodes) is read as the nearest node.
+ *   0 <= m within an int, round >= 0, else PGCN_E_INVALID; m == 0 launches nothing. */
+typedef struct pgcn_neg_sampler pgcn_neg_sampler;
+int pgcn_links_create_dynamic(int n_nodes, long long n_pairs, const int *src, const int *dst,
+                              const int *select /* [n_pairs] or NULL */, pgcn_links **out);
+int pgcn_links_set_dst_range(pgcn_links *l, long long first, long long count, const int *dev_dst,
+                             void *stream);
+int pgcn_links_rebuild(pgcn_links *l, void *stream);
+int pgcn_links_incidence_copy(const pgcn_links *l, int *ptr, int *pair, int *other);
+void pgcn_links_sort_tile(int *entries_per_tile);
+/* timing only (syncs): one rebuild on the null stream with a HIP event behind every stage; us[k],
+ * k < cap, is stage k's microseconds -- per radix pass the histogram, the scan and the scatter,
+ * then the index launches, then the segment records when N2 > T.  Returns the stage count. */
+int pgcn_debug_links_rebuild_times(pgcn_links *l, float *us, int cap);
+int pgcn_neg_sampler_create(int n_nodes, const long long *excl_ptr, const int *excl_idx,
+                            pgcn_neg_sampler **out);
+int pgcn_neg_sampler_destroy(pgcn_neg_sampler *s);
+int pgcn_neg_sample(const pgcn_neg_sampler *sampler, const int *dev_src, long long m,
+                    unsigned long long seed, long long round, int *dev_dst, void *stream);
+
 /* --- link prediction: 1-vs-all ranking counts (k_rank.hip; new: the reference has no pair-level
  * model).  For a held-out link (anchor a, target t) ranking metrics ask where t stands among all
  * candidates v for a.  The rank score over an embedding H [n][ld_h] of logical width d is the
@@ -634,6 +691,20 @@ typedef struct {
    * fixed candidate lists).  Anything else, link_hidden != 0 without a decoder included, is
    * PGCN_E_INVALID. */
   int link_hidden;
+  /* Negatives redrawn on the device before every train_epoch (here, behind link_hidden: no other
+   * member moves).  0: off, the engine as it was, bit for bit.  1..64 with link_decoder == 1: with
+   * P the training split's positive pairs (label 1), the engine's pair list is the data's E pairs
+   * followed by neg_ratio * P DRAWN pairs -- drawn pair p * neg_ratio + j has the src of positive
+   * p (in pair order), label 0 and the training split; the data's own negatives stay.  Before each
+   * train_epoch, on the engine's stream: pgcn_neg_sample with seed = pgcn_params.seed and round =
+   * the epochs run ("epochs": a train_epoch + eval(2) pair is one), over the exclusion rows {the
+   * node, its adjacency row as loaded, the dst of every label-1 pair with that src, of any split},
+   * then pgcn_links_set_dst_range and pgcn_links_rebuild on the engine's rebuildable pair index.
+   * A resumed run redraws what the straight run drew.  Validation and test pairs are never drawn;
+   * pgcn_gcn_predict_links, _link_counts, _score_pairs, _link_ranks, _top_links and "num_pairs"
+   * report the data's E pairs; "neg_pairs" is neg_ratio * P.  A src adjacent to every other node
+   * is PGCN_E_INVALID at creation, as anything else here. */
+  int neg_ratio;
   float dropouts[PGCN_MAX_LAYERS];       /* n_layers */
   /* GraphSAGE layers.  aggregator: 0 = GCN's Â (the engine as it was, bit for bit), 1 = mean,
    * 2 = max; root_weight: 0 / 1, 1 only with aggregator != 0.  With H the layer's input as it
@@ -810,7 +881,7 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
  * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel), "readout" (the readout
  * mode, pgcn_params.readout) and "num_graphs" (its graph count; 0 without a readout),
- * "link_decoder" (pgcn_params.link_decoder), "link_hidden" (pgcn_params.link_hidden) and "num_pairs" (its pair count; 0 without), and
+ * "link_decoder" (pgcn_params.link_decoder), "link_hidden" (pgcn_params.link_hidden) and "num_pairs" (its pair count; 0 without), "neg_pairs" (the drawn pairs behind them; pgcn_params.neg_ratio), and
  * "fused_norm_tails" (how many of them ran the ReLU / residual add /
  * Dropout behind them inside the LayerNorm kernel in the last training forward);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
@@ -959,6 +1030,11 @@ int pgcn_checkpoint_links(const char *path, int *decoder, long long *num_pairs);
  * requires to be 0; the payload gains the decoder tensor [output_dim + 3][round_up4(link_hidden)]
  * and its two Adam moments behind the attention tensor's.  Host-only: 0 for versions 1-8. */
 int pgcn_checkpoint_link_hidden(const char *path, int *link_hidden);
+/* Version 10 = version 8 (link_hidden 0) or 9 saved with pgcn_params.neg_ratio > 0: a fifth 16-byte
+ * block {u32 neg_ratio (1..64); u32 0; u64 0} behind the link block, under the checksum.  The draws
+ * need no state of their own: (seed, epochs) are in the header.  A resume needs the same neg_ratio
+ * (a file of versions 1-9 reads as 0); a weights-only load crosses it.  Host-only. */
+int pgcn_checkpoint_neg_ratio(const char *path, int *neg_ratio);
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever

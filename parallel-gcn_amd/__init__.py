@@ -41,7 +41,7 @@ P = ctypes.POINTER
 class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("link_decoder", c_int),
-                ("hidden_dims", c_int * MAX_LAYERS), ("link_hidden", c_int),
+                ("hidden_dims", c_int * MAX_LAYERS), ("link_hidden", c_int), ("neg_ratio", c_int),
                 ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
                 ("root_weight", c_int), ("epochs", c_int), ("readout", c_int),
                 ("early_stopping", c_int),
@@ -168,6 +168,16 @@ _sig("pgcn_link_mlp_bwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_i
      c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_ll, c_void_p)
 _sig("pgcn_debug_links_incidence", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
      c_void_p, c_void_p)
+_sig("pgcn_links_create_dynamic", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, P(c_void_p))
+_sig("pgcn_links_set_dst_range", c_int, c_void_p, c_ll, c_ll, c_void_p, c_void_p)
+_sig("pgcn_links_rebuild", c_int, c_void_p, c_void_p)
+_sig("pgcn_links_incidence_copy", c_int, c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_links_sort_tile", None, P(c_int))
+_sig("pgcn_debug_links_rebuild_times", c_int, c_void_p, c_void_p, c_int)
+_sig("pgcn_neg_sampler_create", c_int, c_int, c_void_p, c_void_p, P(c_void_p))
+_sig("pgcn_neg_sampler_destroy", c_int, c_void_p)
+_sig("pgcn_neg_sample", c_int, c_void_p, c_void_p, c_ll, ctypes.c_ulonglong, c_ll, c_void_p,
+     c_void_p)
 _sig("pgcn_rank_queries_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p,
      P(c_void_p))
 _sig("pgcn_rank_queries_destroy", c_int, c_void_p)
@@ -232,6 +242,7 @@ _sig("pgcn_checkpoint_sage", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_checkpoint_readout", c_int, ctypes.c_char_p, P(c_int), P(c_int))
 _sig("pgcn_checkpoint_links", c_int, ctypes.c_char_p, P(c_int), P(c_ll))
 _sig("pgcn_checkpoint_link_hidden", c_int, ctypes.c_char_p, P(c_int))
+_sig("pgcn_checkpoint_neg_ratio", c_int, ctypes.c_char_p, P(c_int))
 _sig("pgcn_gcn_predict_links", c_ll, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_link_counts", c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_gcn_score_pairs", c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p)
@@ -551,9 +562,11 @@ def f1_scores(counts):
 
 class Links:
     """A pair index on the device (pgcn_links): n_pairs pairs (src, dst) over n_nodes nodes; the
-    pairs with select >= 0 (all when None) enter the backward's incidence index."""
+    pairs with select >= 0 (all when None) enter the backward's incidence index.  dynamic: the
+    index is built on the device and can be rebuilt after set_dst_range
+    (pgcn_links_create_dynamic)."""
 
-    def __init__(self, n_nodes, src, dst, select=None):
+    def __init__(self, n_nodes, src, dst, select=None, dynamic=False):
         src = np.ascontiguousarray(src, np.int32)
         dst = np.ascontiguousarray(dst, np.int32)
         if src.ndim != 1 or dst.shape != src.shape:
@@ -562,10 +575,41 @@ class Links:
         if sel is not None and sel.shape != src.shape:
             raise ValueError("Links: select [E]")
         h = c_void_p()
-        check(lib.pgcn_links_create(n_nodes, src.size, _ptr(src), _ptr(dst),
-                                    _ptr(sel) if sel is not None else None, ctypes.byref(h)),
-              "links_create")
+        create = lib.pgcn_links_create_dynamic if dynamic else lib.pgcn_links_create
+        check(create(n_nodes, src.size, _ptr(src), _ptr(dst),
+                     _ptr(sel) if sel is not None else None, ctypes.byref(h)), "links_create")
         self._h, self.n_nodes, self.n_pairs = h, n_nodes, int(src.size)
+        self.dynamic = bool(dynamic)
+
+    def set_dst_range(self, first, dev_dst, count, stream=None):
+        """dst[first .. first + count) = dev_dst[0 .. count), a device int32 array (an address or
+        anything with data_ptr()); asynchronous, the index is stale until rebuild()
+        (pgcn_links_set_dst_range)."""
+        check(lib.pgcn_links_set_dst_range(self._h, first, count, _dptr(dev_dst), stream),
+              "links_set_dst_range")
+
+    def rebuild(self, stream=None):
+        """Rebuilds the incidence index on the device, asynchronously (pgcn_links_rebuild)."""
+        check(lib.pgcn_links_rebuild(self._h, stream), "links_rebuild")
+
+    def rebuild_times(self):
+        """Timing only: one rebuild on the null stream, the microseconds of its stages -- per radix
+        pass histogram, scan, scatter; the index; the segment records if any; syncs
+        (pgcn_debug_links_rebuild_times)."""
+        us = np.zeros(64, np.float32)
+        k = lib.pgcn_debug_links_rebuild_times(self._h, _ptr(us), us.size)
+        if k < 0:
+            raise PgcnError(k, "links_rebuild_times")
+        return us[:k]
+
+    def incidence(self):
+        """(ptr [n_nodes + 1], pair, other) as the device holds them; syncs
+        (pgcn_links_incidence_copy)."""
+        ptr = np.zeros(self.n_nodes + 1, np.int32)
+        pair, other = (np.zeros(self.slots(), np.int32) for _ in range(2))
+        check(lib.pgcn_links_incidence_copy(self._h, _ptr(ptr), _ptr(pair), _ptr(other)),
+              "links_incidence_copy")
+        return ptr, pair, other
 
     @property
     def handle(self):
@@ -598,6 +642,41 @@ class Links:
     def close(self):
         if getattr(self, "_h", None) and self._h.value and lib is not None:
             lib.pgcn_links_destroy(self._h)
+            self._h = c_void_p()
+
+    __del__ = close
+
+
+def links_sort_tile():
+    """Entries per workgroup tile of the rebuild's radix passes (pgcn_links_sort_tile)."""
+    t = c_int()
+    lib.pgcn_links_sort_tile(ctypes.byref(t))
+    return t.value
+
+
+class NegSampler:
+    """Negative endpoints drawn on the device (pgcn_neg_sampler): per node a strictly ascending
+    exclusion row (excl_ptr int64 [n + 1], excl_idx) that holds the node itself."""
+
+    def __init__(self, n_nodes, excl_ptr, excl_idx):
+        ep = np.ascontiguousarray(excl_ptr, np.int64)
+        ei = np.ascontiguousarray(excl_idx, np.int32)
+        if ep.shape != (n_nodes + 1,) or ei.ndim != 1 or ep[-1] != ei.size:
+            raise ValueError("NegSampler: excl_ptr [n + 1], excl_idx [excl_ptr[n]]")
+        h = c_void_p()
+        check(lib.pgcn_neg_sampler_create(n_nodes, _ptr(ep), _ptr(ei), ctypes.byref(h)),
+              "neg_sampler_create")
+        self._h, self.n_nodes = h, n_nodes
+
+    def sample(self, dev_src, m, seed, round, dev_dst, stream=None):
+        """dev_dst[e] = a node outside dev_src[e]'s row, e < m, from the counter hash of (seed,
+        round, e); device int32 arrays; asynchronous (pgcn_neg_sample)."""
+        check(lib.pgcn_neg_sample(self._h, _dptr(dev_src), m, seed, round, _dptr(dev_dst), stream),
+              "neg_sample")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and lib is not None:
+            lib.pgcn_neg_sampler_destroy(self._h)
             self._h = c_void_p()
 
     __del__ = close
@@ -854,7 +933,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
                 multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
                 aggregator=None, root_weight=False, readout=None, link_decoder=None,
-                link_hidden=0):
+                link_hidden=0, neg_ratio=0):
     """aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
     own row through its own half of a [d_in][2 d_l] weight (with an aggregator only).
     readout: None (node classification), "sum", "mean" or "max": graph classification over the
@@ -870,6 +949,10 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     if int(link_hidden) != link_hidden or not 0 <= link_hidden <= 128 or \
             (link_hidden and not LINK_DECODERS[link_decoder]):
         raise ValueError("link_hidden: 0, or 1..128 with link_decoder='dot' (the MLP decoder)")
+    if int(neg_ratio) != neg_ratio or not 0 <= neg_ratio <= 64 or \
+            (neg_ratio and not LINK_DECODERS[link_decoder]):
+        raise ValueError("neg_ratio: 0, or 1..64 with link_decoder='dot' (negatives per training "
+                         "positive, redrawn on the device before every epoch)")
     if readout not in READOUTS:
         raise ValueError(f"readout must be one of {sorted(k for k in READOUTS if k)} or None")
     if READOUTS[readout] and multilabel:
@@ -890,6 +973,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     p.readout = READOUTS[readout]
     p.link_decoder = LINK_DECODERS[link_decoder]
     p.link_hidden = int(link_hidden)
+    p.neg_ratio = int(neg_ratio)
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
@@ -1274,6 +1358,14 @@ def checkpoint_links(path):
     return dec.value, e.value
 
 
+def checkpoint_neg_ratio(path):
+    """The neg_ratio a checkpoint was saved with: 0 for versions 1-9 (pgcn_checkpoint_neg_ratio)."""
+    r = c_int()
+    check(lib.pgcn_checkpoint_neg_ratio(os.fsencode(path), ctypes.byref(r)),
+          f"checkpoint_neg_ratio {path}")
+    return r.value
+
+
 def checkpoint_link_hidden(path):
     """Host-only: the link decoder's hidden width of the engine that saved the file -- a version-9
     file's; 0 for versions 1-8.  PgcnError(PGCN_E_IO) for an invalid file."""
@@ -1400,10 +1492,14 @@ EXPORTED = [
     "pgcn_dataset_load_labels",
     "pgcn_readout_chunk_rows", "pgcn_readout_workspace", "pgcn_readout_fwd", "pgcn_readout_bwd",
     "pgcn_dataset_set_graphs", "pgcn_dataset_load_graphs", "pgcn_checkpoint_readout",
+    "pgcn_links_create_dynamic", "pgcn_links_set_dst_range", "pgcn_links_rebuild",
+    "pgcn_links_incidence_copy", "pgcn_links_sort_tile", "pgcn_debug_links_rebuild_times",
+    "pgcn_neg_sampler_create", "pgcn_neg_sampler_destroy", "pgcn_neg_sample",
     "pgcn_links_create", "pgcn_links_destroy", "pgcn_link_segment_slots", "pgcn_links_slots",
     "pgcn_link_score_fwd", "pgcn_link_score_bwd", "pgcn_debug_links_incidence",
     "pgcn_link_mlp_tile", "pgcn_link_mlp_workspace", "pgcn_link_mlp_fwd", "pgcn_link_mlp_bwd",
-    "pgcn_checkpoint_links", "pgcn_checkpoint_link_hidden", "pgcn_gcn_predict_links", "pgcn_gcn_link_counts",
+    "pgcn_checkpoint_links", "pgcn_checkpoint_link_hidden", "pgcn_checkpoint_neg_ratio",
+    "pgcn_gcn_predict_links", "pgcn_gcn_link_counts",
     "pgcn_gcn_score_pairs", "pgcn_dataset_set_links", "pgcn_dataset_load_links",
     "pgcn_rank_queries_create", "pgcn_rank_queries_destroy", "pgcn_link_rank_tile",
     "pgcn_link_rank_scores", "pgcn_link_rank", "pgcn_debug_rank_filter", "pgcn_gcn_link_ranks",

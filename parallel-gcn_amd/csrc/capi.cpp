@@ -45,6 +45,9 @@ struct pgcn_graph {
 struct pgcn_links {
   std::unique_ptr<LinkIndexDev> l;
 };
+struct pgcn_neg_sampler {
+  std::unique_ptr<NegSamplerDev> s;
+};
 struct pgcn_rank_queries {
   std::unique_ptr<RankQueriesDev> q;
 };
@@ -120,6 +123,9 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
                  (p->link_hidden == 0 || p->link_decoder == 1),
              PGCN_E_INVALID, "link_hidden: 0, or 1..128 with link_decoder 1");
   q.link_hidden = p->link_hidden;
+  PGCN_CHECK(p->neg_ratio >= 0 && p->neg_ratio <= 64 && (p->neg_ratio == 0 || p->link_decoder == 1),
+             PGCN_E_INVALID, "neg_ratio: 0, or 1..64 with link_decoder 1");
+  q.neg_ratio = p->neg_ratio;
   return q;
 }
 AdamParams to_adam(const pgcn_params *p) {
@@ -810,6 +816,90 @@ int pgcn_links_destroy(pgcn_links *l) {
   return PGCN_OK;
 }
 
+int pgcn_links_create_dynamic(int n_nodes, long long n_pairs, const int *src, const int *dst,
+                              const int *select, pgcn_links **out) {
+  return guarded([&] {
+    PGCN_CHECK(out, PGCN_E_INVALID, "links_create_dynamic args");
+    validate_pairs(n_nodes, n_pairs, src, dst);
+    check_device();
+    auto h = std::make_unique<pgcn_links>();
+    h->l = std::make_unique<LinkIndexDev>(n_nodes, n_pairs, src, dst, select,
+                                          LinkIndexDev::Dynamic{});
+    *out = h.release();
+  });
+}
+
+int pgcn_links_set_dst_range(pgcn_links *l, long long first, long long count, const int *dev_dst,
+                             void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(l && l->l, PGCN_E_INVALID, "links_set_dst_range: null handle");
+    check_device();
+    l->l->set_dst_range(first, count, dev_dst, as_stream(stream));
+  });
+}
+
+int pgcn_links_rebuild(pgcn_links *l, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(l && l->l, PGCN_E_INVALID, "links_rebuild: null handle");
+    check_device();
+    l->l->rebuild(as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_links_incidence_copy(const pgcn_links *l, int *ptr, int *pair, int *other) {
+  return guarded([&] {
+    PGCN_CHECK(l && l->l && ptr, PGCN_E_INVALID, "links_incidence_copy: a handle and ptr");
+    l->l->incidence_copy(ptr, pair, other);
+  });
+}
+
+int pgcn_debug_links_rebuild_times(pgcn_links *l, float *us, int cap) {
+  int stages = PGCN_E_INVALID;
+  const int rc = guarded([&] {
+    PGCN_CHECK(l && l->l && us && cap >= 0, PGCN_E_INVALID, "links_rebuild_times args");
+    check_device();
+    const std::vector<float> t = l->l->rebuild_stage_times();
+    for (size_t k = 0; k < t.size() && (int)k < cap; k++) us[k] = t[k];
+    stages = (int)t.size();
+  });
+  return rc == PGCN_OK ? stages : rc;
+}
+
+void pgcn_links_sort_tile(int *entries_per_tile) {
+  if (entries_per_tile) *entries_per_tile = kSortTile;
+}
+
+int pgcn_neg_sampler_create(int n_nodes, const long long *excl_ptr, const int *excl_idx,
+                            pgcn_neg_sampler **out) {
+  return guarded([&] {
+    PGCN_CHECK(out, PGCN_E_INVALID, "neg_sampler_create args");
+    validate_exclusion(n_nodes, excl_ptr, excl_idx);
+    check_device();
+    auto h = std::make_unique<pgcn_neg_sampler>();
+    h->s = std::make_unique<NegSamplerDev>(n_nodes, excl_ptr, excl_idx);
+    *out = h.release();
+  });
+}
+
+int pgcn_neg_sampler_destroy(pgcn_neg_sampler *s) {
+  delete s;
+  return PGCN_OK;
+}
+
+int pgcn_neg_sample(const pgcn_neg_sampler *sampler, const int *dev_src, long long m,
+                    unsigned long long seed, long long round, int *dev_dst, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(sampler && sampler->s && m >= 0 && m <= INT_MAX && round >= 0 &&
+                   (m == 0 || (dev_src && dev_dst)),
+               PGCN_E_INVALID, "neg_sample: a sampler, 0 <= m within an int, round >= 0, src, dst");
+    check_device();
+    launch_neg_sample(dev_src, m, sampler->s->n(), sampler->s->ptr(), sampler->s->idx(), seed,
+                      (unsigned long long)round, dev_dst, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_link_segment_slots(void) { return kGatSeg; }
 
 long long pgcn_links_slots(const pgcn_links *l) {
@@ -1133,6 +1223,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->readout = 0;
   p->link_decoder = 0;
   p->link_hidden = 0;
+  p->neg_ratio = 0;
   p->early_stopping = 0;
   p->attention_heads = 1;
   p->attention_dropout = 0.0f;
@@ -1295,6 +1386,7 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
   if (!std::strcmp(key, "link_decoder")) return e.get_params().link_decoder;
   if (!std::strcmp(key, "link_hidden")) return e.get_params().link_hidden;
   if (!std::strcmp(key, "num_pairs")) return e.num_pairs();
+  if (!std::strcmp(key, "neg_pairs")) return e.neg_pairs();
   if (!std::strcmp(key, "fused_norm_tails")) return e.fused_norm_tails();
   if (!std::strcmp(key, "graph_symmetric")) return e.symmetric() ? 1 : 0;
   if (!std::strcmp(key, "graphsum_lds")) return e.graphsum_lds() ? 1 : 0;
@@ -1430,6 +1522,12 @@ int pgcn_checkpoint_link_hidden(const char *path, int *link_hidden) {
   return guarded([&] {
     PGCN_CHECK(path && link_hidden, PGCN_E_INVALID, "checkpoint_link_hidden args");
     *link_hidden = read_checkpoint(path).link_hidden;
+  });
+}
+int pgcn_checkpoint_neg_ratio(const char *path, int *neg_ratio) {
+  return guarded([&] {
+    PGCN_CHECK(path && neg_ratio, PGCN_E_INVALID, "checkpoint_neg_ratio args");
+    *neg_ratio = read_checkpoint(path).neg_ratio;
   });
 }
 int pgcn_params_sizeof(void) { return (int)sizeof(pgcn_params); }

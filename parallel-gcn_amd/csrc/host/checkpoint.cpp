@@ -70,10 +70,20 @@ CkLinksExt links_ext(const Checkpoint &ck) {
   return CkLinksExt{(uint32_t)ck.link_decoder, (uint32_t)ck.link_hidden, (uint64_t)ck.num_pairs};
 }
 
+// version 10: behind the link block
+struct CkNegExt {
+  uint32_t neg_ratio, zero32;
+  uint64_t zero;
+};
+static_assert(sizeof(CkNegExt) == 16, "checkpoint extension layout");
+
+CkNegExt neg_ext(const Checkpoint &ck) { return CkNegExt{(uint32_t)ck.neg_ratio, 0, 0}; }
+
 // versions 7 and 8 carry the heads, SAGE and readout blocks whatever the layer family
 bool link_blocks(uint32_t version) {  // ... and the link block behind them
   return version == (uint32_t)kCheckpointVersionLinks ||
-         version == (uint32_t)kCheckpointVersionLinkMlp;
+         version == (uint32_t)kCheckpointVersionLinkMlp ||
+         version == (uint32_t)kCheckpointVersionNeg;
 }
 bool three_blocks(uint32_t version) {
   return version == (uint32_t)kCheckpointVersionReadout || link_blocks(version);
@@ -92,6 +102,10 @@ uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
   if (link_blocks(h.version)) {
     const CkLinksExt le = links_ext(ck);
     x = fnv1a(x, &le, sizeof le);
+  }
+  if (h.version == (uint32_t)kCheckpointVersionNeg) {
+    const CkNegExt ne = neg_ext(ck);
+    x = fnv1a(x, &ne, sizeof ne);
   }
   if (h.version == (uint32_t)kCheckpointVersionHeads) {
     const CkHeadsExt e = heads_ext(ck);
@@ -204,7 +218,8 @@ bool readout_ok(uint32_t version, long long readout, long long num_graphs, long 
 bool links_ok(uint32_t version, long long decoder, long long num_pairs, long long hidden,
               long long embed) {
   if (!link_blocks(version)) return decoder == 0 && num_pairs == 0 && hidden == 0;
-  const bool mlp = version == (uint32_t)kCheckpointVersionLinkMlp;
+  const bool mlp = version == (uint32_t)kCheckpointVersionLinkMlp ||
+                   (version == (uint32_t)kCheckpointVersionNeg && hidden != 0);
   return decoder == 1 && num_pairs >= 1 && num_pairs < (1LL << 31) &&
          (mlp ? hidden >= 1 && hidden <= 128 && embed <= 128 : hidden == 0);
 }
@@ -243,6 +258,9 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   PGCN_CHECK(links_ok(h.version, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]),
              PGCN_E_INVALID,
              "checkpoint: link decoder / pair count do not match the file's version");
+  PGCN_CHECK((h.version == (uint32_t)kCheckpointVersionNeg)
+                 ? ck.neg_ratio >= 1 && ck.neg_ratio <= 64 : ck.neg_ratio == 0,
+             PGCN_E_INVALID, "checkpoint: neg_ratio does not match the file's version");
   PGCN_CHECK(sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: aggregator / root weight do not match the file's version");
   PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight) +
@@ -260,6 +278,8 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage || v7;
   const CkReadoutExt rext = readout_ext(ck);
   const CkLinksExt lext = links_ext(ck);
+  const CkNegExt next = neg_ext(ck);
+  const bool v10 = h.version == (uint32_t)kCheckpointVersionNeg;
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
   std::FILE *f = std::fopen(tmp.c_str(), "wb");
@@ -269,6 +289,7 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
             (!with_sage || std::fwrite(&sext, sizeof(sext), 1, f) == 1) &&
             (!v7 || std::fwrite(&rext, sizeof(rext), 1, f) == 1) &&
             (!v8 || std::fwrite(&lext, sizeof(lext), 1, f) == 1) &&
+            (!v10 || std::fwrite(&next, sizeof(next), 1, f) == 1) &&
             write_floats(f, ck.results) &&
             write_floats(f, ck.w) && write_floats(f, ck.m) && write_floats(f, ck.v);
   ok = (std::fclose(f) == 0) && ok;
@@ -320,6 +341,12 @@ Checkpoint read_checkpoint(const std::string &path) {
     ck.link_hidden = (int)e.link_hidden;
     ck.link_decoder = (int)e.link_decoder;
     ck.num_pairs = (long long)e.num_pairs;
+  }
+  if (ok && h.version == (uint32_t)kCheckpointVersionNeg) {
+    CkNegExt e{};
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.neg_ratio >= 1 && e.neg_ratio <= 64 &&
+         e.zero32 == 0 && e.zero == 0;
+    ck.neg_ratio = (int)e.neg_ratio;
   }
   ok = ok && links_ok(h.version, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]) && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
        sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight) &&

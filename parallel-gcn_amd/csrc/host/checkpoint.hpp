@@ -83,6 +83,8 @@ constexpr int kCheckpointVersionReadout = 7;  // bits 0-5 known, bit 5 set, + th
 constexpr unsigned kCheckpointLinks = 64u;  // header flags, bit 6 (version 8 only)
 constexpr int kCheckpointVersionLinks = 8;  // bit 6 set, + four blocks
 constexpr int kCheckpointVersionLinkMlp = 9;  // version 8 + link_hidden and the decoder tensor
+// version 8 (link_hidden 0) or 9 + a fifth block {u32 neg_ratio (1..64); u32 0; u64 0}
+constexpr int kCheckpointVersionNeg = 10;
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -104,7 +106,8 @@ struct Checkpoint {
   // version 8's own block; 0 and 0 in every other version
   int link_decoder = 0;
   long long num_pairs = 0;
-  int link_hidden = 0;  // version 9 only
+  int link_hidden = 0;  // versions 9 and 10
+  int neg_ratio = 0;    // version 10 only
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
+#include <numeric>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -341,6 +343,9 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
   PGCN_CHECK(params.link_hidden >= 0 && params.link_hidden <= kLinkMlpMaxHidden &&
                  (params.link_hidden == 0 || params.link_decoder == 1),
              PGCN_E_INVALID, "link_hidden: 0, or 1..128 with link_decoder 1");
+  PGCN_CHECK(params.neg_ratio >= 0 && params.neg_ratio <= 64 &&
+                 (params.neg_ratio == 0 || params.link_decoder == 1),
+             PGCN_E_INVALID, "neg_ratio: 0, or 1..64 with link_decoder 1");
   if (params.link_decoder) {
     PGCN_CHECK(!params.multilabel, PGCN_E_INVALID,
                "link_decoder cannot be combined with multilabel");
@@ -364,6 +369,14 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
       PGCN_CHECK(labelled[s] <= (1LL << 24), PGCN_E_INVALID,
                  "link_decoder: the labelled pairs of a split must not exceed 2^24");
     num_pairs_ = (int)E;
+    if (params.neg_ratio) {  // R drawn pairs per training positive, behind the data's pairs
+      long long pos = 0;
+      for (size_t e = 0; e < E; e++) pos += data.pair_split[e] == 1 && data.pair_label[e] == 1;
+      const long long drawn = pos * params.neg_ratio;
+      PGCN_CHECK(labelled[1] + drawn <= (1LL << 24) && (long long)E + drawn <= INT_MAX,
+                 PGCN_E_INVALID, "neg_ratio: the training pairs with the drawn ones exceed 2^24");
+      neg_pairs_ = (int)drawn;
+    }
     // link_ranks builds its query sets from the pattern and the pairs (host copies)
     rank_graph_ = data.graph;
     rank_pairs_[0] = data.pair_src;
@@ -609,23 +622,51 @@ void GCN::build(const GCNData &data) {
     counts[s] = c;
   }
   for (int s = 1; params.link_decoder && s <= 3; s++) {  // per pair: the split's labelled pairs
-    std::vector<int> t((size_t)num_pairs_, -1);
+    std::vector<int> t((size_t)num_pairs_ + neg_pairs_, -1);
     int c = 0;
     for (int e = 0; e < num_pairs_; e++)
       if (data.pair_split[(size_t)e] == s && data.pair_label[(size_t)e] >= 0) {
         t[(size_t)e] = data.pair_label[(size_t)e];
         c++;
       }
+    if (s == 1) {  // the drawn pairs: label 0, the training split
+      std::fill(t.begin() + num_pairs_, t.end(), 0);
+      c += neg_pairs_;
+    }
     truth[s].allocate(t.size());
     truth[s].upload(t);
     truth_compact[s].allocate(1);
     counts[s] = c;
-    if (s == 1)  // (the only split that runs a backward; host work, outside any capture)
+    if (s == 1 && !params.neg_ratio)  // (the only split that runs a backward; host work)
       links_ = std::make_unique<LinkIndexDev>(N, num_pairs_, data.pair_src.data(),
                                               data.pair_dst.data(), t.data());
+    if (s == 1 && params.neg_ratio) {
+      // a rebuildable index over E + R P pairs; a drawn pair starts as (src, src) and gets its
+      // endpoint before the first training forward (resample_negatives)
+      std::vector<int> src(data.pair_src), dst(data.pair_dst), anchors;
+      for (int e = 0; e < num_pairs_; e++)
+        if (data.pair_split[(size_t)e] == 1 && data.pair_label[(size_t)e] == 1)
+          anchors.insert(anchors.end(), (size_t)params.neg_ratio, data.pair_src[(size_t)e]);
+      src.insert(src.end(), anchors.begin(), anchors.end());
+      dst.insert(dst.end(), anchors.begin(), anchors.end());
+      links_ = std::make_unique<LinkIndexDev>(N, (long long)src.size(), src.data(), dst.data(),
+                                              t.data(), LinkIndexDev::Dynamic{});
+      // the exclusion rows: link top-K's filtered exclude lists of every node, side 0
+      std::vector<int> all((size_t)N);
+      std::iota(all.begin(), all.end(), 0);
+      const TopKFilterHost x = build_topk_filter(
+          N, data.graph.indptr.data(), data.graph.indices.data(), num_pairs_,
+          data.pair_src.data(), data.pair_dst.data(), data.pair_label.data(),
+          data.pair_split.data(), N, all.data(), 0, 1);
+      validate_exclusion(N, x.ptr.data(), x.idx.data());
+      neg_sampler_ = std::make_unique<NegSamplerDev>(N, x.ptr.data(), x.idx.data());
+      neg_src_.allocate(std::max<size_t>(anchors.size(), 1));
+      neg_src_.upload(anchors.data(), anchors.size());
+      neg_dst_.allocate(std::max<size_t>(anchors.size(), 1));
+    }
   }
   if (params.link_decoder) {  // the one-class bit matrix [E][1]: bit 0 = the pair is a link
-    std::vector<uint32_t> b((size_t)num_pairs_, 0u);
+    std::vector<uint32_t> b((size_t)num_pairs_ + neg_pairs_, 0u);  // (a drawn pair: 0)
     for (int e = 0; e < num_pairs_; e++) b[(size_t)e] = data.pair_label[(size_t)e] == 1 ? 1u : 0u;
     label_bits.allocate(b.size());
     label_bits.upload(b);
@@ -1163,7 +1204,7 @@ void GCN::insert_last_layer() {
   }
   if (params.link_decoder) {  // node embedding -> scores [E][4] -> the one-class loss over the pairs
     link_embed = out;
-    link_scores = std::make_shared<Variable>(num_pairs_, 1, true, 4);
+    link_scores = std::make_shared<Variable>(num_pairs_ + neg_pairs_, 1, true, 4);
     if (link_var)
       modules.push_back(std::make_unique<LinkMlpDecoder>(
           out, link_var, link_scores, links_.get(), C, params.link_hidden, link_mlp_ws.get(),
@@ -1471,8 +1512,20 @@ void GCN::backward_pass(FoldScope &fold, TnDeferList *defer) {
 }
 
 // train_epoch (src/gcn.cu:307-343) + eval(2) (src/gcn.cu:293-303), host-sync free
+// neg_ratio: this epoch's negatives -- the draw of round epoch_count, into the pair index, and the
+// index rebuilt -- on the engine's stream, without a sync or an allocation
+void GCN::resample_negatives() {
+  if (!neg_pairs_) return;
+  launch_neg_sample(neg_src_.get(), neg_pairs_, neg_sampler_->n(), neg_sampler_->ptr(),
+                    neg_sampler_->idx(), params.seed, (unsigned long long)epoch_count,
+                    neg_dst_.get(), stream.get());
+  links_->set_dst_range(num_pairs_, neg_pairs_, neg_dst_.get(), stream.get());
+  links_->rebuild(stream.get());
+}
+
 void GCN::enqueue_epoch(bool graph) {
   const int slot4 = graph ? 0 : (int)(epoch_count % ring_cap) * 4;
+  resample_negatives();
   set_split(1);
   TnDeferList defer;
   FoldScope fold(*this, &defer);
@@ -1500,6 +1553,7 @@ void GCN::enqueue_epoch(bool graph) {
 // eval and the next training forward).
 bool GCN::graph_eligible() const {
   if (!knobs_.epoch_graph || !warm || comm || ctx.profile) return false;
+  if (neg_pairs_) return false;  // (the draw's round changes every epoch)
   if (ctx.train_ahead && feats.dense && feats.maskT && !feats.ax) return false;
   // (the same host swaps)
   if (ctx.train_ahead && !feats.dense && knobs_.sparse_dual) return false;
@@ -1567,6 +1621,7 @@ void GCN::epoch_async() {
 
 std::pair<float, float> GCN::train_epoch() {
   const long long slot = epoch_count % ring_cap;
+  resample_negatives();
   set_split(1);
   TnDeferList defer;
   FoldScope fold(*this, &defer);
@@ -1833,6 +1888,11 @@ void GCN::save(const std::string &path) {
       ck.version = kCheckpointVersionLinkMlp;
       ck.link_hidden = params.link_hidden;
     }
+    if (params.neg_ratio) {  // version 10: the ratio in a block of its own
+      ck.version = kCheckpointVersionNeg;
+      ck.link_hidden = params.link_hidden;
+      ck.neg_ratio = params.neg_ratio;
+    }
   }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
@@ -1861,6 +1921,8 @@ void GCN::load(const std::string &path, int flags) {
   if (same && resume) same = ck.aggregator == params.aggregator;
   // (a weights-only load crosses the link decoder: it has no weights, the tensors are the same)
   if (same && resume) same = ck.link_decoder == params.link_decoder && ck.num_pairs == num_pairs_;
+  // (the drawn pairs are part of what a resumed run trains on; weights only crosses the ratio)
+  if (same && resume) same = ck.neg_ratio == params.neg_ratio;
   // (the decoder tensor's shape: a file that has one must match; one without leaves it as it is,
   // weights only)
   same = same && (resume ? ck.link_hidden == params.link_hidden

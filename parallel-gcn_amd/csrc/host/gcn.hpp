@@ -71,6 +71,7 @@ struct GCNParams {
   // 0: the dot product; 1..128 (with link_decoder 1): a LinkMlpDecoder of that hidden width on
   // the packed tensor link_var, one more weight and optimizer entry
   int link_hidden = 0;
+  int neg_ratio = 0;
 };
 
 struct AdamParams {
@@ -211,6 +212,7 @@ class GCN {
   int aggregator() const { return params.aggregator; }
   int num_graphs() const { return num_graphs_; }
   long long num_pairs() const { return num_pairs_; }
+  long long neg_pairs() const { return neg_pairs_; }
   bool root_weight() const { return params.root_weight; }
   // ... of which the last training forward ran its ReLU / add / Dropout tail in the LayerNorm kernel
   int fused_norm_tails() const;
@@ -270,11 +272,18 @@ class GCN {
   // the rows the loss, predict() and confusion() run over: the graphs, or this rank's nodes
   int loss_rows() const { return head_rows() ? head_rows() : part.local_rows(); }
   int loss_prow() const { return head_rows() ? head_rows() : part.maxrows; }
-  int head_rows() const { return params.readout ? num_graphs_ : num_pairs_; }
+  int head_rows() const { return params.readout ? num_graphs_ : num_pairs_ + neg_pairs_; }
   // link_decoder: the pairs (0: none), their index on the device (its backward entries: the
   // training split's labelled pairs), the node embedding the decoder reads and its scores [E][4]
   int num_pairs_ = 0;
   std::unique_ptr<LinkIndexDev> links_;
+  // neg_ratio: the drawn pairs behind the data's (rows num_pairs_ .. + neg_pairs_ of the index, the
+  // scores, the truth and the label bits), their anchors and this round's endpoints on the device,
+  // and the sampler over the exclusion rows; resample_negatives runs before every training forward
+  int neg_pairs_ = 0;
+  std::unique_ptr<NegSamplerDev> neg_sampler_;
+  DeviceBuffer<int> neg_src_, neg_dst_;
+  void resample_negatives();
   shared_ptr<Variable> link_embed, link_scores;
   shared_ptr<Variable> link_var;  // link_hidden > 0: P [output_dim + 3][round_up4(link_hidden)]
   DeviceBuffer<float> link_mlp_ws;  // ... and the decoder backward's workspace

@@ -824,6 +824,138 @@ LinkIndexDev::LinkIndexDev(int n, long long n_pairs, const int *src, const int *
   l_.ws = ws_.get();
 }
 
+LinkIndexDev::LinkIndexDev(int n, long long n_pairs, const int *src, const int *dst,
+                           const int *select, Dynamic)
+    : dynamic_(true) {
+  std::vector<int> sel;
+  for (long long e = 0; e < n_pairs; e++)
+    if (!select || select[e] >= 0) sel.push_back((int)e);
+  PGCN_CHECK(sel.size() < ((size_t)1 << 30), PGCN_E_INVALID,
+             "links: the incidence entries (2 per selected pair) must fit an int");
+  const int total = (int)(2 * sel.size());
+  const int tiles = (int)ceil_div(total, kSortTile);
+  const int long_cap = total / (kGatSeg + 1);
+  const int seg_cap = long_cap ? (int)ceil_div(total, kGatSeg) + long_cap + 1 : 0;
+  const int blocks = (int)ceil_div(n, 256);
+  auto up = [](auto &buf, const auto *host, size_t count) {
+    buf.allocate(std::max<size_t>(count, 1));
+    if (count) buf.upload(host, count);
+  };
+  up(src_, src, (size_t)n_pairs);
+  up(dst_, dst, (size_t)n_pairs);
+  up(sel_, sel.data(), sel.size());
+  ptr_.allocate((size_t)n + 1);
+  ptr_.zero();  // what an index without entries keeps
+  pair_.allocate(std::max(total, 1));
+  other_.allocate(std::max(total, 1));
+  segs_.allocate(std::max(seg_cap, 1));
+  longs_.allocate(std::max(long_cap, 1));
+  ws_.allocate(std::max<size_t>((size_t)seg_cap * kLinkWsStride, 4));
+  ws_.zero();
+  sort_nodes_.allocate(std::max<size_t>(2 * (size_t)total, 1));
+  sort_keys_.allocate(std::max<size_t>(2 * (size_t)total, 1));
+  hist_.allocate(256 * (size_t)tiles + 256);
+  marks_.allocate(2 * (size_t)blocks + 2);
+  slots_ = total;
+  l_.n = n;
+  l_.n_pairs = n_pairs;
+  l_.src = src_.get();
+  l_.dst = dst_.get();
+  l_.inc_ptr = ptr_.get();
+  l_.inc_pair = pair_.get();
+  l_.inc_other = other_.get();
+  l_.n_segs = seg_cap;
+  l_.n_long = long_cap;
+  l_.segs = segs_.get();
+  l_.longs = longs_.get();
+  l_.ws = ws_.get();
+  build_.n = n;
+  build_.total = total;
+  build_.tiles = tiles;
+  build_.sel = sel_.get();
+  build_.src = src_.get();
+  build_.dst = dst_.get();
+  build_.nodes[0] = sort_nodes_.get();
+  build_.nodes[1] = sort_nodes_.get() + total;
+  build_.keys[0] = sort_keys_.get();
+  build_.keys[1] = sort_keys_.get() + total;
+  build_.hist = hist_.get();
+  build_.marks = marks_.get();
+  build_.ptr = ptr_.get();
+  build_.pair = pair_.get();
+  build_.other = other_.get();
+  build_.segs = segs_.get();
+  build_.longs = longs_.get();
+  build_.seg_cap = seg_cap;
+  build_.long_cap = long_cap;
+  rebuild(nullptr);
+  PGCN_HIP(hipStreamSynchronize(nullptr));
+}
+
+void LinkIndexDev::set_dst_range(long long first, long long count, const int *dev_dst,
+                                 hipStream_t s) {
+  PGCN_CHECK(dynamic_, PGCN_E_INVALID, "links_set_dst_range: not a dynamic handle");
+  PGCN_CHECK(first >= 0 && count >= 0 && first <= l_.n_pairs && count <= l_.n_pairs - first &&
+                 (count == 0 || dev_dst),
+             PGCN_E_INVALID, "links_set_dst_range: the range must lie within the pairs");
+  if (count)
+    PGCN_HIP(hipMemcpyAsync(dst_.get() + first, dev_dst, (size_t)count * sizeof(int),
+                            hipMemcpyDeviceToDevice, s));
+}
+
+void LinkIndexDev::rebuild(hipStream_t s) {
+  PGCN_CHECK(dynamic_, PGCN_E_INVALID, "links_rebuild: not a dynamic handle");
+  launch_links_rebuild(build_, s);
+}
+
+std::vector<float> LinkIndexDev::rebuild_stage_times() {
+  PGCN_CHECK(dynamic_, PGCN_E_INVALID, "links_rebuild: not a dynamic handle");
+  std::vector<hipEvent_t> ev((size_t)links_rebuild_stages(build_) + 1);
+  for (auto &e : ev) PGCN_HIP(hipEventCreate(&e));
+  PGCN_HIP(hipEventRecord(ev[0], nullptr));
+  launch_links_rebuild(build_, nullptr, ev.data() + 1);
+  PGCN_HIP(hipStreamSynchronize(nullptr));
+  std::vector<float> us(ev.size() - 1);
+  for (size_t k = 0; k + 1 < ev.size(); k++) {
+    PGCN_HIP(hipEventElapsedTime(&us[k], ev[k], ev[k + 1]));
+    us[k] *= 1e3f;
+  }
+  for (auto &e : ev) (void)hipEventDestroy(e);
+  return us;
+}
+
+void LinkIndexDev::incidence_copy(int *ptr, int *pair, int *other) const {
+  PGCN_HIP(hipDeviceSynchronize());
+  if (ptr) ptr_.download(ptr, (size_t)l_.n + 1);
+  if (pair) pair_.download(pair, (size_t)slots_);
+  if (other) other_.download(other, (size_t)slots_);
+}
+
+void validate_exclusion(int n, const long long *ptr, const int *idx) {
+  PGCN_CHECK(n >= 1 && ptr && ptr[0] == 0, PGCN_E_INVALID,
+             "neg_sampler: n >= 1, excl_ptr [n + 1] from 0");
+  for (int i = 0; i < n; i++) {
+    const long long b = ptr[i], e = ptr[i + 1];
+    PGCN_CHECK(e > b && idx, PGCN_E_INVALID, "neg_sampler: every row holds its own node");
+    PGCN_CHECK(e - b < n, PGCN_E_INVALID,
+               "neg_sampler: a row excludes every node, nothing is left to draw");
+    bool self = false;
+    for (long long k = b; k < e; k++) {
+      PGCN_CHECK(idx[k] >= 0 && idx[k] < n && (k == b || idx[k - 1] < idx[k]), PGCN_E_INVALID,
+                 "neg_sampler: a row must be strictly ascending within [0, n)");
+      self |= idx[k] == i;
+    }
+    PGCN_CHECK(self, PGCN_E_INVALID, "neg_sampler: every row holds its own node");
+  }
+}
+
+NegSamplerDev::NegSamplerDev(int n, const long long *ptr, const int *idx) : n_(n) {
+  ptr_.allocate((size_t)n + 1);
+  ptr_.upload(ptr, (size_t)n + 1);
+  idx_.allocate((size_t)ptr[n]);
+  idx_.upload(idx, (size_t)ptr[n]);
+}
+
 void validate_rank_queries(int n, long long n_queries, const int *anchor, const int *target,
                            const long long *filter_ptr, const int *filter_idx) {
   PGCN_CHECK(n >= 1 && n_queries >= 0 && n_queries <= INT_MAX &&

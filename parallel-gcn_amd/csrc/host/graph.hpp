@@ -243,8 +243,27 @@ void build_incidence(int n, long long n_pairs, const int *src, const int *dst, c
 class LinkIndexDev {
  public:
   LinkIndexDev(int n, long long n_pairs, const int *src, const int *dst, const int *select);
+  // A rebuildable index of fixed capacity (the pair count and the selection): the same index, built
+  // by launch_links_rebuild on the null stream (complete on return), with every buffer a later
+  // rebuild needs.  With N2 = 2 x the selected pairs, at most long_cap = N2 / (kGatSeg + 1) nodes
+  // exceed kGatSeg entries, in at most ceil(N2 / kGatSeg) + long_cap segments; the segment records
+  // and the partial-row workspace hold one row more (k_neg.hip's padding), and index() reports
+  // these capacities as n_segs / n_long.
+  struct Dynamic {};
+  LinkIndexDev(int n, long long n_pairs, const int *src, const int *dst, const int *select,
+               Dynamic);
   const LinkIndex &index() const { return l_; }
   long long slots() const { return slots_; }
+  bool dynamic() const { return dynamic_; }
+  // dst[first .. first + count) = dev_dst[0 .. count) on s (a device copy, no sync); the index
+  // is stale until rebuild.  The values must lie in [0, n): nothing on the host can check them.
+  void set_dst_range(long long first, long long count, const int *dev_dst, hipStream_t s);
+  void rebuild(hipStream_t s);
+  // timing only: one rebuild on the null stream (syncs), the microseconds of its stages in order
+  // -- per radix pass the histogram, the scan, the scatter; the index; the segment records if any
+  std::vector<float> rebuild_stage_times();
+  // device sync + blocking copies: ptr [n + 1], pair / other [slots()] (null: skipped)
+  void incidence_copy(int *ptr, int *pair, int *other) const;
 
  private:
   LinkIndex l_;
@@ -253,6 +272,27 @@ class LinkIndexDev {
   DeviceBuffer<int4> segs_;
   DeviceBuffer<int2> longs_;
   DeviceBuffer<float> ws_;
+  bool dynamic_ = false;
+  LinkBuild build_;
+  DeviceBuffer<int> sel_, sort_nodes_;
+  DeviceBuffer<unsigned> sort_keys_, hist_, marks_;
+};
+
+// The sampler's exclusion CSR on the device, of arrays validate_exclusion accepted.
+// validate_exclusion: PGCN_E_INVALID unless n >= 1, ptr [n + 1] starts at 0 and ascends, every row
+// is strictly ascending within [0, n), holds its own node and leaves at least one node free.
+void validate_exclusion(int n, const long long *ptr, const int *idx);
+class NegSamplerDev {
+ public:
+  NegSamplerDev(int n, const long long *ptr, const int *idx);
+  int n() const { return n_; }
+  const long long *ptr() const { return ptr_.get(); }
+  const int *idx() const { return idx_.get(); }
+
+ private:
+  int n_;
+  DeviceBuffer<long long> ptr_;
+  DeviceBuffer<int> idx_;
 };
 
 // A ranking query set as k_rank.hip takes it: PGCN_E_INVALID for an endpoint outside [0, n), a

@@ -107,7 +107,9 @@ __global__ __launch_bounds__(kItemThreads) void k_link_score_bwd(
   }
 }
 
-// one wave per long node: its segments' partials in segment order
+// one wave per long node: its segments' partials in segment order.  (A rebuildable index pads
+// l.longs with records {0, first} whose range [first, first + ceil(len_0 / kGatSeg)) is a spare
+// segment holding node 0's whole list -- k_neg.hip's header: keep deriving nseg from inc_ptr.)
 template <int GL>
 __global__ __launch_bounds__(kItemThreads) void k_link_score_bwd_merge(const LinkIndex l, int d,
                                                                        float *__restrict__ dH,

@@ -497,6 +497,43 @@ void launch_link_mlp_fwd(const LinkIndex &l, const float *H, int ld_h, int d, co
 void launch_link_mlp_bwd(const LinkIndex &l, const float *H, int ld_h, int d, const float *P,
                          int ld_p, int h, const float *G, int ld_g, float *dH, int ld_dh,
                          float *dP, int ld_dp, void *ws, long long ws_bytes, hipStream_t s);
+// ---- link prediction: negative sampling and the device incidence build (k_neg.hip) -------------
+// dst[e] = the r-th node outside the strictly ascending exclusion row of src[e] (device arrays;
+// excl_ptr [n + 1], every row holds its own node and fewer than n entries), r in [0, n - len) from
+// the counter hash of (seed, round, e) in the file's header: one launch, a lane per draw.  An
+// anchor outside [0, n) is read as the nearest node.
+void launch_neg_sample(const int *src, long long m, int n, const long long *excl_ptr,
+                       const int *excl_idx, unsigned long long seed, unsigned long long round,
+                       int *dst, hipStream_t s);
+// The buffers of a rebuildable LinkIndex (LinkIndexDev owns them): sel, the ascending ids of the
+// total / 2 selected pairs; the sort's ping-pong entries and its [256][tiles] digit counts + 256
+// row totals; marks [2 ceil(n / 256) + 2] (two count rows + their totals); the index arrays; the
+// capacities of the segment and long-node records (LinkIndexDev's dynamic constructor has the
+// bound).
+constexpr int kSortTile = 2048;  // entries per workgroup of a radix pass
+struct LinkBuild {
+  int n = 0, total = 0, tiles = 0;
+  const int *sel = nullptr, *src = nullptr, *dst = nullptr;
+  int *nodes[2] = {nullptr, nullptr};
+  unsigned *keys[2] = {nullptr, nullptr};
+  unsigned *hist = nullptr, *marks = nullptr;
+  int *ptr = nullptr, *pair = nullptr, *other = nullptr;
+  int4 *segs = nullptr;
+  int2 *longs = nullptr;
+  int seg_cap = 0, long_cap = 0;
+};
+// 8-bit digits of a node id below n: ceil(bits(n - 1) / 8), at least 1
+int link_sort_passes(int n);
+// The incidence index of build_incidence and the records of gat_segments, from src / dst as they
+// are on the device at this point of the stream: 3 launches per radix pass, two more for the
+// index, three more when long_cap > 0.  Allocates nothing, never syncs.  The records behind the
+// real ones are the harmless padding the file's header describes, so the backward kernels run
+// with n_segs = seg_cap and n_long = long_cap whatever the rebuild found.  An endpoint outside
+// [0, n) is read as the nearest node.
+// stage_end (timing only): links_rebuild_stages(b) events, recorded on s behind every stage --
+// per pass the histogram, the scan and the scatter, then the index, then the segment records.
+int links_rebuild_stages(const LinkBuild &b);
+void launch_links_rebuild(const LinkBuild &b, hipStream_t s, hipEvent_t *stage_end = nullptr);
 // ---- link prediction: 1-vs-all ranking counts (k_rank.hip) -------------------------------------
 // The rank score r(a, v) is the k-ordered fp32 fmaf chain over the d columns of rows a and v -- not
 // launch_link_score_fwd's order -- which is what the sweep's f32 MFMA tiles compute bit for bit.

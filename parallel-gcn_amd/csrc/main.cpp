@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -35,6 +35,8 @@
 // is used as loaded: keep validation and test positives out of it.
 // link_hidden=<H> (with link=dot; 1..128): the Hadamard-MLP decoder of that hidden width in the dot
 // product's place (pgcn_params.link_hidden); rank= and recommend= are refused on such an engine.
+// neg_ratio=<R> (with link=dot; 1..64): R negatives per training positive, redrawn on the device
+// before every epoch (pgcn_params.neg_ratio).
 // rank=1 (with link=): after the run, one line with the filtered ranking metrics of the test split
 // (pgcn_gcn_link_ranks; mean ties) for both sides: `rank side=dst queries=.. mrr=.. hits@10=..
 // hits@50=.. hits@100=.. side=src ...`; rank=<file> also writes `src dst greater equal` per test
@@ -134,6 +136,7 @@ static bool load_params(const char *path, pgcn_params *p, int *embed) {
     else if (k == "readout") p->readout = readout_id(v);
     else if (k == "link") p->link_decoder = link_id(v);
     else if (k == "link_hidden") p->link_hidden = std::atoi(v.c_str());
+    else if (k == "neg_ratio") p->neg_ratio = std::atoi(v.c_str());
     else if (k == "embed") *embed = std::atoi(v.c_str());
   }
   return true;
@@ -154,7 +157,7 @@ int main(int argc, char **argv) {
   float attn_dropout = -1.0f;
   int root_weight = -1;
   std::string aggregator, readout, link;
-  int embed = 32, embed_arg = -1, link_hidden = -1;
+  int embed = 32, embed_arg = -1, link_hidden = -1, neg_ratio = -1;
   for (int i = 2; i < argc; i++) {
     if (!std::strncmp(argv[i], "file=", 5)) file = argv[i] + 5;
     if (!std::strncmp(argv[i], "root=", 5)) root = argv[i] + 5;
@@ -176,6 +179,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "readout=", 8)) readout = argv[i] + 8;
     if (!std::strncmp(argv[i], "link=", 5)) link = argv[i] + 5;
     if (!std::strncmp(argv[i], "link_hidden=", 12)) link_hidden = std::atoi(argv[i] + 12);
+    if (!std::strncmp(argv[i], "neg_ratio=", 10)) neg_ratio = std::atoi(argv[i] + 10);
     if (!std::strncmp(argv[i], "embed=", 6)) embed_arg = std::atoi(argv[i] + 6);
     if (!std::strncmp(argv[i], "rank=", 5)) rank = argv[i] + 5;
     if (!std::strncmp(argv[i], "recommend=", 10)) recommend = argv[i] + 10;
@@ -199,6 +203,7 @@ int main(int argc, char **argv) {
   if (!readout.empty()) p.readout = readout_id(readout);
   if (!link.empty()) p.link_decoder = link_id(link);
   if (link_hidden >= 0) p.link_hidden = link_hidden;
+  if (neg_ratio >= 0) p.neg_ratio = neg_ratio;
   if (embed_arg >= 0) embed = embed_arg;
   pgcn_dataset *ds = nullptr;
   const int lst = cache ? pgcn_dataset_load_cached(root.c_str(), name, &ds, nullptr)
