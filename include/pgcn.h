@@ -526,6 +526,29 @@ long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indi
                                  int filtered, long long *n_filter, int *anchor, int *target,
                                  long long *ptr, int *idx);
 
+/* --- link prediction: 1-vs-all ranking counts under the MLP decoder (k_rank_mlp.hip; new: the
+ * reference has no pair-level model).  pgcn_link_rank's counts with the decoder's score in r's
+ * place: s(a, v) is what pgcn_link_mlp_fwd writes for the pair (a, v), BIT FOR BIT (P, ld_p, h: as
+ * there) -- the same rounded products H[a][i] * H[v][i], the same f32 MFMA accumulation from zero
+ * with i ascending, the same epilogue order -- so
+ *     greater[e] = #{ v in [0, n) : v != t_e, v not in F_e, s(a_e, v) >  s(a_e, t_e) }
+ *     equal[e]   = #{ v in [0, n) : v != t_e, v not in F_e, s(a_e, v) == s(a_e, t_e) }
+ * equal what a caller would count from pgcn_link_mlp_fwd on all n_queries * n explicit pairs,
+ * without those pairs or their scores in memory.  At most four launches: the thresholds (the pair
+ * forward itself on the handle's anchors and targets), the counts' zeroing, the sweep -- workgroups
+ * of pgcn_link_rank_mlp_tile's queries_per_block queries over candidates_per_chunk-candidate
+ * chunks, W1 resident in LDS, a grid of query blocks x candidate splits, the splits a function of
+ * (n_queries, n) only, counts added with unsigned integer atomics -- and with list entries the
+ * filter correction (64-pair tiles of the forward's tile code).  Asynchronous, allocates nothing
+ * (the handle owns the thresholds; two calls on one handle must not overlap), no float atomics: two
+ * calls give the same bits.  Limits: pgcn_link_mlp_fwd's (1 <= d, h <= 128, ld_h and ld_p multiples
+ * of 4 and >= d / h, H and P 16-byte aligned) and pgcn_link_rank's; anything else is
+ * PGCN_E_INVALID before the device is touched; n_queries == 0 launches nothing.  The cost is
+ * 2 n_queries n d h flops, h times the dot sweep's. */
+void pgcn_link_rank_mlp_tile(int *queries_per_block, int *candidates_per_chunk);
+int pgcn_link_rank_mlp(const pgcn_rank_queries *q, const float *H, int ld_h, int d, const float *P,
+                       int ld_p, int h, unsigned int *greater, unsigned int *equal, void *stream);
+
 /* --- link prediction: 1-vs-all top-K retrieval (k_topk.hip; new: the reference has no pair-level
  * model).  "For this node, which nodes should it be linked to?": per query the k best candidates
  * by the rank score, never forming the [n_queries][n] score matrix.
@@ -687,8 +710,8 @@ typedef struct {
    * are Glorot-uniform, b1 = b2 = 0, drawn after every other variable, so a seed's encoder weights
    * are the dot engine's.  pgcn_gcn_predict_links / _link_counts / _score_pairs run the MLP;
    * pgcn_gcn_link_ranks and pgcn_gcn_top_links return PGCN_E_INVALID on such an engine (a 1-vs-all
-   * sweep over an MLP score is not the dot-product sweep: evaluate with pgcn_gcn_score_pairs over
-   * fixed candidate lists).  Anything else, link_hidden != 0 without a decoder included, is
+   * sweep over an MLP score is not the dot-product sweep): rank with pgcn_gcn_link_ranks_decoder,
+   * retrieve with pgcn_gcn_score_pairs over fixed candidate lists.  Anything else, link_hidden != 0 without a decoder included, is
    * PGCN_E_INVALID. */
   int link_hidden;
   /* Negatives redrawn on the device before every train_epoch (here, behind link_hidden: no other
@@ -1090,6 +1113,12 @@ long long pgcn_gcn_predict_links(pgcn_gcn *g, float *scores, float *probs);
 int pgcn_gcn_link_counts(pgcn_gcn *g, int split, long long *counts);
 long long pgcn_gcn_link_ranks(pgcn_gcn *g, int split, int side, int filtered, long long *greater,
                               long long *equal);
+/* pgcn_gcn_link_ranks by the MLP decoder's score (pgcn_link_rank_mlp over the output embedding
+ * and the decoder's parameters): the same contract, query sets and cache.  PGCN_E_INVALID on an
+ * engine without link_hidden, which has no decoder to rank by.  Asked for by name: the call costs
+ * link_hidden times pgcn_gcn_link_ranks' flops. */
+long long pgcn_gcn_link_ranks_decoder(pgcn_gcn *g, int split, int side, int filtered,
+                                      long long *greater, long long *equal);
 long long pgcn_gcn_top_links(pgcn_gcn *g, const int *nodes, long long m, int k, int side,
                              int filtered, int *idx, float *score);
 int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m, float *scores);
@@ -1260,7 +1289,8 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * 512 entries per feature), "spmm_tree_256" / "spmm_tree_1024" (its fixed-tree form, csc_tree),
  * "launches" (every kernel launch of the library), "link_fwd" / "link_bwd" (the pair-score
  * forward and backward calls that launched), "rank_sweep" / "rank_filter" (pgcn_link_rank's
- * sweep and filter-correction launches), "topk_sweep" / "topk_merge" (pgcn_link_topk's two).
+ * sweep and filter-correction launches), "topk_sweep" / "topk_merge" (pgcn_link_topk's two),
+ * "rank_mlp_sweep" / "rank_mlp_filter" (pgcn_link_rank_mlp's sweep and filter-correction launches).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

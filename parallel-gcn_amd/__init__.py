@@ -188,6 +188,10 @@ _sig("pgcn_link_rank", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void
 _sig("pgcn_debug_rank_filter", c_ll, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
      c_void_p, c_int, c_int, c_int, P(c_ll), c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_link_ranks", c_ll, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)
+_sig("pgcn_link_rank_mlp_tile", None, P(c_int), P(c_int))
+_sig("pgcn_link_rank_mlp", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+     c_void_p, c_void_p)
+_sig("pgcn_gcn_link_ranks_decoder", c_ll, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)
 _sig("pgcn_topk_queries_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_int,
      P(c_void_p))
 _sig("pgcn_topk_queries_destroy", c_int, c_void_p)
@@ -348,7 +352,8 @@ KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gat
                 "gemm_nn", "gemm_tn", "gemm_nn_w", "gemm_tn_w", "gat_fwd", "gat_bwd", "gat_heads",
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
                 "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter",
-                "topk_sweep", "topk_merge", "link_mlp_fwd", "link_mlp_bwd")
+                "topk_sweep", "topk_merge", "link_mlp_fwd", "link_mlp_bwd", "rank_mlp_sweep",
+                "rank_mlp_filter")
 
 
 def path_counts(reset=False, thread=False):
@@ -726,6 +731,13 @@ class RankQueries:
     def handle(self):
         return self._h
 
+    def rank_mlp(self, H, ld_h, d, P, ld_p, h, greater, equal, stream=None):
+        """The ranking counts under the Hadamard-MLP decoder (pgcn_link_rank_mlp): H, P, greater,
+        equal are device addresses (or objects with data_ptr()); greater / equal: uint32 [Q], the
+        candidates whose Links.mlp_fwd score with the anchor is above / exactly the target's."""
+        check(lib.pgcn_link_rank_mlp(self._h, _dptr(H), ld_h, d, _dptr(P), ld_p, h, _dptr(greater),
+                                     _dptr(equal), stream), "link_rank_mlp")
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value and lib is not None:
             lib.pgcn_rank_queries_destroy(self._h)
@@ -738,6 +750,14 @@ def link_rank_tile():
     """(queries per workgroup, candidates per tile) of the ranking sweep (pgcn_link_rank_tile)."""
     tq, tc = c_int(), c_int()
     lib.pgcn_link_rank_tile(ctypes.byref(tq), ctypes.byref(tc))
+    return tq.value, tc.value
+
+
+def link_rank_mlp_tile():
+    """(queries per workgroup, candidates per chunk) of the ranking sweep under the MLP decoder
+    (pgcn_link_rank_mlp_tile)."""
+    tq, tc = c_int(), c_int()
+    lib.pgcn_link_rank_mlp_tile(ctypes.byref(tq), ctypes.byref(tc))
     return tq.value, tc.value
 
 
@@ -1142,19 +1162,23 @@ class GCN:
         check(lib.pgcn_gcn_link_counts(self._h, split, _ptr(out)), "link_counts")
         return out
 
-    def link_ranks(self, split, side="dst", filtered=True):
+    def link_ranks(self, split, side="dst", filtered=True, decoder=False):
         """(greater, equal) int64 [Q]: for `split`'s Q positive pairs in pair order, the candidates
         scoring above / exactly the true endpoint from an eval-mode forward (side 'dst': the
         destination is ranked among all nodes, 'src': the source; filtered: the anchor, its
-        neighbours and its known links do not compete).  See rank_from_counts, mrr, hits_at."""
+        neighbours and its known links do not compete).  decoder=True ranks by the MLP decoder's
+        score on a link_hidden engine (pgcn_gcn_link_ranks_decoder: link_hidden times the dot
+        sweep's flops, so asked for by name); the default ranks the dot product and refuses such
+        an engine.  See rank_from_counts, mrr, hits_at."""
         if side not in RANK_SIDES:
             raise ValueError("side must be 'dst' or 'src'")
         args = (self._h, split, RANK_SIDES[side], 1 if filtered else 0)
-        q = lib.pgcn_gcn_link_ranks(*args, None, None)
+        entry = lib.pgcn_gcn_link_ranks_decoder if decoder else lib.pgcn_gcn_link_ranks
+        q = entry(*args, None, None)
         if q < 0:
             raise PgcnError(int(q), "link_ranks")
         greater, equal = np.zeros(q, np.int64), np.zeros(q, np.int64)
-        got = lib.pgcn_gcn_link_ranks(*args, _ptr(greater), _ptr(equal))
+        got = entry(*args, _ptr(greater), _ptr(equal))
         if got < 0:
             raise PgcnError(int(got), "link_ranks")
         assert got == q
@@ -1503,6 +1527,7 @@ EXPORTED = [
     "pgcn_gcn_score_pairs", "pgcn_dataset_set_links", "pgcn_dataset_load_links",
     "pgcn_rank_queries_create", "pgcn_rank_queries_destroy", "pgcn_link_rank_tile",
     "pgcn_link_rank_scores", "pgcn_link_rank", "pgcn_debug_rank_filter", "pgcn_gcn_link_ranks",
+    "pgcn_link_rank_mlp_tile", "pgcn_link_rank_mlp", "pgcn_gcn_link_ranks_decoder",
     "pgcn_topk_queries_create", "pgcn_topk_queries_destroy", "pgcn_topk_queries_workspace",
     "pgcn_link_topk_tile", "pgcn_link_topk_splits", "pgcn_link_topk_chunk", "pgcn_link_topk",
     "pgcn_debug_topk_filter", "pgcn_gcn_top_links",

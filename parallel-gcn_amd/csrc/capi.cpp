@@ -31,7 +31,8 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "spmm_tree_256", "spmm_tree_1024", "launches",
                                           "link_fwd",   "link_bwd",   "rank_sweep",
                                           "rank_filter", "topk_sweep", "topk_merge",
-                                          "link_mlp_fwd", "link_mlp_bwd"};
+                                          "link_mlp_fwd", "link_mlp_bwd",
+                                          "rank_mlp_sweep", "rank_mlp_filter"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -1041,6 +1042,26 @@ int pgcn_link_rank(const pgcn_rank_queries *q, const float *H, int ld_h, int d,
   });
 }
 
+void pgcn_link_rank_mlp_tile(int *queries_per_block, int *candidates_per_chunk) {
+  if (queries_per_block) *queries_per_block = kRankMlpTQ;
+  if (candidates_per_chunk) *candidates_per_chunk = kRankMlpTC;
+}
+
+int pgcn_link_rank_mlp(const pgcn_rank_queries *q, const float *H, int ld_h, int d, const float *P,
+                       int ld_p, int h, unsigned int *greater, unsigned int *equal, void *stream) {
+  return guarded([&] {
+    check_link_mlp_dims(d, h, {ld_h}, {ld_p}, {});
+    PGCN_CHECK(q && q->q && H && P && aligned16(H) && aligned16(P), PGCN_E_INVALID,
+               "link_rank_mlp: null or misaligned argument");
+    PGCN_CHECK(q->q->queries().n_queries == 0 || (greater && equal), PGCN_E_INVALID,
+               "link_rank_mlp: greater and equal [n_queries]");
+    check_device();
+    launch_link_rank_mlp(q->q->queries(), H, ld_h, d, P, ld_p, h, greater, equal,
+                         as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indices,
                                  long long n_pairs, const int *pair_src, const int *pair_dst,
                                  const int *pair_label, const int *pair_split, int split, int side,
@@ -1579,6 +1600,15 @@ long long pgcn_gcn_link_ranks(pgcn_gcn *g, int split, int side, int filtered, lo
   const int st = guarded([&] {
     PGCN_CHECK(g, PGCN_E_INVALID, "gcn_link_ranks: null engine");
     n = g->g->link_ranks(split, side, filtered, greater, equal);
+  });
+  return st == PGCN_OK ? n : st;
+}
+long long pgcn_gcn_link_ranks_decoder(pgcn_gcn *g, int split, int side, int filtered,
+                                      long long *greater, long long *equal) {
+  long long n = -1;
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_link_ranks_decoder: null engine");
+    n = g->g->link_ranks(split, side, filtered, greater, equal, true);
   });
   return st == PGCN_OK ? n : st;
 }

@@ -2126,11 +2126,14 @@ void GCN::score_pairs(const int *src, const int *dst, long long m, float *scores
   for (long long e = 0; e < m; e++) scores[e] = raw[(size_t)e * 4];
 }
 
-long long GCN::link_ranks(int split, int side, int filtered, long long *greater, long long *equal) {
+long long GCN::link_ranks(int split, int side, int filtered, long long *greater, long long *equal,
+                          bool decoder) {
   PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "link_ranks: not a link engine");
-  PGCN_CHECK(!link_var, PGCN_E_INVALID,
-             "link_ranks: the 1-vs-all sweep ranks the dot product only; with link_hidden > 0 "
-             "evaluate with score_pairs over fixed candidate lists");
+  PGCN_CHECK(decoder || !link_var, PGCN_E_INVALID,
+             "link_ranks: the default sweep ranks the dot product only; with link_hidden > 0 ask "
+             "for the decoder's ranking by name (pgcn_gcn_link_ranks_decoder)");
+  PGCN_CHECK(!decoder || link_var, PGCN_E_INVALID,
+             "link_ranks_decoder: the engine has no decoder to rank by (link_hidden == 0)");
   PGCN_CHECK(split >= 1 && split <= 3 && (side == 0 || side == 1) &&
                  (filtered == 0 || filtered == 1) && !greater == !equal,
              PGCN_E_INVALID,
@@ -2156,8 +2159,13 @@ long long GCN::link_ranks(int split, int side, int filtered, long long *greater,
   const int Q = rs.q->queries().n_queries;
   predict_forward();
   const Variable &h = *link_embed;
-  launch_link_rank(rs.q->queries(), h.dev_data.get(), h.ld, params.output_dim, rs.counts.get(),
-                   rs.counts.get() + Q, stream.get());
+  if (decoder)
+    launch_link_rank_mlp(rs.q->queries(), h.dev_data.get(), h.ld, params.output_dim,
+                         link_var->dev_data.get(), link_var->ld, params.link_hidden,
+                         rs.counts.get(), rs.counts.get() + Q, stream.get());
+  else
+    launch_link_rank(rs.q->queries(), h.dev_data.get(), h.ld, params.output_dim, rs.counts.get(),
+                     rs.counts.get() + Q, stream.get());
   sync();
   std::vector<unsigned> raw((size_t)(2 * Q));
   rs.counts.download(raw.data(), raw.size());

@@ -177,7 +177,8 @@ class GCN {
   // the destination is ranked among all nodes, side 1: the source; filtered: build_rank_filter's
   // lists): their number, and with outputs their greater / equal counts.  Both outputs null: the
   // number only, nothing runs.  The query set of a (split, side, filtered) is built once
-  long long link_ranks(int split, int side, int filtered, long long *greater, long long *equal);
+  long long link_ranks(int split, int side, int filtered, long long *greater, long long *equal,
+                       bool decoder = false);
   // the same forward, then launch_link_topk over the output embedding for m anchor nodes: idx /
   // score [m][k] on the host (side, filtered: build_topk_filter's lists).  kTopKChunk queries at a
   // time, the query set and the device outputs of a chunk freed after it

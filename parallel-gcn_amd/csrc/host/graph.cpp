@@ -1151,7 +1151,8 @@ RankQueriesDev::RankQueriesDev(int n, long long n_queries, const int *anchor, co
   };
   up(anchor_, anchor, (size_t)n_queries);
   up(target_, target, (size_t)n_queries);
-  thr_.allocate(std::max<size_t>((size_t)n_queries, 1));
+  // (four words per query: the MLP ranking's thresholds are the pair forward's {score, 0, 0, 0})
+  thr_.allocate(std::max<size_t>((size_t)n_queries * 4, 1));
   thr_.zero();
   q_.n = n;
   q_.n_queries = (int)n_queries;
@@ -1163,6 +1164,7 @@ RankQueriesDev::RankQueriesDev(int n, long long n_queries, const int *anchor, co
     up(fidx_, filter_idx, (size_t)filter_ptr[n_queries]);
     q_.filter_ptr = fptr_.get();
     q_.filter_idx = fidx_.get();
+    q_.n_filter = filter_ptr[n_queries];
   }
 }
 

@@ -17,7 +17,8 @@ enum KernelPath {
   KP_GEMM_NN, KP_GEMM_TN, KP_GEMM_NN_W, KP_GEMM_TN_W, KP_GAT_FWD, KP_GAT_BWD, KP_GAT_HEADS,
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
   KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_RANK_SWEEP, KP_RANK_FILTER,
-  KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_LINK_MLP_FWD, KP_LINK_MLP_BWD, KP_COUNT
+  KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_LINK_MLP_FWD, KP_LINK_MLP_BWD,
+  KP_RANK_MLP_SWEEP, KP_RANK_MLP_FILTER, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -545,9 +546,10 @@ constexpr int kRankTC = 64;   // candidates per tile
 struct RankQueries {
   int n = 0, n_queries = 0;
   const int *anchor = nullptr, *target = nullptr;
-  float *thr = nullptr;                   // [n_queries]
+  float *thr = nullptr;                   // [n_queries][4] (k_rank.hip: its first [n_queries])
   const long long *filter_ptr = nullptr;  // [n_queries + 1], null: no lists
   const int *filter_idx = nullptr;
+  long long n_filter = 0;                 // filter_ptr[n_queries]
 };
 // candidate splits of the sweep's grid: a function of (Q, n) only
 int rank_splits(int Q, int n);
@@ -560,6 +562,20 @@ void launch_rank_scores(const int *src, const int *dst, long long m, const float
 // blocks x rank_splits; integer atomics), the filter correction (a wave per query; with lists)
 void launch_link_rank(const RankQueries &q, const float *H, int ld_h, int d, unsigned *greater,
                       unsigned *equal, hipStream_t s);
+// ---- link prediction: 1-vs-all ranking counts under the MLP decoder (k_rank_mlp.hip) -------------
+// launch_link_rank's counts with launch_link_mlp_fwd's score of the pair (a_e, v) in r's place, the
+// same bits as that launch gives: the thresholds are the forward itself on the pairs (a_e, t_e)
+// (q.thr as [n_queries][4]), the sweep and the filter correction are built from the forward's tile
+// code (link_mlp_tile.hpp).
+constexpr int kRankMlpTQ = 64;  // queries per workgroup of the sweep
+constexpr int kRankMlpTC = 64;  // candidates per chunk
+// candidate splits of the sweep's grid: a function of (Q, n) only; a split holds at least 8 chunks
+int rank_mlp_splits(int Q, int n);
+// Four launches at most: thresholds, the counts' zeroing, the sweep (query blocks x rank_mlp_splits;
+// integer atomics), the filter correction (64-pair tiles; with list entries).  Allocates nothing,
+// never syncs.
+void launch_link_rank_mlp(const RankQueries &q, const float *H, int ld_h, int d, const float *P,
+                          int ld_p, int h, unsigned *greater, unsigned *equal, hipStream_t s);
 // ---- link prediction: 1-vs-all top-K retrieval (k_topk.hip) ------------------------------------
 // Per query (anchor a_e, ascending exclude list X_e) the k candidates v in [0, n) \ X_e first in
 // the order "higher r(a_e, v), then lower v"; the positions from the candidate count on hold idx -1,

@@ -34,11 +34,12 @@
 // are per pair, and predict= writes one line `src dst score probability` per pair.  The adjacency
 // is used as loaded: keep validation and test positives out of it.
 // link_hidden=<H> (with link=dot; 1..128): the Hadamard-MLP decoder of that hidden width in the dot
-// product's place (pgcn_params.link_hidden); rank= and recommend= are refused on such an engine.
+// product's place (pgcn_params.link_hidden); rank= then ranks by the decoder's score
+// (pgcn_gcn_link_ranks_decoder), recommend= is refused on such an engine.
 // neg_ratio=<R> (with link=dot; 1..64): R negatives per training positive, redrawn on the device
 // before every epoch (pgcn_params.neg_ratio).
 // rank=1 (with link=): after the run, one line with the filtered ranking metrics of the test split
-// (pgcn_gcn_link_ranks; mean ties) for both sides: `rank side=dst queries=.. mrr=.. hits@10=..
+// (pgcn_gcn_link_ranks, with link_hidden= its _decoder form; mean ties) for both sides: `rank side=dst queries=.. mrr=.. hits@10=..
 // hits@50=.. hits@100=.. side=src ...`; rank=<file> also writes `src dst greater equal` per test
 // positive pair for the dst side.
 // recommend=<file> [topk=<K>, default 10, at most 128] (with link=): after the run, one line per
@@ -299,9 +300,10 @@ int main(int argc, char **argv) {
   if (st == PGCN_OK && !rank.empty() && rank != "0" && p.link_decoder) {
     printf("rank");
     for (int side = 0; side < 2 && st == PGCN_OK; side++) {
-      const long long q = pgcn_gcn_link_ranks(g, 3, side, 1, nullptr, nullptr);
+      const auto ranks = p.link_hidden > 0 ? pgcn_gcn_link_ranks_decoder : pgcn_gcn_link_ranks;
+      const long long q = ranks(g, 3, side, 1, nullptr, nullptr);
       std::vector<long long> greater((size_t)std::max(q, 0LL)), equal(greater.size());
-      const long long got = q < 0 ? q : pgcn_gcn_link_ranks(g, 3, side, 1, greater.data(), equal.data());
+      const long long got = q < 0 ? q : ranks(g, 3, side, 1, greater.data(), equal.data());
       if (got < 0) {
         st = (int)got;
         break;
