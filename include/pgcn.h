@@ -610,6 +610,40 @@ long long pgcn_debug_topk_filter(int n_nodes, const int *indptr, const int *indi
                                  const int *nodes, int side, int filtered, long long *n_exclude,
                                  long long *ptr, int *idx);
 
+/* --- link prediction: 1-vs-all top-K retrieval under the MLP decoder (k_topk_mlp.hip; new: the
+ * reference has no pair-level model).  pgcn_link_topk's definition -- candidates [0, n) minus the
+ * exclude list, the order "higher score, then lower index" with -0.0 == +0.0, the padding -1 /
+ * -inf from min(k, candidates) on -- with the decoder's score in r's place: s(a, v) is what
+ * pgcn_link_mlp_fwd writes for the pair (a, v), BIT FOR BIT (P, ld_p, h: as there), so idx / score
+ * equal what a caller would select from pgcn_link_mlp_fwd on all n_queries * n explicit pairs,
+ * without those pairs or their scores in memory.  Limits: 1 <= k <= 128, 1 <= d, h <= 128, ld_h and
+ * ld_p multiples of 4 and >= d / h, H and P 16-byte aligned, inputs finite.
+ *
+ * The sweep is pgcn_link_rank_mlp's -- workgroups of pgcn_link_topk_mlp_tile's queries_per_block
+ * queries over candidates_per_chunk-candidate chunks, W1 resident in LDS, the per-query f32 MFMA
+ * loop and epilogue the very code of that sweep -- with a selecting epilogue: a wave owns one
+ * 32-candidate block of every chunk, so per query and candidate split it keeps TWO append buffers.
+ * The workspace therefore differs from pgcn_link_topk's:
+ *     n_queries * pgcn_link_topk_mlp_splits(n_queries, n_nodes) * 2 * cap(k) * 8 bytes.
+ * pgcn_topk_queries_create_mlp is pgcn_topk_queries_create (the same arguments and validation)
+ * with a workspace of that size; pgcn_topk_queries_workspace reports it.  The handle records which
+ * sweep it was sized for: pgcn_link_topk on an _mlp handle, and pgcn_link_topk_mlp on a plain one,
+ * return PGCN_E_INVALID and launch nothing.
+ *
+ * pgcn_link_topk_mlp: exactly TWO launches whatever the data, none when n_queries == 0 -- the sweep
+ * (a grid of query blocks x pgcn_link_topk_mlp_splits, a function of (n_queries, n_nodes) only and
+ * the one the launcher uses; no split is empty) and pgcn_link_topk's merge over 2 x splits lists
+ * per query.  Asynchronous, allocates nothing, no atomics: two calls give the same bits; two calls
+ * on one handle must not overlap.  The cost is 2 n_queries n d h flops, h times the dot sweep's. */
+int pgcn_topk_queries_create_mlp(int n_nodes, long long n_queries, const int *anchor,
+                                 const long long *exclude_ptr /* [n_queries + 1] or NULL */,
+                                 const int *exclude_idx, int k, pgcn_topk_queries **out);
+void pgcn_link_topk_mlp_tile(int *queries_per_block, int *candidates_per_chunk, int *k_max);
+int pgcn_link_topk_mlp_splits(long long n_queries, int n_nodes); /* host only, pure */
+int pgcn_link_topk_mlp(const pgcn_topk_queries *q, const float *H, int ld_h, int d, const float *P,
+                       int ld_p, int h, int *idx /* dev [n_queries][k] */,
+                       float *score /* dev [n_queries][k] */, void *stream);
+
 /* --- cross entropy + accuracy (src/module.cu:484-541, src/gcn.cu:264-289) -------------- */
 /* Rows with truth >= 0: logits max-shifted in place; if training grad = (softmax - 1[t])
  * / count, zero elsewhere.  Writes per-block partial sums (loss, wrong) to `partials`
@@ -711,8 +745,8 @@ typedef struct {
    * are the dot engine's.  pgcn_gcn_predict_links / _link_counts / _score_pairs run the MLP;
    * pgcn_gcn_link_ranks and pgcn_gcn_top_links return PGCN_E_INVALID on such an engine (a 1-vs-all
    * sweep over an MLP score is not the dot-product sweep): rank with pgcn_gcn_link_ranks_decoder,
-   * retrieve with pgcn_gcn_score_pairs over fixed candidate lists.  Anything else, link_hidden != 0 without a decoder included, is
-   * PGCN_E_INVALID. */
+   * retrieve with pgcn_gcn_top_links_decoder.  Anything else, link_hidden != 0 without a decoder
+   * included, is PGCN_E_INVALID. */
   int link_hidden;
   /* Negatives redrawn on the device before every train_epoch (here, behind link_hidden: no other
    * member moves).  0: off, the engine as it was, bit for bit.  1..64 with link_decoder == 1: with
@@ -1121,6 +1155,12 @@ long long pgcn_gcn_link_ranks_decoder(pgcn_gcn *g, int split, int side, int filt
                                       long long *greater, long long *equal);
 long long pgcn_gcn_top_links(pgcn_gcn *g, const int *nodes, long long m, int k, int side,
                              int filtered, int *idx, float *score);
+/* pgcn_gcn_top_links by the MLP decoder's score (pgcn_link_topk_mlp over the output embedding and
+ * the decoder's parameters): the same contract, exclude lists and chunks of pgcn_link_topk_chunk()
+ * nodes (at most 320 MiB of workspace per chunk).  PGCN_E_INVALID on an engine without
+ * link_hidden.  Asked for by name: the call costs link_hidden times pgcn_gcn_top_links' flops. */
+long long pgcn_gcn_top_links_decoder(pgcn_gcn *g, const int *nodes, long long m, int k, int side,
+                                     int filtered, int *idx, float *score);
 int pgcn_gcn_score_pairs(pgcn_gcn *g, const int *src, const int *dst, long long m, float *scores);
 /* per-call device timing of the GraphSum kernels (enable before the timed region) */
 int pgcn_gcn_profile(pgcn_gcn *g, int enable);
@@ -1290,7 +1330,8 @@ long long pgcn_debug_lds_counts(int n_rows, int n_cols, const int *indptr, const
  * "launches" (every kernel launch of the library), "link_fwd" / "link_bwd" (the pair-score
  * forward and backward calls that launched), "rank_sweep" / "rank_filter" (pgcn_link_rank's
  * sweep and filter-correction launches), "topk_sweep" / "topk_merge" (pgcn_link_topk's two),
- * "rank_mlp_sweep" / "rank_mlp_filter" (pgcn_link_rank_mlp's sweep and filter-correction launches).
+ * "rank_mlp_sweep" / "rank_mlp_filter" (pgcn_link_rank_mlp's sweep and filter-correction launches),
+ * "topk_mlp_sweep" / "topk_mlp_merge" (pgcn_link_topk_mlp's two).
  * A non-null name returns its count (then zeroes it
  * when reset bit 0 is set); a null name with reset bit 0 zeroes every counter.  Bit 1 of reset
  * selects the counters of the calling host thread instead of the process-wide ones (each rank

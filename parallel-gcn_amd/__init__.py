@@ -200,6 +200,14 @@ _sig("pgcn_link_topk_tile", None, P(c_int), P(c_int), P(c_int))
 _sig("pgcn_link_topk_splits", c_int, c_ll, c_int)
 _sig("pgcn_link_topk_chunk", c_int)
 _sig("pgcn_link_topk", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_topk_queries_create_mlp", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_int,
+     P(c_void_p))
+_sig("pgcn_link_topk_mlp_tile", None, P(c_int), P(c_int), P(c_int))
+_sig("pgcn_link_topk_mlp_splits", c_int, c_ll, c_int)
+_sig("pgcn_link_topk_mlp", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+     c_void_p, c_void_p)
+_sig("pgcn_gcn_top_links_decoder", c_ll, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_void_p,
+     c_void_p)
 _sig("pgcn_debug_topk_filter", c_ll, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
      c_void_p, c_ll, c_void_p, c_int, c_int, P(c_ll), c_void_p, c_void_p)
 _sig("pgcn_gcn_top_links", c_ll, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_void_p, c_void_p)
@@ -353,7 +361,7 @@ KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gat
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
                 "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter",
                 "topk_sweep", "topk_merge", "link_mlp_fwd", "link_mlp_bwd", "rank_mlp_sweep",
-                "rank_mlp_filter")
+                "rank_mlp_filter", "topk_mlp_sweep", "topk_mlp_merge")
 
 
 def path_counts(reset=False, thread=False):
@@ -793,9 +801,11 @@ RANK_SIDES = {"dst": 0, "src": 1, 0: 0, 1: 1}
 class TopKQueries:
     """A top-K query set on the device (pgcn_topk_queries): per query an anchor over n_nodes nodes
     and, with exclude_ptr [Q + 1] / exclude_idx, a strictly ascending list of candidates to leave
-    out (it may hold the anchor); k results per query.  It owns the workspace of pgcn_link_topk."""
+    out (it may hold the anchor); k results per query.  It owns the workspace of pgcn_link_topk, or
+    with decoder=True (pgcn_topk_queries_create_mlp) that of pgcn_link_topk_mlp; each call refuses
+    the other kind of handle."""
 
-    def __init__(self, n_nodes, anchor, exclude_ptr=None, exclude_idx=None, k=10):
+    def __init__(self, n_nodes, anchor, exclude_ptr=None, exclude_idx=None, k=10, decoder=False):
         anchor = np.ascontiguousarray(anchor, np.int32)
         if anchor.ndim != 1:
             raise ValueError("TopKQueries: anchor [Q]")
@@ -806,12 +816,19 @@ class TopKQueries:
             if xp.shape != (anchor.size + 1,) or xi.ndim != 1 or (xp.size and xp[-1] != xi.size):
                 raise ValueError("TopKQueries: exclude_ptr [Q + 1], exclude_idx [exclude_ptr[Q]]")
         h = c_void_p()
-        check(lib.pgcn_topk_queries_create(n_nodes, anchor.size, _ptr(anchor),
-                                           _ptr(xp) if xp is not None else None,
-                                           _ptr(xi) if xi is not None else None, int(k),
-                                           ctypes.byref(h)), "topk_queries_create")
+        create = lib.pgcn_topk_queries_create_mlp if decoder else lib.pgcn_topk_queries_create
+        check(create(n_nodes, anchor.size, _ptr(anchor), _ptr(xp) if xp is not None else None,
+                     _ptr(xi) if xi is not None else None, int(k), ctypes.byref(h)),
+              "topk_queries_create")
         self._h, self.n_nodes, self.n_queries, self.k = h, n_nodes, int(anchor.size), int(k)
-        self.filtered = xp is not None
+        self.filtered, self.decoder = xp is not None, bool(decoder)
+
+    def topk_mlp(self, H, ld_h, d, P, ld_p, h, idx, score, stream=None):
+        """The k best candidates per query under the Hadamard-MLP decoder (pgcn_link_topk_mlp): H,
+        P, idx [Q][k] int32 and score [Q][k] float32 are torch tensors on the device; a handle
+        made with decoder=True."""
+        check(lib.pgcn_link_topk_mlp(self._h, _dptr(H), ld_h, d, _dptr(P), ld_p, h, _dptr(idx),
+                                     _dptr(score), stream), "link_topk_mlp")
 
     @property
     def handle(self):
@@ -841,6 +858,20 @@ def link_topk_tile():
 def link_topk_splits(n_queries, n_nodes):
     """Candidate splits of the top-K sweep's grid for (n_queries, n_nodes): host only."""
     return int(lib.pgcn_link_topk_splits(int(n_queries), int(n_nodes)))
+
+
+def link_topk_mlp_tile():
+    """(queries per workgroup, candidates per chunk, largest k) of the top-K sweep under the MLP
+    decoder (pgcn_link_topk_mlp_tile)."""
+    tq, tc, km = c_int(), c_int(), c_int()
+    lib.pgcn_link_topk_mlp_tile(ctypes.byref(tq), ctypes.byref(tc), ctypes.byref(km))
+    return tq.value, tc.value, km.value
+
+
+def link_topk_mlp_splits(n_queries, n_nodes):
+    """Candidate splits of that sweep's grid for (n_queries, n_nodes): host only.  A query's
+    workspace is 2 x this many lists."""
+    return int(lib.pgcn_link_topk_mlp_splits(int(n_queries), int(n_nodes)))
 
 
 def link_topk_chunk():
@@ -1184,12 +1215,15 @@ class GCN:
         assert got == q
         return greater, equal
 
-    def top_links(self, nodes, k=10, side="dst", filtered=True):
+    def top_links(self, nodes, k=10, side="dst", filtered=True, decoder=False):
         """(idx int32 [m][k], scores float32 [m][k]): per node of `nodes` the k nodes with the
         highest rank score against it from an eval-mode forward, ties to the lower index (side
         'dst': destinations for the node as a source, 'src': sources for it as a destination;
         filtered: the node, its neighbours and its known links are left out).  Rows with fewer than
-        k candidates end in idx -1, score -inf.  The training state is untouched."""
+        k candidates end in idx -1, score -inf.  decoder=True retrieves by the MLP decoder's score
+        on a link_hidden engine (pgcn_gcn_top_links_decoder: link_hidden times the dot sweep's
+        flops, so asked for by name); the default retrieves by the dot product and refuses such an
+        engine.  The training state is untouched."""
         if side not in RANK_SIDES:
             raise ValueError("side must be 'dst' or 'src'")
         nodes = np.ascontiguousarray(nodes, np.int32)
@@ -1198,8 +1232,9 @@ class GCN:
         k = int(k)
         idx = np.zeros((nodes.size, max(k, 0)), np.int32)
         sc = np.zeros((nodes.size, max(k, 0)), np.float32)
-        got = lib.pgcn_gcn_top_links(self._h, _ptr(nodes), nodes.size, k, RANK_SIDES[side],
-                                     1 if filtered else 0, _ptr(idx), _ptr(sc))
+        entry = lib.pgcn_gcn_top_links_decoder if decoder else lib.pgcn_gcn_top_links
+        got = entry(self._h, _ptr(nodes), nodes.size, k, RANK_SIDES[side], 1 if filtered else 0,
+                    _ptr(idx), _ptr(sc))
         if got < 0:
             raise PgcnError(int(got), "top_links")
         return idx, sc
@@ -1531,4 +1566,6 @@ EXPORTED = [
     "pgcn_topk_queries_create", "pgcn_topk_queries_destroy", "pgcn_topk_queries_workspace",
     "pgcn_link_topk_tile", "pgcn_link_topk_splits", "pgcn_link_topk_chunk", "pgcn_link_topk",
     "pgcn_debug_topk_filter", "pgcn_gcn_top_links",
+    "pgcn_topk_queries_create_mlp", "pgcn_link_topk_mlp_tile", "pgcn_link_topk_mlp_splits",
+    "pgcn_link_topk_mlp", "pgcn_gcn_top_links_decoder",
 ]

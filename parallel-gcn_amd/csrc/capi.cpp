@@ -32,7 +32,8 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "link_fwd",   "link_bwd",   "rank_sweep",
                                           "rank_filter", "topk_sweep", "topk_merge",
                                           "link_mlp_fwd", "link_mlp_bwd",
-                                          "rank_mlp_sweep", "rank_mlp_filter"};
+                                          "rank_mlp_sweep", "rank_mlp_filter",
+                                          "topk_mlp_sweep", "topk_mlp_merge"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -1082,17 +1083,32 @@ long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indi
   return st == PGCN_OK ? n : st;
 }
 
-int pgcn_topk_queries_create(int n_nodes, long long n_queries, const int *anchor,
-                             const long long *exclude_ptr, const int *exclude_idx, int k,
-                             pgcn_topk_queries **out) {
+namespace {
+int topk_queries_create(int n_nodes, long long n_queries, const int *anchor,
+                        const long long *exclude_ptr, const int *exclude_idx, int k, bool mlp,
+                        pgcn_topk_queries **out) {
   return guarded([&] {
     PGCN_CHECK(out, PGCN_E_INVALID, "topk_queries_create args");
     validate_topk_queries(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k);
     check_device();
     auto h = std::make_unique<pgcn_topk_queries>();
-    h->q = std::make_unique<TopKQueriesDev>(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k);
+    h->q = std::make_unique<TopKQueriesDev>(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k,
+                                            mlp);
     *out = h.release();
   });
+}
+}  // namespace
+
+int pgcn_topk_queries_create(int n_nodes, long long n_queries, const int *anchor,
+                             const long long *exclude_ptr, const int *exclude_idx, int k,
+                             pgcn_topk_queries **out) {
+  return topk_queries_create(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k, false, out);
+}
+
+int pgcn_topk_queries_create_mlp(int n_nodes, long long n_queries, const int *anchor,
+                                 const long long *exclude_ptr, const int *exclude_idx, int k,
+                                 pgcn_topk_queries **out) {
+  return topk_queries_create(n_nodes, n_queries, anchor, exclude_ptr, exclude_idx, k, true, out);
 }
 
 int pgcn_topk_queries_destroy(pgcn_topk_queries *q) {
@@ -1126,6 +1142,30 @@ int pgcn_link_topk(const pgcn_topk_queries *q, const float *H, int ld_h, int d, 
                "link_topk: idx and score [n_queries][k]");
     check_device();
     launch_link_topk(q->q->queries(), H, ld_h, d, idx, score, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+void pgcn_link_topk_mlp_tile(int *queries_per_block, int *candidates_per_chunk, int *k_max) {
+  if (queries_per_block) *queries_per_block = kRankMlpTQ;
+  if (candidates_per_chunk) *candidates_per_chunk = kRankMlpTC;
+  if (k_max) *k_max = kTopKMax;
+}
+
+int pgcn_link_topk_mlp_splits(long long n_queries, int n_nodes) {
+  return topk_mlp_splits(n_queries, n_nodes);
+}
+
+int pgcn_link_topk_mlp(const pgcn_topk_queries *q, const float *H, int ld_h, int d, const float *P,
+                       int ld_p, int h, int *idx, float *score, void *stream) {
+  return guarded([&] {
+    check_link_mlp_dims(d, h, {ld_h}, {ld_p}, {});
+    PGCN_CHECK(q && q->q && H && P && aligned16(H) && aligned16(P), PGCN_E_INVALID,
+               "link_topk_mlp: null or misaligned argument");
+    PGCN_CHECK(q->q->queries().n_queries == 0 || (idx && score), PGCN_E_INVALID,
+               "link_topk_mlp: idx and score [n_queries][k]");
+    check_device();
+    launch_link_topk_mlp(q->q->queries(), H, ld_h, d, P, ld_p, h, idx, score, as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
 }
@@ -1617,6 +1657,15 @@ long long pgcn_gcn_top_links(pgcn_gcn *g, const int *nodes, long long m, int k, 
   const int st = guarded([&] {
     PGCN_CHECK(g, PGCN_E_INVALID, "gcn_top_links: null engine");
     g->g->top_links(nodes, m, k, side, filtered, idx, score);
+  });
+  return st == PGCN_OK ? m : st;
+}
+
+long long pgcn_gcn_top_links_decoder(pgcn_gcn *g, const int *nodes, long long m, int k, int side,
+                                     int filtered, int *idx, float *score) {
+  const int st = guarded([&] {
+    PGCN_CHECK(g, PGCN_E_INVALID, "gcn_top_links_decoder: null engine");
+    g->g->top_links(nodes, m, k, side, filtered, idx, score, true);
   });
   return st == PGCN_OK ? m : st;
 }

@@ -2177,11 +2177,13 @@ long long GCN::link_ranks(int split, int side, int filtered, long long *greater,
 }
 
 void GCN::top_links(const int *nodes, long long m, int k, int side, int filtered, int *idx,
-                    float *score) {
+                    float *score, bool decoder) {
   PGCN_CHECK(params.link_decoder && link_embed, PGCN_E_INVALID, "top_links: not a link engine");
-  PGCN_CHECK(!link_var, PGCN_E_INVALID,
-             "top_links: the 1-vs-all sweep ranks the dot product only; with link_hidden > 0 "
-             "evaluate with score_pairs over fixed candidate lists");
+  PGCN_CHECK(decoder || !link_var, PGCN_E_INVALID,
+             "top_links: the default sweep ranks the dot product only; with link_hidden > 0 ask "
+             "for the decoder's retrieval by name (pgcn_gcn_top_links_decoder)");
+  PGCN_CHECK(!decoder || link_var, PGCN_E_INVALID,
+             "top_links_decoder: the engine has no decoder to rank by (link_hidden == 0)");
   PGCN_CHECK(m >= 0 && (m == 0 || (nodes && idx && score)) && k >= 1 && k <= kTopKMax &&
                  (side == 0 || side == 1) && (filtered == 0 || filtered == 1),
              PGCN_E_INVALID, "top_links: nodes, idx, score; 1 <= k <= 128, side 0 / 1, filtered 0 / 1");
@@ -2199,11 +2201,16 @@ void GCN::top_links(const int *nodes, long long m, int k, int side, int filtered
         rank_pairs_[0].data(), rank_pairs_[1].data(), rank_pairs_[2].data(),
         rank_pairs_[3].data(), c, nodes + b, side, filtered);
     const TopKQueriesDev q(params.num_nodes, c, nodes + b, filtered ? f.ptr.data() : nullptr,
-                           f.idx.data(), k);
+                           f.idx.data(), k, decoder);
     DeviceBuffer<int> di((size_t)c * k);
     DeviceBuffer<float> ds((size_t)c * k);
-    launch_link_topk(q.queries(), h.dev_data.get(), h.ld, params.output_dim, di.get(), ds.get(),
-                     stream.get());
+    if (decoder)
+      launch_link_topk_mlp(q.queries(), h.dev_data.get(), h.ld, params.output_dim,
+                           link_var->dev_data.get(), link_var->ld, params.link_hidden, di.get(),
+                           ds.get(), stream.get());
+    else
+      launch_link_topk(q.queries(), h.dev_data.get(), h.ld, params.output_dim, di.get(), ds.get(),
+                       stream.get());
     sync();
     di.download(idx + b * k, (size_t)c * k);
     ds.download(score + b * k, (size_t)c * k);

@@ -181,9 +181,10 @@ class GCN {
                        bool decoder = false);
   // the same forward, then launch_link_topk over the output embedding for m anchor nodes: idx /
   // score [m][k] on the host (side, filtered: build_topk_filter's lists).  kTopKChunk queries at a
-  // time, the query set and the device outputs of a chunk freed after it
+  // time, the query set and the device outputs of a chunk freed after it.  decoder: by the MLP
+  // decoder's score (launch_link_topk_mlp; a link_hidden engine, which the default call refuses)
   void top_links(const int *nodes, long long m, int k, int side, int filtered, int *idx,
-                 float *score);
+                 float *score, bool decoder = false);
   long long adam_steps() const { return optimizer.steps(); }
   void set_profile(bool on);
   void profile_read_mm(double *ms, long long *calls, double *flops);  // XW contractions

@@ -1121,18 +1121,21 @@ void validate_topk_queries(int n, long long n_queries, const int *anchor,
 }
 
 TopKQueriesDev::TopKQueriesDev(int n, long long n_queries, const int *anchor,
-                               const long long *exclude_ptr, const int *exclude_idx, int k) {
+                               const long long *exclude_ptr, const int *exclude_idx, int k,
+                               bool mlp) {
   auto up = [](auto &buf, const auto *host, size_t count) {
     buf.allocate(std::max<size_t>(count, 1));
     if (count) buf.upload(host, count);
   };
   up(anchor_, anchor, (size_t)n_queries);
-  ws_bytes_ = topk_workspace_bytes(n_queries, n, k);
+  ws_bytes_ = mlp ? topk_mlp_workspace_bytes(n_queries, n, k)
+                  : topk_workspace_bytes(n_queries, n, k);
   ws_.allocate(std::max<size_t>((size_t)ws_bytes_ / sizeof(unsigned long long), 1));
   q_.n = n;
   q_.n_queries = (int)n_queries;
   q_.k = k;
-  q_.splits = topk_splits(n_queries, n);
+  q_.splits = mlp ? topk_mlp_splits(n_queries, n) : topk_splits(n_queries, n);
+  q_.mlp = mlp ? 1 : 0;
   q_.anchor = anchor_.get();
   q_.ws = ws_.get();
   if (exclude_ptr) {

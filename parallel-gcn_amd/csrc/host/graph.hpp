@@ -354,12 +354,13 @@ void validate_topk_queries(int n, long long n_queries, const int *anchor,
                            const long long *exclude_ptr, const int *exclude_idx, int k);
 
 // A top-K query set on the device, of arrays validate_topk_queries accepted.  It owns every byte a
-// call needs (topk_workspace_bytes), so two calls on one set must not overlap.  Construction is
-// host work and blocking copies: not inside a stream capture.
+// call needs (topk_workspace_bytes; mlp: topk_mlp_workspace_bytes, for launch_link_topk_mlp), so
+// two calls on one set must not overlap.  Construction is host work and blocking copies: not inside
+// a stream capture.
 class TopKQueriesDev {
  public:
   TopKQueriesDev(int n, long long n_queries, const int *anchor, const long long *exclude_ptr,
-                 const int *exclude_idx, int k);
+                 const int *exclude_idx, int k, bool mlp = false);
   const TopKQueries &queries() const { return q_; }
   long long workspace() const { return ws_bytes_; }
 

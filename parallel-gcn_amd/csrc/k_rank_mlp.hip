@@ -31,47 +31,24 @@
 //       forward's own tile code (z staged in LDS, mlp_pre, mlp_lane_sum, mlp_tile_score); an entry
 //       the sweep counted leaves its query's counts (integer atomics).
 // Every count is an integer sum: two calls give the same bits.
+// The staging and a query's score (the MFMA loop and the epilogue) live in rank_mlp_sweep.hpp, shared
+// with k_topk_mlp.hip.
 #include <algorithm>
 
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rank_sweep.hpp"
 #include "link_mlp_tile.hpp"
+#include "rank_mlp_sweep.hpp"
 
 #pragma clang fp contract(off)
 
 namespace pgcn {
-static_assert(kRankMlpTQ == kLinkMlpTile && kRankMlpTC == kLinkMlpTile,
-              "the sweep keeps its chunk in the image's z rows and its block's words in G / Red");
-
 __global__ __launch_bounds__(kMlpThreads) void k_rank_mlp_zero(unsigned *__restrict__ a,
                                                                unsigned *__restrict__ b, int Q) {
   for (int e = blockIdx.x * kMlpThreads + threadIdx.x; e < Q; e += gridDim.x * kMlpThreads)
     a[e] = b[e] = 0u;
 }
-
-namespace {
-// chunk c of the candidates into registers (no branch: clamped addresses), registers into LDS
-template <int ND, int UT>
-__device__ __forceinline__ void rank_mlp_load_chunk(float4 *stage, const float *__restrict__ H,
-                                                    int ld_h, int d, int n, int c, int tid) {
-  using L = MlpLds<ND, UT>;
-#pragma unroll
-  for (int i = 0; i < L::NG; i++) {
-    const int idx = i * kMlpThreads + tid;
-    stage[i] = load_chunk(H, ld_h, d, n, c * kRankMlpTC + idx / L::CPR, idx % L::CPR);
-  }
-}
-template <int ND, int UT>
-__device__ __forceinline__ void rank_mlp_store_rows(float *rows, const float4 *stage, int tid) {
-  using L = MlpLds<ND, UT>;
-#pragma unroll
-  for (int i = 0; i < L::NG; i++) {
-    const int idx = i * kMlpThreads + tid;
-    put_split<L::HD>(rows + (idx / L::CPR) * L::S, idx % L::CPR, stage[i]);
-  }
-}
-}  // namespace
 
 template <int ND, int UT>
 __global__ __launch_bounds__(kMlpThreads) void k_rank_mlp_sweep(
@@ -94,13 +71,7 @@ __global__ __launch_bounds__(kMlpThreads) void k_rank_mlp_sweep(
   const float b2 = P[(long long)(d + 2) * ld_p];
   float4 stage[L::NG];
   // the block's anchor rows (zero rows from Q on), thresholds and targets, once
-#pragma unroll
-  for (int i = 0; i < L::NG; i++) {
-    const int idx = i * kMlpThreads + tid, q = q0 + idx / L::CPR;
-    const float4 r = load_chunk(H, ld_h, d, n, anchor[min(q, Q - 1)], idx % L::CPR);
-    stage[i] = q < Q ? r : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  }
-  rank_mlp_store_rows<ND, UT>(As, stage, tid);
+  rank_mlp_gather_anchors<ND, UT>(As, stage, anchor, q0, Q, H, ld_h, d, n, tid);
   if (tid < kRankMlpTQ) {
     const int q = q0 + tid;
     lds[L::oG + tid] = q < Q ? thr[4 * (long long)q] : 0.0f;
@@ -121,36 +92,7 @@ __global__ __launch_bounds__(kMlpThreads) void k_rank_mlp_sweep(
     for (int qi = 0; qh + 2 * qi < nq; qi++) {
       const int qs = qh + 2 * qi;
       const float *a_row = As + qs * L::S + half * L::HD;
-      f32x16 acc[2][L::NQ];
-#pragma unroll
-      for (int u = 0; u < 2; u++)
-#pragma unroll
-        for (int q = 0; q < L::NQ; q++)
-#pragma unroll
-          for (int r = 0; r < 16; r++) acc[u][q][r] = 0.0f;
-      for (int j = 0; j < groups; j++) {
-        const float4 a = *reinterpret_cast<const float4 *>(a_row + 4 * j);
-        const float4 b = *reinterpret_cast<const float4 *>(c_row + 4 * j);
-        const float zx = a.x * b.x, zy = a.y * b.y, zz = a.z * b.z, zw = a.w * b.w;
-#pragma unroll
-        for (int ut = 0; ut < UT; ut++) {
-          const float4 w = *reinterpret_cast<const float4 *>(w_row + 32 * ut * L::S + 4 * j);
-          f32x16 &t = acc[ut & 1][ut >> 1];
-          t = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, zx, t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, zy, t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, zz, t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, zw, t, 0, 0, 0);
-        }
-      }
-      // the forward's epilogue: wave uh's lane sum and exchange, red[0] + red[1], + b2
-      float s = mlp_lane_sum<ND, UT>(lds, acc[0], 0, half);
-      s = s + __shfl_xor(s, 32, 64);
-      if (UT > 1) {
-        float s1 = mlp_lane_sum<ND, UT>(lds, acc[1], 1, half);
-        s1 = s1 + __shfl_xor(s1, 32, 64);
-        s = s + s1;
-      }
-      s = s + b2;
+      const float s = rank_mlp_query_score<ND, UT>(lds, a_row, c_row, w_row, groups, b2, half);
       const float th = lds[L::oG + qs];
       const bool ok = v < n && v != tgs[qs];
       const unsigned long long bg = __ballot(ok && s > th), be = __ballot(ok && s == th);

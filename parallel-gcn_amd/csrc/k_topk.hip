@@ -3,9 +3,8 @@
 // v in [0, n) \ X with the highest rank score r(a, v) (k_rank.hip's fmaf chain, which the f32 MFMA
 // computes bit for bit), ties to the lower index, without ever storing the [Q][n] score matrix.
 //
-// A selection key is 64 bits, ordered(score) << 32 | ~v: ordered() maps a float (its zero
-// canonicalised to +0 first) to an unsigned that compares as the float does, so a greater key is a
-// candidate that precedes.  Keys of distinct candidates are distinct; 0 is "no entry".
+// The 64-bit selection key, the sort, the prune and the merge kernel live in topk_select.hpp,
+// shared with k_topk_mlp.hip.
 //
 //   k_topk_sweep<NV, E>: k_rank_sweep's workgroup, tiles, staging and MFMA loop (rank_sweep.hpp).
 //       A wave owns its 32 queries over its split's candidate range, so everything per query is
@@ -21,8 +20,8 @@
 //       sorts (a bitonic network over shuffles), keeps the k best and refreshes tau.
 //       Every query is pruned once more at the end of the range, which leaves k keys in descending
 //       order (0 where the split had fewer candidates) at the front of its buffer.
-//   k_topk_merge<E>: a wave per query folds the splits' k keys, one split at a time, into its k
-//       best by the same sort, and writes idx / score with the padding (-1, -inf).
+//   k_topk_merge<E> (topk_select.hpp): a wave per query folds the splits' k keys, one split at a
+//       time, into its k best by the same sort, and writes idx / score with the padding (-1, -inf).
 // Two launches whatever the data.  No atomics; every step is a function of the inputs alone, so two
 // calls give the same bits.
 #include <algorithm>
@@ -31,110 +30,11 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rank_sweep.hpp"
+#include "topk_select.hpp"
 
 #pragma clang fp contract(off)
 
 namespace pgcn {
-
-namespace {
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 topk_key(float s, int v) {
-  s = s + 0.0f;  // -0 -> +0: the key must not see a zero's sign
-  const unsigned b = __float_as_uint(s);
-  const unsigned o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((u64)o << 32) | (u64)(~(unsigned)v);
-}
-__device__ __forceinline__ float topk_key_score(u64 key) {
-  const unsigned o = (unsigned)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
-// lanes of one wave exchange data through memory: what was stored before is visible after
-__device__ __forceinline__ void wave_mem_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// the wave's 64 E keys, element i = 64 e + lane in key[e], into descending order of i
-template <int E>
-__device__ __forceinline__ void wave_sort_desc(u64 (&key)[E], int lane) {
-#pragma unroll
-  for (int k2 = 2; k2 <= 64 * E; k2 <<= 1) {
-#pragma unroll
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      if (j >= 64) {  // partners are registers of one lane; the block's direction is e's alone
-        const int je = j / 64;
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-          if (e & je) continue;
-          const bool desc = ((64 * e) & k2) == 0;
-          const u64 a = key[e], b = key[e | je];
-          const u64 hi = a > b ? a : b, lo = a > b ? b : a;
-          key[e] = desc ? hi : lo;
-          key[e | je] = desc ? lo : hi;
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-          const u64 other = __shfl_xor(key[e], j, 64);
-          const bool desc = ((64 * e + lane) & k2) == 0, lower = (lane & j) == 0;
-          const u64 hi = key[e] > other ? key[e] : other, lo = key[e] > other ? other : key[e];
-          key[e] = (desc == lower) ? hi : lo;
-        }
-      }
-    }
-  }
-}
-
-// element i of the sorted keys, i wave-uniform
-template <int E>
-__device__ __forceinline__ u64 wave_key_at(const u64 (&key)[E], int i) {
-  u64 mine = key[0];
-#pragma unroll
-  for (int e = 1; e < E; e++) mine = (i >> 6) == e ? key[e] : mine;
-  return __shfl(mine, i & 63, 64);
-}
-
-// is v in the ascending list idx[lo .. hi)
-__device__ __forceinline__ bool list_holds(const int *__restrict__ idx, long long lo, long long hi,
-                                           int v) {
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    const int x = idx[mid];
-    if (x == v) return true;
-    if (x < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return false;
-}
-
-// the whole wave: buf[0 .. count), of which the entries from `clean` on have not met the exclude
-// list idx[lo .. hi) yet -> the k best of the candidates among them in descending order at
-// buf[0 .. k), 0 behind the last; returns how many those are (at most k) and in *tau the k-th best
-// score, -inf when there are fewer than k
-template <int E>
-__device__ __forceinline__ int wave_prune(u64 *buf, int count, int clean, int k, int lane,
-                                          const int *__restrict__ idx, long long lo, long long hi,
-                                          float *tau) {
-  u64 key[E];
-  int valid = 0;
-#pragma unroll
-  for (int e = 0; e < E; e++) {
-    const int i = 64 * e + lane;
-    key[e] = i < count ? buf[i] : 0ull;
-    if (i >= clean && i < count && list_holds(idx, lo, hi, (int)~(unsigned)key[e])) key[e] = 0ull;
-    valid += __popcll(__ballot(key[e] != 0ull));
-  }
-  wave_sort_desc<E>(key, lane);
-#pragma unroll
-  for (int e = 0; e < E; e++)
-    if (64 * e + lane < k) buf[64 * e + lane] = key[e];
-  *tau = valid >= k ? topk_key_score(wave_key_at<E>(key, k - 1)) : -INFINITY;
-  return min(valid, k);
-}
-}  // namespace
 
 // NV: as k_rank_sweep.  E: keys per lane of a prune, the append buffers hold cap = 64 E >= k + 64
 template <int NV, int E>
@@ -240,38 +140,6 @@ __global__ __launch_bounds__(kRankThreads) void k_topk_sweep(
   }
 }
 
-// a wave per query: the k best of its splits' k keys, then idx / score with the padding
-template <int E>
-__global__ __launch_bounds__(kRankThreads) void k_topk_merge(const u64 *__restrict__ ws, int Q,
-                                                             int splits, int k,
-                                                             int *__restrict__ idx,
-                                                             float *__restrict__ score) {
-  constexpr int CAP = 64 * E, HALF = E / 2;
-  const int lane = threadIdx.x % kWave;
-  const int q = blockIdx.x * (kRankThreads / kWave) + threadIdx.x / kWave;
-  if (q >= Q) return;
-  u64 key[E];
-#pragma unroll
-  for (int e = 0; e < E; e++) key[e] = 0ull;
-  for (int s = 0; s < splits; s++) {
-    const u64 *buf = ws + ((long long)q * splits + s) * CAP;
-    // (the running best sits sorted in the elements below 64 HALF >= k; the split's keys go behind)
-#pragma unroll
-    for (int e = 0; e < HALF; e++)
-      key[HALF + e] = 64 * e + lane < k ? buf[64 * e + lane] : 0ull;
-    wave_sort_desc<E>(key, lane);
-  }
-#pragma unroll
-  for (int e = 0; e < HALF; e++) {
-    const int i = 64 * e + lane;
-    if (i < k) {
-      const u64 x = key[e];
-      idx[(long long)q * k + i] = x ? (int)~(unsigned)x : -1;
-      score[(long long)q * k + i] = x ? topk_key_score(x) : -INFINITY;
-    }
-  }
-}
-
 int topk_splits(long long Q, int n) {
   const int q = (int)std::min<long long>(std::max<long long>(Q, 1), INT_MAX);
   const long long tiles = ceil_div(std::max(n, 1), kRankTC);
@@ -279,7 +147,7 @@ int topk_splits(long long Q, int n) {
   return (int)ceil_div(tiles, ceil_div(tiles, rank_splits(q, n)));
 }
 
-int topk_cap(int k) { return k <= 64 ? 128 : 256; }
+int topk_cap(int k) { return topk_cap_of(k); }
 
 long long topk_workspace_bytes(long long Q, int n, int k) {
   return Q * topk_splits(Q, n) * topk_cap(k) * (long long)sizeof(u64);
@@ -290,6 +158,9 @@ void launch_link_topk(const TopKQueries &q, const float *H, int ld_h, int d, int
   PGCN_CHECK(d >= 1 && d <= kLinkMaxWidth && q.n >= 1 && q.n_queries >= 0 && q.k >= 1 &&
                  q.k <= kTopKMax,
              PGCN_E_INVALID, "link_topk: 1 <= d <= 128, 1 <= k <= 128");
+  PGCN_CHECK(!q.mlp, PGCN_E_INVALID,
+             "link_topk: the handle's workspace was sized for the MLP sweep "
+             "(pgcn_topk_queries_create)");
   if (q.n_queries == 0) return;
   const int Q = q.n_queries;
   const int tiles = (int)ceil_div(q.n, kRankTC), splits = topk_splits(Q, q.n);

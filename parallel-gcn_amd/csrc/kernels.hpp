@@ -18,7 +18,7 @@ enum KernelPath {
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
   KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_RANK_SWEEP, KP_RANK_FILTER,
   KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_LINK_MLP_FWD, KP_LINK_MLP_BWD,
-  KP_RANK_MLP_SWEEP, KP_RANK_MLP_FILTER, KP_COUNT
+  KP_RANK_MLP_SWEEP, KP_RANK_MLP_FILTER, KP_TOPK_MLP_SWEEP, KP_TOPK_MLP_MERGE, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -588,7 +588,10 @@ struct TopKQueries {
   const int *anchor = nullptr;
   const long long *exclude_ptr = nullptr;  // [n_queries + 1], null: no lists
   const int *exclude_idx = nullptr;
-  void *ws = nullptr;  // topk_workspace_bytes(n_queries, n, k)
+  void *ws = nullptr;  // topk_workspace_bytes(n_queries, n, k); mlp: topk_mlp_workspace_bytes
+  // which sweep splits and ws were sized for: launch_link_topk (0) or launch_link_topk_mlp (1);
+  // each launcher refuses the other kind
+  int mlp = 0;
 };
 // candidate splits of the sweep's grid (rank_splits' ranges, the ones that hold a tile): a function
 // of (Q, n) only
@@ -601,6 +604,20 @@ long long topk_workspace_bytes(long long Q, int n, int k);
 // topk_splits), the merge (a wave per query)
 void launch_link_topk(const TopKQueries &q, const float *H, int ld_h, int d, int *idx, float *score,
                       hipStream_t s);
+// ---- link prediction: 1-vs-all top-K retrieval under the MLP decoder (k_topk_mlp.hip) ------------
+// launch_link_topk's answer with launch_link_mlp_fwd's score of the pair (a_e, v) in r's place, the
+// same bits as that launch gives.  The sweep is k_rank_mlp_sweep's (rank_mlp_sweep.hpp) with a
+// selecting epilogue; per (query, split) it keeps TWO append buffers, one per 32-candidate block
+// of a chunk, so a query set sized for it (TopKQueries::mlp) owns
+// Q * topk_mlp_splits(Q, n) * 2 * topk_cap(k) * 8 bytes.
+// candidate splits of the sweep's grid (rank_mlp_splits' ranges, the ones that hold a chunk): a
+// function of (Q, n) only
+int topk_mlp_splits(long long Q, int n);
+long long topk_mlp_workspace_bytes(long long Q, int n, int k);
+// idx / score [n_queries][k].  Two launches whatever the data: the sweep (query blocks x
+// topk_mlp_splits), k_topk_merge over 2 x splits lists per query
+void launch_link_topk_mlp(const TopKQueries &q, const float *H, int ld_h, int d, const float *P,
+                          int ld_p, int h, int *idx, float *score, hipStream_t s);
 int xent_blocks(int n);
 // the output layer's product and the loss in one pass (k_xent_fwd<true>): logits = H W
 // (H [n][ldh], kh <= 16 columns; W [kh][ldw]) written max-shifted like launch_xent_fwd's

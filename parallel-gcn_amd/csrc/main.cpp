@@ -35,7 +35,7 @@
 // is used as loaded: keep validation and test positives out of it.
 // link_hidden=<H> (with link=dot; 1..128): the Hadamard-MLP decoder of that hidden width in the dot
 // product's place (pgcn_params.link_hidden); rank= then ranks by the decoder's score
-// (pgcn_gcn_link_ranks_decoder), recommend= is refused on such an engine.
+// (pgcn_gcn_link_ranks_decoder) and recommend= retrieves by it (pgcn_gcn_top_links_decoder).
 // neg_ratio=<R> (with link=dot; 1..64): R negatives per training positive, redrawn on the device
 // before every epoch (pgcn_params.neg_ratio).
 // rank=1 (with link=): after the run, one line with the filtered ranking metrics of the test split
@@ -44,7 +44,7 @@
 // positive pair for the dst side.
 // recommend=<file> [topk=<K>, default 10, at most 128] (with link=): after the run, one line per
 // node `node v1 s1 v2 s2 ...` with the K best destinations for the node as a source
-// (pgcn_gcn_top_links: dst side, filtered -- the node, its neighbours and its known links are left
+// (pgcn_gcn_top_links, with link_hidden= its _decoder form: dst side, filtered -- the node, its neighbours and its known links are left
 // out -- best first, ties to the lower index; a node with fewer than K candidates gets a shorter
 // line).
 #include <algorithm>
@@ -344,7 +344,8 @@ int main(int argc, char **argv) {
     std::vector<int> nodes((size_t)m), idx((size_t)m * (size_t)std::max(topk, 0));
     std::vector<float> score(idx.size());
     for (long long i = 0; i < m; i++) nodes[(size_t)i] = (int)i;
-    const long long got = pgcn_gcn_top_links(g, nodes.data(), m, topk, 0, 1, idx.data(), score.data());
+    const auto top = p.link_hidden > 0 ? pgcn_gcn_top_links_decoder : pgcn_gcn_top_links;
+    const long long got = top(g, nodes.data(), m, topk, 0, 1, idx.data(), score.data());
     FILE *f = got >= 0 ? std::fopen(recommend.c_str(), "w") : nullptr;
     if (!f) {
       fprintf(stderr, "cannot write recommendations to %s%s%s\n", recommend.c_str(),
