@@ -186,6 +186,42 @@ int pgcn_debug_layernorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, 
                                   const float *res, int res_ld, const uint64_t *drop_mask,
                                   long long drop_base, float drop_scale, void *stream);
 
+/* --- BatchNorm over the rows of a node variable (new: the reference has no such module) -----
+ * Per column c over the n rows, with this call's own statistics (no running averages):
+ *   mean_c = (1/n) sum_i x[i][c];  var_c = (1/n) sum_i (x[i][c] - mean_c)^2   (biased)
+ *   rstd_c = 1 / sqrtf(var_c + eps);  xhat = (x - mean_c) * rstd_c;  y = gamma_c * xhat + beta_c
+ * The variance comes from centred second moments: tiles of pgcn_batchnorm_tile_rows(d) rows
+ * take a two-pass mean / M2 each, and the tile records are merged pairwise in tile order -- never
+ * E[x^2] - mean^2.  1 <= d <= 1024; every ld a multiple of 4 and >= d; every row 16-byte aligned;
+ * gamma, beta [d].  The float4s covering columns [0, round_up4(d)) of y are written, zero from
+ * column d on; padding columns of x are never read into the result; x == y is allowed.  stats
+ * [2][round_up4(d)] (required) receives {mean, rstd}; xhat [n][ld_xhat] (NULL: not kept) the
+ * normalised rows the backward reads.  workspace: pgcn_batchnorm_fwd_workspace(n, d) bytes,
+ * 16-byte aligned.  n == 1 gives xhat = 0, y = beta, rstd = 1 / sqrtf(eps).
+ * backward: dbeta_c = sum_i dy[i][c], dgamma_c = sum_i dy[i][c] * xhat[i][c] (per-workgroup
+ * partials in `workspace`, pgcn_batchnorm_bwd_workspace(n, d) bytes, then one reducing launch),
+ * dx[i][c] = gamma_c * rstd_c * (dy[i][c] - dbeta_c / n - xhat[i][c] * dgamma_c / n); dx == dy is
+ * allowed.  Every summation order depends on (n, d) only: two calls give the same bits.  No float
+ * atomics.  PGCN_E_INVALID for bad arguments (nothing is launched); n == 0 launches nothing; the
+ * calls are asynchronous on `stream`, allocate nothing and may be captured. */
+int pgcn_batchnorm_tile_rows(int d);
+size_t pgcn_batchnorm_fwd_workspace(int n, int d);
+int pgcn_batchnorm_fwd(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                       const float *gamma, const float *beta, float eps, float *xhat,
+                       int ld_xhat, float *stats, void *workspace, void *stream);
+size_t pgcn_batchnorm_bwd_workspace(int n, int d);
+int pgcn_batchnorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
+                       const float *stats, const float *gamma, int n, int d, float *dx, int ld_dx,
+                       float *dgamma, float *dbeta, void *workspace, void *stream);
+/* The forward with the engine's fused tail in the apply launch's final write (kernel tests), as
+ * pgcn_debug_layernorm_fwd_tail. */
+int pgcn_debug_batchnorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                                  const float *gamma, const float *beta, float eps, float *xhat,
+                                  int ld_xhat, float *stats, void *workspace, uint8_t *relu_mask,
+                                  int relu_ld, const float *res, int res_ld,
+                                  const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                                  void *stream);
+
 /* --- graph attention over a node variable (new: the reference has one aggregation) ---------
  * Single head, additive (GAT).  `g` comes from pgcn_graph_create with a square pattern; its
  * values are not used.  Every CSR slot s = (i, j) counts as the pattern has it (self loops, a
@@ -735,6 +771,20 @@ typedef struct {
    * one more variable, the last (index pgcn_gcn_num_vars - 1): scores [E][1]. */
   int link_decoder;
   int hidden_dims[PGCN_MAX_LAYERS];      /* n_layers - 1 */
+  /* (Here, behind hidden_dims: the members before it keep their offsets.)  != 0: every hidden
+   * layer 0 <= l <= n_layers - 2 gets a BatchNorm between its aggregation (GraphSum, attention or
+   * SAGE) and its ReLU, where layer_norm puts a LayerNorm: H_l = relu(gamma_l * xhat + beta_l)
+   * [+ A], xhat the column-normalised aggregation output over all num_nodes rows
+   * (pgcn_batchnorm_fwd, eps 1e-5).  Every pass, training or eval, covers all the nodes and
+   * normalises with its own statistics: there are no running averages and no momentum
+   * (PyTorch's track_running_stats=False), and no state beyond gamma / beta.  gamma = 1 and beta
+   * = 0 at the start (no RNG draw: weights and dropout masks equal the plain engine's); Adam
+   * updates them without weight decay.  They live in the scale / shift tensor layer_norm uses
+   * (same shape, same variable index 3 * n_layers + 1, same place in the optimizer).  Hidden
+   * widths up to 1024.  Not with layer_norm, and single GPU only: the edge-cut creators return
+   * PGCN_E_INVALID (the column statistics would need an all-reduce across the ranks, which is
+   * not built).  0: the engine as it was, bit for bit. */
+  int batch_norm;
   /* The link decoder's hidden width (here, behind hidden_dims: the members around link_decoder
    * keep their offsets).  0: the dot product above (the engine as it was, bit for
    * bit).  1..128 with link_decoder == 1: the Hadamard-MLP decoder of pgcn_link_mlp_fwd with that
@@ -936,11 +986,12 @@ int pgcn_gcn_destroy(pgcn_gcn *g);
  * "residual_layers" (layers with a ResidualConnection, pgcn_params.residual) and
  * "fused_residuals" (how many of them the last training forward added inside a GraphSum's
  * final write instead of a launch of their own), "norm_layers" (layers with a LayerNorm,
- * pgcn_params.layer_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel), "readout" (the readout
+ * pgcn_params.layer_norm), "batch_norm_layers" (layers with a BatchNorm, pgcn_params.batch_norm), "multilabel" (1: a multi-label engine, pgcn_params.multilabel), "readout" (the readout
  * mode, pgcn_params.readout) and "num_graphs" (its graph count; 0 without a readout),
  * "link_decoder" (pgcn_params.link_decoder), "link_hidden" (pgcn_params.link_hidden) and "num_pairs" (its pair count; 0 without), "neg_pairs" (the drawn pairs behind them; pgcn_params.neg_ratio), and
  * "fused_norm_tails" (how many of them ran the ReLU / residual add /
- * Dropout behind them inside the LayerNorm kernel in the last training forward);
+ * Dropout behind them inside the LayerNorm kernel in the last training forward; the BatchNorm
+ * layers whose apply launch ran that tail count too);
  * "norm_padding_nonzero" (diagnostics, syncs: non-zero elements in the edge-cut padding rows of
  * the normalised variables -- always 0); "attention_layers" (layers whose aggregation is graph
  * attention, pgcn_params.attention: n_layers or 0; on such an engine "reassociated", "eval_ax_us"
@@ -972,7 +1023,8 @@ int pgcn_gcn_run(pgcn_gcn *g, int verbose);
  * backward, NOT masked by the layer's ReLU: the masked gradient G * [Z_l > 0] that the
  * GraphSum backward reads is kept in a buffer of the engine's own, so that G can be added to
  * the grad of var2 of layer l-1 when the layer's Matmul backward writes it.
- * LayerNorm engines (pgcn_params.layer_norm) have one more variable, index 3 * n_layers + 1: the
+ * LayerNorm engines (pgcn_params.layer_norm; BatchNorm engines, pgcn_params.batch_norm, in every
+ * respect of this paragraph alike) have one more variable, index 3 * n_layers + 1: the
  * scale / shift tensor, per hidden layer gamma_l[d_l] then beta_l[d_l], layers in order (which =
  * 1: its gradient); pgcn_gcn_num_vars is 3 * n_layers + 2 for them.  pgcn_gcn_set_var accepts
  * it.  The LayerNorm backward transforms in place the buffer the layer's GraphSum backward
@@ -1014,7 +1066,8 @@ int pgcn_gcn_load(pgcn_gcn *g, const char *path, int flags);
  * epochs, weight count}.  PGCN_E_IO as pgcn_gcn_load. */
 int pgcn_checkpoint_info(const char *path, long long info[8]);
 /* Host-only: the file's header flags (>= 0; bit 0: saved by a residual engine; bit 1: by a
- * LayerNorm engine; bit 2: by a multi-label engine; bit 3: by an attention engine), validated as
+ * LayerNorm engine; bit 2: by a multi-label engine; bit 3: by an attention engine; ...; bit 7: by
+ * a BatchNorm engine), validated as
  * pgcn_checkpoint_info does, or a status < 0 (PGCN_E_IO also for flag bits this library does
  * not know). */
 int pgcn_checkpoint_flags(const char *path);
@@ -1092,6 +1145,19 @@ int pgcn_checkpoint_link_hidden(const char *path, int *link_hidden);
  * need no state of their own: (seed, epochs) are in the header.  A resume needs the same neg_ratio
  * (a file of versions 1-9 reads as 0); a weights-only load crosses it.  Host-only. */
 int pgcn_checkpoint_neg_ratio(const char *path, int *neg_ratio);
+/* flags bit 7: saved by a BatchNorm engine (pgcn_params.batch_norm).  Such an engine writes a
+ * version-11 file: the header with bit 7 set and bit 1 clear, then one 16-byte block
+ *   {u32 inner_version (2..10); u32 0; u64 0}
+ * and behind it exactly what a file of inner_version holds behind its header for the flags with
+ * bit 7 cleared and bit 1 set -- the file the same engine would write with layer_norm in place of
+ * batch_norm: its blocks, and the payloads with the scale / shift tensor where a LayerNorm
+ * engine's has it.  The block is under the checksum.  A flags-0 load refuses a file whose bit 7
+ * differs from the engine's (a LayerNorm engine refuses a BatchNorm file and the reverse); a
+ * weights-only load crosses it as it crosses bit 1, and between the two norms the scale / shift
+ * tensor is taken.  Every other engine keeps writing its version byte for byte; in files of
+ * versions 1-10 the bit stays unknown.  pgcn_checkpoint_info reports version 11, and the other
+ * host-only readers accept it. */
+#define PGCN_CKPT_BATCHNORM 128
 /* sizeof(pgcn_params) of this library (bindings check their struct layout against it) */
 int pgcn_params_sizeof(void);
 /* An eval-mode forward over every row this rank owns (no split, no row restriction whatever

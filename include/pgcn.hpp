@@ -366,6 +366,8 @@ struct GCNParams {
   // every hidden layer gets a LayerNorm between its GraphSum and its ReLU
   // (pgcn_params.layer_norm, pgcn.h)
   bool layer_norm{false};
+  // ... or a BatchNorm there, never both (pgcn_params.batch_norm, pgcn.h)
+  bool batch_norm{false};
 };
 
 struct GCNData {

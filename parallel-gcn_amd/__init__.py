@@ -41,7 +41,8 @@ P = ctypes.POINTER
 class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("link_decoder", c_int),
-                ("hidden_dims", c_int * MAX_LAYERS), ("link_hidden", c_int), ("neg_ratio", c_int),
+                ("hidden_dims", c_int * MAX_LAYERS), ("batch_norm", c_int),
+                ("link_hidden", c_int), ("neg_ratio", c_int),
                 ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
                 ("root_weight", c_int), ("epochs", c_int), ("readout", c_int),
                 ("early_stopping", c_int),
@@ -126,6 +127,16 @@ _sig("pgcn_layernorm_bwd", c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_
 _sig("pgcn_debug_layernorm_fwd_tail", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
      c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
      c_void_p, c_ll, c_float, c_void_p)
+_sig("pgcn_batchnorm_tile_rows", c_int, c_int)
+_sig("pgcn_batchnorm_fwd_workspace", c_size_t, c_int, c_int)
+_sig("pgcn_batchnorm_fwd", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+     c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_batchnorm_bwd_workspace", c_size_t, c_int, c_int)
+_sig("pgcn_batchnorm_bwd", c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+     c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_debug_batchnorm_fwd_tail", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+     c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+     c_int, c_void_p, c_ll, c_float, c_void_p)
 _sig("pgcn_gat_scores", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
      c_void_p, c_void_p)
 _sig("pgcn_gat_fwd", c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
@@ -984,8 +995,11 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
                 multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
                 aggregator=None, root_weight=False, readout=None, link_decoder=None,
-                link_hidden=0, neg_ratio=0):
-    """aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
+                link_hidden=0, neg_ratio=0, batch_norm=False):
+    """batch_norm: a BatchNorm between every hidden layer's aggregation and its ReLU, over all
+    the nodes with the pass's own statistics (no running averages); not with layer_norm, single
+    GPU only -- the engine refuses both.
+    aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
     own row through its own half of a [d_in][2 d_l] weight (with an aggregator only).
     readout: None (node classification), "sum", "mean" or "max": graph classification over the
     graphs attached with Dataset.set_graphs / load_graphs (not with multilabel).
@@ -1027,6 +1041,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     p.neg_ratio = int(neg_ratio)
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
+    p.batch_norm = 1 if batch_norm else 0
     p.reassociate_last = 1 if reassociate_last else 0
     p.seed = seed
     p.num_nodes, p.input_dim, p.output_dim = ds.num_nodes, ds.input_dim, ds.output_dim
@@ -1378,6 +1393,7 @@ CKPT_ATTENTION = 8  # version-4 files: the attention tensor last in the payloads
 CKPT_SAGE = 16  # version-6 files: a GraphSAGE engine's, with the {aggregator, root_weight} block
 CKPT_READOUT = 32  # version-7 files: a graph-classification engine's, with its three blocks
 CKPT_LINKS = 64  # version-8 files: a link-prediction engine's, with its four blocks
+CKPT_BATCHNORM = 128  # version-11 files: a BatchNorm engine's, an inner version behind a block
 
 
 def checkpoint_flags(path):
@@ -1388,6 +1404,12 @@ def checkpoint_flags(path):
     st = lib.pgcn_checkpoint_flags(os.fsencode(path))
     check(min(st, 0), f"checkpoint_flags {path}")
     return st
+
+
+def checkpoint_batch_norm(path):
+    """Host-only: whether a BatchNorm engine saved the file (header flags bit 7, CKPT_BATCHNORM:
+    a version-11 file).  PgcnError(PGCN_E_IO) for an invalid file."""
+    return bool(checkpoint_flags(path) & CKPT_BATCHNORM)
 
 
 def checkpoint_attention(path):
@@ -1519,6 +1541,8 @@ EXPORTED = [
     "pgcn_relu_bwd", "pgcn_residual_fwd", "pgcn_residual_bwd", "pgcn_params_sizeof",
     "pgcn_layernorm_fwd", "pgcn_layernorm_bwd_workspace", "pgcn_layernorm_bwd",
     "pgcn_debug_layernorm_fwd_tail",
+    "pgcn_batchnorm_tile_rows", "pgcn_batchnorm_fwd_workspace", "pgcn_batchnorm_fwd",
+    "pgcn_batchnorm_bwd_workspace", "pgcn_batchnorm_bwd", "pgcn_debug_batchnorm_fwd_tail",
     "pgcn_gat_scores", "pgcn_gat_fwd", "pgcn_gat_bwd_workspace", "pgcn_gat_bwd",
     "pgcn_gat_scores_mh", "pgcn_gat_fwd_mh", "pgcn_gat_bwd_workspace_mh", "pgcn_gat_bwd_mh",
     "pgcn_graph_create_mean", "pgcn_agg_max_fwd", "pgcn_agg_max_bwd",

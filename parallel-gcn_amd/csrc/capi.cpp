@@ -103,6 +103,7 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.seed = p->seed;
   q.residual = p->residual != 0;
   q.layer_norm = p->layer_norm != 0;
+  q.batch_norm = p->batch_norm != 0;
   q.multilabel = p->multilabel != 0;
   q.attention = p->attention != 0;
   q.attention_heads = p->attention_heads == 0 ? 1 : p->attention_heads;
@@ -206,7 +207,7 @@ const char *pgcn_status_string(int s) {
   }
 }
 
-int pgcn_version(void) { return 112; }
+int pgcn_version(void) { return 113; }
 
 // ---------------------------------------------------------------- graph + kernels
 int pgcn_graph_create(int n, const int *indptr, const int *indices, pgcn_graph **out) {
@@ -1186,6 +1187,95 @@ long long pgcn_debug_topk_filter(int n_nodes, const int *indptr, const int *indi
   return st == PGCN_OK ? m : st;
 }
 
+namespace {
+void batchnorm_fwd_checked(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                           const float *gamma, const float *beta, float eps, float *xhat,
+                           int ld_xhat, float *stats, void *workspace, const GsEpilogue *epi,
+                           void *stream) {
+  PGCN_CHECK(n >= 0 && d >= 1 && d <= kBatchNormMaxWidth && ln_ld_ok(ld_x, d) && ln_ld_ok(ld_y, d),
+             PGCN_E_INVALID, "batchnorm_fwd: 1 <= d <= 1024, ld % 4 == 0, ld >= d");
+  PGCN_CHECK(eps >= 0.0f && (!xhat || ln_ld_ok(ld_xhat, d)), PGCN_E_INVALID,
+             "batchnorm_fwd: ld_xhat % 4 == 0 >= d");
+  PGCN_CHECK(n == 0 || (x && y && gamma && beta && stats && workspace && aligned16(x) &&
+                        aligned16(y) && aligned16(xhat) && aligned16(workspace)),
+             PGCN_E_INVALID, "batchnorm_fwd: null or misaligned argument");
+  if (epi && epi->mode) {
+    PGCN_CHECK(ld_y == d && ln_ld_ok(epi->relu_ld, d) && (!epi->res || ln_ld_ok(epi->res_ld, d)) &&
+                   aligned16(epi->res) && (reinterpret_cast<uintptr_t>(epi->relu_mask) & 3) == 0 &&
+                   epi->drop_base >= 0,
+               PGCN_E_INVALID, "batchnorm_fwd_tail: the tail needs ld_y == d and padded strides");
+  }
+  check_device();
+  if (n == 0) return;
+  launch_batchnorm_fwd(x, ld_x, y, ld_y, n, d, gamma, beta, eps, xhat, ld_xhat, stats, workspace,
+                       epi, as_stream(stream));
+  PGCN_HIP(hipGetLastError());
+}
+}  // namespace
+
+int pgcn_batchnorm_tile_rows(int d) {
+  return d >= 1 && d <= kBatchNormMaxWidth ? batchnorm_tile_rows(d) : 0;
+}
+
+size_t pgcn_batchnorm_fwd_workspace(int n, int d) {
+  if (n < 0 || d < 1 || d > kBatchNormMaxWidth) return 0;
+  return batchnorm_fwd_workspace(n, d);
+}
+
+int pgcn_batchnorm_fwd(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                       const float *gamma, const float *beta, float eps, float *xhat,
+                       int ld_xhat, float *stats, void *workspace, void *stream) {
+  return guarded([&] {
+    batchnorm_fwd_checked(x, ld_x, y, ld_y, n, d, gamma, beta, eps, xhat, ld_xhat, stats,
+                          workspace, nullptr, stream);
+  });
+}
+
+int pgcn_debug_batchnorm_fwd_tail(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                                  const float *gamma, const float *beta, float eps, float *xhat,
+                                  int ld_xhat, float *stats, void *workspace, uint8_t *relu_mask,
+                                  int relu_ld, const float *res, int res_ld,
+                                  const uint64_t *drop_mask, long long drop_base, float drop_scale,
+                                  void *stream) {
+  return guarded([&] {
+    GsEpilogue e;
+    e.mode = 1;
+    e.relu_mask = relu_mask;
+    e.relu_ld = relu_ld;
+    e.res = const_cast<float *>(res);  // (mode 1 reads it)
+    e.res_ld = res_ld;
+    e.drop_mask = drop_mask;
+    e.drop_base = drop_base;
+    e.drop_cols = d;
+    e.drop_scale = drop_scale;
+    batchnorm_fwd_checked(x, ld_x, y, ld_y, n, d, gamma, beta, eps, xhat, ld_xhat, stats,
+                          workspace, &e, stream);
+  });
+}
+
+size_t pgcn_batchnorm_bwd_workspace(int n, int d) {
+  if (n < 0 || d < 1 || d > kBatchNormMaxWidth) return 0;
+  return batchnorm_bwd_workspace(n, d);
+}
+
+int pgcn_batchnorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
+                       const float *stats, const float *gamma, int n, int d, float *dx, int ld_dx,
+                       float *dgamma, float *dbeta, void *workspace, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(n >= 0 && d >= 1 && d <= kBatchNormMaxWidth && ln_ld_ok(ld_dy, d) &&
+                   ln_ld_ok(ld_xhat, d) && ln_ld_ok(ld_dx, d),
+               PGCN_E_INVALID, "batchnorm_bwd: 1 <= d <= 1024, ld % 4 == 0, ld >= d");
+    PGCN_CHECK(n == 0 || (dy && xhat && stats && gamma && dx && dgamma && dbeta && workspace &&
+                          aligned16(dy) && aligned16(xhat) && aligned16(dx)),
+               PGCN_E_INVALID, "batchnorm_bwd: null or misaligned argument");
+    check_device();
+    if (n == 0) return;
+    launch_batchnorm_bwd(dy, ld_dy, xhat, ld_xhat, stats, gamma, n, d, dx, ld_dx, dgamma, dbeta,
+                         workspace, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
 int pgcn_xent_blocks(int n) { return xent_blocks(n); }
 
 int pgcn_xent_fwd(float *logits, int ld, float *grad, const int *truth, int n, int c, int count,
@@ -1298,6 +1388,7 @@ void pgcn_params_default(pgcn_params *p) {
   p->multilabel = 0;
   p->seed = 0;
   p->layer_norm = 0;
+  p->batch_norm = 0;
   p->residual = 0;
 }
 
@@ -1436,6 +1527,7 @@ long long pgcn_gcn_query(pgcn_gcn *g, const char *key) {
     return st == PGCN_OK ? n : st;
   }
   if (!std::strcmp(key, "norm_layers")) return e.norm_layers();
+  if (!std::strcmp(key, "batch_norm_layers")) return e.batch_norm_layers();
   if (!std::strcmp(key, "attention_layers")) return e.attention_layers();
   if (!std::strcmp(key, "attention_heads")) return e.attention_heads();
   if (!std::strcmp(key, "attention_dropout_layers")) return e.attention_dropout_layers();

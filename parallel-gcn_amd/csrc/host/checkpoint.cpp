@@ -79,6 +79,29 @@ static_assert(sizeof(CkNegExt) == 16, "checkpoint extension layout");
 
 CkNegExt neg_ext(const Checkpoint &ck) { return CkNegExt{(uint32_t)ck.neg_ratio, 0, 0}; }
 
+// version 11: directly behind the header, before the inner version's own blocks
+struct CkBatchNormExt {
+  uint32_t inner_version, zero32;
+  uint64_t zero;
+};
+static_assert(sizeof(CkBatchNormExt) == 16, "checkpoint extension layout");
+
+// A version-11 file holds, behind its block, an inner version's layout for the flags with bit 1
+// in place of bit 7: everything below the header works on that (version, flags) pair.
+uint32_t layout_version(const Checkpoint &ck, uint32_t version) {
+  return version == (uint32_t)kCheckpointVersionBatchNorm ? (uint32_t)ck.inner_version : version;
+}
+uint32_t layout_flags(uint32_t version, uint32_t flags) {
+  return version == (uint32_t)kCheckpointVersionBatchNorm
+             ? (flags & ~kCheckpointBatchNorm) | kCheckpointLayerNorm
+             : flags;
+}
+// (the header's own bits of a version-11 file; the inner pair is checked by version_flags_ok)
+bool batchnorm_header_ok(uint32_t version, uint32_t flags) {
+  return version != (uint32_t)kCheckpointVersionBatchNorm ||
+         ((flags & kCheckpointBatchNorm) && !(flags & kCheckpointLayerNorm));
+}
+
 // versions 7 and 8 carry the heads, SAGE and readout blocks whatever the layer family
 bool link_blocks(uint32_t version) {  // ... and the link block behind them
   return version == (uint32_t)kCheckpointVersionLinks ||
@@ -91,7 +114,12 @@ bool three_blocks(uint32_t version) {
 
 uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
   uint64_t x = fnv1a(kFnvBasis, &h, offsetof(CkHeader, checksum));
-  if (three_blocks(h.version)) {
+  const uint32_t ver = layout_version(ck, h.version);  // (the blocks below are that version's)
+  if (h.version == (uint32_t)kCheckpointVersionBatchNorm) {
+    const CkBatchNormExt be{ver, 0, 0};
+    x = fnv1a(x, &be, sizeof be);
+  }
+  if (three_blocks(ver)) {
     const CkHeadsExt e = heads_ext(ck);
     const CkSageExt se = sage_ext(ck);
     const CkReadoutExt re = readout_ext(ck);
@@ -99,19 +127,19 @@ uint64_t ck_hash(const CkHeader &h, const Checkpoint &ck) {
     x = fnv1a(x, &se, sizeof se);
     x = fnv1a(x, &re, sizeof re);
   }
-  if (link_blocks(h.version)) {
+  if (link_blocks(ver)) {
     const CkLinksExt le = links_ext(ck);
     x = fnv1a(x, &le, sizeof le);
   }
-  if (h.version == (uint32_t)kCheckpointVersionNeg) {
+  if (ver == (uint32_t)kCheckpointVersionNeg) {
     const CkNegExt ne = neg_ext(ck);
     x = fnv1a(x, &ne, sizeof ne);
   }
-  if (h.version == (uint32_t)kCheckpointVersionHeads) {
+  if (ver == (uint32_t)kCheckpointVersionHeads) {
     const CkHeadsExt e = heads_ext(ck);
     x = fnv1a(x, &e, sizeof e);
   }
-  if (h.version == (uint32_t)kCheckpointVersionSage) {
+  if (ver == (uint32_t)kCheckpointVersionSage) {
     const CkSageExt e = sage_ext(ck);
     x = fnv1a(x, &e, sizeof e);
   }
@@ -246,45 +274,50 @@ void write_checkpoint(const std::string &path, const Checkpoint &ck) {
   for (int l = 0; l < L; l++) h.dropouts[l] = ck.dropouts[(size_t)l];
   h.seed = ck.seed;
   h.flags = ck.flags;
-  PGCN_CHECK(version_flags_ok(h.version, ck.flags), PGCN_E_INVALID,
+  // (version 11: the checks and the blocks below are those of the inner version's layout)
+  const uint32_t ver = layout_version(ck, h.version), flg = layout_flags(h.version, h.flags);
+  PGCN_CHECK(batchnorm_header_ok(h.version, h.flags) && version_flags_ok(ver, flg), PGCN_E_INVALID,
              "checkpoint: flags unknown to the file's version");
   h.adam_steps = ck.adam_steps;
   h.draw_epochs = ck.draw_epochs;
   h.epochs = ck.epochs;
   h.n_results = (int64_t)(ck.results.size() / 4);
   h.n_weights = (int64_t)ck.w.size();
-  PGCN_CHECK(readout_ok(h.version, ck.readout, ck.num_graphs, ck.num_nodes), PGCN_E_INVALID,
+  PGCN_CHECK(readout_ok(ver, ck.readout, ck.num_graphs, ck.num_nodes), PGCN_E_INVALID,
              "checkpoint: readout / graph count do not match the file's version");
-  PGCN_CHECK(links_ok(h.version, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]),
+  PGCN_CHECK(links_ok(ver, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]),
              PGCN_E_INVALID,
              "checkpoint: link decoder / pair count do not match the file's version");
-  PGCN_CHECK((h.version == (uint32_t)kCheckpointVersionNeg)
+  PGCN_CHECK((ver == (uint32_t)kCheckpointVersionNeg)
                  ? ck.neg_ratio >= 1 && ck.neg_ratio <= 64 : ck.neg_ratio == 0,
              PGCN_E_INVALID, "checkpoint: neg_ratio does not match the file's version");
-  PGCN_CHECK(sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
+  PGCN_CHECK(sage_ok(ver, flg, h.dims, L, ck.aggregator, ck.root_weight), PGCN_E_INVALID,
              "checkpoint: aggregator / root weight do not match the file's version");
-  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight) +
+  PGCN_CHECK(h.n_weights == expected_weights(h.dims, L, flg, ck.root_weight) +
                                 link_mlp_count(ck.link_hidden, h.dims[L]),
              PGCN_E_INVALID,
              "checkpoint: weight count does not match the layer dims");
-  PGCN_CHECK(heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout),
+  PGCN_CHECK(heads_ok(ver, flg, h.dims, L, ck.heads, ck.attention_dropout),
              PGCN_E_INVALID,
              "checkpoint: heads / attention dropout do not match the file's version");
   const CkHeadsExt ext = heads_ext(ck);
-  const bool v7 = three_blocks(h.version);
-  const bool v8 = link_blocks(h.version);
-  const bool with_ext = h.version == (uint32_t)kCheckpointVersionHeads || v7;
+  const bool v7 = three_blocks(ver);
+  const bool v8 = link_blocks(ver);
+  const bool with_ext = ver == (uint32_t)kCheckpointVersionHeads || v7;
   const CkSageExt sext = sage_ext(ck);
-  const bool with_sage = h.version == (uint32_t)kCheckpointVersionSage || v7;
+  const bool with_sage = ver == (uint32_t)kCheckpointVersionSage || v7;
   const CkReadoutExt rext = readout_ext(ck);
   const CkLinksExt lext = links_ext(ck);
   const CkNegExt next = neg_ext(ck);
-  const bool v10 = h.version == (uint32_t)kCheckpointVersionNeg;
+  const bool v10 = ver == (uint32_t)kCheckpointVersionNeg;
   h.checksum = ck_hash(h, ck);
   const std::string tmp = path + ".tmp";
   std::FILE *f = std::fopen(tmp.c_str(), "wb");
   if (!f) throw Error(PGCN_E_IO, "checkpoint: cannot write " + tmp);
+  const CkBatchNormExt bext{ver, 0, 0};
+  const bool v11 = h.version == (uint32_t)kCheckpointVersionBatchNorm;
   bool ok = std::fwrite(&h, sizeof(h), 1, f) == 1 &&
+            (!v11 || std::fwrite(&bext, sizeof(bext), 1, f) == 1) &&
             (!with_ext || std::fwrite(&ext, sizeof(ext), 1, f) == 1) &&
             (!with_sage || std::fwrite(&sext, sizeof(sext), 1, f) == 1) &&
             (!v7 || std::fwrite(&rext, sizeof(rext), 1, f) == 1) &&
@@ -306,21 +339,30 @@ Checkpoint read_checkpoint(const std::string &path) {
   CkHeader h{};
   Checkpoint ck;
   bool ok = std::fread(&h, sizeof(h), 1, f) == 1 && std::memcmp(h.magic, kCkMagic, 8) == 0 &&
-            version_flags_ok(h.version, h.flags) && h.n_layers >= 2 &&
-            h.n_layers <= PGCN_MAX_LAYERS && h.num_nodes > 0;
+            batchnorm_header_ok(h.version, h.flags);
+  if (ok && h.version == (uint32_t)kCheckpointVersionBatchNorm) {
+    CkBatchNormExt e{};
+    ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero32 == 0 && e.zero == 0 &&
+         e.inner_version < (uint32_t)kCheckpointVersionBatchNorm;
+    ck.inner_version = (int)e.inner_version;
+  }
+  // (version 11: the checks and the blocks below are those of the inner version's layout)
+  const uint32_t ver = layout_version(ck, h.version), flg = layout_flags(h.version, h.flags);
+  ok = ok && version_flags_ok(ver, flg) && h.n_layers >= 2 && h.n_layers <= PGCN_MAX_LAYERS &&
+       h.num_nodes > 0;
   const int L = ok ? (int)h.n_layers : 0;
   for (int l = 0; ok && l <= L; l++) ok = h.dims[l] > 0 && h.dims[l] <= (1 << 24);
   ok = ok && h.adam_steps >= 0 && h.draw_epochs >= 0 && h.epochs >= 0 && h.n_results >= 0 &&
        h.n_results <= kCheckpointMaxResults && h.n_results <= h.epochs &&
        h.n_weights < (1LL << 31);
-  const bool v7 = ok && three_blocks(h.version);
-  if (ok && (h.version == (uint32_t)kCheckpointVersionHeads || v7)) {
+  const bool v7 = ok && three_blocks(ver);
+  if (ok && (ver == (uint32_t)kCheckpointVersionHeads || v7)) {
     CkHeadsExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.heads <= 32;
     ck.heads = (int)e.heads;
     ck.attention_dropout = e.attention_dropout;
   }
-  if (ok && (h.version == (uint32_t)kCheckpointVersionSage || v7)) {
+  if (ok && (ver == (uint32_t)kCheckpointVersionSage || v7)) {
     CkSageExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.zero == 0 && e.aggregator <= 2 &&
          e.root_weight <= 1;
@@ -334,7 +376,7 @@ Checkpoint read_checkpoint(const std::string &path) {
     ck.readout = (int)e.readout;
     ck.num_graphs = (int)e.num_graphs;
   }
-  if (ok && link_blocks(h.version)) {
+  if (ok && link_blocks(ver)) {
     CkLinksExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.link_hidden <= 128 && e.link_decoder <= 1 &&
          e.num_pairs < (1ull << 31);
@@ -342,16 +384,16 @@ Checkpoint read_checkpoint(const std::string &path) {
     ck.link_decoder = (int)e.link_decoder;
     ck.num_pairs = (long long)e.num_pairs;
   }
-  if (ok && h.version == (uint32_t)kCheckpointVersionNeg) {
+  if (ok && ver == (uint32_t)kCheckpointVersionNeg) {
     CkNegExt e{};
     ok = std::fread(&e, sizeof(e), 1, f) == 1 && e.neg_ratio >= 1 && e.neg_ratio <= 64 &&
          e.zero32 == 0 && e.zero == 0;
     ck.neg_ratio = (int)e.neg_ratio;
   }
-  ok = ok && links_ok(h.version, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]) && heads_ok(h.version, h.flags, h.dims, L, ck.heads, ck.attention_dropout) &&
-       sage_ok(h.version, h.flags, h.dims, L, ck.aggregator, ck.root_weight) &&
-       readout_ok(h.version, ck.readout, ck.num_graphs, h.num_nodes) &&
-       h.n_weights == expected_weights(h.dims, L, h.flags, ck.root_weight) +
+  ok = ok && links_ok(ver, ck.link_decoder, ck.num_pairs, ck.link_hidden, h.dims[L]) && heads_ok(ver, flg, h.dims, L, ck.heads, ck.attention_dropout) &&
+       sage_ok(ver, flg, h.dims, L, ck.aggregator, ck.root_weight) &&
+       readout_ok(ver, ck.readout, ck.num_graphs, h.num_nodes) &&
+       h.n_weights == expected_weights(h.dims, L, flg, ck.root_weight) +
                           link_mlp_count(ck.link_hidden, h.dims[L]);
   ok = ok && read_floats(f, ck.results, h.n_results * 4) && read_floats(f, ck.w, h.n_weights) &&
        read_floats(f, ck.m, h.n_weights) && read_floats(f, ck.v, h.n_weights);

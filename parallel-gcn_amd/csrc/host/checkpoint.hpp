@@ -54,8 +54,15 @@
 // Version 9 = version 8 saved with pgcn_params.link_hidden > 0: the link block's second u32 holds
 // link_hidden (1..128; version 8 requires 0 there), and the payload gains the decoder tensor
 // [dims[L] + 3][round_up4(link_hidden)] -- and its two Adam moments -- behind the attention tensor.
+// Version 11 = saved by a BatchNorm engine (pgcn_params.batch_norm): flags bit 7 always set, bit 1
+// never, and directly behind the header one 16-byte block
+//   block  u32 inner_version (2..10); u32 0; u64 0
+// followed by what a file of inner_version holds behind its header for the flags with bit 7
+// cleared and bit 1 set: the file the same engine would write with layer_norm in place of
+// batch_norm (its blocks; the scale / shift tensor in the payloads as in version 2).  Every other
+// engine keeps writing versions 1-10 byte for byte; there bit 7 stays unknown.
 // checksum = FNV-1a 64 of the header's bytes before it, continued over the extension (versions
-// 5 and 6; the blocks of versions 7 and 8) and the payload.
+// 5 and 6; the blocks of versions 7, 8 and 11) and the payload.
 // draw_epochs counts the training forwards since the engine was built: the dropout stream
 // stands at glorot_draws + draw_epochs * period (GCN::init_dropout_rng), so no RNG state is
 // stored and the file does not depend on the world size.  Nothing newer than the reference:
@@ -85,6 +92,8 @@ constexpr int kCheckpointVersionLinks = 8;  // bit 6 set, + four blocks
 constexpr int kCheckpointVersionLinkMlp = 9;  // version 8 + link_hidden and the decoder tensor
 // version 8 (link_hidden 0) or 9 + a fifth block {u32 neg_ratio (1..64); u32 0; u64 0}
 constexpr int kCheckpointVersionNeg = 10;
+constexpr unsigned kCheckpointBatchNorm = 128u;  // header flags, bit 7 (version 11 only)
+constexpr int kCheckpointVersionBatchNorm = 11;  // bit 7 set, + the inner-version block
 // ... of a version-1 file
 constexpr unsigned kCheckpointKnownFlags = kCheckpointResidual | kCheckpointMultilabel;
 
@@ -108,6 +117,8 @@ struct Checkpoint {
   long long num_pairs = 0;
   int link_hidden = 0;  // versions 9 and 10
   int neg_ratio = 0;    // version 10 only
+  // version 11 only: the version whose layout follows the block (flags bit 1 for bit 7)
+  int inner_version = 0;
   long long adam_steps = 0, draw_epochs = 0, epochs = 0;
   std::vector<float> results;  // rows x {train_loss, train_acc, val_loss, val_acc}
   // every weight tensor in layer order (+ the norm tensor, + the attention tensor)

@@ -288,6 +288,14 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
     for (int h : params.hidden_dims)
       PGCN_CHECK(h <= kLayerNormMaxWidth, PGCN_E_INVALID,
                  "layer_norm: hidden dims up to 1024");
+  if (params.batch_norm) {
+    PGCN_CHECK(!params.layer_norm, PGCN_E_INVALID,
+               "batch_norm cannot be combined with layer_norm");
+    PGCN_CHECK(!dist, PGCN_E_INVALID,
+               "batch_norm: single GPU only (the column statistics would need an all-reduce)");
+    for (int h : params.hidden_dims)
+      PGCN_CHECK(h <= kBatchNormMaxWidth, PGCN_E_INVALID, "batch_norm: hidden dims up to 1024");
+  }
   PGCN_CHECK(params.output_dim >= 1 && params.output_dim <= 128, PGCN_E_INVALID,
              "output_dim must be in [1,128]");
   PGCN_CHECK(data.num_nodes == params.num_nodes, PGCN_E_INVALID, "num_nodes mismatch");
@@ -727,8 +735,9 @@ void GCN::build(const GCNData &data) {
   // (root_weight: W_l is [d_in][2 d_l], the root half first -- glorot's fan-out is 2 d_l)
   for (int l = 0; l < L; l++)
     wtotal += (long long)dims[(size_t)l] * weight_cols(dims[(size_t)l + 1]);
-  long long ntotal = 0;  // layer_norm: gamma and beta of every hidden layer, behind the weights
-  if (params.layer_norm)
+  // layer_norm / batch_norm: gamma and beta of every hidden layer, behind the weights
+  long long ntotal = 0;
+  if (params.layer_norm || params.batch_norm)
     for (int h : params.hidden_dims) ntotal += 2LL * h;
   long long atotal = 0;  // attention: a_dst and a_src of every layer, behind everything else
   if (params.attention)
@@ -973,10 +982,11 @@ void GCN::fuse_epilogues() {
   for (size_t i = 0; i < n; i++) {
     // LayerNorm -> ReLU [-> ResidualConnection] [-> Dropout]: the GraphSum before it keeps no
     // forward tail (its next module is not the ReLU); the LayerNorm's final write takes it
-    if (auto *ln = dynamic_cast<LayerNorm *>(modules[i].get())) {
+    // (a BatchNorm's apply launch takes the same tail)
+    auto norm_tail = [&](auto *ln) {
       const Variable *v = ln->variable();
       auto *relu = i + 1 < n ? dynamic_cast<ReLU *>(modules[i + 1].get()) : nullptr;
-      if (!relu || relu->variable() != v || v->ld != v->cols) continue;
+      if (!relu || relu->variable() != v || v->ld != v->cols) return;
       ln->fwd_relu = relu;
       auto *res = i + 2 < n ? dynamic_cast<ResidualConnection *>(modules[i + 2].get()) : nullptr;
       if (res && res->current() == v && res->previous()->ld == v->ld) ln->fwd_res = res;
@@ -984,6 +994,13 @@ void GCN::fuse_epilogues() {
       auto *drop = di < n ? dynamic_cast<Dropout *>(modules[di].get()) : nullptr;
       if (res && !ln->fwd_res) drop = nullptr;  // (an add the tail cannot take stays in order)
       if (drop && drop->variable() == v) ln->fwd_drop = drop;
+    };
+    if (auto *ln = dynamic_cast<LayerNorm *>(modules[i].get())) {
+      norm_tail(ln);
+      continue;
+    }
+    if (auto *bn = dynamic_cast<BatchNorm *>(modules[i].get())) {
+      norm_tail(bn);
       continue;
     }
     auto *gs = dynamic_cast<GraphSum *>(modules[i].get());
@@ -1116,6 +1133,12 @@ void GCN::insert_layer_norm(const shared_ptr<Variable> &var2, int layer) {
   if (!norm_var) return;
   long long off = 0;
   for (int l = 0; l < layer; l++) off += 2LL * params.hidden_dims[(size_t)l];
+  if (params.batch_norm) {  // ... or the BatchNorm, in the same place on the same tensor
+    auto bn = std::make_unique<BatchNorm>(var2, norm_var, off, part.local_rows());
+    bnorms_.push_back(bn.get());
+    modules.push_back(std::move(bn));
+    return;
+  }
   auto ln = std::make_unique<LayerNorm>(var2, norm_var, off, part.local_rows());
   norms_.push_back(ln.get());
   modules.push_back(std::move(ln));
@@ -1746,6 +1769,7 @@ void GCN::run(bool verbose) {
 int GCN::fused_norm_tails() const {
   int n = 0;
   for (const LayerNorm *l : norms_) n += l->last_fused ? 1 : 0;
+  for (const BatchNorm *l : bnorms_) n += l->last_fused ? 1 : 0;
   return n;
 }
 
@@ -1894,6 +1918,11 @@ void GCN::save(const std::string &path) {
       ck.neg_ratio = params.neg_ratio;
     }
   }
+  if (params.batch_norm) {  // version 11: the LayerNorm engine's file behind a block, bit 7 for 1
+    ck.inner_version = ck.version;
+    ck.version = kCheckpointVersionBatchNorm;
+    ck.flags = (ck.flags & ~kCheckpointLayerNorm) | kCheckpointBatchNorm;
+  }
   ck.adam_steps = optimizer.steps();
   ck.draw_epochs = draw_epochs;
   ck.epochs = epoch_count;
@@ -1931,7 +1960,8 @@ void GCN::load(const std::string &path, int flags) {
     // (a weights-only load ignores the residual flag: the tensors have the same shapes)
     // (... and crosses the LayerNorm flag: the scale / shift tensor is taken where both have it)
     same = ck.seed == params.seed && !(ck.flags & kCheckpointResidual) == residuals_.empty() &&
-           !(ck.flags & kCheckpointLayerNorm) == !norm_var &&
+           !(ck.flags & kCheckpointLayerNorm) == !params.layer_norm &&
+           !(ck.flags & kCheckpointBatchNorm) == !params.batch_norm &&
            !(ck.flags & kCheckpointMultilabel) == !params.multilabel &&
            !(ck.flags & kCheckpointAttention) == !attn_var &&
            // (versions 1-4 read as 1 head, no attention dropout; a weights-only load crosses
@@ -1944,14 +1974,16 @@ void GCN::load(const std::string &path, int flags) {
   PGCN_CHECK(ck.adam_steps < (1LL << 31), PGCN_E_INVALID, "load: step count");
   sync();
   size_t at = 0;
+  // (a BatchNorm file carries the scale / shift tensor where a LayerNorm file does)
+  const bool file_norm = (ck.flags & (kCheckpointLayerNorm | kCheckpointBatchNorm)) != 0;
   for (const auto &w : weights) {
     // weights only, a file without the norm tensor: gamma / beta keep their values (a file with
     // it into a plain engine: the tensor behind the layer weights is not read)
-    if (w == norm_var && !(ck.flags & kCheckpointLayerNorm)) continue;
+    if (w == norm_var && !file_norm) continue;
     if (w == attn_var && !(ck.flags & kCheckpointAttention)) continue;  // (the same for attn)
     if (w == link_var && !ck.link_hidden) continue;  // (... and the decoder tensor keeps its init)
     // (a file's norm tensor sits before its attention tensor: skipped by an engine without one)
-    if (w == attn_var && (ck.flags & kCheckpointLayerNorm) && !norm_var)
+    if (w == attn_var && file_norm && !norm_var)
       for (int h : params.hidden_dims) at += 2 * (size_t)h;
     w->dev_data.upload(ck.w.data() + at, (size_t)w->size);
     at += (size_t)w->size;

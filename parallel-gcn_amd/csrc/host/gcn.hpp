@@ -43,6 +43,9 @@ struct GCNParams {
   // every hidden layer gets a LayerNorm between its GraphSum and its ReLU (LayerNorm,
   // module.hpp); its scale / shift tensor is one more weight (no decay) behind the layers'
   bool layer_norm = false;
+  // ... or a BatchNorm there (BatchNorm, module.hpp), on the same scale / shift tensor; never
+  // both, and single GPU only
+  bool batch_norm = false;
   // multi-label classification: GCNData::label_bits targets, BCEWithLogitsLoss as the last
   // module (the output Matmul unfused), count = labelled rows x classes
   bool multilabel = false;
@@ -207,6 +210,7 @@ class GCN {
   // ... of which the last training forward ran inside a GraphSum's final write
   int fused_residuals() const;
   int norm_layers() const { return (int)norms_.size(); }
+  int batch_norm_layers() const { return (int)bnorms_.size(); }
   int attention_layers() const { return attn_var ? L : 0; }
   // the heads of its hidden layers, and the layers that drop attention weights in training
   int attention_heads() const { return attn_var ? params.attention_heads : 1; }
@@ -246,6 +250,7 @@ class GCN {
   void join_side();
   std::vector<const ResidualConnection *> residuals_;
   std::vector<const LayerNorm *> norms_;
+  std::vector<const BatchNorm *> bnorms_;  // batch_norm: in their place, on the same norm_var
   // layer_norm: per hidden layer gamma_l[d_l] then beta_l[d_l], one tensor (one optimizer entry:
   // the one-batch Adam paths take at most kAdamBatch tensors), the last of `weights` and of
   // `variables`; null without layer_norm

@@ -987,7 +987,11 @@ LayerNorm::LayerNorm(shared_ptr<Variable> in_, shared_ptr<Variable> norm_, long 
   ws.allocate(std::max<size_t>(layernorm_bwd_workspace(rows, in->cols) / sizeof(float), 1));
 }
 
-void LayerNorm::forward(bool training, const Stream &s) const {
+// the forward tail a normalisation's final write takes (LayerNorm, BatchNorm): the modules
+// behind it are told to skip this pass
+static GsEpilogue norm_tail(const Variable *in, bool training, ReLU *fwd_relu,
+                            const ResidualConnection *fwd_res, const Dropout *fwd_drop,
+                            const Stream &s) {
   GsEpilogue e;
   if (fwd_relu && in->ld == in->cols) {  // the tail's element order is the storage order
     e.mode = 1;
@@ -1008,6 +1012,11 @@ void LayerNorm::forward(bool training, const Stream &s) const {
     }
     fwd_relu->skip_forward = true;
   }
+  return e;
+}
+
+void LayerNorm::forward(bool training, const Stream &s) const {
+  const GsEpilogue e = norm_tail(in.get(), training, fwd_relu, fwd_res, fwd_drop, s);
   if (training) last_fused = e.mode != 0;
   const float *gamma = norm->dev_data.get() + offset;
   launch_layernorm_fwd(in->dev_data.get(), in->ld, in->dev_data.get(), in->ld, rows, in->cols,
@@ -1020,6 +1029,41 @@ void LayerNorm::backward(const Stream &s) const {
   float *g = in->dev_grad_z ? in->dev_grad_z.get() : in->dev_grad.get();
   float *dgamma = norm->dev_grad.get() + offset;
   launch_layernorm_bwd(g, in->ld, xhat.get(), in->ld, rstd.get(), norm->dev_data.get() + offset,
+                       rows, in->cols, g, in->ld, dgamma, dgamma + in->cols, ws.get(), s.get());
+}
+
+// ------------------------------------------------------------------------------------------
+// BatchNorm (k_batchnorm.hip)
+// ------------------------------------------------------------------------------------------
+BatchNorm::BatchNorm(shared_ptr<Variable> in_, shared_ptr<Variable> norm_, long long offset_,
+                     int rows_)
+    : in(std::move(in_)), norm(std::move(norm_)), offset(offset_), rows(rows_) {
+  PGCN_CHECK(in && norm && in->cols >= 1 && in->cols <= kBatchNormMaxWidth && rows >= 0 &&
+                 rows <= in->rows && offset >= 0 && offset + 2LL * in->cols <= norm->size,
+             PGCN_E_INVALID, "batch_norm: widths up to 1024");
+  xhat.allocate((size_t)std::max(in->rows, 1) * in->ld);
+  xhat.zero();
+  stats.allocate(2 * (size_t)round_up4(in->cols));
+  stats.zero();
+  const size_t bytes = std::max(batchnorm_fwd_workspace(rows, in->cols),
+                                batchnorm_bwd_workspace(rows, in->cols));
+  ws.allocate(std::max<size_t>(bytes / sizeof(float), 1));
+}
+
+void BatchNorm::forward(bool training, const Stream &s) const {
+  const GsEpilogue e = norm_tail(in.get(), training, fwd_relu, fwd_res, fwd_drop, s);
+  if (training) last_fused = e.mode != 0;
+  const float *gamma = norm->dev_data.get() + offset;
+  launch_batchnorm_fwd(in->dev_data.get(), in->ld, in->dev_data.get(), in->ld, rows, in->cols,
+                       gamma, gamma + in->cols, kEps, training ? xhat.get() : nullptr, in->ld,
+                       stats.get(), ws.get(), &e, s.get());
+}
+
+void BatchNorm::backward(const Stream &s) const {
+  if (!in->dev_grad || !norm->dev_grad) return;
+  float *g = in->dev_grad_z ? in->dev_grad_z.get() : in->dev_grad.get();
+  float *dgamma = norm->dev_grad.get() + offset;
+  launch_batchnorm_bwd(g, in->ld, xhat.get(), in->ld, stats.get(), norm->dev_data.get() + offset,
                        rows, in->cols, g, in->ld, dgamma, dgamma + in->cols, ws.get(), s.get());
 }
 

@@ -532,6 +532,31 @@ class LayerNorm : public Module {
   mutable bool last_fused = false;  // the last training forward ran that tail
 };
 
+// BatchNorm in LayerNorm's place (pgcn_params.batch_norm; single GPU): in = gamma * xhat + beta in
+// place, xhat normalised per COLUMN over the `rows` rows with the pass's own statistics, in
+// training and in eval alike (no running averages).  gamma / beta and their gradients sit where
+// LayerNorm's do.  xhat, the column statistics and the kernels' workspace are sized at build; a
+// training forward keeps xhat and stats for the backward, which transforms the gradient buffer
+// in place as LayerNorm's does.
+class BatchNorm : public Module {
+  shared_ptr<Variable> in, norm;
+  long long offset;
+  int rows;
+  DeviceBuffer<float> xhat, stats, ws;
+
+ public:
+  static constexpr float kEps = 1e-5f;
+  BatchNorm(shared_ptr<Variable> in_, shared_ptr<Variable> norm_, long long offset_, int rows_);
+  void forward(bool training, const Stream &s) const override;
+  void backward(const Stream &s) const override;
+  const Variable *variable() const { return in.get(); }
+  // the tail run in the apply launch's final write, as LayerNorm's (GCN::fuse_epilogues)
+  ReLU *fwd_relu = nullptr;
+  const ResidualConnection *fwd_res = nullptr;
+  const Dropout *fwd_drop = nullptr;
+  mutable bool last_fused = false;  // the last training forward ran that tail
+};
+
 // include/module.cuh:103-124: c = a * b
 class Matmul : public Module {
   shared_ptr<Variable> a, b, c;

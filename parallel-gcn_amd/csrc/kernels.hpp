@@ -353,6 +353,29 @@ size_t layernorm_bwd_workspace(int n, int d);
 void launch_layernorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
                           const float *rstd, const float *gamma, int n, int d, float *dx, int ld_dx,
                           float *dgamma, float *dbeta, void *workspace, hipStream_t s);
+// ---- BatchNorm over a node variable's rows (k_batchnorm.hip) --------------------------------
+// Per column c over the n rows: mean_c, the biased variance var_c from centred second moments
+// (per-tile two passes over a resident tile, the tiles merged pairwise -- never E[x^2] - mean^2),
+// rstd_c = 1 / sqrtf(var_c + eps); xhat = (x - mean_c) * rstd_c; y = gamma_c * xhat + beta_c.
+// Shapes and padding rules as launch_layernorm_fwd's.  Three launches: the tile statistics into
+// `workspace` (batchnorm_fwd_workspace(n, d) bytes: per tile of batchnorm_tile_rows(d) rows
+// {count, 0, 0, 0, mean[round_up4(d)], M2[round_up4(d)]}), the merge into stats [2][round_up4(d)]
+// = {mean, rstd}, the apply (xhat: also written where non-null; epi as LayerNorm's).  Every
+// summation order depends on (n, d) only; no float atomics.
+constexpr int kBatchNormMaxWidth = 1024;
+int batchnorm_tile_rows(int d);
+size_t batchnorm_fwd_workspace(int n, int d);
+void launch_batchnorm_fwd(const float *x, int ld_x, float *y, int ld_y, int n, int d,
+                          const float *gamma, const float *beta, float eps, float *xhat,
+                          int ld_xhat, float *stats, void *workspace, const GsEpilogue *epi,
+                          hipStream_t s);
+// dgamma[c] = sum over the rows of dy * xhat, dbeta[c] = sum of dy (per-workgroup partials in
+// `workspace`, rows in row order, then one reducing launch in block order); then dx = gamma_c *
+// rstd_c * (dy - dbeta_c / n - xhat * dgamma_c / n), one elementwise launch (dx == dy allowed)
+size_t batchnorm_bwd_workspace(int n, int d);
+void launch_batchnorm_bwd(const float *dy, int ld_dy, const float *xhat, int ld_xhat,
+                          const float *stats, const float *gamma, int n, int d, float *dx,
+                          int ld_dx, float *dgamma, float *dbeta, void *workspace, hipStream_t s);
 // ---- Graph attention over the CSR slots of a square pattern (k_gat.hip) ---------------------
 // Additive (GAT), per head: u_i = P_i . a_dst, v_j = P_j . a_src, e_s = leaky(u_i + v_j) per
 // slot s = (i, j), alpha = softmax of e over the row's slots, Z_i = sum alpha_s P_j.  1 <= d <=

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [batch_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -8,7 +8,8 @@
 // num_blocks_factor/num_threads are accepted and ignored) -- our own tiny parser, GetPot is
 // not vendored; residual=1, in the file or on the command line, adds the reference's
 // ResidualConnection to the middle layers of equal width, pgcn_params.residual; layer_norm=1
-// likewise puts a LayerNorm between every hidden layer's GraphSum and ReLU, pgcn_params.layer_norm).  no_feature=1 is the PART2 NO_FEATURE build (feature values 1.0).
+// likewise puts a LayerNorm between every hidden layer's GraphSum and ReLU, pgcn_params.layer_norm;
+// batch_norm=1 a BatchNorm instead, pgcn_params.batch_norm).  no_feature=1 is the PART2 NO_FEATURE build (feature values 1.0).
 // New with the engine: load= resumes from a checkpoint before the run (the epoch lines go on
 // from its epoch count, up to `epochs`), save= writes one after it, predict= writes one line
 // `node class confidence` per node after it; epochs= overrides the parameter file's.
@@ -128,6 +129,7 @@ static bool load_params(const char *path, pgcn_params *p, int *embed) {
     else if (k == "seed") p->seed = (unsigned)std::strtoul(v.c_str(), nullptr, 10);
     else if (k == "residual") p->residual = std::atoi(v.c_str());
     else if (k == "layer_norm") p->layer_norm = std::atoi(v.c_str());
+    else if (k == "batch_norm") p->batch_norm = std::atoi(v.c_str());
     else if (k == "attention") p->attention = std::atoi(v.c_str());
     else if (k == "multilabel") p->multilabel = std::atoi(v.c_str());
     else if (k == "heads") p->attention_heads = std::atoi(v.c_str());
@@ -154,7 +156,7 @@ int main(int argc, char **argv) {
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
   std::string load, save, predict, rank, recommend;
   int topk = 10;
-  int epochs = -1, residual = -1, layer_norm = -1, multilabel = -1, attention = -1, heads = -1;
+  int epochs = -1, residual = -1, layer_norm = -1, batch_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
   int root_weight = -1;
   std::string aggregator, readout, link;
@@ -170,6 +172,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "epochs=", 7)) epochs = std::atoi(argv[i] + 7);
     if (!std::strncmp(argv[i], "residual=", 9)) residual = std::atoi(argv[i] + 9);
     if (!std::strncmp(argv[i], "layer_norm=", 11)) layer_norm = std::atoi(argv[i] + 11);
+    if (!std::strncmp(argv[i], "batch_norm=", 11)) batch_norm = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "multilabel=", 11)) multilabel = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "attention=", 10)) attention = std::atoi(argv[i] + 10);
     if (!std::strncmp(argv[i], "heads=", 6)) heads = std::atoi(argv[i] + 6);
@@ -195,6 +198,7 @@ int main(int argc, char **argv) {
   if (epochs >= 0) p.epochs = epochs;
   if (residual >= 0) p.residual = residual;
   if (layer_norm >= 0) p.layer_norm = layer_norm;
+  if (batch_norm >= 0) p.batch_norm = batch_norm;
   if (multilabel >= 0) p.multilabel = multilabel;
   if (attention >= 0) p.attention = attention;
   if (heads >= 0) p.attention_heads = heads;
