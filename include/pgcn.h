@@ -340,6 +340,71 @@ int pgcn_agg_max_fwd(const pgcn_graph *g, const float *in, int ld_in, int d,
 int pgcn_agg_max_bwd(const pgcn_graph *g, const float *G, int ld_g, const int *arg, int ld_arg,
                      int d, float *din, int ld_din, void *stream);
 
+/* --- GraphSAGE neighbour sampling: fanout draws and sampled aggregation (k_nbr.hip; new
+ *     kernels) --------------------------------------------------------------------------------
+ * pgcn_nbr_sample is a sampled pattern of fixed row stride K = fanout over the square pattern
+ * of `g` (1 <= K <= 64, nnz and n * K within an int; `g` must outlive the handle, its values are
+ * not used).  Every buffer is allocated at creation for the worst case; before the first draw
+ * the sample is empty (every cnt 0).
+ * pgcn_nbr_sample_draw: for row i with the L slots [b, b + L) of `indices`:
+ *     L <= K: the row keeps all L slots in order, cnt_i = L;
+ *     L >  K: cnt_i = K distinct slots, a uniform K-subset by Floyd's algorithm -- exact, no
+ *             rejection loop.  With mix and the 64-bit wrapping arithmetic of pgcn_neg_sample
+ *             and GAMMA = 0x9E3779B97F4A7C15:
+ *               k     = mix(seed + GAMMA * (round + 1))
+ *               key_i = mix(k + GAMMA * (i + 1))
+ *               for t = 0 .. K - 1:  m = L - K + t
+ *                                    r = ((mix(key_i + GAMMA * (t + 1)) >> 32) * (m + 1)) >> 32
+ *                                    pick_t = r unless r is among pick_0 .. pick_{t-1}, else m
+ *             and the row keeps the slots b + pick_t.
+ *   The kept slots are stored ASCENDING at positions [i K, i K + cnt_i) of slot (the global
+ *   slot) and nbr (indices[slot]); the K - cnt_i positions behind them hold -1.  Stateless: the
+ *   same (seed, round, i, row) gives the same picks on any launch.  round >= 0.
+ *   The same call rebuilds, behind the draw, the TRANSPOSED index of the sampled pattern: node j's
+ *   list t_ptr[j] .. t_ptr[j + 1] holds the entries {t_row: the row i that kept a slot into j,
+ *   t_slot: that slot} in ascending (i, position) order -- a stable LSD radix sort of the n K
+ *   entries by neighbour (pgcn_links_rebuild's sort kernels; 8-bit digits, ceil(bits(n) / 8)
+ *   passes) and the segment records of the lists longer than pgcn_link_segment_slots() entries,
+ *   all on the device.  t_ptr[n] is the number of kept entries; t_row / t_slot are -1 behind it.
+ *   Asynchronous on `stream`, allocates nothing, never syncs, may be captured.
+ * pgcn_nbr_sample_copy: a debug read-back (syncs the device) to host memory: cnt [n], slot and
+ *   nbr [n K], t_ptr [n + 1], t_row and t_slot [n K]; any of them may be NULL.
+ * pgcn_nbr_agg_fwd, mode 1 (mean): out_i = add_i + (1.0f / (float)cnt_i) * S_i, S_i the fp32 sum
+ *     of in_nbr over row i's kept entries in stored order, sequentially from +0 (add == NULL:
+ *     without the add); arg is not touched.
+ *   mode 2 (max): out_i[c] = add_i[c] + the exact maximum over the kept entries of in_nbr[c],
+ *     arg_i[c] (may be NULL) the GLOBAL slot that won, under pgcn_agg_max_fwd's tie rule: the
+ *     lowest slot of equal values.
+ *   A row without a kept entry: out_i = add_i (or 0), arg_i = -1.
+ * pgcn_nbr_agg_bwd, with G = dLoss/dout: din_j = sum over node j's transposed list of
+ *     G_i * (1.0f / (float)cnt_i) (mean; arg unused, may be NULL), or of the G_i[c] whose
+ *     arg_i[c] equals the entry's slot (max).  A list of at most T = pgcn_link_segment_slots()
+ *     entries is summed by one wave: with GL = 1, 2, 4, 8, 16, 32 for d <= 4, 8, 16, 32, 64, 128,
+ *     group q of the 64 / GL groups adds entries q, q + 64 / GL, ... in list order and the groups
+ *     meet in xor butterflies over the lane offsets GL .. 32.  A longer list is cut into T-entry
+ *     segments, each summed that way, and the partials are added in segment order.  A node nobody
+ *     sampled gets a zero row.  The gradient of `add` is G itself.
+ * Widths, strides, alignment and padding are pgcn_agg_max_fwd's: 1 <= d <= 128, every ld a
+ * multiple of 4 and >= d; the float4s / int4s covering [0, round_up4(d)) of out, arg and din are
+ * written -- 0 (arg: -1) from column d on -- and columns beyond them are left alone; padding
+ * columns of the inputs never reach a result.  Anything else -- a fanout outside 1..64, a mode
+ * other than 1 or 2, a null handle -- is PGCN_E_INVALID before anything touches the device.  The
+ * calls are asynchronous and allocate nothing; no float atomics, every order depends on the
+ * sample and d only, so two calls give the same bits.  The backward's segment partials live in
+ * the handle: two backward calls on one sample must not overlap. */
+typedef struct pgcn_nbr_sample pgcn_nbr_sample;
+int pgcn_nbr_sample_create(const pgcn_graph *g, int fanout, pgcn_nbr_sample **out);
+int pgcn_nbr_sample_destroy(pgcn_nbr_sample *s);
+int pgcn_nbr_sample_draw(pgcn_nbr_sample *s, unsigned long long seed, long long round,
+                         void *stream);
+int pgcn_nbr_sample_copy(const pgcn_nbr_sample *s, int *cnt, int *slot, int *nbr, int *t_ptr,
+                         int *t_row, int *t_slot);
+int pgcn_nbr_agg_fwd(const pgcn_nbr_sample *s, int mode, const float *in, int ld_in, int d,
+                     const float *add /* [n][ld_add] or NULL */, int ld_add, float *out,
+                     int ld_out, int *arg /* [n][ld_arg] or NULL */, int ld_arg, void *stream);
+int pgcn_nbr_agg_bwd(const pgcn_nbr_sample *s, int mode, const float *G, int ld_g, const int *arg,
+                     int ld_arg, int d, float *din, int ld_din, void *stream);
+
 /* --- graph-level readout over contiguous row ranges (k_readout.hip; new: the reference has
  *     no graph-level model) -------------------------------------------------------------------
  * A batch of G graphs is one node variable whose rows [graph_ptr[g], graph_ptr[g + 1]) belong to
@@ -785,6 +850,23 @@ typedef struct {
    * PGCN_E_INVALID (the column statistics would need an all-reduce across the ranks, which is
    * not built).  0: the engine as it was, bit for bit. */
   int batch_norm;
+  /* GraphSAGE neighbour sampling (here, behind batch_norm: no other member moves).  0: off, the
+   * engine as it was, bit for bit, checkpoint bytes included.  1..64 with aggregator != 0:
+   * TRAINING aggregates over at most `fanout` sampled slots of every row.  Before each
+   * train_epoch, on the engine's stream, layer l (0 .. n_layers - 1) draws its own sample:
+   * pgcn_nbr_sample_draw with seed = pgcn_params.seed and round = epochs run * n_layers + l
+   * ("epochs": a train_epoch + eval(2) pair is one), so layers and epochs draw independently.
+   * The training forward and backward of every SAGE layer run pgcn_nbr_agg_fwd / _bwd (mean:
+   * Z_i = R_i + (1 / cnt_i) sum over the kept slots; max: over the kept slots); every evaluation
+   * forward, pgcn_gcn_predict and the link entries run the full neighbourhood exactly as with
+   * fanout 0.  It composes with whatever aggregator composes with.  A fanout engine runs its
+   * epochs eagerly (pgcn_gcn_epoch_async captures no epoch graph: the round changes every
+   * epoch).  fanout is a training setting like epochs: checkpoints carry no trace of it (same
+   * version, same bytes), and because the draws are a function of (seed, epochs run, layer, row)
+   * a resumed run with the same fanout redraws what the straight run drew.  Single GPU only, as
+   * aggregator.  Anything else, fanout != 0 without an aggregator included, is
+   * PGCN_E_INVALID. */
+  int fanout;
   /* The link decoder's hidden width (here, behind hidden_dims: the members around link_decoder
    * keep their offsets).  0: the dot product above (the engine as it was, bit for
    * bit).  1..128 with link_decoder == 1: the Hadamard-MLP decoder of pgcn_link_mlp_fwd with that

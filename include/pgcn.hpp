@@ -368,6 +368,9 @@ struct GCNParams {
   bool layer_norm{false};
   // ... or a BatchNorm there, never both (pgcn_params.batch_norm, pgcn.h)
   bool batch_norm{false};
+  // GraphSAGE neighbour sampling: training aggregates over at most `fanout` sampled slots per
+  // row, redrawn every epoch; 0 = off (pgcn_params.fanout, pgcn.h)
+  int fanout{0};
 };
 
 struct GCNData {

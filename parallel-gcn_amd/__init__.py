@@ -42,6 +42,7 @@ class PgcnParams(ctypes.Structure):
     _fields_ = [("num_nodes", c_int), ("input_dim", c_int), ("output_dim", c_int),
                 ("n_layers", c_int), ("link_decoder", c_int),
                 ("hidden_dims", c_int * MAX_LAYERS), ("batch_norm", c_int),
+                ("fanout", c_int),
                 ("link_hidden", c_int), ("neg_ratio", c_int),
                 ("dropouts", c_float * MAX_LAYERS), ("aggregator", c_int),
                 ("root_weight", c_int), ("epochs", c_int), ("readout", c_int),
@@ -166,6 +167,15 @@ _sig("pgcn_readout_bwd", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c
      c_int, c_int, c_void_p, c_int, c_void_p)
 _sig("pgcn_links_create", c_int, c_int, c_ll, c_void_p, c_void_p, c_void_p, P(c_void_p))
 _sig("pgcn_links_destroy", c_int, c_void_p)
+_sig("pgcn_nbr_sample_create", c_int, c_void_p, c_int, P(c_void_p))
+_sig("pgcn_nbr_sample_destroy", c_int, c_void_p)
+_sig("pgcn_nbr_sample_draw", c_int, c_void_p, ctypes.c_ulonglong, c_ll, c_void_p)
+_sig("pgcn_nbr_sample_copy", c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+     c_void_p)
+_sig("pgcn_nbr_agg_fwd", c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+     c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_nbr_agg_bwd", c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+     c_int, c_void_p)
 _sig("pgcn_link_segment_slots", c_int)
 _sig("pgcn_links_slots", c_ll, c_void_p)
 _sig("pgcn_link_score_fwd", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p)
@@ -372,7 +382,8 @@ KERNEL_PATHS = ("xs_nn_ring", "xs_tn_ring", "xs_nn", "xs_tn", "gs_ring", "gs_gat
                 "spmm_csr", "spmm_csr_dual", "spmm_csc_256", "spmm_csc_1024", "spmm_tree_256",
                 "spmm_tree_1024", "launches", "link_fwd", "link_bwd", "rank_sweep", "rank_filter",
                 "topk_sweep", "topk_merge", "link_mlp_fwd", "link_mlp_bwd", "rank_mlp_sweep",
-                "rank_mlp_filter", "topk_mlp_sweep", "topk_mlp_merge")
+                "rank_mlp_filter", "topk_mlp_sweep", "topk_mlp_merge", "nbr_draw", "nbr_fwd",
+                "nbr_bwd")
 
 
 def path_counts(reset=False, thread=False):
@@ -706,6 +717,47 @@ class NegSampler:
     __del__ = close
 
 
+class NbrSample:
+    """A fanout neighbour sample over the square pattern of a pgcn_graph handle, drawn and
+    indexed on the device (pgcn_nbr_sample); the graph handle must outlive it."""
+
+    def __init__(self, graph, n_nodes, fanout):
+        h = c_void_p()
+        check(lib.pgcn_nbr_sample_create(graph, fanout, ctypes.byref(h)), "nbr_sample_create")
+        self._h, self.n_nodes, self.fanout = h, n_nodes, fanout
+
+    def draw(self, seed, round, stream=None):
+        """The draw of (seed, round) and the transposed index behind it; asynchronous."""
+        check(lib.pgcn_nbr_sample_draw(self._h, seed, round, stream), "nbr_sample_draw")
+
+    def copy(self):
+        """Host copies (syncs): cnt [n], slot / nbr [n][K], t_ptr [n + 1], t_row / t_slot [n K]."""
+        n, K = self.n_nodes, self.fanout
+        cnt, t_ptr = np.zeros(n, np.int32), np.zeros(n + 1, np.int32)
+        slot, nbr, t_row, t_slot = (np.zeros(n * K, np.int32) for _ in range(4))
+        check(lib.pgcn_nbr_sample_copy(self._h, _ptr(cnt), _ptr(slot), _ptr(nbr), _ptr(t_ptr),
+                                       _ptr(t_row), _ptr(t_slot)), "nbr_sample_copy")
+        return cnt, slot.reshape(n, K), nbr.reshape(n, K), t_ptr, t_row, t_slot
+
+    def agg_fwd(self, mode, dev_in, ld_in, d, dev_add, ld_add, dev_out, ld_out, dev_arg=None,
+                ld_arg=0, stream=None):
+        """mode 1 mean, 2 max, over the sampled rows (pgcn_nbr_agg_fwd); device addresses."""
+        return lib.pgcn_nbr_agg_fwd(self._h, mode, _dptr(dev_in), ld_in, d, _dptr(dev_add), ld_add,
+                                    _dptr(dev_out), ld_out, _dptr(dev_arg), ld_arg, stream)
+
+    def agg_bwd(self, mode, dev_g, ld_g, dev_arg, ld_arg, d, dev_din, ld_din, stream=None):
+        """The backward over the transposed sampled index (pgcn_nbr_agg_bwd)."""
+        return lib.pgcn_nbr_agg_bwd(self._h, mode, _dptr(dev_g), ld_g, _dptr(dev_arg), ld_arg, d,
+                                    _dptr(dev_din), ld_din, stream)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and lib is not None:
+            lib.pgcn_nbr_sample_destroy(self._h)
+            self._h = c_void_p()
+
+    __del__ = close
+
+
 def links_incidence(n_nodes, src, dst, select=None):
     """Host-only: (ptr [n_nodes + 1], pair, other) -- the incidence index pgcn_links_create
     builds (pgcn_debug_links_incidence)."""
@@ -995,8 +1047,11 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
                 reassociate_last=True, seed=0, residual=False, layer_norm=False,
                 multilabel=False, attention=False, attention_heads=1, attention_dropout=0.0,
                 aggregator=None, root_weight=False, readout=None, link_decoder=None,
-                link_hidden=0, neg_ratio=0, batch_norm=False):
-    """batch_norm: a BatchNorm between every hidden layer's aggregation and its ReLU, over all
+                link_hidden=0, neg_ratio=0, batch_norm=False, fanout=0):
+    """fanout: 0, or 1..64 with an aggregator: training aggregates over at most that many
+    neighbours per node, sampled anew on the device before every epoch; evaluation and prediction
+    use the whole neighbourhood.  A training setting like epochs: checkpoints do not carry it.
+    batch_norm: a BatchNorm between every hidden layer's aggregation and its ReLU, over all
     the nodes with the pass's own statistics (no running averages); not with layer_norm, single
     GPU only -- the engine refuses both.
     aggregator: None (GCN's Â), "mean" or "max" (GraphSAGE layers); root_weight: the layer's
@@ -1042,6 +1097,7 @@ def make_params(ds, hidden_dims=(16,), dropouts=(0.5, 0.5), epochs=100, early_st
     p.residual = 1 if residual else 0
     p.layer_norm = 1 if layer_norm else 0
     p.batch_norm = 1 if batch_norm else 0
+    p.fanout = int(fanout)
     p.reassociate_last = 1 if reassociate_last else 0
     p.seed = seed
     p.num_nodes, p.input_dim, p.output_dim = ds.num_nodes, ds.input_dim, ds.output_dim
@@ -1578,6 +1634,8 @@ EXPORTED = [
     "pgcn_links_create_dynamic", "pgcn_links_set_dst_range", "pgcn_links_rebuild",
     "pgcn_links_incidence_copy", "pgcn_links_sort_tile", "pgcn_debug_links_rebuild_times",
     "pgcn_neg_sampler_create", "pgcn_neg_sampler_destroy", "pgcn_neg_sample",
+    "pgcn_nbr_sample_create", "pgcn_nbr_sample_destroy", "pgcn_nbr_sample_draw",
+    "pgcn_nbr_sample_copy", "pgcn_nbr_agg_fwd", "pgcn_nbr_agg_bwd",
     "pgcn_links_create", "pgcn_links_destroy", "pgcn_link_segment_slots", "pgcn_links_slots",
     "pgcn_link_score_fwd", "pgcn_link_score_bwd", "pgcn_debug_links_incidence",
     "pgcn_link_mlp_tile", "pgcn_link_mlp_workspace", "pgcn_link_mlp_fwd", "pgcn_link_mlp_bwd",

@@ -33,7 +33,8 @@ const char *const kPathNames[KP_COUNT] = {"xs_nn_ring", "xs_tn_ring", "xs_nn",  
                                           "rank_filter", "topk_sweep", "topk_merge",
                                           "link_mlp_fwd", "link_mlp_bwd",
                                           "rank_mlp_sweep", "rank_mlp_filter",
-                                          "topk_mlp_sweep", "topk_mlp_merge"};
+                                          "topk_mlp_sweep", "topk_mlp_merge",
+                                          "nbr_draw",   "nbr_fwd",    "nbr_bwd"};
 }  // namespace
 void note_path(KernelPath p) {
   g_path_hits[p].fetch_add(1, std::memory_order_relaxed);
@@ -49,6 +50,9 @@ struct pgcn_links {
 };
 struct pgcn_neg_sampler {
   std::unique_ptr<NegSamplerDev> s;
+};
+struct pgcn_nbr_sample {
+  std::unique_ptr<NbrSampleDev> s;
 };
 struct pgcn_rank_queries {
   std::unique_ptr<RankQueriesDev> q;
@@ -81,12 +85,19 @@ void refuse_single_gpu_only(const pgcn_params *p) {
   // (the mean is linear and could be partitioned; the max needs a max / arg exchange)
   PGCN_CHECK(!p->aggregator && !p->root_weight, PGCN_E_INVALID,
              "aggregator: single GPU only (edge-cut SAGE layers are not supported)");
+  PGCN_CHECK(!p->fanout, PGCN_E_INVALID, "fanout: single GPU only, as the SAGE layers it samples");
   // (a graph's rows may lie on several ranks: its readout would need an exchange of its own)
   PGCN_CHECK(!p->readout, PGCN_E_INVALID,
              "readout: single GPU only (edge-cut graph classification is not supported)");
   // (a pair's endpoints may lie on two ranks: its score would need an exchange of its own)
   PGCN_CHECK(!p->link_decoder, PGCN_E_INVALID,
              "link_decoder: single GPU only (edge-cut link prediction is not supported)");
+}
+
+// neighbour sampling needs SAGE layers (checked before the device is looked for)
+void check_fanout(const pgcn_params *p) {
+  PGCN_CHECK(p->fanout >= 0 && p->fanout <= kNbrMaxFanout && (p->fanout == 0 || p->aggregator != 0),
+             PGCN_E_INVALID, "fanout: 0, or 1..64 with aggregator != 0");
 }
 
 GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
@@ -104,6 +115,8 @@ GCNParams to_params(const pgcn_params *p, const pgcn_data *d) {
   q.residual = p->residual != 0;
   q.layer_norm = p->layer_norm != 0;
   q.batch_norm = p->batch_norm != 0;
+  check_fanout(p);
+  q.fanout = p->fanout;
   q.multilabel = p->multilabel != 0;
   q.attention = p->attention != 0;
   q.attention_heads = p->attention_heads == 0 ? 1 : p->attention_heads;
@@ -738,6 +751,86 @@ int pgcn_agg_max_bwd(const pgcn_graph *g, const float *G, int ld_g, const int *a
     check_device();
     const GatPattern &p = g->g->gat_pattern();
     launch_agg_max_bwd(p, g->g->sage_ws(), G, ld_g, arg, ld_arg, d, din, ld_din,
+                       as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_nbr_sample_create(const pgcn_graph *g, int fanout, pgcn_nbr_sample **out) {
+  return guarded([&] {
+    PGCN_CHECK(fanout >= 1 && fanout <= kNbrMaxFanout, PGCN_E_INVALID,
+               "nbr_sample_create: 1 <= fanout <= 64");
+    PGCN_CHECK(g && g->g && out, PGCN_E_INVALID, "nbr_sample_create: null argument");
+    PGCN_CHECK(g->g->rows() == g->g->cols() && g->g->nnz() <= INT_MAX &&
+                   (long long)g->g->rows() * fanout <= INT_MAX,
+               PGCN_E_INVALID,
+               "nbr_sample_create: square pattern, nnz and n * fanout within an int");
+    check_device();
+    auto h = std::make_unique<pgcn_nbr_sample>();
+    h->s = std::make_unique<NbrSampleDev>(g->g.get(), fanout);
+    *out = h.release();
+  });
+}
+
+int pgcn_nbr_sample_destroy(pgcn_nbr_sample *s) {
+  delete s;
+  return PGCN_OK;
+}
+
+int pgcn_nbr_sample_draw(pgcn_nbr_sample *s, unsigned long long seed, long long round,
+                         void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(s && s->s && round >= 0, PGCN_E_INVALID, "nbr_sample_draw: a handle, round >= 0");
+    check_device();
+    s->s->draw(seed, (unsigned long long)round, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_nbr_sample_copy(const pgcn_nbr_sample *s, int *cnt, int *slot, int *nbr, int *t_ptr,
+                         int *t_row, int *t_slot) {
+  return guarded([&] {
+    PGCN_CHECK(s && s->s, PGCN_E_INVALID, "nbr_sample_copy: null handle");
+    s->s->copy(cnt, slot, nbr, t_ptr, t_row, t_slot);
+  });
+}
+
+namespace {
+void check_nbr_dims(int mode, int d, std::initializer_list<int> lds) {
+  PGCN_CHECK(mode == kNbrMean || mode == kNbrMax, PGCN_E_INVALID,
+             "nbr_agg: mode 1 (mean) or 2 (max)");
+  PGCN_CHECK(d >= 1 && d <= kSageMaxWidth, PGCN_E_INVALID, "nbr_agg: 1 <= d <= 128");
+  for (int ld : lds) PGCN_CHECK(ln_ld_ok(ld, d), PGCN_E_INVALID, "nbr_agg: ld % 4 == 0, ld >= d");
+}
+}  // namespace
+
+int pgcn_nbr_agg_fwd(const pgcn_nbr_sample *s, int mode, const float *in, int ld_in, int d,
+                     const float *add, int ld_add, float *out, int ld_out, int *arg, int ld_arg,
+                     void *stream) {
+  return guarded([&] {
+    check_nbr_dims(mode, d, {ld_in, ld_out});
+    if (add) check_nbr_dims(mode, d, {ld_add});
+    if (arg) check_nbr_dims(mode, d, {ld_arg});
+    PGCN_CHECK(s && s->s && in && out && aligned16(in) && aligned16(out) && aligned16(add) &&
+                   aligned16(arg),
+               PGCN_E_INVALID, "nbr_agg_fwd: null or misaligned argument");
+    check_device();
+    launch_nbr_agg_fwd(s->s->sample(), mode, in, ld_in, d, add, ld_add, out, ld_out, arg, ld_arg,
+                       as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_nbr_agg_bwd(const pgcn_nbr_sample *s, int mode, const float *G, int ld_g, const int *arg,
+                     int ld_arg, int d, float *din, int ld_din, void *stream) {
+  return guarded([&] {
+    check_nbr_dims(mode, d, {ld_g, ld_din});
+    if (mode == kNbrMax) check_nbr_dims(mode, d, {ld_arg});
+    PGCN_CHECK(s && s->s && G && din && (mode != kNbrMax || arg) && aligned16(G) &&
+                   aligned16(din) && aligned16(arg),
+               PGCN_E_INVALID, "nbr_agg_bwd: null or misaligned argument");
+    check_device();
+    launch_nbr_agg_bwd(s->s->sample(), mode, G, ld_g, arg, ld_arg, d, din, ld_din,
                        as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
@@ -1389,12 +1482,14 @@ void pgcn_params_default(pgcn_params *p) {
   p->seed = 0;
   p->layer_norm = 0;
   p->batch_norm = 0;
+  p->fanout = 0;
   p->residual = 0;
 }
 
 int pgcn_gcn_create(const pgcn_params *p, const pgcn_data *d, int device, pgcn_gcn **out) {
   return guarded([&] {
     PGCN_CHECK(p && d && out, PGCN_E_INVALID, "gcn_create args");
+    check_fanout(p);
     check_device();
     GCNData data = to_data(d, p);
     auto h = std::make_unique<pgcn_gcn>();

@@ -766,6 +766,7 @@ GCN::GCN(GCNParams const *params_, AdamParams const *adam_params_, GCNData const
   q.residual = params_->residual;
   q.layer_norm = params_->layer_norm;
   q.batch_norm = params_->batch_norm;
+  q.fanout = params_->fanout;
   pgcn::AdamParams a;
   a.learning_rate = adam_params_->learning_rate;
   a.beta1 = adam_params_->beta1;

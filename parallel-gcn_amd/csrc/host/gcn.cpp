@@ -319,6 +319,9 @@ GCN::GCN(const GCNParams &params_, const AdamParams &adam, const GCNData &data, 
              "aggregator must be 0 (GCN), 1 (mean) or 2 (max)");
   PGCN_CHECK(params.aggregator != 0 || !params.root_weight, PGCN_E_INVALID,
              "root_weight needs aggregator != 0");
+  PGCN_CHECK(params.fanout >= 0 && params.fanout <= kNbrMaxFanout &&
+                 (params.fanout == 0 || params.aggregator != 0),
+             PGCN_E_INVALID, "fanout: 0, or 1..64 with aggregator != 0");
   if (params.aggregator != 0) {
     PGCN_CHECK(!params.attention, PGCN_E_INVALID, "aggregator != 0 cannot be combined with attention");
     PGCN_CHECK(!dist, PGCN_E_INVALID,
@@ -1110,9 +1113,11 @@ void GCN::insert_first_layer() {
 void GCN::insert_aggregation(const shared_ptr<Variable> &var1, const shared_ptr<Variable> &var2,
                              int dim, int layer, bool last) {
   if (params.aggregator != 0) {
-    modules.push_back(std::make_unique<SageAggregate>(var1, var2, graph.get(), mean_fwd_graph.get(),
-                                                      mean_bwd_graph.get(), dim, params.aggregator,
-                                                      params.root_weight));
+    auto sage = std::make_unique<SageAggregate>(var1, var2, graph.get(), mean_fwd_graph.get(),
+                                                mean_bwd_graph.get(), dim, params.aggregator,
+                                                params.root_weight, params.fanout);
+    sages_.push_back(sage.get());
+    modules.push_back(std::move(sage));
     return;
   }
   if (!attn_var) {
@@ -1546,9 +1551,18 @@ void GCN::resample_negatives() {
   links_->rebuild(stream.get());
 }
 
+// fanout: this epoch's neighbour samples, one per SAGE layer, with their transposed indexes
+void GCN::resample_neighbours() {
+  if (!params.fanout) return;
+  for (size_t l = 0; l < sages_.size(); l++)
+    sages_[l]->draw(params.seed, (unsigned long long)epoch_count * (unsigned long long)L + l,
+                    stream);
+}
+
 void GCN::enqueue_epoch(bool graph) {
   const int slot4 = graph ? 0 : (int)(epoch_count % ring_cap) * 4;
   resample_negatives();
+  resample_neighbours();
   set_split(1);
   TnDeferList defer;
   FoldScope fold(*this, &defer);
@@ -1576,7 +1590,7 @@ void GCN::enqueue_epoch(bool graph) {
 // eval and the next training forward).
 bool GCN::graph_eligible() const {
   if (!knobs_.epoch_graph || !warm || comm || ctx.profile) return false;
-  if (neg_pairs_) return false;  // (the draw's round changes every epoch)
+  if (neg_pairs_ || params.fanout) return false;  // (the draws' round changes every epoch)
   if (ctx.train_ahead && feats.dense && feats.maskT && !feats.ax) return false;
   // (the same host swaps)
   if (ctx.train_ahead && !feats.dense && knobs_.sparse_dual) return false;
@@ -1645,6 +1659,7 @@ void GCN::epoch_async() {
 std::pair<float, float> GCN::train_epoch() {
   const long long slot = epoch_count % ring_cap;
   resample_negatives();
+  resample_neighbours();
   set_split(1);
   TnDeferList defer;
   FoldScope fold(*this, &defer);

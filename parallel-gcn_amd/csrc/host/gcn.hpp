@@ -46,6 +46,10 @@ struct GCNParams {
   // ... or a BatchNorm there (BatchNorm, module.hpp), on the same scale / shift tensor; never
   // both, and single GPU only
   bool batch_norm = false;
+  // neighbour sampling (aggregator != 0 only): every SageAggregate owns an NbrSampleDev of this
+  // fanout, drawn before each training epoch with round = epoch_count * L + layer; a training
+  // forward / backward runs k_nbr.hip on it, every evaluation the full neighbourhood.  0: off
+  int fanout = 0;
   // multi-label classification: GCNData::label_bits targets, BCEWithLogitsLoss as the last
   // module (the output Matmul unfused), count = labelled rows x classes
   bool multilabel = false;
@@ -291,6 +295,10 @@ class GCN {
   std::unique_ptr<NegSamplerDev> neg_sampler_;
   DeviceBuffer<int> neg_src_, neg_dst_;
   void resample_negatives();
+  // fanout: the SAGE layers in layer order; resample_neighbours draws layer l's sample of round
+  // epoch_count * L + l on the engine's stream before every training forward
+  std::vector<const SageAggregate *> sages_;
+  void resample_neighbours();
   shared_ptr<Variable> link_embed, link_scores;
   shared_ptr<Variable> link_var;  // link_hidden > 0: P [output_dim + 3][round_up4(link_hidden)]
   DeviceBuffer<float> link_mlp_ws;  // ... and the decoder backward's workspace

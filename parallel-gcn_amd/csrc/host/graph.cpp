@@ -956,6 +956,71 @@ NegSamplerDev::NegSamplerDev(int n, const long long *ptr, const int *idx) : n_(n
   idx_.upload(idx, (size_t)ptr[n]);
 }
 
+NbrSampleDev::NbrSampleDev(DevGraph *graph, int fanout) {
+  PGCN_CHECK(fanout >= 1 && fanout <= kNbrMaxFanout, PGCN_E_INVALID,
+             "nbr_sample: 1 <= fanout <= 64");
+  PGCN_CHECK(graph && graph->rows() == graph->cols() && graph->nnz() <= INT_MAX &&
+                 (long long)graph->rows() * fanout <= INT_MAX,
+             PGCN_E_INVALID, "nbr_sample: a square pattern, nnz and n * fanout within an int");
+  const GatPattern &g = graph->gat_pattern();
+  const int n = g.n;
+  const size_t total = (size_t)n * fanout, cap = std::max<size_t>(total, 1);
+  const int long_cap = (int)(total / (kGatSeg + 1));
+  const int seg_cap = long_cap ? (int)ceil_div((long long)total, kGatSeg) + long_cap + 1 : 0;
+  cnt_.allocate(std::max(n, 1));
+  cnt_.zero();
+  t_ptr_.allocate((size_t)n + 1);
+  t_ptr_.zero();
+  for (DeviceBuffer<int> *b : {&slot_, &nbr_, &t_row_, &t_slot_}) {
+    b->allocate(cap);
+    PGCN_HIP(hipMemset(b->get(), 0xFF, cap * sizeof(int)));
+  }
+  sort_nodes_.allocate(2 * cap);
+  sort_keys_.allocate(2 * cap);
+  hist_.allocate(256 * (size_t)ceil_div((long long)cap, kSortTile) + 256);
+  marks_.allocate(2 * (size_t)ceil_div(std::max(n, 1), 256) + 2);
+  segs_.allocate(std::max(seg_cap, 1));
+  longs_.allocate(std::max(long_cap, 1));
+  segs_.zero();  // (before the first draw: empty ranges, and long records of node 0's empty list)
+  longs_.zero();
+  ws_.allocate(std::max<size_t>((size_t)seg_cap * kSageWsStride, 4));
+  ws_.zero();
+  PGCN_HIP(hipDeviceSynchronize());
+  p_.n = n;
+  p_.fanout = fanout;
+  p_.indptr = g.indptr;
+  p_.indices = g.indices;
+  p_.cnt = cnt_.get();
+  p_.slot = slot_.get();
+  p_.nbr = nbr_.get();
+  p_.t_ptr = t_ptr_.get();
+  p_.t_row = t_row_.get();
+  p_.t_slot = t_slot_.get();
+  p_.segs = segs_.get();
+  p_.longs = longs_.get();
+  p_.seg_cap = seg_cap;
+  p_.long_cap = long_cap;
+  p_.ws = ws_.get();
+  p_.nodes[0] = sort_nodes_.get();
+  p_.nodes[1] = sort_nodes_.get() + cap;
+  p_.keys[0] = sort_keys_.get();
+  p_.keys[1] = sort_keys_.get() + cap;
+  p_.hist = hist_.get();
+  p_.marks = marks_.get();
+}
+
+void NbrSampleDev::copy(int *cnt, int *slot, int *nbr, int *t_ptr, int *t_row,
+                        int *t_slot) const {
+  PGCN_HIP(hipDeviceSynchronize());
+  const size_t total = (size_t)p_.n * p_.fanout;
+  if (cnt && p_.n) cnt_.download(cnt, (size_t)p_.n);
+  if (t_ptr) t_ptr_.download(t_ptr, (size_t)p_.n + 1);
+  if (slot && total) slot_.download(slot, total);
+  if (nbr && total) nbr_.download(nbr, total);
+  if (t_row && total) t_row_.download(t_row, total);
+  if (t_slot && total) t_slot_.download(t_slot, total);
+}
+
 void validate_rank_queries(int n, long long n_queries, const int *anchor, const int *target,
                            const long long *filter_ptr, const int *filter_idx) {
   PGCN_CHECK(n >= 1 && n_queries >= 0 && n_queries <= INT_MAX &&

@@ -295,6 +295,34 @@ class NegSamplerDev {
   DeviceBuffer<int> idx_;
 };
 
+// A neighbour sample over a square pattern for k_nbr.hip: every buffer of an NbrSample at its
+// worst-case capacity for `fanout` -- with N = n * fanout entries at most long_cap = N / (kGatSeg
+// + 1) nodes are sampled more than kGatSeg times, in at most ceil(N / kGatSeg) + long_cap
+// segments, plus the padding's one.  It reads the graph's device pattern (gat_pattern(): built
+// here if the graph has none yet), so the graph must outlive it.  Before the first draw the
+// sample is empty: cnt = 0, no transposed entry.  The backward's segment partials live here, so
+// two backward calls on one sample must not overlap.  Construction allocates and syncs: not inside
+// a stream capture.
+class NbrSampleDev {
+ public:
+  NbrSampleDev(DevGraph *graph, int fanout);
+  const NbrSample &sample() const { return p_; }
+  void draw(unsigned long long seed, unsigned long long round, hipStream_t s) const {
+    launch_nbr_draw(p_, seed, round, s);
+  }
+  // device sync + blocking copies (null: skipped): cnt [n], slot / nbr [n K], t_ptr [n + 1],
+  // t_row / t_slot [n K]
+  void copy(int *cnt, int *slot, int *nbr, int *t_ptr, int *t_row, int *t_slot) const;
+
+ private:
+  NbrSample p_;
+  DeviceBuffer<int> cnt_, slot_, nbr_, t_ptr_, t_row_, t_slot_, sort_nodes_;
+  DeviceBuffer<unsigned> sort_keys_, hist_, marks_;
+  DeviceBuffer<int4> segs_;
+  DeviceBuffer<int2> longs_;
+  DeviceBuffer<float> ws_;
+};
+
 // A ranking query set as k_rank.hip takes it: PGCN_E_INVALID for an endpoint outside [0, n), a
 // query count beyond an int, a filter list that is not strictly ascending (so deduplicated), has
 // an entry outside [0, n) or holds its query's target.  filter_ptr null: no lists.  Host only.

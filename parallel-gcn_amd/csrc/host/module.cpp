@@ -746,7 +746,7 @@ void GraphAttention::backward(const Stream &s) const {
 // ------------------------------------------------------------------------------------------
 SageAggregate::SageAggregate(shared_ptr<Variable> in_, shared_ptr<Variable> out_,
                              DevGraph *graph_, DevGraph *mean_fwd_, DevGraph *mean_bwd_, int dim_,
-                             int aggregator_, bool root_)
+                             int aggregator_, bool root_, int fanout_)
     : in(std::move(in_)), out(std::move(out_)), graph(graph_), mean_fwd(mean_fwd_),
       mean_bwd(mean_bwd_), dim(dim_), aggregator(aggregator_), root(root_),
       ld_s((dim_ + 3) / 4 * 4) {
@@ -760,6 +760,7 @@ SageAggregate::SageAggregate(shared_ptr<Variable> in_, shared_ptr<Variable> out_
                                  mean_bwd->rows() == graph->rows()),
              PGCN_E_INVALID, "sage: aggregator 1 (mean, with its two graphs) or 2 (max)");
   const size_t n = (size_t)std::max(graph->rows(), 1);
+  if (fanout_) sample = std::make_unique<NbrSampleDev>(graph, fanout_);
   if (aggregator == 2) {  // (host build and upload: now, not in an epoch)
     graph->sage_ws();
     arg.allocate(n * ld_s);
@@ -786,6 +787,11 @@ void SageAggregate::forward(bool training, const Stream &s) const {
     Q = q.get();
     ld_q = ld_s;
   }
+  if (sample && training) {
+    launch_nbr_agg_fwd(sample->sample(), aggregator, Q, ld_q, dim, R, in->ld, out->dev_data.get(),
+                       out->ld, aggregator == 2 ? arg.get() : nullptr, ld_s, s.get());
+    return;
+  }
   if (aggregator == 2) {
     launch_agg_max_fwd(graph->gat_pattern(), graph->sage_ws(), Q, ld_q, dim, R, in->ld,
                        out->dev_data.get(), out->ld, training ? arg.get() : nullptr, ld_s, s.get());
@@ -793,6 +799,11 @@ void SageAggregate::forward(bool training, const Stream &s) const {
   }
   mean_fwd->graphsum(Q, ld_q, out->dev_data.get(), out->ld, dim, s.get());
   if (R) launch_copy_cols(R, in->ld, out->dev_data.get(), out->ld, n, dim, true, s.get());
+}
+
+void SageAggregate::draw(unsigned long long seed, unsigned long long round,
+                         const Stream &s) const {
+  if (sample) sample->draw(seed, round, s.get());
 }
 
 void SageAggregate::backward(const Stream &s) const {
@@ -803,7 +814,10 @@ void SageAggregate::backward(const Stream &s) const {
   float *din = in->dev_grad.get();
   float *dQ = staged() ? dq.get() : root ? din + dim : din;
   const int ld_dq = staged() ? ld_s : in->ld;
-  if (aggregator == 2)
+  if (sample)
+    launch_nbr_agg_bwd(sample->sample(), aggregator, g, out->ld, arg.get(), ld_s, dim, dQ, ld_dq,
+                       s.get());
+  else if (aggregator == 2)
     launch_agg_max_bwd(graph->gat_pattern(), graph->sage_ws(), g, out->ld, arg.get(), ld_s, dim,
                        dQ, ld_dq, s.get());
   else

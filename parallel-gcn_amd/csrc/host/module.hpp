@@ -393,6 +393,10 @@ class GraphAttention : public Module {
 // it.  When dim is no multiple of 4 (an output layer) the Q half of `in` does not start on the
 // 16-byte grid: Q and dQ then pass through the staging buffers `q` / `dq` (one strided copy each
 // way).  Single GPU only.
+// fanout != 0 (neighbour sampling, k_nbr.hip): the module owns an NbrSampleDev over `graph`; the
+// engine calls draw() before each training epoch, a TRAINING forward runs launch_nbr_agg_fwd on
+// the sample (R added in its final write, for the mean too; the max keeps the winning global
+// slots in `arg`) and the backward launch_nbr_agg_bwd; an evaluation forward is the one above.
 class SageAggregate : public Module {
   shared_ptr<Variable> in, out;
   DevGraph *graph, *mean_fwd, *mean_bwd;
@@ -401,11 +405,14 @@ class SageAggregate : public Module {
   DeviceBuffer<int> arg;
   DeviceBuffer<float> q, dq;
   int ld_s;  // the stride of arg, q and dq: round_up4(dim)
+  std::unique_ptr<NbrSampleDev> sample;  // fanout != 0
   bool staged() const { return root && dim % 4 != 0; }
 
  public:
   SageAggregate(shared_ptr<Variable> in_, shared_ptr<Variable> out_, DevGraph *graph_,
-                DevGraph *mean_fwd_, DevGraph *mean_bwd_, int dim_, int aggregator_, bool root_);
+                DevGraph *mean_fwd_, DevGraph *mean_bwd_, int dim_, int aggregator_, bool root_,
+                int fanout_ = 0);
+  void draw(unsigned long long seed, unsigned long long round, const Stream &s) const;
   void forward(bool training, const Stream &s) const override;
   void backward(const Stream &s) const override;
 };

@@ -365,13 +365,41 @@ void launch_links_rebuild(const LinkBuild &b, hipStream_t s, hipEvent_t *stage_e
               in.nodes, b.total, b.n, b.ptr);
   stage();
   if (b.long_cap == 0) return;  // no list can exceed kGatSeg
-  const int B = (int)ceil_div(b.n, kNegThreads);
-  PGCN_LAUNCH(k_seg_mark, dim3((unsigned)B), thr, 0, s, b.ptr, b.n, b.marks, B);
-  PGCN_LAUNCH(k_scan_rows, dim3(2), thr, 0, s, b.marks, B);
-  const long long cover = std::max<long long>(b.n, std::max(b.seg_cap, b.long_cap));
-  PGCN_LAUNCH(k_seg_write, dim3((unsigned)ceil_div(cover, kNegThreads)), thr, 0, s, b.ptr, b.n,
-              b.marks, B, b.segs, b.seg_cap, b.longs, b.long_cap);
+  launch_index_segments(b.ptr, b.n, b.marks, b.segs, b.seg_cap, b.longs, b.long_cap, s);
   stage();
+}
+
+void launch_index_segments(const int *ptr, int n, unsigned *marks, int4 *segs, int seg_cap,
+                           int2 *longs, int long_cap, hipStream_t s) {
+  const dim3 thr(kNegThreads);
+  const int B = (int)ceil_div(n, kNegThreads);
+  PGCN_LAUNCH(k_seg_mark, dim3((unsigned)B), thr, 0, s, ptr, n, marks, B);
+  PGCN_LAUNCH(k_scan_rows, dim3(2), thr, 0, s, marks, B);
+  const long long cover = std::max<long long>(n, std::max(seg_cap, long_cap));
+  PGCN_LAUNCH(k_seg_write, dim3((unsigned)ceil_div(cover, kNegThreads)), thr, 0, s, ptr, n, marks,
+              B, segs, seg_cap, longs, long_cap);
+}
+
+int launch_sort_by_node(int total, int n_ids, int *const nodes[2], unsigned *const keys[2],
+                        unsigned *hist, hipStream_t s) {
+  const int tiles = (int)ceil_div(total, kSortTile), passes = link_sort_passes(n_ids);
+  const dim3 grid((unsigned)tiles), thr(kNegThreads);
+  SortIn in{nullptr, nullptr, nullptr, nodes[1], keys[1], n_ids};
+  for (int p = 0; p < passes; p++) {
+    const int shift = 8 * p, to = p & 1;
+    PGCN_LAUNCH(k_sort_hist<false>, grid, thr, 0, s, in, total, shift, hist, tiles);
+    PGCN_LAUNCH(k_scan_rows, dim3(256), thr, 0, s, hist, tiles);
+    PGCN_LAUNCH(k_sort_scatter<false>, grid, thr, 0, s, in, total, shift, hist, tiles, nodes[to],
+                keys[to]);
+    in.nodes = nodes[to];
+    in.keys = keys[to];
+  }
+  return (passes - 1) & 1;
+}
+
+void launch_index_ptr(const int *nodes, int total, int n, int *ptr, hipStream_t s) {
+  PGCN_LAUNCH(k_inc_ptr, dim3((unsigned)ceil_div((long long)n + 1, kNegThreads)),
+              dim3(kNegThreads), 0, s, nodes, total, n, ptr);
 }
 
 }  // namespace pgcn

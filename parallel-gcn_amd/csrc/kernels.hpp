@@ -18,7 +18,8 @@ enum KernelPath {
   KP_SPMM_CSR, KP_SPMM_CSR_DUAL, KP_SPMM_CSC_256, KP_SPMM_CSC_1024, KP_SPMM_TREE_256,
   KP_SPMM_TREE_1024, KP_LAUNCHES, KP_LINK_FWD, KP_LINK_BWD, KP_RANK_SWEEP, KP_RANK_FILTER,
   KP_TOPK_SWEEP, KP_TOPK_MERGE, KP_LINK_MLP_FWD, KP_LINK_MLP_BWD,
-  KP_RANK_MLP_SWEEP, KP_RANK_MLP_FILTER, KP_TOPK_MLP_SWEEP, KP_TOPK_MLP_MERGE, KP_COUNT
+  KP_RANK_MLP_SWEEP, KP_RANK_MLP_FILTER, KP_TOPK_MLP_SWEEP, KP_TOPK_MLP_MERGE,
+  KP_NBR_DRAW, KP_NBR_FWD, KP_NBR_BWD, KP_COUNT
 };
 void note_path(KernelPath p);
 // every kernel launch of the library goes through this (counted: "launches")
@@ -558,6 +559,57 @@ int link_sort_passes(int n);
 // per pass the histogram, the scan and the scatter, then the index, then the segment records.
 int links_rebuild_stages(const LinkBuild &b);
 void launch_links_rebuild(const LinkBuild &b, hipStream_t s, hipEvent_t *stage_end = nullptr);
+// The rebuild's stages on their own, for other fixed-capacity indexes (k_nbr.hip) -- the same
+// kernels.  launch_sort_by_node: the stable LSD radix sort of `total` >= 1 entries {node in [0,
+// n_ids), key} that lie in nodes[1] / keys[1] (pass 0 writes buffer 0, pass 1 buffer 1, ...; hist
+// as LinkBuild's for ceil(total / kSortTile) tiles); returns the buffer that holds the result.
+// launch_index_ptr: ptr[i], i in [0, n], = the first sorted entry whose node is >= i.
+// launch_index_segments: the segment and long-node records of ptr [n + 1] with their padding
+// (marks [2 ceil(n / 256) + 2]; long_cap >= 1).
+int launch_sort_by_node(int total, int n_ids, int *const nodes[2], unsigned *const keys[2],
+                        unsigned *hist, hipStream_t s);
+void launch_index_ptr(const int *nodes, int total, int n, int *ptr, hipStream_t s);
+void launch_index_segments(const int *ptr, int n, unsigned *marks, int4 *segs, int seg_cap,
+                           int2 *longs, int long_cap, hipStream_t s);
+// ---- GraphSAGE neighbour sampling: fanout draws and sampled aggregation (k_nbr.hip) ------------
+// A sampled pattern of fixed row stride K = fanout over a square CSR pattern (NbrSampleDev,
+// host/graph.hpp, owns the buffers): row i keeps cnt[i] = min(len_i, K) of its slots, ascending, at
+// slot / nbr [i K .. i K + cnt[i]) -- the global CSR slot and its neighbour -- and -1 behind them.
+// The transposed index lists, for node j, the entries that sampled j in ascending (row, position)
+// order: t_ptr [n + 1], t_row / t_slot [n K] (real entries first, -1 behind t_ptr[n]); lists above
+// kGatSeg entries have the segment records of LinkIndex, padded to their capacities as
+// launch_links_rebuild pads its own, and ws [seg_cap][kSageWsStride] holds their partial rows.
+constexpr int kNbrMaxFanout = 64;
+enum { kNbrMean = 1, kNbrMax = 2 };
+struct NbrSample {
+  int n = 0, fanout = 0;
+  const int *indptr = nullptr, *indices = nullptr;  // the pattern (device)
+  int *cnt = nullptr, *slot = nullptr, *nbr = nullptr;
+  int *t_ptr = nullptr, *t_row = nullptr, *t_slot = nullptr;
+  int4 *segs = nullptr;
+  int2 *longs = nullptr;
+  int seg_cap = 0, long_cap = 0;
+  float *ws = nullptr;
+  int *nodes[2] = {nullptr, nullptr};  // the sort's ping-pong entries [n K] each ...
+  unsigned *keys[2] = {nullptr, nullptr};
+  unsigned *hist = nullptr, *marks = nullptr;  // ... and its counts, as LinkBuild's
+};
+// The draw of (seed, round) -- the file's header has the generator -- and the transposed index
+// behind it: one draw launch, 3 per radix pass of link_sort_passes(n + 1), two for the index, three
+// more when n K > kGatSeg.  Allocates nothing, never syncs.
+void launch_nbr_draw(const NbrSample &p, unsigned long long seed, unsigned long long round,
+                     hipStream_t s);
+// out_i = add_i + (1.0f / cnt_i) * (sum over row i's kept entries, in stored order, of in_nbr)
+// (kNbrMean; arg untouched) or add_i + their maximum with arg_i = the winning global slot
+// (kNbrMax; launch_agg_max_fwd's tie rule, empty-row result and padding).  One launch.
+void launch_nbr_agg_fwd(const NbrSample &p, int mode, const float *in, int ld_in, int d,
+                        const float *add, int ld_add, float *out, int ld_out, int *arg, int ld_arg,
+                        hipStream_t s);
+// din_j = sum over node j's transposed list of G_i * (1.0f / cnt_i) (mean), or of the G_i[c] with
+// arg_i[c] == the entry's slot (max): every row written, a node nobody sampled a zero row; lists
+// above kGatSeg entries through p.ws and a merge launch in segment order.
+void launch_nbr_agg_bwd(const NbrSample &p, int mode, const float *G, int ld_g, const int *arg,
+                        int ld_arg, int d, float *din, int ld_din, hipStream_t s);
 // ---- link prediction: 1-vs-all ranking counts (k_rank.hip) -------------------------------------
 // The rank score r(a, v) is the k-ordered fp32 fmaf chain over the d columns of rows a and v -- not
 // launch_link_score_fwd's order -- which is what the sweep's f32 MFMA tiles compute bit for bit.

@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [batch_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [batch_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [fanout=<K>] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -24,7 +24,9 @@
 // the published GAT), both also keys of the parameter file.
 // aggregator=mean|max (or 1|2) [root_weight=1] (command line or parameter file): GraphSAGE layers
 // in the GraphSums' place, pgcn_params.aggregator / root_weight; `gcn-par cora aggregator=max
-// root_weight=1` trains the max-pooling variant with a self term.
+// root_weight=1` trains the max-pooling variant with a self term.  fanout=<K> (1..64, with an
+// aggregator): training aggregates over K neighbours sampled anew every epoch, evaluation over
+// the whole neighbourhood, pgcn_params.fanout; `gcn-par reddit aggregator=mean fanout=25`.
 // readout=sum|mean|max (or 1|2|3; command line or parameter file): graph classification,
 // pgcn_params.readout -- the nodes are a batch of graphs read from the sidecar file
 // data/<name>.graphs (line g: `<rows> <label> <split>`), loss and accuracy are per graph, and
@@ -130,6 +132,7 @@ static bool load_params(const char *path, pgcn_params *p, int *embed) {
     else if (k == "residual") p->residual = std::atoi(v.c_str());
     else if (k == "layer_norm") p->layer_norm = std::atoi(v.c_str());
     else if (k == "batch_norm") p->batch_norm = std::atoi(v.c_str());
+    else if (k == "fanout") p->fanout = std::atoi(v.c_str());
     else if (k == "attention") p->attention = std::atoi(v.c_str());
     else if (k == "multilabel") p->multilabel = std::atoi(v.c_str());
     else if (k == "heads") p->attention_heads = std::atoi(v.c_str());
@@ -158,7 +161,7 @@ int main(int argc, char **argv) {
   int topk = 10;
   int epochs = -1, residual = -1, layer_norm = -1, batch_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
-  int root_weight = -1;
+  int root_weight = -1, fanout = -1;
   std::string aggregator, readout, link;
   int embed = 32, embed_arg = -1, link_hidden = -1, neg_ratio = -1;
   for (int i = 2; i < argc; i++) {
@@ -173,6 +176,7 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "residual=", 9)) residual = std::atoi(argv[i] + 9);
     if (!std::strncmp(argv[i], "layer_norm=", 11)) layer_norm = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "batch_norm=", 11)) batch_norm = std::atoi(argv[i] + 11);
+    if (!std::strncmp(argv[i], "fanout=", 7)) fanout = std::atoi(argv[i] + 7);
     if (!std::strncmp(argv[i], "multilabel=", 11)) multilabel = std::atoi(argv[i] + 11);
     if (!std::strncmp(argv[i], "attention=", 10)) attention = std::atoi(argv[i] + 10);
     if (!std::strncmp(argv[i], "heads=", 6)) heads = std::atoi(argv[i] + 6);
@@ -199,6 +203,7 @@ int main(int argc, char **argv) {
   if (residual >= 0) p.residual = residual;
   if (layer_norm >= 0) p.layer_norm = layer_norm;
   if (batch_norm >= 0) p.batch_norm = batch_norm;
+  if (fanout >= 0) p.fanout = fanout;
   if (multilabel >= 0) p.multilabel = multilabel;
   if (attention >= 0) p.attention = attention;
   if (heads >= 0) p.attention_heads = heads;
