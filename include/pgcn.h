@@ -627,6 +627,81 @@ long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indi
                                  int filtered, long long *n_filter, int *anchor, int *target,
                                  long long *ptr, int *idx);
 
+/* --- link prediction: neighbourhood heuristics CN / AA / RA (k_heur.hip; new: the reference has
+ * no pair-level model).  The baselines every link-prediction result is compared with first, as
+ * exact integers on the device.
+ *
+ * Definitions.  The input is a CSR pattern as the loader gives it: rows may be unsorted, hold
+ * duplicates and the implicit self loop, and the pattern may be directed.
+ *   Cleaned neighbourhood  G(u): the distinct column indices of row u other than u, ascending;
+ *       deg(u) = |G(u)|.
+ *   Reverse neighbourhood  Gt(z) = { v : z in G(v) }, ascending; on a symmetric pattern = G(z).
+ *   Fixed-point weight  w_kind(z), an unsigned 64-bit integer computed on the host in double when
+ *       the index is created:
+ *         CN (kind 1): 1;
+ *         AA (kind 2): llrint(ldexp(1.0 / log((double)deg(z)), 32)) for deg(z) >= 2, else 0;
+ *         RA (kind 3): llrint(ldexp(1.0 / (double)deg(z), 32))      for deg(z) >= 1, else 0.
+ *   Score  S_kind(a, v) = sum over z in G(a) & G(v) of w_kind(z), an unsigned 64-bit sum (below
+ *       n * 2^33: it cannot overflow).  a == v is not special: S(a, a) = sum over G(a) of w(z).
+ *       Integer addition does not depend on its order, so every kernel below gives the same bits
+ *       for the same (a, v) and scores are compared exactly with > and == (the rank kernels above
+ *       reach the same by fixing an fmaf chain).
+ *   Float score: (float)S for CN, (float)((double)S * 2^-32) for AA / RA.
+ * The adjacency is the graph as given: a held-out (validation / test) positive that is still an
+ * edge of it counts its own endpoints' neighbourhoods -- keep such pairs out of the pattern.
+ *
+ * pgcn_cn_index is built from host indptr / indices: validated on the host before a device is
+ * looked for -- PGCN_E_INVALID for a null pointer, n_nodes < 1, an indptr that does not start at 0
+ * or descends, an index out of range -- then cleaned, transposed, weighted and uploaded, with the
+ * sweep's workspace: W = min(512, 2^30 / (12 n_nodes)) (at least 1) workgroup rows of 12 n_nodes
+ * bytes -- a dense 64-bit accumulator row and a touched list.  That is at most 1 GiB up to
+ * 89,478,485 nodes; above, W = 1 and the one row's 12 n_nodes bytes exceed the budget (the sweep
+ * cannot run on less).  pgcn_cn_index_workspace reports the bytes; an allocation that fails is
+ * PGCN_E_NOMEM.  pgcn_cn_index_weights copies w_kind to host memory [n_nodes].
+ *
+ * pgcn_link_heur_score: for m explicit pairs (dev_src, dev_dst: device arrays; an endpoint outside
+ * [0, n_nodes) is read as the nearest node, as pgcn_neg_sample reads an anchor) dev_fx[e] = S and /
+ * or dev_scores[e] = its float score; either output may be NULL, not both.  ONE launch: a lane
+ * group per pair (8 to 64 lanes by the mean cleaned row length) splits the shorter row and searches
+ * the longer, whose top search levels are staged in LDS above 128 entries.
+ * pgcn_link_heur_rank: pgcn_link_rank's counts with S in r's place, for every query e of q, with
+ * T = S(a_e, t_e):
+ *     greater[e] = #{ v in [0, n) : v != t_e, v not in F_e, S(a_e, v) >  T }
+ *     equal[e]   = #{ v in [0, n) : v != t_e, v not in F_e, S(a_e, v) == T }
+ * without [n_queries][n] storage.  At most three launches: the thresholds (the pair kernel on the
+ * handle's anchors and targets, into the handle's threshold words), the sweep (min(n_queries, W)
+ * persistent workgroups, each expanding its queries' 2-hop neighbourhoods into its own accumulator
+ * row with integer atomics, leaving the row zeroed and storing both counts) and, with filter
+ * entries, the correction (a lane group per entry, integer atomics).
+ * Both calls are asynchronous, allocate nothing, use no float atomics and may be captured; m == 0
+ * and n_queries == 0 launch nothing.  Two rank calls on one index, or on one query set, must not
+ * overlap (they share the workspace, resp. the thresholds).  Argument errors are PGCN_E_INVALID
+ * before the device is touched: kind outside 1..3, a null handle, m beyond an int, both outputs
+ * NULL, a query set whose n_nodes differs from the index's.
+ *
+ * The same two on host arrays, for callers without device buffers (they copy, launch on the null
+ * stream and sync): pgcn_cn_index_score_pairs writes scores[e], the float score of (src_e, dst_e),
+ * e < m; pgcn_cn_index_link_ranks is pgcn_gcn_link_ranks with the heuristic in the model's place --
+ * the query set pgcn_debug_rank_filter builds from the pattern (indptr / indices over the index's
+ * nodes) and the pair list for (split, side, filtered), then pgcn_link_heur_rank; it returns the
+ * query count (both arrays NULL: the count only, no device needed) or a status < 0. */
+typedef struct pgcn_cn_index pgcn_cn_index;
+int pgcn_cn_index_create(int n_nodes, const int *indptr, const int *indices, pgcn_cn_index **out);
+int pgcn_cn_index_destroy(pgcn_cn_index *x);
+long long pgcn_cn_index_workspace(const pgcn_cn_index *x); /* device bytes of the sweep's rows */
+int pgcn_cn_index_weights(const pgcn_cn_index *x, int kind, unsigned long long *w /* host [n] */);
+int pgcn_link_heur_score(const pgcn_cn_index *x, int kind, const int *dev_src, const int *dev_dst,
+                         long long m, unsigned long long *dev_fx, float *dev_scores, void *stream);
+int pgcn_link_heur_rank(const pgcn_cn_index *x, int kind, const pgcn_rank_queries *q,
+                        unsigned int *greater, unsigned int *equal, void *stream);
+int pgcn_cn_index_score_pairs(const pgcn_cn_index *x, int kind, const int *src, const int *dst,
+                              long long m, float *scores /* host [m] */);
+long long pgcn_cn_index_link_ranks(const pgcn_cn_index *x, int kind, const int *indptr,
+                                   const int *indices, long long n_pairs, const int *pair_src,
+                                   const int *pair_dst, const int *pair_label,
+                                   const int *pair_split, int split, int side, int filtered,
+                                   long long *greater, long long *equal);
+
 /* --- link prediction: 1-vs-all ranking counts under the MLP decoder (k_rank_mlp.hip; new: the
  * reference has no pair-level model).  pgcn_link_rank's counts with the decoder's score in r's
  * place: s(a, v) is what pgcn_link_mlp_fwd writes for the pair (a, v), BIT FOR BIT (P, ld_p, h: as

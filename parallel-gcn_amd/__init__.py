@@ -209,6 +209,16 @@ _sig("pgcn_link_rank", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void
 _sig("pgcn_debug_rank_filter", c_ll, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p,
      c_void_p, c_int, c_int, c_int, P(c_ll), c_void_p, c_void_p, c_void_p, c_void_p)
 _sig("pgcn_gcn_link_ranks", c_ll, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)
+_sig("pgcn_cn_index_create", c_int, c_int, c_void_p, c_void_p, P(c_void_p))
+_sig("pgcn_cn_index_destroy", c_int, c_void_p)
+_sig("pgcn_cn_index_workspace", c_ll, c_void_p)
+_sig("pgcn_cn_index_weights", c_int, c_void_p, c_int, c_void_p)
+_sig("pgcn_link_heur_score", c_int, c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
+     c_void_p)
+_sig("pgcn_link_heur_rank", c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p)
+_sig("pgcn_cn_index_score_pairs", c_int, c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p)
+_sig("pgcn_cn_index_link_ranks", c_ll, c_void_p, c_int, c_void_p, c_void_p, c_ll, c_void_p, c_void_p,
+     c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p)
 _sig("pgcn_link_rank_mlp_tile", None, P(c_int), P(c_int))
 _sig("pgcn_link_rank_mlp", c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
      c_void_p, c_void_p)
@@ -1014,6 +1024,129 @@ def link_auc(scores, labels):
     return float((rank[y == 1].sum() - pos * (pos + 1) / 2.0) / (pos * neg))
 
 
+HEUR_KINDS = {"cn": 1, "aa": 2, "ra": 3, 1: 1, 2: 2, 3: 3}
+
+
+class CnIndex:
+    """The neighbourhood-heuristic index of a CSR pattern on the device (pgcn_cn_index): Common
+    Neighbours ('cn'), Adamic-Adar ('aa') and Resource Allocation ('ra') as exact 64-bit
+    fixed-point sums over the cleaned rows (include/pgcn.h has the definitions).  The pattern is
+    used as given: held-out positives must not be edges of it."""
+
+    def __init__(self, n_nodes, indptr, indices):
+        ip = np.ascontiguousarray(indptr, np.int32)
+        ix = np.ascontiguousarray(indices, np.int32)
+        if ip.shape != (n_nodes + 1,) or ix.ndim != 1 or ip[-1] != ix.size:
+            raise ValueError("CnIndex: indptr [n + 1], indices [indptr[n]]")
+        h = c_void_p()
+        check(lib.pgcn_cn_index_create(n_nodes, _ptr(ip), _ptr(ix), ctypes.byref(h)),
+              "cn_index_create")
+        self._h, self.n_nodes = h, n_nodes
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def workspace(self):
+        """Device bytes of the rank sweep's accumulator rows and touched lists."""
+        return int(lib.pgcn_cn_index_workspace(self._h))
+
+    def weights(self, kind):
+        """uint64 [n]: the fixed-point weight of every node as a common neighbour."""
+        w = np.zeros(self.n_nodes, np.uint64)
+        check(lib.pgcn_cn_index_weights(self._h, HEUR_KINDS[kind], _ptr(w)), "cn_index_weights")
+        return w
+
+    def score(self, src, dst, kind="cn", raw=False, stream=None):
+        """The scores of the pairs (src[e], dst[e]) (pgcn_link_heur_score): float32 [m], or with
+        raw=True the exact sums (CN: the count; AA / RA: in units of 2^-32).  int32 torch tensors
+        on the device give a device tensor (raw: int64, holding the unsigned bits) without a
+        sync; numpy arrays are copied over and give a numpy array (raw: uint64)."""
+        import torch
+        host = not hasattr(src, "data_ptr")
+        if host:
+            src = torch.from_numpy(np.ascontiguousarray(src, np.int32)).cuda()
+            dst = torch.from_numpy(np.ascontiguousarray(dst, np.int32)).cuda()
+        if src.dtype != torch.int32 or dst.dtype != torch.int32 or src.ndim != 1 or \
+                dst.shape != src.shape or not (src.is_contiguous() and dst.is_contiguous()):
+            raise ValueError("CnIndex.score: src [m], dst [m], contiguous int32")
+        out = torch.zeros(src.numel(), dtype=torch.int64 if raw else torch.float32,
+                          device=src.device)
+        check(lib.pgcn_link_heur_score(self._h, HEUR_KINDS[kind], _dptr(src), _dptr(dst),
+                                       src.numel(), _dptr(out) if raw else None,
+                                       None if raw else _dptr(out), stream), "link_heur_score")
+        if not host:
+            return out
+        torch.cuda.synchronize()
+        out = out.cpu().numpy()
+        return out.view(np.uint64) if raw else out
+
+    def rank(self, queries, kind="cn", stream=None):
+        """(greater, equal) int64 [Q] of a RankQueries set over the same nodes
+        (pgcn_link_heur_rank): the candidates whose score with the anchor is above / exactly the
+        target's, the target and the query's filter list left out.  Syncs."""
+        import torch
+        g = torch.zeros(max(queries.n_queries, 1), dtype=torch.int32, device="cuda")
+        e = torch.zeros_like(g)
+        check(lib.pgcn_link_heur_rank(self._h, HEUR_KINDS[kind], queries.handle, _dptr(g), _dptr(e),
+                                      stream), "link_heur_rank")
+        q = queries.n_queries
+        torch.cuda.synchronize()
+        return tuple(t.cpu().numpy().view(np.uint32)[:q].astype(np.int64) for t in (g, e))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and lib is not None:
+            lib.pgcn_cn_index_destroy(self._h)
+            self._h = c_void_p()
+
+    __del__ = close
+
+
+def heuristic_link_ranks(ds, split, kind="cn", side="dst", filtered=True):
+    """(greater, equal) int64 [Q] of a link dataset's `split` positives under a neighbourhood
+    heuristic: GCN.link_ranks' query sets (rank_filter) scored by CnIndex over ds's adjacency
+    instead of a trained model; ready for rank_from_counts / mrr / hits_at.  The adjacency is used
+    as loaded: keep validation and test positives out of it."""
+    if ds.pair_src is None:
+        raise ValueError("heuristic_link_ranks: the dataset has no pairs (set_links / load_links)")
+    if side not in RANK_SIDES:
+        raise ValueError("side must be 'dst' or 'src'")
+    index = CnIndex(ds.num_nodes, ds.graph_indptr, ds.graph_indices)
+    pairs = [np.ascontiguousarray(x, np.int32)
+             for x in (ds.pair_src, ds.pair_dst, ds.pair_label, ds.pair_split)]
+    args = (index.handle, HEUR_KINDS[kind], _ptr(ds.graph_indptr), _ptr(ds.graph_indices),
+            pairs[0].size, *(_ptr(x) for x in pairs), split, RANK_SIDES[side], 1 if filtered else 0)
+    try:
+        q = lib.pgcn_cn_index_link_ranks(*args, None, None)
+        if q < 0:
+            raise PgcnError(int(q), "cn_index_link_ranks")
+        greater, equal = np.zeros(q, np.int64), np.zeros(q, np.int64)
+        got = lib.pgcn_cn_index_link_ranks(*args, _ptr(greater), _ptr(equal))
+        if got < 0:
+            raise PgcnError(int(got), "cn_index_link_ranks")
+        return greater, equal
+    finally:
+        index.close()
+
+
+def heuristic_pair_scores(ds, kind="cn"):
+    """float32 [num_pairs]: the heuristic's score of every pair of a link dataset, in pair order;
+    link_auc(scores[sel], ds.pair_label[sel]) is a split's AUC."""
+    if ds.pair_src is None:
+        raise ValueError("heuristic_pair_scores: the dataset has no pairs (set_links / load_links)")
+    index = CnIndex(ds.num_nodes, ds.graph_indptr, ds.graph_indices)
+    src = np.ascontiguousarray(ds.pair_src, np.int32)
+    dst = np.ascontiguousarray(ds.pair_dst, np.int32)
+    out = np.zeros(src.size, np.float32)
+    try:
+        check(lib.pgcn_cn_index_score_pairs(index.handle, HEUR_KINDS[kind], _ptr(src), _ptr(dst),
+                                            src.size, _ptr(out)), "cn_index_score_pairs")
+        return out
+    finally:
+        index.close()
+
+
 def sample_negative_pairs(ds, src, ratio=1, seed=0):
     """Negative pairs for link prediction, on the host: for every entry of `src`, `ratio` pairs
     (src, dst) with dst drawn uniformly from the nodes, redrawn while it is src itself or a
@@ -1650,4 +1783,7 @@ EXPORTED = [
     "pgcn_debug_topk_filter", "pgcn_gcn_top_links",
     "pgcn_topk_queries_create_mlp", "pgcn_link_topk_mlp_tile", "pgcn_link_topk_mlp_splits",
     "pgcn_link_topk_mlp", "pgcn_gcn_top_links_decoder",
+    "pgcn_cn_index_create", "pgcn_cn_index_destroy", "pgcn_cn_index_workspace",
+    "pgcn_cn_index_weights", "pgcn_link_heur_score", "pgcn_link_heur_rank",
+    "pgcn_cn_index_score_pairs", "pgcn_cn_index_link_ranks",
 ]

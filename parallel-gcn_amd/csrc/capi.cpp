@@ -60,6 +60,9 @@ struct pgcn_rank_queries {
 struct pgcn_topk_queries {
   std::unique_ptr<TopKQueriesDev> q;
 };
+struct pgcn_cn_index {
+  std::unique_ptr<CnIndexDev> x;
+};
 struct pgcn_gcn {
   std::unique_ptr<GCN> g;
 };
@@ -1155,6 +1158,119 @@ int pgcn_link_rank_mlp(const pgcn_rank_queries *q, const float *H, int ld_h, int
                          as_stream(stream));
     PGCN_HIP(hipGetLastError());
   });
+}
+
+int pgcn_cn_index_create(int n_nodes, const int *indptr, const int *indices, pgcn_cn_index **out) {
+  return guarded([&] {
+    PGCN_CHECK(out, PGCN_E_INVALID, "cn_index_create args");
+    CnIndexHost host = build_cn_index(n_nodes, indptr, indices);
+    check_device();
+    auto h = std::make_unique<pgcn_cn_index>();
+    h->x = std::make_unique<CnIndexDev>(n_nodes, std::move(host));
+    *out = h.release();
+  });
+}
+
+int pgcn_cn_index_destroy(pgcn_cn_index *x) {
+  delete x;
+  return PGCN_OK;
+}
+
+long long pgcn_cn_index_workspace(const pgcn_cn_index *x) {
+  return x && x->x ? x->x->workspace() : (long long)PGCN_E_INVALID;
+}
+
+int pgcn_cn_index_weights(const pgcn_cn_index *x, int kind, unsigned long long *w) {
+  return guarded([&] {
+    PGCN_CHECK(x && x->x && kind >= kHeurCN && kind <= kHeurRA && w, PGCN_E_INVALID,
+               "cn_index_weights: an index, kind 1..3, w [n]");
+    const std::vector<unsigned long long> &t = x->x->weights(kind);
+    std::memcpy(w, t.data(), t.size() * sizeof(unsigned long long));
+  });
+}
+
+int pgcn_link_heur_score(const pgcn_cn_index *x, int kind, const int *dev_src, const int *dev_dst,
+                         long long m, unsigned long long *dev_fx, float *dev_scores,
+                         void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(x && x->x && kind >= kHeurCN && kind <= kHeurRA && m >= 0 && m <= INT_MAX &&
+                   (dev_fx || dev_scores) && (m == 0 || (dev_src && dev_dst)),
+               PGCN_E_INVALID,
+               "link_heur_score: an index, kind 1..3, 0 <= m within an int, src, dst, fx or scores");
+    check_device();
+    launch_heur_score(x->x->index(), kind, dev_src, dev_dst, m, dev_fx, dev_scores,
+                      as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_link_heur_rank(const pgcn_cn_index *x, int kind, const pgcn_rank_queries *q,
+                        unsigned int *greater, unsigned int *equal, void *stream) {
+  return guarded([&] {
+    PGCN_CHECK(x && x->x && q && q->q && kind >= kHeurCN && kind <= kHeurRA, PGCN_E_INVALID,
+               "link_heur_rank: an index, a query set, kind 1..3");
+    PGCN_CHECK(q->q->queries().n == x->x->index().n, PGCN_E_INVALID,
+               "link_heur_rank: the query set is over another node count than the index");
+    PGCN_CHECK(q->q->queries().n_queries == 0 || (greater && equal), PGCN_E_INVALID,
+               "link_heur_rank: greater and equal [n_queries]");
+    check_device();
+    launch_heur_rank(x->x->index(), kind, q->q->queries(), greater, equal, as_stream(stream));
+    PGCN_HIP(hipGetLastError());
+  });
+}
+
+int pgcn_cn_index_score_pairs(const pgcn_cn_index *x, int kind, const int *src, const int *dst,
+                              long long m, float *scores) {
+  return guarded([&] {
+    PGCN_CHECK(x && x->x && kind >= kHeurCN && kind <= kHeurRA && m >= 0 && m <= INT_MAX &&
+                   (m == 0 || (src && dst && scores)),
+               PGCN_E_INVALID,
+               "cn_index_score_pairs: an index, kind 1..3, 0 <= m within an int, src, dst, scores");
+    if (m == 0) return;
+    check_device();
+    DeviceBuffer<int> d_src((size_t)m), d_dst((size_t)m);
+    DeviceBuffer<float> d_scores((size_t)m);
+    d_src.upload(src, (size_t)m);
+    d_dst.upload(dst, (size_t)m);
+    launch_heur_score(x->x->index(), kind, d_src.get(), d_dst.get(), m, nullptr, d_scores.get(),
+                      nullptr);
+    PGCN_HIP(hipGetLastError());
+    PGCN_HIP(hipStreamSynchronize(nullptr));
+    d_scores.download(scores, (size_t)m);
+  });
+}
+
+long long pgcn_cn_index_link_ranks(const pgcn_cn_index *x, int kind, const int *indptr,
+                                   const int *indices, long long n_pairs, const int *pair_src,
+                                   const int *pair_dst, const int *pair_label,
+                                   const int *pair_split, int split, int side, int filtered,
+                                   long long *greater, long long *equal) {
+  long long n = -1;
+  const int st = guarded([&] {
+    PGCN_CHECK(x && x->x && kind >= kHeurCN && kind <= kHeurRA, PGCN_E_INVALID,
+               "cn_index_link_ranks: an index, kind 1..3");
+    PGCN_CHECK((greater == nullptr) == (equal == nullptr), PGCN_E_INVALID,
+               "cn_index_link_ranks: greater and equal, or neither");
+    const int nodes = x->x->index().n;
+    const RankFilterHost f = build_rank_filter(nodes, indptr, indices, n_pairs, pair_src, pair_dst,
+                                               pair_label, pair_split, split, side, filtered);
+    n = (long long)f.anchor.size();
+    if (!greater || n == 0) return;
+    check_device();
+    RankQueriesDev q(nodes, n, f.anchor.data(), f.target.data(), filtered ? f.ptr.data() : nullptr,
+                     f.idx.data());
+    DeviceBuffer<unsigned> counts(2 * (size_t)n);
+    launch_heur_rank(x->x->index(), kind, q.queries(), counts.get(), counts.get() + n, nullptr);
+    PGCN_HIP(hipGetLastError());
+    PGCN_HIP(hipStreamSynchronize(nullptr));
+    std::vector<unsigned> host(2 * (size_t)n);
+    counts.download(host.data(), host.size());
+    for (long long e = 0; e < n; e++) {
+      greater[e] = host[(size_t)e];
+      equal[e] = host[(size_t)(n + e)];
+    }
+  });
+  return st == PGCN_OK ? n : (long long)st;
 }
 
 long long pgcn_debug_rank_filter(int n_nodes, const int *indptr, const int *indices,

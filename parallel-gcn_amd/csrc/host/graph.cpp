@@ -1021,6 +1021,84 @@ void NbrSampleDev::copy(int *cnt, int *slot, int *nbr, int *t_ptr, int *t_row,
   if (t_slot && total) t_slot_.download(t_slot, total);
 }
 
+CnIndexHost build_cn_index(int n, const int *indptr, const int *indices) {
+  PGCN_CHECK(n >= 1 && indptr && indptr[0] == 0, PGCN_E_INVALID,
+             "cn_index: n >= 1, indptr [n + 1] from 0");
+  for (int i = 0; i < n; i++)
+    PGCN_CHECK(indptr[i + 1] >= indptr[i], PGCN_E_INVALID, "cn_index: indptr must ascend");
+  const int nnz = indptr[n];
+  PGCN_CHECK(nnz == 0 || indices, PGCN_E_INVALID, "cn_index: indices");
+  for (int k = 0; k < nnz; k++)
+    PGCN_CHECK(indices[k] >= 0 && indices[k] < n, PGCN_E_INVALID, "cn_index: column out of range");
+
+  CnIndexHost h;
+  // the cleaned rows: distinct columns other than the row, ascending
+  h.ptr.assign((size_t)n + 1, 0);
+  h.idx.reserve((size_t)nnz);
+  std::vector<int> row;
+  for (int i = 0; i < n; i++) {
+    row.assign(indices + indptr[i], indices + indptr[i + 1]);
+    std::sort(row.begin(), row.end());
+    row.erase(std::unique(row.begin(), row.end()), row.end());
+    for (int c : row)
+      if (c != i) h.idx.push_back(c);
+    h.ptr[(size_t)i + 1] = (int)h.idx.size();
+  }
+  // the reverse rows (pgcn_csr_transpose's counting pass: rows visited in order, so ascending)
+  const size_t clean = h.idx.size();
+  h.tptr.assign((size_t)n + 1, 0);
+  for (size_t k = 0; k < clean; k++) h.tptr[(size_t)h.idx[k] + 1]++;
+  for (int i = 0; i < n; i++) h.tptr[(size_t)i + 1] += h.tptr[(size_t)i];
+  h.tidx.resize(clean);
+  std::vector<int> fill(h.tptr.begin(), h.tptr.end() - 1);
+  for (int i = 0; i < n; i++)
+    for (int k = h.ptr[(size_t)i]; k < h.ptr[(size_t)i + 1]; k++)
+      h.tidx[(size_t)fill[(size_t)h.idx[(size_t)k]]++] = i;
+  // the weights, in double: CN 1, AA 2^32 / log(deg) from degree 2, RA 2^32 / deg from degree 1
+  for (auto &w : h.w) w.assign((size_t)n, 0ull);
+  for (int i = 0; i < n; i++) {
+    const int deg = h.ptr[(size_t)i + 1] - h.ptr[(size_t)i];
+    h.w[0][(size_t)i] = 1ull;
+    if (deg >= 2)
+      h.w[1][(size_t)i] = (unsigned long long)std::llrint(std::ldexp(1.0 / std::log((double)deg), 32));
+    if (deg >= 1)
+      h.w[2][(size_t)i] = (unsigned long long)std::llrint(std::ldexp(1.0 / (double)deg, 32));
+  }
+  return h;
+}
+
+CnIndexDev::CnIndexDev(int n, CnIndexHost &&h) {
+  auto up = [](auto &buf, const auto &host) {
+    buf.allocate(std::max<size_t>(host.size(), 1));
+    if (!host.empty()) buf.upload(host.data(), host.size());
+  };
+  up(ptr_, h.ptr);
+  up(idx_, h.idx);
+  up(tptr_, h.tptr);
+  up(tidx_, h.tidx);
+  w_.allocate(3 * (size_t)n);
+  for (int k = 0; k < 3; k++) {
+    w_.upload(h.w[k].data(), (size_t)n, (size_t)k * n);
+    w_host_[k] = std::move(h.w[k]);
+  }
+  const int wgs = heur_workgroups(n);
+  acc_.allocate((size_t)wgs * n);
+  acc_.zero();
+  touched_.allocate((size_t)wgs * n);
+  touched_.zero();
+  ws_bytes_ = (long long)wgs * n * (long long)(sizeof(unsigned long long) + sizeof(int));
+  x_.n = n;
+  x_.group = heur_group((long long)h.idx.size(), n);
+  x_.workgroups = wgs;
+  x_.ptr = ptr_.get();
+  x_.idx = idx_.get();
+  x_.tptr = tptr_.get();
+  x_.tidx = tidx_.get();
+  for (int k = 0; k < 3; k++) x_.w[k] = w_.get() + (size_t)k * n;
+  x_.acc = acc_.get();
+  x_.touched = touched_.get();
+}
+
 void validate_rank_queries(int n, long long n_queries, const int *anchor, const int *target,
                            const long long *filter_ptr, const int *filter_idx) {
   PGCN_CHECK(n >= 1 && n_queries >= 0 && n_queries <= INT_MAX &&

@@ -375,6 +375,36 @@ class RankQueriesDev {
   DeviceBuffer<float> thr_;
 };
 
+// The neighbourhood-heuristic index of a CSR pattern as the loader gives it (rows unsorted, with
+// duplicates and self loops, possibly directed), on the host: the cleaned rows (distinct columns
+// other than the row, ascending), their transpose (ascending) and the fixed-point weight tables
+// of include/pgcn.h, computed in double.  PGCN_E_INVALID for a null pointer, n < 1, an indptr
+// that does not start at 0 or descends, a column outside [0, n).  Host only.
+struct CnIndexHost {
+  std::vector<int> ptr, idx, tptr, tidx;
+  std::vector<unsigned long long> w[3];
+};
+CnIndexHost build_cn_index(int n, const int *indptr, const int *indices);
+
+// A CnIndexHost on the device for k_heur.hip, with the sweep's workspace (heur_workgroups(n) rows
+// of 12 n bytes, zeroed here and left zeroed by every call).  It keeps the weight tables on the
+// host too.  Two rank calls on one index must not overlap.  Construction is blocking copies: not
+// inside a stream capture.
+class CnIndexDev {
+ public:
+  CnIndexDev(int n, CnIndexHost &&h);
+  const CnIndex &index() const { return x_; }
+  long long workspace() const { return ws_bytes_; }
+  const std::vector<unsigned long long> &weights(int kind) const { return w_host_[kind - 1]; }
+
+ private:
+  CnIndex x_;
+  long long ws_bytes_ = 0;
+  std::vector<unsigned long long> w_host_[3];
+  DeviceBuffer<int> ptr_, idx_, tptr_, tidx_, touched_;
+  DeviceBuffer<unsigned long long> w_, acc_;
+};
+
 // A top-K query set as k_topk.hip takes it: PGCN_E_INVALID for an anchor outside [0, n), a query
 // count beyond an int, k outside [1, kTopKMax], an exclude list that is not strictly ascending or
 // has an entry outside [0, n) (it may hold the anchor).  exclude_ptr null: no lists.  Host only.

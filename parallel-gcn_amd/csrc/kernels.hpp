@@ -625,6 +625,9 @@ struct RankQueries {
   const long long *filter_ptr = nullptr;  // [n_queries + 1], null: no lists
   const int *filter_idx = nullptr;
   long long n_filter = 0;                 // filter_ptr[n_queries]
+  // the same words as [n_queries] 64-bit integer thresholds (k_heur.hip: the first half of
+  // the buffer's 16 n_queries bytes, which hipMalloc aligned for them)
+  unsigned long long *thr_u64() const { return reinterpret_cast<unsigned long long *>(thr); }
 };
 // candidate splits of the sweep's grid: a function of (Q, n) only
 int rank_splits(int Q, int n);
@@ -651,6 +654,53 @@ int rank_mlp_splits(int Q, int n);
 // never syncs.
 void launch_link_rank_mlp(const RankQueries &q, const float *H, int ld_h, int d, const float *P,
                           int ld_p, int h, unsigned *greater, unsigned *equal, hipStream_t s);
+// ---- link prediction: neighbourhood heuristics CN / AA / RA (k_heur.hip) -----------------------
+// S_kind(a, v) = the unsigned 64-bit sum of w_kind(z) over the common cleaned neighbours z of a and
+// v (include/pgcn.h has the contract): exact, so every kernel gives the same bits for a pair.
+// The index on the device (CnIndexDev, host/graph.hpp, owns the buffers): the cleaned rows (ptr
+// [n + 1], idx: distinct, ascending, without the row's own node), the reverse rows (tptr, tidx:
+// ascending), the three weight tables, and the sweep's workspace -- per workgroup a dense row acc
+// [n] (zero between calls) and a touched list [n].
+enum { kHeurCN = 1, kHeurAA = 2, kHeurRA = 3 };
+// the sweep's workspace: 12 n bytes a workgroup, at most 2 kCUs workgroups within this many bytes
+constexpr long long kHeurWorkspaceBudget = 1ll << 30;
+struct CnIndex {
+  int n = 0;
+  int group = 8;       // lanes per pair of the pair kernel: heur_group(nnz, n)
+  int workgroups = 1;  // rows of the workspace: heur_workgroups(n)
+  const int *ptr = nullptr, *idx = nullptr, *tptr = nullptr, *tidx = nullptr;
+  const unsigned long long *w[3] = {nullptr, nullptr, nullptr};
+  unsigned long long *acc = nullptr;
+  int *touched = nullptr;
+};
+// what one launch of the pair kernel serves: m explicit pairs (src, dst; fx and / or scores), or
+// the m = n_filter entries of a query set's lists (src: the anchors; the entry's sum leaves
+// greater / equal of its query by thr)
+struct HeurPairs {
+  const int *src = nullptr, *dst = nullptr;
+  long long m = 0;
+  unsigned long long *fx = nullptr;
+  float *scores = nullptr;
+  int n_queries = 0;
+  const long long *filter_ptr = nullptr;
+  const int *filter_idx = nullptr;
+  const unsigned long long *thr = nullptr;
+  unsigned *greater = nullptr, *equal = nullptr;
+};
+// lanes per pair for cleaned rows of mean length nnz / n: 8, 16, 32 or 64
+int heur_group(long long nnz, int n);
+// workgroups of the sweep (and rows of its workspace): a function of the device and n only
+int heur_workgroups(int n);
+// fx[e] = S_kind(src_e, dst_e), scores[e] = its float (either may be null, not both); src, dst on
+// the device, an endpoint outside [0, n) read as the nearest node.  One launch; m == 0 none.
+void launch_heur_score(const CnIndex &x, int kind, const int *src, const int *dst, long long m,
+                       unsigned long long *fx, float *scores, hipStream_t s);
+// launch_link_rank's counts with S_kind in r's place.  Three launches at most: the thresholds
+// (into q.thr_u64()), the sweep (min(Q, x.workgroups) persistent workgroups, which store both
+// counts of every query), the filter correction (a lane group per list entry; with entries).  Allocates
+// nothing, never syncs; two calls on one index, or on one query set, must not overlap.
+void launch_heur_rank(const CnIndex &x, int kind, const RankQueries &q, unsigned *greater,
+                      unsigned *equal, hipStream_t s);
 // ---- link prediction: 1-vs-all top-K retrieval (k_topk.hip) ------------------------------------
 // Per query (anchor a_e, ascending exclude list X_e) the k candidates v in [0, n) \ X_e first in
 // the order "higher r(a_e, v), then lower v"; the positions from the candidate count on hold idx -1,

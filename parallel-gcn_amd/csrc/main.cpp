@@ -1,5 +1,5 @@
 // parallel-gcn_amd/csrc/main.cpp -- `gcn-par <dataset> [file=<params>] [root=<dir>] [cache=1]
-//   [epochs=<n>] [residual=1] [layer_norm=1] [batch_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [fanout=<K>] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
+//   [epochs=<n>] [residual=1] [layer_norm=1] [batch_norm=1] [attention=1] [heads=<K>] [attn_dropout=<p>] [aggregator=mean|max] [root_weight=1] [fanout=<K>] [multilabel=1] [readout=sum|mean|max] [link=dot embed=<D> [link_hidden=<H>] [neg_ratio=<R>] [rank=1|<file>] [recommend=<file> [topk=<K>]]] [heuristic=cn|aa|ra] [load=<checkpoint>] [save=<checkpoint>] [predict=<file>]`
 // The reference's entry point (src/main.cpp:9-61): parse the dataset with the kept loader,
 // build the GCN, run the epochs printing the reference's epoch lines.  Parameters come from
 // a key=value file with the reference's keys (parameters/parameters_<ds>.txt layout:
@@ -50,14 +50,21 @@
 // (pgcn_gcn_top_links, with link_hidden= its _decoder form: dst side, filtered -- the node, its neighbours and its known links are left
 // out -- best first, ties to the lower index; a node with fewer than K candidates gets a shorter
 // line).
+// heuristic=cn|aa|ra (needs data/<name>.links): trains nothing -- the Common Neighbours, Adamic-Adar
+// or Resource Allocation baseline over the adjacency as loaded (pgcn_cn_index): one line
+// `heuristic kind=.. pairs=.. auc=..` with the test split's AUC (pgcn_cn_index_score_pairs), then
+// the line rank=1 prints, from pgcn_cn_index_link_ranks over the same filtered query sets.  Keep validation
+// and test positives out of the adjacency: a heuristic reads a held-out edge directly.
 #include <algorithm>
 #include <vector>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string>
+#include <utility>
 
 #include "../../include/pgcn.h"
 
@@ -94,6 +101,94 @@ static int link_id(const std::string &v) {
   char *end = nullptr;
   const long x = std::strtol(v.c_str(), &end, 10);
   return (end && *end == '\0' && !v.empty()) ? (int)x : -1;
+}
+
+// heuristic=: cn / aa / ra by name or 1 / 2 / 3; 0: unknown
+static int heuristic_id(const std::string &v) {
+  if (v == "cn" || v == "1") return 1;
+  if (v == "aa" || v == "2") return 2;
+  if (v == "ra" || v == "3") return 3;
+  return 0;
+}
+
+// one side of the rank line: the ranking metrics of (greater, equal) counts, mean ties
+static void print_rank_side(int side, const std::vector<long long> &greater,
+                            const std::vector<long long> &equal) {
+  const long long q = (long long)greater.size();
+  double rr = 0.0;
+  long long hits[3] = {0, 0, 0};
+  const double at[3] = {10.0, 50.0, 100.0};
+  for (long long e = 0; e < q; e++) {
+    const double r = (double)greater[(size_t)e] + (double)equal[(size_t)e] / 2.0 + 1.0;
+    rr += 1.0 / r;
+    for (int k = 0; k < 3; k++) hits[k] += r <= at[k];
+  }
+  const double den = q > 0 ? (double)q : 1.0;
+  printf(" side=%s queries=%lld mrr=%.6f hits@10=%.6f hits@50=%.6f hits@100=%.6f",
+         side == 0 ? "dst" : "src", q, rr / den, hits[0] / den, hits[1] / den, hits[2] / den);
+}
+
+// the area under the ROC curve of the test split's labelled pairs (Mann-Whitney, tied scores
+// sharing their mean rank); nan when a class is empty
+static double test_auc(const pgcn_data &view, const std::vector<float> &score) {
+  std::vector<std::pair<float, int>> s;
+  for (int e = 0; e < view.num_pairs; e++)
+    if (view.pair_split[e] == 3 && view.pair_label[e] >= 0)
+      s.emplace_back(score[(size_t)e], view.pair_label[e]);
+  std::sort(s.begin(), s.end());
+  double pos = 0.0, neg = 0.0, rank_sum = 0.0;
+  for (size_t b = 0; b < s.size();) {
+    size_t e = b;
+    while (e < s.size() && s[e].first == s[b].first) e++;
+    const double mean_rank = ((double)b + 1.0 + (double)e) / 2.0;  // ranks b + 1 .. e
+    for (size_t k = b; k < e; k++) {
+      if (s[k].second == 1) {
+        pos += 1.0;
+        rank_sum += mean_rank;
+      } else {
+        neg += 1.0;
+      }
+    }
+    b = e;
+  }
+  if (pos == 0.0 || neg == 0.0) return std::nan("");
+  return (rank_sum - pos * (pos + 1.0) / 2.0) / (pos * neg);
+}
+
+// heuristic=cn|aa|ra: no training -- the test split's AUC and filtered ranking metrics of the
+// neighbourhood heuristic over the adjacency as loaded
+static int run_heuristic(const pgcn_data &view, int kind, const char *kind_name) {
+  const long long m = view.num_pairs;
+  pgcn_cn_index *index = nullptr;
+  int st = pgcn_cn_index_create(view.num_nodes, view.graph_indptr, view.graph_indices, &index);
+  std::vector<float> score((size_t)m);
+  if (st == PGCN_OK)
+    st = pgcn_cn_index_score_pairs(index, kind, view.pair_src, view.pair_dst, m, score.data());
+  if (st != PGCN_OK) {
+    fprintf(stderr, "heuristic failed: %s\n", pgcn_status_string(st));
+    return EXIT_FAILURE;
+  }
+  printf("heuristic kind=%s pairs=%lld auc=%.6f\n", kind_name, m, test_auc(view, score));
+  printf("rank");
+  for (int side = 0; side < 2; side++) {
+    const auto ranks = [&](long long *greater, long long *equal) {
+      return pgcn_cn_index_link_ranks(index, kind, view.graph_indptr, view.graph_indices, m,
+                                      view.pair_src, view.pair_dst, view.pair_label,
+                                      view.pair_split, 3, side, 1, greater, equal);
+    };
+    const long long q = ranks(nullptr, nullptr);
+    std::vector<long long> greater((size_t)std::max(q, 0LL)), equal(greater.size());
+    const long long got = q < 0 ? q : ranks(greater.data(), equal.data());
+    if (got < 0) {
+      printf("\n");
+      fprintf(stderr, "ranking failed: %s\n", pgcn_status_string((int)got));
+      return EXIT_FAILURE;
+    }
+    print_rank_side(side, greater, equal);
+  }
+  printf("\n");
+  pgcn_cn_index_destroy(index);
+  return EXIT_SUCCESS;
 }
 
 static bool load_params(const char *path, pgcn_params *p, int *embed) {
@@ -157,7 +252,7 @@ int main(int argc, char **argv) {
   std::string root = ".", file;
   bool cache = false;  // cache=1: read/write the binary dataset cache data/<name>.pgcnbin
   bool no_feature = false;  // no_feature=1: the PART2 NO_FEATURE build (feature values 1.0)
-  std::string load, save, predict, rank, recommend;
+  std::string load, save, predict, rank, recommend, heuristic;
   int topk = 10;
   int epochs = -1, residual = -1, layer_norm = -1, batch_norm = -1, multilabel = -1, attention = -1, heads = -1;
   float attn_dropout = -1.0f;
@@ -192,6 +287,11 @@ int main(int argc, char **argv) {
     if (!std::strncmp(argv[i], "rank=", 5)) rank = argv[i] + 5;
     if (!std::strncmp(argv[i], "recommend=", 10)) recommend = argv[i] + 10;
     if (!std::strncmp(argv[i], "topk=", 5)) topk = std::atoi(argv[i] + 5);
+    if (!std::strncmp(argv[i], "heuristic=", 10)) heuristic = argv[i] + 10;
+  }
+  if (!heuristic.empty() && !heuristic_id(heuristic)) {
+    fprintf(stderr, "heuristic= must be cn, aa or ra\n");
+    return EXIT_FAILURE;
   }
   pgcn_params p;
   pgcn_params_default(&p);
@@ -223,6 +323,18 @@ int main(int argc, char **argv) {
     return EXIT_FAILURE;
   }
   if (no_feature) pgcn_dataset_binarize(ds);
+  if (!heuristic.empty()) {
+    const std::string links = root + "/data/" + name + ".links";
+    if (pgcn_dataset_load_links(ds, links.c_str(), 1) != PGCN_OK) {
+      fprintf(stderr, "heuristic=%s needs the pair file %s: it is missing or unreadable\n",
+              heuristic.c_str(), links.c_str());
+      return EXIT_FAILURE;
+    }
+    pgcn_data pairs;
+    int in_dim = 0, out_dim = 0;
+    pgcn_dataset_view(ds, &pairs, &in_dim, &out_dim);
+    return run_heuristic(pairs, heuristic_id(heuristic), heuristic.c_str());
+  }
   if (p.multilabel) {
     const std::string labels = root + "/data/" + name + ".labels";
     if (pgcn_dataset_load_labels(ds, labels.c_str(), 0) != PGCN_OK) {
@@ -317,17 +429,7 @@ int main(int argc, char **argv) {
         st = (int)got;
         break;
       }
-      double rr = 0.0;
-      long long hits[3] = {0, 0, 0};
-      const double at[3] = {10.0, 50.0, 100.0};
-      for (long long e = 0; e < q; e++) {
-        const double r = (double)greater[(size_t)e] + (double)equal[(size_t)e] / 2.0 + 1.0;
-        rr += 1.0 / r;
-        for (int k = 0; k < 3; k++) hits[k] += r <= at[k];
-      }
-      const double den = q > 0 ? (double)q : 1.0;
-      printf(" side=%s queries=%lld mrr=%.6f hits@10=%.6f hits@50=%.6f hits@100=%.6f",
-             side == 0 ? "dst" : "src", q, rr / den, hits[0] / den, hits[1] / den, hits[2] / den);
+      print_rank_side(side, greater, equal);
       if (side == 0 && rank != "1") {
         FILE *f = std::fopen(rank.c_str(), "w");
         if (!f) {
